@@ -496,6 +496,33 @@ def golden_check(latent0, i23d, arch, sample_steps):
             "rel_l2": round(err, 6), "tol": 1e-2, "ok": bool(err < 1e-2)}
 
 
+DUMP_BUDGET = 60 * 10 ** 6             # bytes: --dump-outputs stays under 64 MB with the .npy headers
+
+
+def host_outputs(out, budget=DUMP_BUDGET):
+    """What one step hands its caller - the gathered latents and this rank's frames of parallel.sharded_step - as float32 host arrays of
+    at most `budget` bytes in all.  The two groups of arrays (latents: one row per sample; frames: one row per (sample, view) pair) take
+    the budget smallest group first, each at most an equal share of what is left.  A group over its share keeps a fixed, seeded choice of
+    rows, the same for all its arrays, so two runs with the same arguments dump the same elements; the frames' `pair_index` tells which
+    (sample, view) each kept row is."""
+    import numpy as np
+    lat, frames = out
+    groups = [{'latents': lat}, {k: v for k, v in frames.items() if torch.is_tensor(v)}]
+    rows_of = [next(iter(g.values())).shape[0] for g in groups]
+    row_bytes = [sum(v[0].numel() for v in g.values()) * 4 if n else 0 for g, n in zip(groups, rows_of)]
+    left, arrays = budget, {}
+    order = sorted(range(len(groups)), key=lambda i: rows_of[i] * row_bytes[i])
+    for pos, gi in enumerate(order):
+        n, rb = rows_of[gi], row_bytes[gi]
+        k = min(n, left // (len(order) - pos) // rb) if rb else n
+        left -= k * rb
+        rows = None if k == n else torch.from_numpy(np.sort(np.random.default_rng(gi).choice(n, k, replace=False)))
+        for name, v in groups[gi].items():
+            v = v if rows is None else v[rows.to(v.device)]
+            arrays[name] = v.detach().float().cpu().numpy()
+    return arrays
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -520,7 +547,12 @@ def main():
                          "(prints value_unfolded; 0 = skip)")
     ap.add_argument("--dist", action="store_true",
                     help="go through torch.distributed.run + an RCCL process group even with --gpus 1 (the N-GPU code path on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0: all latents, its own frames) as DIR/<name>.npy, float32, "
+                         "at most 64 MB in all (a fixed, seeded choice of rows beyond that)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     i23d = args.workload == "i23d"
     unet = args.workload == "unet"
     args.batch = args.batch or (4 if unet else 32 if i23d else 8)
@@ -630,6 +662,9 @@ def main():
             Bt, args.views, rank, world)
         return lat_all, frames
 
+    # the renderer's stratified / importance noise comes from the default generators: seeded, so that the same arguments give the
+    # same frames from run to run (a process does not start from a fixed seed)
+    torch.manual_seed(gseed * 1000 + rank)
     for _ in range(args.warmup):
         out = one_step()
     # dominant-kernel timing INSIDE the timed region: HIP events on the launch stream around the MLP fc1 GEMM of the middle
@@ -656,6 +691,7 @@ def main():
     dt = parallel.max_over_ranks(dt)
     ok = bool(torch.isfinite(out[0]).all()) and bool(torch.isfinite(out[1]['image_raw']).all())
     out_timed = out
+    dumped = host_outputs(out) if (args.dump_outputs and rank == 0) else None      # before any later step can reuse a buffer
     fc1_events = dit._fc1_probe['events'] if getattr(dit, '_fc1_probe', None) else []      # the timed region's launches only
     dit._fc1_probe = None
     # The same step with the unconditional half's cross-attention NOT folded (what a non-zero uc context costs): a few extra steps
@@ -777,6 +813,12 @@ def main():
             clk.__exit__()
         if not args.no_cpu_baseline and world == 1:
             rec["cpu_baseline"] = cpu_baseline(args.arch, args.sample_steps, args.views, args.res, B, i23d=i23d)
+        if dumped is not None:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+            rec["dump_outputs"] = {"dir": args.dump_outputs, "arrays": {k: list(a.shape) for k, a in dumped.items()}}
         print(json.dumps(rec), flush=True)
     parallel.barrier()
     parallel.shutdown()

@@ -151,6 +151,43 @@ def test_bench_refuses_wrong_gpu_counts(argv, env, msg):
     assert '"metric"' not in r.stdout
 
 
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--warmup", "-1"]])
+def test_bench_refuses_bad_step_counts(argv):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + argv, capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps must be >= 1" in (r.stderr + r.stdout), (r.returncode, r.stderr[-400:])
+    assert '"metric"' not in r.stdout
+
+
+def test_bench_dump_outputs_budget_and_sample():
+    """bench.py --dump-outputs at the default t23d shapes (8 samples x 40 views @ 256^2 = 500 MB of frames): float32, under the
+    budget, the latents whole, the frames a seeded choice of pairs that is the same from call to call and labelled by pair_index."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    S, V, R = 8, 40, 256
+    lat = torch.randn(S, 12, 32, 32, generator=g)
+    P = S * V
+    frames = {'image_raw': torch.randn(P, 3, R, R, generator=g).half(), 'image_depth': torch.randn(P, 1, R, R, generator=g),
+              'weights_samples': torch.rand(P, 1, R, R, generator=g), 'image_mask': torch.rand(P, 1, R, R, generator=g),
+              'pair_index': torch.tensor([(s, v) for s in range(S) for v in range(V)], dtype=torch.int64)}
+    a = bench.host_outputs((lat, frames))
+    assert set(a) == {'latents'} | set(frames)
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BUDGET
+    np.testing.assert_array_equal(a['latents'], lat.numpy())
+    k = a['image_raw'].shape[0]
+    assert 0 < k < P and all(v.shape[0] == k for n, v in a.items() if n != 'latents')
+    idx = (a['pair_index'][:, 0] * V + a['pair_index'][:, 1]).astype(np.int64)
+    assert (np.diff(idx) > 0).all()
+    for n in ('image_raw', 'image_depth', 'weights_samples', 'image_mask'):
+        np.testing.assert_array_equal(a[n], frames[n][torch.from_numpy(idx)].float().numpy())
+    b = bench.host_outputs((lat, frames))
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+    small = bench.host_outputs((lat[:2], {n: v[:4] for n, v in frames.items()}))      # under budget: everything, unsampled
+    assert small['latents'].shape[0] == 2 and small['pair_index'].shape[0] == 4
+
+
 def test_renderer_variants_outside_the_hot_path_are_refused():
     """Triplane(sr_kwargs=..., bcg_synthesis_kwargs=..., lrm_decoder=True) change what the ray marcher composites
     (nsr/triplane.py:476-500): not built, and not silently ignored either.  No released sampler builds them (every launcher passes

@@ -87,7 +87,11 @@ def test_oracle_edm_euler_matches_reference_golden():
     z = synth_input('z', (2, 12, 32, 32), 41)
     cond = {'crossattn': synth_input('c', (2, 77, 768), 41), 'vector': synth_input('v', (2, 768), 41)}
     uc = {k: torch.zeros_like(v) for k, v in cond.items()}
-    assert torch.equal(osamp.legacy_ddpm_sigmas(10), torch.from_numpy(g['sigmas']))
+    # the reference takes the fp32 ** 0.5 of torch's CPU kernels, which is not correctly rounded and whose last bit depends on the
+    # host's vector unit: the golden holds the generating host's bits, another CPU may land one ulp away on a few entries
+    s10, g10 = osamp.legacy_ddpm_sigmas(10), torch.from_numpy(g['sigmas'])
+    assert s10.dtype == g10.dtype == torch.float32 and s10.shape == g10.shape
+    assert int((s10.view(torch.int32) - g10.view(torch.int32)).abs().max()) <= 1
     tr = []
     y = osamp.edm_euler_sample(lambda x, t, c: odit.t23d_forward(sd, x, t, c, 2), z, cond, uc, 10, 6.5, tr)
     assert rel_l2(tr[0], g['first']) < 1e-5 and rel_l2(y, g['final']) < 1e-4
