@@ -1,4 +1,4 @@
-"""ctypes binding of libln3d_hip.so (the C ABI of include/ln3d.h).
+"""ctypes binding of libln3d_hip.so (the C ABI of include/ln3d.h and include/ln3d_encoder.h).
 
 There is NO fallback: if the library is missing or a kernel launch fails the product raises.
 """
@@ -18,6 +18,8 @@ SYMBOLS = [
     "ln3d_device_cus", "ln3d_probe_mfma_bf16",
     "ln3d_groupnorm_any", "ln3d_im2col3x3_strided", "ln3d_geglu", "ln3d_attention_small", "ln3d_nchw_to_cl_bf16", "ln3d_cl_to_nchw_f32",
     "ln3d_mix_prediction",
+    # include/ln3d_encoder.h (the multi-view VAE encoder)
+    "ln3d_im2col3x3_pad01", "ln3d_frame_mean", "ln3d_mv_posterior",
 ]
 
 EPI_F32, EPI_BF16, EPI_GELU_ERF, EPI_GELU_TANH, EPI_SILU, EPI_GATE_RES, EPI_HEADS, EPI_F32_SILU, EPI_QUICK_GELU, EPI_CROSS_ATTN = range(10)

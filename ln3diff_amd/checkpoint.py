@@ -4,7 +4,9 @@ The module mirrors keep the reference's state-dict keys (incl. the xformers Fuse
 `mlp.mlp.{1,3}.bias`), so loading is prefix resolution + a strict shape check:
   * diffusion model: saved by TrainLoop as `model_rec*/model_joint_denoise*` files or inside the HF `yslan/LN3Diff`
     safetensors under `ddpm_model.` (nsr/train_util_diffusion.py:780-843 loads with strict=True after stripping),
-  * VAE decoder + tri-plane renderer: under `rec_model.decoder.` / `decoder.` (nsr/train_nv_util.py).
+  * VAE decoder + tri-plane renderer: under `rec_model.decoder.` / `decoder.` (nsr/train_nv_util.py),
+  * VAE encoder (vit/mv_encoder.py): the same prefixes with `encoder.` - which of them the released VAE `.pt` files use has not been
+    checked against a real checkpoint; all four are tried.
 Files: `.safetensors` (safetensors.torch.load_file) or torch pickles of a flat state dict (optionally under 'state_dict').
 """
 import torch
@@ -49,6 +51,7 @@ def load_into(module, sd, prefixes=("",), strict=True):
 
 DIT_PREFIXES = ("ddpm_model.", "module.", "model.", "")
 DECODER_PREFIXES = ("rec_model.decoder.", "auto_encoder.decoder.", "decoder.", "module.decoder.", "")
+ENCODER_PREFIXES = ("rec_model.encoder.", "auto_encoder.encoder.", "encoder.", "module.encoder.")
 CONDITIONER_PREFIXES = ("conditioner.embedders.0.", "cond_stage_model.", "")
 
 
@@ -58,7 +61,7 @@ def covers(sd, module, prefixes):
     return sum(1 for k in own if any((p + k) in sd for p in prefixes))
 
 
-def load_checkpoint(path, dit=None, decoder=None, conditioner=None, strict=True, skip_absent=False):
+def load_checkpoint(path, dit=None, decoder=None, conditioner=None, strict=True, skip_absent=False, encoder=None):
     """skip_absent: a component none of whose tensors is in the file is left alone (reported as absent) instead of raising - the
     joint `--resume_checkpoint` files hold denoiser AND decoder, the `--ddpm_model_path` / `--rec_model_path` ones only one."""
     sd = read_state_dict(path)
@@ -68,10 +71,14 @@ def load_checkpoint(path, dit=None, decoder=None, conditioner=None, strict=True,
             rep['dit'], dit = 'absent', None
         if decoder is not None and covers(sd, decoder, DECODER_PREFIXES) == 0:
             rep['decoder'], decoder = 'absent', None
+        if encoder is not None and covers(sd, encoder, ENCODER_PREFIXES) == 0:
+            rep['encoder'], encoder = 'absent', None
     if dit is not None:
         rep['dit'] = load_into(dit, sd, DIT_PREFIXES, strict)
     if decoder is not None:
         rep['decoder'] = load_into(decoder, sd, DECODER_PREFIXES, strict)
+    if encoder is not None:
+        rep['encoder'] = load_into(encoder, sd, ENCODER_PREFIXES, strict)
     if conditioner is not None:
         rep['conditioner'] = load_into(conditioner, sd, CONDITIONER_PREFIXES, strict)
     return rep

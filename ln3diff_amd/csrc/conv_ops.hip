@@ -1,8 +1,10 @@
 // Channel-last helpers for the conv decoder of the tri-plane VAE (ldm Decoder): GroupNorm(+swish),
-// im2col for 3x3 convs (optionally fused with the nearest-2x upsample), layout conversion.
+// im2col for 3x3 convs (optionally fused with the nearest-2x upsample), layout conversion; and for the multi-view encoder
+// (include/ln3d_encoder.h): the pad-(0,1,0,1) stride-2 im2col of its Downsample, frame pooling and the fused posterior.
 // The convolutions themselves run on the MFMA GEMM (gemm_bf16.hip) with fused bias / residual epilogues.
 #include "common.h"
 #include "../../include/ln3d.h"
+#include "../../include/ln3d_encoder.h"
 
 // ------------------------------------------------------------------ GroupNorm (+swish) on f32 [N, HW, C] -> bf16
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* x, float* stats, int HW, int C, int groups, int pix_per_block) {
@@ -131,5 +133,111 @@ extern "C" int ln3d_planes_to_nchw(const float* src, float* dst, int NP, int C, 
   if (!src || !dst || C != 32) return LN3D_ERR_BAD_ARG;
   const int HW = H * W;
   hipLaunchKernelGGL(cl_to_nchw_kernel, dim3((HW + 31) / 32, NP * 3), dim3(256), 0, (hipStream_t)stream, src, dst, C, HW);
+  return ln3d_check_launch();
+}
+
+// ------------------------------------------------------------------ encoder Downsample: F.pad(x, (0,1,0,1)) + 3x3 conv, stride 2, padding 0
+// col[(n*Ho*Wo + oy*Wo + ox), (ky*3+kx)*C + c] = x[n, 2*oy+ky, 2*ox+kx, c] (0 at or past H / W), zero pad to Kpad
+__global__ void im2col3x3_pad01_kernel(const bf16_t* x, bf16_t* col, int H, int W, int C, int Ho, int Wo, int Kpad, int64_t total8) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // one 16-B (8 x bf16) piece
+  if (i >= total8) return;
+  const int k8 = Kpad / 8;
+  const int64_t row = i / k8;
+  const int kk = (int)(i % k8) * 8;
+  const int ox = (int)(row % Wo), oy = (int)((row / Wo) % Ho);
+  const int64_t n = row / ((int64_t)Wo * Ho);
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if (kk < 9 * C) {
+    const int tap = kk / C, c = kk % C, ky = tap / 3, kx = tap % 3;
+    const int yy = 2 * oy + ky, xx = 2 * ox + kx;
+    if (yy < H && xx < W) v = *reinterpret_cast<const uint4*>(x + (((int64_t)n * H + yy) * W + xx) * C + c);
+  }
+  *reinterpret_cast<uint4*>(col + row * Kpad + kk) = v;
+}
+extern "C" int ln3d_im2col3x3_pad01(const void* x, void* col, int N, int H, int W, int C, int Kpad, void* stream) {
+  if (!x || !col || N <= 0 || H < 2 || W < 2 || C <= 0 || C % 8 || Kpad % 8 || Kpad < 9 * C) return LN3D_ERR_BAD_ARG;
+  const int Ho = (H - 2) / 2 + 1, Wo = (W - 2) / 2 + 1;           // floor((H + 1 - 3) / 2) + 1
+  const int64_t total8 = (int64_t)N * Ho * Wo * (Kpad / 8);
+  hipLaunchKernelGGL(im2col3x3_pad01_kernel, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+                     (bf16_t*)col, H, W, C, Ho, Wo, Kpad, total8);
+  return ln3d_check_launch();
+}
+
+// ------------------------------------------------------------------ frame pooling: [B*F, HW, C] channel-last -> mean over F, NCHW [B, C, HW]
+// frames summed in order, then / F (the arithmetic of ln3d_mv_posterior's own pooling, so both routes give the same bits)
+__global__ void frame_mean_kernel(const float* h, float* out, int F, int HW, int C, int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       // over B * C * HW (output order)
+  if (i >= total) return;
+  const int p = (int)(i % HW);
+  const int64_t bc = i / HW;
+  const int64_t b = bc / C; const int c = (int)(bc - b * C);
+  float s = 0.f;
+  for (int f = 0; f < F; ++f) s += h[((b * F + f) * HW + p) * C + c];
+  out[i] = s / (float)F;
+}
+extern "C" int ln3d_frame_mean(const float* h, float* out, int B, int F, int HW, int C, void* stream) {
+  if (!h || !out || B <= 0 || F <= 0 || HW <= 0 || C <= 0) return LN3D_ERR_BAD_ARG;
+  const int64_t total = (int64_t)B * C * HW;
+  hipLaunchKernelGGL(frame_mean_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h, out, F, HW, C, total);
+  return ln3d_check_launch();
+}
+
+// ------------------------------------------------------------------ fused multi-view posterior (include/ln3d_encoder.h)
+// One thread per (object b, pixel p): the 6C = 24 pooled channels stay in registers, the grouped 1x1 quant_conv is 24 dot products
+// of 8, then the 12 (c, n) pairs of the [B, 2C, 3, HW] view are written to every output.  Memory-bound and tiny (B * 1024 threads);
+// exact tanhf / expf (not the fast intrinsics): logvar reaches the latent through exp and log_q through exp twice.
+#define MVP_C 4
+__global__ __launch_bounds__(256) void mv_posterior_kernel(const float* h, int64_t s_frame, int64_t s_pix, int64_t s_ch, const float* qw,
+                                                          const float* qb, const float* eps, float* mean_o, float* logvar_o, float* z_o,
+                                                          float* tok_o, float* logq_o, float* ent_o, int B, int F, int HW) {
+  constexpr int CM = 6 * MVP_C, GI = 2 * MVP_C;                  // moments, channels per quant_conv group
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * HW) return;
+  const int p = (int)(i % HW);
+  const int64_t b = i / HW;
+  float avg[CM];
+#pragma unroll
+  for (int k = 0; k < CM; ++k) avg[k] = 0.f;
+  for (int f = 0; f < F; ++f) {
+    const float* hp = h + (b * F + f) * s_frame + (int64_t)p * s_pix;
+#pragma unroll
+    for (int k = 0; k < CM; ++k) avg[k] += hp[k * s_ch];
+  }
+#pragma unroll
+  for (int k = 0; k < CM; ++k) avg[k] = avg[k] / (float)F;
+  auto moment = [&](int o) {
+    const int g0 = (o / GI) * GI;
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < GI; ++j) acc += qw[o * GI + j] * avg[g0 + j];
+    return acc + qb[o];
+  };
+  const float half_log_2pi = 0.91893853320467274f;
+#pragma unroll
+  for (int c = 0; c < MVP_C; ++c)
+#pragma unroll
+    for (int n = 0; n < 3; ++n) {
+      const float mean = moment(c * 3 + n);
+      const float logvar = tanhf(moment((MVP_C + c) * 3 + n) / 20.0f) * 20.0f;
+      const float stdv = expf(0.5f * logvar), var = expf(logvar);
+      const int64_t o = ((b * MVP_C + c) * 3 + n) * HW + p;        // [B, C, 3, HW]
+      const float z = eps ? mean + stdv * eps[o] : mean;
+      const float ns = (z - mean) / var;
+      mean_o[o] = mean;
+      logvar_o[o] = logvar;
+      z_o[o] = z;
+      logq_o[o] = -0.5f * ns * ns - half_log_2pi - logvar;
+      ent_o[o] = logvar + (half_log_2pi + 0.5f);
+      tok_o[(b * 3 * HW + (int64_t)n * HW + p) * MVP_C + c] = z;     // [B, 3*HW, C]
+    }
+}
+extern "C" int ln3d_mv_posterior(const float* h, int64_t s_frame, int64_t s_pix, int64_t s_ch, const float* qw, const float* qb, const float* eps,
+                                 float* mean, float* logvar, float* z, float* latent_tok, float* log_q, float* entropy, int B, int F, int HW, int C,
+                                 void* stream) {
+  if (!h || !qw || !qb || !mean || !logvar || !z || !latent_tok || !log_q || !entropy) return LN3D_ERR_BAD_ARG;
+  if (B <= 0 || F <= 0 || HW <= 0 || C != MVP_C || s_frame < 0 || s_pix < 0 || s_ch < 0) return LN3D_ERR_BAD_ARG;
+  const int64_t n = (int64_t)B * HW;
+  hipLaunchKernelGGL(mv_posterior_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h, s_frame, s_pix, s_ch, qw, qb,
+                     eps, mean, logvar, z, latent_tok, log_q, entropy, B, F, HW);
   return ln3d_check_launch();
 }

@@ -1,7 +1,14 @@
 """`AE` - the reconstruction-model wrapper the reference's drivers talk to (nsr/script_util.py:25-377): everything goes through
-`forward(img, c, latent, behaviour, ...)` "for DDP use".  Only the decoder half is on the sampling hot path, so the behaviours
-that `render_video_given_triplane` / `eval_i23d_and_export` use are implemented on the HIP decoder; the encoder behaviours
-raise (the image encoder of the VAE is out of scope).
+`forward(img, c, latent, behaviour, ...)` "for DDP use".  The decoder behaviours that `render_video_given_triplane` /
+`eval_i23d_and_export` use run on the HIP decoder.  The encoder behaviours need the released multi-view encoder
+(vit/mv_encoder.py, dino_version 'mv-sd-dit-dynaInp-trilatent'); `AE(None, decoder, ...)` - the sampling configuration - raises
+NotImplementedError for them.
+
+    enc                        : img [B*F, 10, S, S] -> pooled encoder output [B, 24, S/8, S/8]
+    encoder_vae                : enc + decoder.vae_reparameterization(., True) (the frame mean is fused into the posterior kernel)
+    dec / dec_wo_triplane      : encoder output -> decoder.vit_decode (sampled posterior) [-> triplane_decode]
+    enc_dec / enc_dec_wo_triplane : the two above on img
+    (encoder behaviours accept `eps` [B, 4, 3, H*W]: the posterior noise instead of the CPU-generator draw)
 
     decode_after_vae_no_render : latent dict -> + 'latent_after_vit' [B,96,128,128] (+ 'planes_channel_last' for the renderer)
     triplane_dec               : tri-planes (dict or tensor) + c [V,25] -> Triplane.forward dict (image_raw, image_depth, ...)
@@ -21,6 +28,11 @@ class AE(nn.Module):
                  dino_version='sd_dit', clip_dtype=None, no_dim_up_mlp=True, dim_up_mlp_as_func=False, uvit_skip_encoder=False,
                  confnet=None):
         super().__init__()
+        if encoder is not None:
+            from ..vit.mv_encoder import RELEASED_DINO_VERSION, MVEncoderGSDynamicInp
+            if dino_version != RELEASED_DINO_VERSION or not isinstance(encoder, MVEncoderGSDynamicInp):
+                raise NotImplementedError(f"AE: the encoder behaviours are built for the released multi-view encoder only "
+                                          f"(MVEncoderGSDynamicInp, dino_version={RELEASED_DINO_VERSION!r}); got dino_version={dino_version!r}")
         self.encoder = encoder
         self.decoder = decoder
         self.img_size = img_size
@@ -41,11 +53,45 @@ class AE(nn.Module):
         ret_dict = self.decode_after_vae_no_render(ret_dict, img_size)
         return self.decoder.triplane_decode(ret_dict, c, return_raw_only=return_raw_only, **kwargs)
 
+    def encode(self, img):
+        return self.encoder(img)
+
+    def encoder_vae(self, img, eps=None):
+        """encode + vae_reparameterization(., True), with the per-frame encoder output handed to the posterior kernel (which takes the
+        frame mean itself: the same bits as pooling first)."""
+        h = self.encoder.forward_frames(img)
+        return self.decoder.vae_reparameterization(h, True, eps=eps, num_frames=self.encoder.num_frames)
+
+    def decode_wo_triplane(self, latent, c=None, img_size=None, eps=None):
+        return self.decoder.vit_decode(latent, img_size or self.img_size, eps=eps)
+
+    def decode(self, latent, c, img_size=None, return_raw_only=False, eps=None, **kwargs):
+        ret = self.decode_wo_triplane(latent, c, img_size, eps=eps)
+        return self.decoder.triplane_decode(ret, c, return_raw_only=return_raw_only, **kwargs)
+
     @torch.no_grad()
     def forward(self, img=None, c=None, latent=None, behaviour='enc_dec', coordinates=None, directions=None, return_raw_only=False,
                 *args, **kwargs):
         if behaviour in _ENCODER_BEHAVIOURS:
-            raise NotImplementedError(f"AE behaviour '{behaviour}' needs the VAE encoder, which is outside the sampling hot path")
+            if self.encoder is None:
+                raise NotImplementedError(f"AE behaviour '{behaviour}' needs the VAE encoder: this AE was built without one "
+                                          f"(pass the released MVEncoderGSDynamicInp, vit/mv_encoder.py)")
+            eps = kwargs.pop('eps', None)
+            if behaviour == 'enc':
+                return self.encode(img)
+            if behaviour == 'encoder_vae':
+                return self.encoder_vae(img, eps)
+            if behaviour == 'enc_dec':           # the reference: encode, vit_decode (sampled posterior), triplane_decode
+                h = self.encoder.forward_frames(img)
+                ret = self.decoder.vit_decode(h, self.img_size, eps=eps, num_frames=self.encoder.num_frames)
+                return self.decoder.triplane_decode(ret, c, return_raw_only=return_raw_only, **kwargs)
+            if behaviour == 'enc_dec_wo_triplane':
+                h = self.encoder.forward_frames(img)
+                return self.decoder.vit_decode(h, self.img_size, eps=eps, num_frames=self.encoder.num_frames)
+            assert latent is not None
+            if behaviour == 'dec':
+                return self.decode(latent, c, self.img_size, return_raw_only=return_raw_only, eps=eps, **kwargs)
+            return self.decode_wo_triplane(latent, c, self.img_size, eps=eps)          # dec_wo_triplane
         if behaviour == 'decode_after_vae_no_render':
             return self.decode_after_vae_no_render(latent, self.img_size)
         if behaviour == 'decode_after_vae':

@@ -325,3 +325,50 @@ def cl_to_nchw_f32(x, y, N, Cc, HW):
 
 def mix_prediction(eps, x, mixing_logit, sqrt_one_minus_ab, N, Cc, HW):
     L.check(L.lib().ln3d_mix_prediction(_p(eps), _p(x), _p(mixing_logit), C.c_float(sqrt_one_minus_ab), N, Cc, HW, _stream()), "mix_prediction")
+
+
+# ---------------------------------------------------------------- multi-view VAE encoder (include/ln3d_encoder.h, csrc/conv_ops.hip)
+def im2col3x3_pad01(x, col, N, H, W, Cc, Kpad):
+    """Downsample of the encoder: F.pad(x, (0, 1, 0, 1)) + 3x3 conv stride 2 padding 0, as an im2col gather ([N*Ho*Wo, Kpad] bf16)."""
+    _chk_dev(x, col)
+    Ho, Wo = (H - 2) // 2 + 1, (W - 2) // 2 + 1
+    if x.numel() < N * H * W * Cc or col.numel() < N * Ho * Wo * Kpad:
+        raise ValueError("im2col3x3_pad01: buffers smaller than the problem")
+    L.check(L.lib().ln3d_im2col3x3_pad01(_p(x), _p(col), N, H, W, Cc, Kpad, _stream()), "im2col3x3_pad01")
+
+
+def _channel_last_view(h):
+    """h: [N, C, H, W] whose memory is channel-last ([N, H, W, C] contiguous) - what Encoder.forward_frames returns."""
+    N, Cc, H, W = h.shape
+    return h.stride() == (H * W * Cc, 1, W * Cc, Cc)
+
+
+def frame_mean(h, out, B, F, HW, Cc):
+    """h [B*F, C, H, W] (channel-last memory) -> out f32 [B, C, H, W] contiguous: mean over each object's F frames."""
+    _chk_dev(h, out)
+    if h.dtype != torch.float32 or out.dtype != torch.float32 or not _channel_last_view(h) or not out.is_contiguous():
+        raise ValueError("frame_mean: h must be an f32 channel-last [B*F, C, H, W] view, out a contiguous f32 tensor")
+    if h.shape[0] != B * F or h.shape[1] != Cc or h.shape[2] * h.shape[3] != HW or out.numel() != B * Cc * HW:
+        raise ValueError("frame_mean: shapes do not match (B, F, HW, C)")
+    L.check(L.lib().ln3d_frame_mean(_p(h), _p(out), B, F, HW, Cc, _stream()), "frame_mean")
+
+
+def mv_posterior(h, qw, qb, eps, B, F, E=4):
+    """Fused posterior (ln3d_mv_posterior): h [B*F, 6E, H, W] f32 of any strides with a uniform pixel stride (the per-frame channel-last
+    encoder output, or the pooled NCHW one with F = 1); qw [6E, 2E] / qb [6E] f32 (quant_conv); eps f32 [B, E, 3, H*W] or None (mode).
+    Returns dict of f32 tensors: mean, logvar, z, log_q, entropy [B, E, 3, H*W] and latent_tok [B, 3*H*W, E] (E = ldm_embed_dim)."""
+    _chk_dev(h, qw, qb, eps)
+    N, Cm, H, W = h.shape
+    HW = H * W
+    if h.dtype != torch.float32 or N != B * F or Cm != 6 * E or h.stride(2) != W * h.stride(3):
+        raise ValueError(f"mv_posterior: h {tuple(h.shape)} / strides {h.stride()}: expected f32 [{B * F}, {6 * E}, H, W] with a uniform pixel stride")
+    if qw.dtype != torch.float32 or qw.numel() != 12 * E * E or not qw.is_contiguous() or qb.numel() != 6 * E or not qb.is_contiguous():
+        raise ValueError("mv_posterior: quant_conv weight [6E, 2E] / bias [6E] must be contiguous f32")
+    if eps is not None and (eps.dtype != torch.float32 or tuple(eps.shape) != (B, E, 3, HW) or not eps.is_contiguous()):
+        raise ValueError(f"mv_posterior: eps must be a contiguous f32 [{B}, {E}, 3, {HW}] tensor")
+    out = {k: torch.empty(B, E, 3, HW, device=h.device, dtype=torch.float32) for k in ('mean', 'logvar', 'z', 'log_q', 'entropy')}
+    out['latent_tok'] = torch.empty(B, 3 * HW, E, device=h.device, dtype=torch.float32)
+    L.check(L.lib().ln3d_mv_posterior(_p(h), C.c_int64(h.stride(0)), C.c_int64(h.stride(3)), C.c_int64(h.stride(1)), _p(qw), _p(qb), _p(eps),
+                                      _p(out['mean']), _p(out['logvar']), _p(out['z']), _p(out['latent_tok']), _p(out['log_q']),
+                                      _p(out['entropy']), B, F, HW, E, _stream()), "mv_posterior")
+    return out

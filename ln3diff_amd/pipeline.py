@@ -297,3 +297,39 @@ class GuidedDiffusionEngine:
     @torch.no_grad()
     def eval_ddpm_sample(self, camera, **kw):
         return self.eval_cldm(None, camera, **kw)
+
+
+@torch.no_grad()
+def reconstruct(rec_model, img, cams, latent_dir=None, ins_names=None, sample_posterior=True, eps=None, export_mesh=False, mesh_size=192,
+                mesh_thres=10, mesh_path=None, resolution=None, jitter=None, u_fine=None):
+    """Posed views -> tri-plane latent -> renders (and meshes): TrainLoop.eval_novelview_loop(save_latent=True) of the VAE
+    reconstruction launcher (vae_xl_reconstruction.sh; nsr/train_nv_util.py:1176-1213).  rec_model: `AE` with the released encoder;
+    img [B*F, 10, 256, 256] (F = rec_model.encoder.num_frames views per object); cams [V, 25] rendered for every object.
+    The latent is 'encoder_vae' (posterior sampled as the reference does, or the mode with sample_posterior=False; eps [B, 4, 3, H*W]
+    overrides the CPU-generator draw).  latent_dir: writes <latent_dir>/<ins>/latent.npy = latent_normalized_2Ddiffusion[b] [12, 32, 32].
+    The encoded latent is already in VAE space, so it is rendered with triplane_scaling_divider = 1.  Returns the
+    render_video_given_triplane dict plus 'latent' (the encoder_vae dict)."""
+    import os
+    import numpy as np
+    from .nsr.script_util import AE
+    if not isinstance(rec_model, AE) or rec_model.encoder is None:
+        raise ValueError("reconstruct needs an AE built with the released encoder (AE(encoder, decoder, ..., dino_version=...))")
+    if sample_posterior:
+        lat = rec_model(img=img, behaviour='encoder_vae', eps=eps)
+    else:
+        h = rec_model.encoder.forward_frames(img)
+        lat = rec_model.decoder.vae_reparameterization(h, False, num_frames=rec_model.encoder.num_frames)
+    z = lat['latent_normalized_2Ddiffusion']
+    B = z.shape[0]
+    if latent_dir is not None:
+        names = ins_names or [str(b) for b in range(B)]
+        if len(names) != B:
+            raise ValueError(f"{len(names)} instance names for {B} objects")
+        zc = z.cpu().numpy()
+        for b, name in enumerate(names):
+            os.makedirs(os.path.join(latent_dir, name), exist_ok=True)
+            np.save(os.path.join(latent_dir, name, 'latent.npy'), zc[b])
+    out = render_video_given_triplane(z.clone(), rec_model, cams, triplane_scaling_divider=1.0, export_mesh=export_mesh, mesh_size=mesh_size,
+                                      mesh_thres=mesh_thres, mesh_path=mesh_path, resolution=resolution, jitter=jitter, u_fine=u_fine)
+    out['latent'] = lat
+    return out

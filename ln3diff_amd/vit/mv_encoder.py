@@ -1,0 +1,354 @@
+"""Multi-view VAE encoder of the released tri-plane VAE (`mv-sd-dit-dynaInp-trilatent`) on the HIP path: posed views -> the
+pre-posterior encoder output that `vae_reparameterization` of the decoder class turns into the tri-plane latent.
+
+Same constructor arguments and state-dict keys as the reference's ldm/modules/diffusionmodules/model.py `Encoder` (:459-561) and
+`MVEncoderGSDynamicInp` (:603-623), with ldm/modules/attention.py `SpatialTransformer3D` / `BasicTransformerBlock3D` (:390-463) as
+the middle attention (`attn_type="mv-vanilla"`).  Input [B*F, in_channels, S, S]: F = num_frames consecutive views of one object
+(the released input has 10 channels: normalised RGB, Pluecker rays o x d | d, normalised depth; datasets/g_buffer_objaverse.py).
+
+Everything runs channel-last on the device ([N, H*W, C] f32 activations, bf16 GEMM operands, fp32 accumulation / norms / softmax):
+
+  conv 3x3        ln3d_im2col3x3 -> ln3d_gemm_bf16 (+ bias / + residual epilogue); the input is cast and zero-padded 10 -> 16 channels
+                  by ln3d_nchw_to_cl_bf16
+  Downsample      ln3d_im2col3x3_pad01 (pad (0,1,0,1), stride 2, padding 0) -> GEMM
+  ResnetBlock     ln3d_groupnorm_swish (GroupNorm(32, eps 1e-6) + swish) -> conv -> GN + swish -> conv with the residual epilogue onto
+                  x (nin_shortcut: a 1x1 GEMM first when the width changes)
+  mid.attn_1      GroupNorm -> proj_in GEMM -> LayerNorm (ln3d_norm_modulate) -> q|k|v GEMM splitting heads -> ln3d_attention_bf16 over
+                  ALL F*H*W tokens of an object (attn1: `(b f) l c -> b (f l) c` is the row order already) -> to_out (residual
+                  epilogue); the same per frame (attn2); LayerNorm -> GEGLU (GEMM + ln3d_geglu) -> GEMM; proj_out onto the input
+  pooling         ln3d_frame_mean (forward) or inside ln3d_mv_posterior (AE 'encoder_vae' / 'enc_dec': the decoder's
+                  vae_reparameterization reads the per-frame output directly)
+
+There is no CPU fallback.  Not built: attn_resolutions (the released encoder attends in the middle only), resamp_with_conv=False,
+temb, the 4-view `MVEncoder` with its fusion_layer and the other dino_versions (they raise).
+"""
+import torch
+import torch.nn as nn
+
+from .. import ops, _cache
+from ..dit.dit_models_xformers import Workspace, f32, self_attention_hip
+from ..guided_diffusion.unet import CrossAttention, FeedForward, _pack_conv3, _pack_lin
+
+RELEASED_DINO_VERSION = 'mv-sd-dit-dynaInp-trilatent'
+_MFMA_MIN_TOKENS = 256          # self-attention over at least this many tokens runs on the MFMA attention kernels (as in the U-Net)
+
+
+def Normalize(in_channels):     # model.py:29-30
+    return nn.GroupNorm(num_groups=32, num_channels=in_channels, eps=1e-6, affine=True)
+
+
+class ResnetBlock(nn.Module):   # model.py:94-153 with temb_channels=0 (the Encoder's)
+    def __init__(self, *, in_channels, out_channels=None, conv_shortcut=False, dropout=0.0, temb_channels=0):
+        super().__init__()
+        if conv_shortcut or temb_channels:
+            raise NotImplementedError("ResnetBlock: conv_shortcut / temb are not used by the encoder")
+        out_channels = in_channels if out_channels is None else out_channels
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.norm1 = Normalize(in_channels)
+        self.conv1 = nn.Conv2d(in_channels, out_channels, 3, 1, 1)
+        self.norm2 = Normalize(out_channels)
+        self.dropout = nn.Dropout(dropout)
+        self.conv2 = nn.Conv2d(out_channels, out_channels, 3, 1, 1)
+        if in_channels != out_channels:
+            self.nin_shortcut = nn.Conv2d(in_channels, out_channels, 1, 1, 0)
+
+
+class Downsample(nn.Module):    # model.py:72-91, with_conv=True
+    def __init__(self, in_channels, with_conv=True):
+        super().__init__()
+        if not with_conv:
+            raise NotImplementedError("Downsample(with_conv=False): resamp_with_conv is True in the released encoder")
+        self.with_conv = True
+        self.conv = nn.Conv2d(in_channels, in_channels, 3, 2, 0)
+
+
+class BasicTransformerBlock3D(nn.Module):       # attention.py:315-329 (init), :390-402 (forward)
+    def __init__(self, dim, n_heads, d_head, dropout=0., context_dim=None, gated_ff=True, checkpoint=True, disable_self_attn=False):
+        super().__init__()
+        if context_dim is not None or disable_self_attn:
+            raise NotImplementedError("BasicTransformerBlock3D: the encoder's blocks are self-attention only (context_dim=None)")
+        self.disable_self_attn = False
+        self.attn1 = CrossAttention(query_dim=dim, heads=n_heads, dim_head=d_head, dropout=dropout)
+        self.ff = FeedForward(dim, dropout=dropout, glu=gated_ff)
+        self.attn2 = CrossAttention(query_dim=dim, heads=n_heads, dim_head=d_head, dropout=dropout)
+        self.norm1, self.norm2, self.norm3 = nn.LayerNorm(dim), nn.LayerNorm(dim), nn.LayerNorm(dim)
+
+
+class SpatialTransformer3D(nn.Module):          # attention.py:405-463 (use_linear=False)
+    def __init__(self, in_channels, n_heads, d_head, depth=1, dropout=0., context_dim=None, disable_self_attn=False, use_linear=False,
+                 use_checkpoint=True):
+        super().__init__()
+        if use_linear:
+            raise NotImplementedError("SpatialTransformer3D(use_linear=True) is not used by the encoder")
+        self.in_channels, self.n_heads, self.d_head = in_channels, n_heads, d_head
+        inner = n_heads * d_head
+        self.norm = Normalize(in_channels)
+        self.proj_in = nn.Conv2d(in_channels, inner, 1, 1, 0)
+        self.transformer_blocks = nn.ModuleList([BasicTransformerBlock3D(inner, n_heads, d_head, dropout=dropout, context_dim=context_dim,
+                                                                         disable_self_attn=disable_self_attn) for _ in range(depth)])
+        self.proj_out = nn.Conv2d(inner, in_channels, 1, 1, 0)      # zero_module in the reference; loaded weights replace it
+        self.use_linear = False
+
+
+class Encoder(nn.Module):
+    """ldm Encoder (model.py:459-561) with the multi-view middle attention: forward(x) -> conv_out output [N, 2*z_channels, H/8, W/8]
+    (per frame, not pooled).  `forward_frames` returns the same values as a channel-last tensor seen through an NCHW view."""
+
+    def __init__(self, *, ch, out_ch, ch_mult=(1, 2, 4, 8), num_res_blocks, attn_resolutions, dropout=0.0, resamp_with_conv=True,
+                 in_channels, resolution, z_channels, double_z=True, use_linear_attn=False, attn_type="vanilla", attn_kwargs=None,
+                 add_fusion_layer=False, num_frames=None, **ignore_kwargs):
+        super().__init__()
+        if attn_type != "mv-vanilla" or use_linear_attn:
+            raise NotImplementedError(f"Encoder(attn_type={attn_type!r}): only the multi-view 'mv-vanilla' middle attention of the released "
+                                      f"encoder is built")
+        if len(attn_resolutions):
+            raise NotImplementedError("Encoder(attn_resolutions != []): the released encoder attends in the middle only")
+        if add_fusion_layer:
+            raise NotImplementedError("Encoder(add_fusion_layer=True): the 4-view MVEncoder with its fusion layer is not built")
+        attn_kwargs = dict(attn_kwargs or {})
+        widths = sorted({ch * m for m in (1,) + tuple(ch_mult)})
+        for w in widths:
+            if w % 32 or 256 % w:          # ln3d_groupnorm_swish: GroupNorm(32) with the channel count dividing 256
+                raise ValueError(f"Encoder: channel width {w} (ch x ch_mult) must be one of 32, 64, 128, 256 (GroupNorm(32) kernel)")
+        inner = attn_kwargs.get('n_heads', 8) * attn_kwargs.get('d_head', 64)
+        if inner % 128 or inner > 1536:
+            raise ValueError(f"Encoder: transformer width {inner} - the LayerNorm kernel takes multiples of 128 up to 1536")
+        self.ch, self.temb_ch = ch, 0
+        self.num_resolutions, self.num_res_blocks = len(ch_mult), num_res_blocks
+        self.resolution, self.in_channels = resolution, in_channels
+        self.z_channels, self.double_z = z_channels, double_z
+        self.num_frames = 1 if num_frames is None else num_frames
+        self.conv_in = nn.Conv2d(in_channels, ch, 3, 1, 1)
+        in_ch_mult = (1,) + tuple(ch_mult)
+        self.in_ch_mult = in_ch_mult
+        self.down = nn.ModuleList()
+        block_in = ch
+        for i_level in range(self.num_resolutions):
+            block = nn.ModuleList()
+            block_in = ch * in_ch_mult[i_level]
+            block_out = ch * ch_mult[i_level]
+            for _ in range(num_res_blocks):
+                block.append(ResnetBlock(in_channels=block_in, out_channels=block_out, dropout=dropout))
+                block_in = block_out
+            down = nn.Module()
+            down.block = block
+            down.attn = nn.ModuleList()
+            if i_level != self.num_resolutions - 1:
+                down.downsample = Downsample(block_in, resamp_with_conv)
+            self.down.append(down)
+        self.mid = nn.Module()
+        self.mid.block_1 = ResnetBlock(in_channels=block_in, out_channels=block_in, dropout=dropout)
+        self.mid.attn_1 = SpatialTransformer3D(block_in, **attn_kwargs)
+        self.mid.block_2 = ResnetBlock(in_channels=block_in, out_channels=block_in, dropout=dropout)
+        self.norm_out = Normalize(block_in)
+        self.conv_out = nn.Conv2d(block_in, 2 * z_channels if double_z else z_channels, 3, 1, 1)
+        self._packed, self._ws = None, None
+        _cache.watch(self)
+
+    def _apply(self, fn, *a, **k):
+        _cache.bump()
+        return super()._apply(fn, *a, **k)
+
+    # ------------------------------------------------------------------ packing
+    def _ensure_packed(self, dev):
+        if _cache.fresh(self._packed, dev):
+            return
+        gn = lambda g: (f32(g.weight, dev), f32(g.bias, dev), float(g.eps))
+
+        def res(b):
+            q = {'n1': gn(b.norm1), 'c1': _pack_conv3(b.conv1, dev), 'n2': gn(b.norm2), 'c2': _pack_conv3(b.conv2, dev)}
+            if hasattr(b, 'nin_shortcut'):
+                q['nin'] = _pack_lin(b.nin_shortcut.weight, b.nin_shortcut.bias, dev)
+            return q
+        P = {'device': dev}
+        P['conv_in'] = _pack_conv3(self.conv_in, dev, cin_pad=(self.in_channels + 7) // 8 * 8)
+        P['down'] = [{'blocks': [res(b) for b in d.block], 'down': _pack_conv3(d.downsample.conv, dev) if hasattr(d, 'downsample') else None}
+                     for d in self.down]
+        P['mid1'], P['mid2'] = res(self.mid.block_1), res(self.mid.block_2)
+        a = self.mid.attn_1
+        ln = lambda n: (f32(n.weight - 1.0, dev), f32(n.bias, dev), float(n.eps))           # y = LN(x) (1 + (w - 1)) + b
+        qkv = lambda at: _pack_lin(torch.cat([at.to_q.weight, at.to_k.weight, at.to_v.weight], 0), None, dev)
+        blocks = [{'n1': ln(b.norm1), 'n2': ln(b.norm2), 'n3': ln(b.norm3),
+                   'qkv1': qkv(b.attn1), 'o1': _pack_lin(b.attn1.to_out[0].weight, b.attn1.to_out[0].bias, dev),
+                   'qkv2': qkv(b.attn2), 'o2': _pack_lin(b.attn2.to_out[0].weight, b.attn2.to_out[0].bias, dev),
+                   'ff1': _pack_lin(b.ff.net[0].proj.weight, b.ff.net[0].proj.bias, dev),
+                   'ff2': _pack_lin(b.ff.net[2].weight, b.ff.net[2].bias, dev)} for b in a.transformer_blocks]
+        P['attn'] = {'n': gn(a.norm), 'pin': _pack_lin(a.proj_in.weight, a.proj_in.bias, dev),
+                     'pout': _pack_lin(a.proj_out.weight, a.proj_out.bias, dev), 'blocks': blocks, 'heads': a.n_heads, 'dh': a.d_head}
+        P['norm_out'] = gn(self.norm_out)
+        P['conv_out'] = _pack_conv3(self.conv_out, dev)
+        self._packed = _cache.stamp(P, self)
+        self._ws = Workspace(dev)
+
+    # ------------------------------------------------------------------ pieces (h: f32 [N*H*W, C] channel-last)
+    def _new(self, rows, cols, dtype=torch.float32):
+        return torch.empty(rows, cols, device=self._packed['device'], dtype=dtype)
+
+    def _bf(self, h):
+        y = torch.empty_like(h, dtype=torch.bfloat16)
+        ops.cast_bf16(h, y)
+        return y
+
+    def _gn(self, h, nw, N, HW, C, swish):
+        y = self._new(N * HW, C, torch.bfloat16)
+        st = torch.empty(N * 64 * (1 + (HW + 255) // 256), device=h.device, dtype=torch.float32)    # sums + per-chunk partials (ln3d.h)
+        ops.groupnorm_swish(h, nw[0], nw[1], y, st, N, HW, C, 32, nw[2], swish)
+        return y
+
+    def _conv3(self, a_bf, N, H, W, pc, out, epi=ops.EPI_F32):
+        col = self._new(N * H * W, pc['kpad'], torch.bfloat16)
+        ops.im2col3x3(a_bf, col, N, H, W, pc['cin'], 1, pc['kpad'])
+        ops.gemm(col, pc['w'], pc['b'], epi, out)
+
+    def _res(self, x, q, N, H, W):
+        cin, cout, HW = q['c1']['cin'], q['c1']['cout'], H * W
+        a = self._gn(x, q['n1'], N, HW, cin, True)
+        t = self._new(N * HW, cout)
+        self._conv3(a, N, H, W, q['c1'], t)
+        a2 = self._gn(t, q['n2'], N, HW, cout, True)
+        if 'nin' in q:
+            s = self._new(N * HW, cout)
+            ops.gemm(self._bf(x), q['nin']['w'], q['nin']['b'], ops.EPI_F32, s)
+        else:
+            s = x                                   # the block's input is not needed again: the residual lands in place
+        self._conv3(a2, N, H, W, q['c2'], s, epi=ops.EPI_GATE_RES)
+        return s
+
+    def _down(self, h, pc, N, H, W):
+        Ho, Wo = (H - 2) // 2 + 1, (W - 2) // 2 + 1
+        col = self._new(N * Ho * Wo, pc['kpad'], torch.bfloat16)
+        ops.im2col3x3_pad01(self._bf(h), col, N, H, W, pc['cin'], pc['kpad'])
+        out = self._new(N * Ho * Wo, pc['cout'])
+        ops.gemm(col, pc['w'], pc['b'], ops.EPI_F32, out)
+        return out, Ho, Wo
+
+    def _self_attend(self, a_bf, qkv, Bo, L, heads, dh, tag):
+        """Self-attention of Bo sequences of L tokens (rows of a_bf in sequence order) -> bf16 [Bo*L, heads*dh]."""
+        inner = heads * dh
+        if dh % 8 == 0 and dh <= 128 and L >= _MFMA_MIN_TOKENS and L % 32 == 0:
+            return self_attention_hip(self._ws, tag, a_bf, Bo, L, inner, heads, qkv['w'], qkv['b'])
+        if L > 1024:
+            raise ValueError(f"SpatialTransformer3D: {L} tokens per sequence need the MFMA attention kernels (a multiple of 32, head size "
+                             f"a multiple of 8 up to 128); got head size {dh}")
+        y = self._new(Bo * L, 3 * inner, torch.bfloat16)
+        ops.gemm(a_bf, qkv['w'], None, ops.EPI_BF16, y)
+        o = self._new(Bo * L, inner, torch.bfloat16)
+        ops.attention_small(y, y[:, inner:], y[:, 2 * inner:], o, Bo, heads, L, L, dh, 3 * inner, 3 * inner, 3 * inner, dh ** -0.5)
+        return o
+
+    def _transformer(self, h, q, N, H, W, F):
+        HW, C = H * W, h.shape[1]
+        heads, dh = q['heads'], q['dh']
+        inner, rows = heads * dh, N * HW
+        a = self._gn(h, q['n'], N, HW, C, False)
+        tok = self._new(rows, inner)
+        ops.gemm(a, q['pin']['w'], q['pin']['b'], ops.EPI_F32, tok)
+        for b in q['blocks']:
+            def ln(nw):
+                y = self._new(rows, inner, torch.bfloat16)
+                ops.norm_modulate(tok, y, rows, inner, kind=0, eps=nw[2], shift=nw[1], scale=nw[0], mod_rows=rows, mod_ld=0)
+                return y
+            # attn1 over the F frames of each object jointly: rows are (object, frame, pixel), so `(b f) l c -> b (f l) c` is a view
+            o = self._self_attend(ln(b['n1']), b['qkv1'], N // F, F * HW, heads, dh, 'j%d_' % F)
+            ops.gemm(o, b['o1']['w'], b['o1']['b'], ops.EPI_GATE_RES, tok)
+            o = self._self_attend(ln(b['n2']), b['qkv2'], N, HW, heads, dh, 'f_')                 # attn2: within each frame
+            ops.gemm(o, b['o2']['w'], b['o2']['b'], ops.EPI_GATE_RES, tok)
+            g = self._new(rows, b['ff1']['cout'])
+            ops.gemm(ln(b['n3']), b['ff1']['w'], b['ff1']['b'], ops.EPI_F32, g)
+            gg = self._new(rows, b['ff1']['cout'] // 2, torch.bfloat16)
+            ops.geglu(g, gg, rows, b['ff1']['cout'] // 2)
+            ops.gemm(gg, b['ff2']['w'], b['ff2']['b'], ops.EPI_GATE_RES, tok)
+        ops.gemm(self._bf(tok), q['pout']['w'], q['pout']['b'], ops.EPI_GATE_RES, h)
+        return h
+
+    # ------------------------------------------------------------------ forward
+    def _check_input(self, x, F):
+        if x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise ValueError(f"encoder input {tuple(x.shape)}: expected [B*F, {self.in_channels}, H, W]")
+        if x.shape[0] % F:
+            raise ValueError(f"encoder input batch {x.shape[0]} is not a multiple of num_frames={F} (consecutive frames form one object)")
+        if x.shape[2] % 8 or x.shape[3] % 8:
+            raise ValueError(f"encoder input {x.shape[2]}x{x.shape[3]}: the three Downsamples need sides divisible by 8")
+        if not x.is_cuda:
+            raise RuntimeError("ln3diff_amd encoder runs on the HIP device only (no CPU fallback)")
+
+    @torch.no_grad()
+    def forward_frames(self, x, stages=None):
+        """x [B*F, in_channels, S, S] -> conv_out per frame as [B*F, 2*z_channels, S/8, S/8] (an NCHW view of channel-last memory).
+        stages: optional dict that receives NCHW copies of every stage (level outputs, middle before / after the attention)."""
+        F = self.num_frames
+        self._check_input(x, F)
+        dev = x.device
+        self._ensure_packed(dev)
+        P = self._packed
+        N, Cin, H, W = x.shape
+        pc = P['conv_in']
+        x_cl = self._new(N * H * W, pc['cin'], torch.bfloat16)
+        ops.nchw_to_cl_bf16(x.contiguous().float(), x_cl, N, Cin, H * W, pc['cin'])
+        h = self._new(N * H * W, pc['cout'])
+        self._conv3(x_cl, N, H, W, pc, h)
+
+        def keep(name, t, H, W):
+            if stages is not None:
+                stages[name] = t.view(N, H, W, -1).permute(0, 3, 1, 2).contiguous()
+        keep('conv_in', h, H, W)
+        for lvl, d in enumerate(P['down']):
+            for q in d['blocks']:
+                h = self._res(h, q, N, H, W)
+            keep(f'down{lvl}', h, H, W)
+            if d['down'] is not None:
+                h, H, W = self._down(h, d['down'], N, H, W)
+                keep(f'down{lvl}_ds', h, H, W)
+        h = self._res(h, P['mid1'], N, H, W)
+        keep('mid_block_1', h, H, W)
+        h = self._transformer(h, P['attn'], N, H, W, F)
+        keep('mid_attn_1', h, H, W)
+        h = self._res(h, P['mid2'], N, H, W)
+        keep('mid_block_2', h, H, W)
+        a = self._gn(h, P['norm_out'], N, H * W, h.shape[1], True)
+        out = self._new(N * H * W, P['conv_out']['cout'])
+        self._conv3(a, N, H, W, P['conv_out'], out)
+        return out.view(N, H, W, -1).permute(0, 3, 1, 2)
+
+    @torch.no_grad()
+    def forward(self, x, **kwargs):
+        return self.forward_frames(x).contiguous()
+
+
+class MVEncoderGSDynamicInp(Encoder):
+    """model.py:603-623: the Encoder over F = num_frames views per object, then the mean over each object's frames ->
+    [B, 2*z_channels, S/8, S/8].  The middle attention always groups self.num_frames frames; the `num_frames` argument of forward
+    only changes the pooling (as in the reference)."""
+
+    def __init__(self, *, ch, out_ch, ch_mult=(1, 2, 4, 8), num_res_blocks, attn_resolutions, dropout=0, resamp_with_conv=True, in_channels,
+                 resolution, z_channels, double_z=True, use_linear_attn=False, attn_type="mv-vanilla", num_frames, **ignore_kwargs):
+        if num_frames <= 4:
+            raise ValueError(f"MVEncoderGSDynamicInp: num_frames={num_frames}; the reference asserts num_frames > 4 (model.py:618)")
+        super().__init__(ch=ch, out_ch=out_ch, ch_mult=ch_mult, num_res_blocks=num_res_blocks, attn_resolutions=attn_resolutions,
+                         dropout=dropout, resamp_with_conv=resamp_with_conv, in_channels=in_channels, resolution=resolution,
+                         z_channels=z_channels, double_z=double_z, use_linear_attn=use_linear_attn, attn_type=attn_type,
+                         add_fusion_layer=False, num_frames=num_frames, **ignore_kwargs)
+
+    @torch.no_grad()
+    def forward(self, x, num_frames=None):
+        F = self.num_frames if num_frames is None else num_frames
+        if F <= 4:
+            raise ValueError(f"MVEncoderGSDynamicInp: num_frames={F}; the reference asserts num_frames > 4")
+        if x.shape[0] % F:
+            raise ValueError(f"encoder input batch {x.shape[0]} is not a multiple of num_frames={F}")
+        h = self.forward_frames(x)
+        N, C, H, W = h.shape
+        out = torch.empty(N // F, C, H, W, device=h.device, dtype=torch.float32)
+        ops.frame_mean(h, out, N // F, F, H * W, C)
+        return out
+
+
+def create_encoder(dino_version=RELEASED_DINO_VERSION, encoder_in_channels=10, sd_E_ch=64, sd_E_num_res_blocks=1, z_channels=12,
+                   num_frames=6, resolution=256, **_):
+    """The encoder branch of nsr/script_util.py create_model (:1294-1340) for the released VAE (vae_xl_reconstruction.sh)."""
+    if dino_version != RELEASED_DINO_VERSION:
+        raise NotImplementedError(f"dino_version {dino_version!r}: only the released multi-view encoder ({RELEASED_DINO_VERSION!r}) is built; "
+                                  f"the 4-view MVEncoder with its fusion layer (DiT2-B/2 VAE) and the other encoders are not")
+    return MVEncoderGSDynamicInp(double_z=True, resolution=resolution, in_channels=encoder_in_channels, ch=sd_E_ch, ch_mult=[1, 2, 4, 4],
+                                 num_res_blocks=sd_E_num_res_blocks, num_frames=num_frames, dropout=0.0, attn_resolutions=[], out_ch=3,
+                                 z_channels=z_channels, attn_kwargs={'n_heads': 8, 'd_head': 64})

@@ -20,6 +20,18 @@ from ..dit.dit_models_xformers import Workspace, bf16, f32
 from ..nsr.triplane import Triplane
 
 
+class DiagonalGaussianDistribution:
+    """The posterior object of the reference (utils/torch_utils/distributions/distributions.py:44-88, soft_clamp=True) as far as the
+    encoder path produces it: mean / logvar [B, C, 3, H*W] (logvar already soft-clamped by ln3d_mv_posterior); mode() is the mean.
+    Sampling, log_p and the entropy are computed inside the fused kernel (vae_reparameterization)."""
+
+    def __init__(self, mean, logvar):
+        self.mean, self.logvar = mean, logvar
+
+    def mode(self):
+        return self.mean
+
+
 def _conv(cin, cout, k):
     return nn.Conv2d(cin, cout, k, padding=k // 2)
 
@@ -251,6 +263,55 @@ class RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout
             ops.planes_to_nchw(planes_cl, nchw, B, 32, H, W)
             ret_dict['latent_after_vit'] = nchw
         return ret_dict
+
+    # ------------------------------------------------------------------ posterior (encoder side: vit_triplane.py:912-933, :1152-1199)
+    def _quant_packed(self, dev):
+        q = self.__dict__.get('_quant')
+        if not _cache.fresh(q, dev):
+            qc = self.superresolution['quant_conv']
+            q = _cache.stamp({'device': dev, 'w': f32(qc.weight.reshape(qc.weight.shape[0], -1), dev), 'b': f32(qc.bias, dev)}, self)
+            self.__dict__['_quant'] = q
+        return q
+
+    def _posterior(self, h, eps, num_frames):
+        if not h.is_cuda:
+            raise RuntimeError("ln3diff_amd posterior runs on the HIP device only (no CPU fallback)")
+        if h.shape[0] % num_frames:
+            raise ValueError(f"posterior input batch {h.shape[0]} is not a multiple of num_frames={num_frames}")
+        q = self._quant_packed(h.device)
+        B = h.shape[0] // num_frames
+        if eps is not None:
+            eps = eps.to(h.device, torch.float32).reshape(B, self.ldm_embed_dim, 3, -1).contiguous()
+        return ops.mv_posterior(h, q['w'], q['b'], eps, B, num_frames, self.ldm_embed_dim)
+
+    @torch.no_grad()
+    def vae_encode(self, h, num_frames=1):
+        """h: encoder output [B, 2*3*ldm_z_channels, H, W] -> DiagonalGaussianDistribution(soft_clamp=True) over [B, C, 3, H*W].
+        num_frames > 1: h is the per-frame output [B*F, ...] (Encoder.forward_frames) and the frame mean is taken first."""
+        r = self._posterior(h, None, num_frames)
+        return DiagonalGaussianDistribution(r['mean'], r['logvar'])
+
+    @torch.no_grad()
+    def vae_reparameterization(self, latent, sample_posterior, eps=None, num_frames=1):
+        """latent: encoder output [B, 24, 32, 32] (any strides with a uniform pixel stride; num_frames > 1: the per-frame output of
+        Encoder.forward_frames, pooled inside the same kernel).  sample_posterior: mean + std * eps with eps drawn like the reference,
+        torch.randn(mean.shape) on the CPU generator, then moved to the device (or the caller's `eps` [B, C, 3, H*W]); False: the mode."""
+        B = latent.shape[0] // num_frames
+        HW = latent.shape[2] * latent.shape[3]
+        if sample_posterior and eps is None:
+            eps = torch.randn(B, self.ldm_embed_dim, 3, HW)
+        r = self._posterior(latent, eps if sample_posterior else None, num_frames)
+        H, W = latent.shape[2], latent.shape[3]           # token_size * vae_p for the released 256 x 256 input
+        return dict(normal_entropy=r['entropy'], latent_normalized=r['latent_tok'],
+                    latent_normalized_2Ddiffusion=r['z'].view(B, -1, H, W), log_q_2Ddiffusion=r['log_q'].view(B, -1, H, W),
+                    log_q=r['log_q'], posterior=DiagonalGaussianDistribution(r['mean'], r['logvar']))
+
+    @torch.no_grad()
+    def vit_decode(self, latent, img_size, sample_posterior=True, eps=None, num_frames=1, **kwargs):
+        """vit_triplane.py:879-885: reparameterise (sampling by default), backbone, postprocess."""
+        ret_dict = self.vae_reparameterization(latent, sample_posterior, eps=eps, num_frames=num_frames)
+        tok = self.vit_decode_backbone(ret_dict, img_size)
+        return self.vit_decode_postprocess(tok, ret_dict)
 
     @torch.no_grad()
     def triplane_decode(self, vit_decode_out, c, return_raw_only=False, **kwargs):
