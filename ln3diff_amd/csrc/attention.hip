@@ -38,12 +38,6 @@ struct AttnP {
 // sequences where latency hiding matters; 2 (256 VGPRs, no spills in the masked tail block) for short ones (cross-attention).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// bench-only ablations (tools/attn_abl.hip builds this file with -DLN3D_ATTN_ABL=n): 1 = no v_exp, 2 = no MFMA, 4 = no barrier/DMA wait
-#ifndef LN3D_ATTN_ABL
-#define LN3D_ATTN_ABL 0
-#endif
-
-
 // DT = true head size when the heads are stored zero-padded to DH (DiT-XL/2: 72 in 128-wide rows, r4): the S^T products run over
 // ceil(DT / 16) k-steps and the PV products over ceil(DT / 32) blocks of output rows instead of DH / 16 and DH / 32 (5 + 3 of
 // 8 + 4 for 72: the padding contributes exact zeros), and O is written COMPACT, DT dims per head (row stride ldo = H * DT), so the
@@ -51,13 +45,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // its counted waits stay those of the DH-wide layout).
 template <int DH, int OCC, int DT = DH>
 __global__ __launch_bounds__(512, OCC) void attn_kernel(AttnP p) {
-#ifndef LN3D_ATTN_NST128
-#define LN3D_ATTN_NST128 3       // bench-only: ring depth of the 128-wide instantiations (4 x 32 KB still fits the CU: one workgroup either way)
-#endif
-#ifndef LN3D_ATTN_PRIO
-#define LN3D_ATTN_PRIO 0         // bench-only: static priority for waves 4-7 (what attn_kres_kernel does) so that the two waves of a SIMD drift apart
-#endif
-  constexpr int NST = DH == 64 ? 4 : (DH == 80 ? 3 : LN3D_ATTN_NST128);           // ring depth
+  constexpr int NST = DH == 64 ? 4 : 3;           // ring depth (128 wide: 4 x 32 KB would still fit the CU, one workgroup either way)
   // DH = 80 (r6: DiT-XL/2's 72-wide and the U-Net's 80-wide heads, stored 80 wide instead of 128): the K rows (160 B) sit in LDS at a
   // 176-byte pitch - 11 chunks, an odd count, so that the 8 rows a b128 read phase touches fall into 8 different bank groups without a
   // swizzle (XOR needs a power-of-two row) - and the V^T tile keeps room for 96 rows (3 MFMA row blocks; rows 80 - 95 are never loaded and
@@ -79,7 +67,6 @@ __global__ __launch_bounds__(512, OCC) void attn_kernel(AttnP p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
-  if constexpr (LN3D_ATTN_PRIO != 0) { if (wid >= 4) __builtin_amdgcn_s_setprio(LN3D_ATTN_PRIO); }
   // block -> (head, query block): the query blocks of a head run on ONE XCD (block b runs on XCD b % 8), next to each other in
   // dispatch order, so that the head's K / V^T stream is fetched into that XCD's L2 once (r4; a (query block, head) grid spread
   // them over three XCDs)
@@ -165,7 +152,6 @@ __global__ __launch_bounds__(512, OCC) void attn_kernel(AttnP p) {
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
         const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sb + k_off + kt * 32 * KROWB + (((2 * ds + hi) ^ kkey_r) << 4));
-        if constexpr (LN3D_ATTN_ABL & 2) { st[kt][ds] += (float)kf[0] * (float)qf[ds][0]; } else
         st[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ds], st[kt], 0, 0, 0);
       }
     }
@@ -205,7 +191,7 @@ __global__ __launch_bounds__(512, OCC) void attn_kernel(AttnP p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float a = fmaf(st[kt][r], p.scale_log2, -m_run);
-        const float pv = (LN3D_ATTN_ABL & 1) ? a : __builtin_amdgcn_exp2f(a);
+        const float pv = __builtin_amdgcn_exp2f(a);
         st[kt][r] = pv;
         psum += pv;
       }
@@ -224,7 +210,6 @@ __global__ __launch_bounds__(512, OCC) void attn_kernel(AttnP p) {
 #pragma unroll
       for (int dt = 0; dt < NDT; ++dt) {
         const bf16x8 vf = *reinterpret_cast<const bf16x8*>(sb + v_off + dt * 32 * 128 + (((2 * s + hi) ^ vkey_r) << 4));
-        if constexpr (LN3D_ATTN_ABL & 2) { oacc[dt][s] += (float)vf[0] * (float)pb[s][0]; } else
         oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pb[s], oacc[dt], 0, 0, 0);
       }
     }
@@ -248,7 +233,7 @@ __global__ __launch_bounds__(512, OCC) void attn_kernel(AttnP p) {
     if ((kbv) + NST - 1 < nkb) A_ISSUE((kbv) + NST - 1); /* ring slot of block kb-1: every wave is past it */   \
   }
   for (int kb = 0; kb + 1 < nkb; ++kb) {
-    if constexpr (!(LN3D_ATTN_ABL & 4)) { A_WAIT(kb); }
+    A_WAIT(kb);
     process(kb, std::false_type{});
   }
   A_WAIT(nkb - 1);
@@ -437,10 +422,7 @@ __global__ __launch_bounds__(512, 2) void attn_stream_kernel(AttnP p) {
   // S^T of a 32-key tile from its K fragments, C operand = cinit (0 for the first tile of a query block)
   auto qk_tile = [&](f32x16& st, const bf16x8 (&kf)[NDS], const f32x16& cinit) __attribute__((always_inline)) {
 #pragma unroll
-    for (int ds = 0; ds < NDS; ++ds) {
-      if constexpr (LN3D_ATTN_ABL & 2) { if (ds == 0) st = cinit; asm volatile("" :: "v"(kf[ds])); } else
-      st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ds], qf[ds], ds == 0 ? cinit : st, 0, 0, 0);
-    }
+    for (int ds = 0; ds < NDS; ++ds) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ds], qf[ds], ds == 0 ? cinit : st, 0, 0, 0);
   };
   auto tile_max = [&](const f32x16& st) __attribute__((always_inline)) {
     float mx = max3f(st[0], st[1], st[2]);
@@ -492,7 +474,7 @@ __global__ __launch_bounds__(512, 2) void attn_stream_kernel(AttnP p) {
   // middle of the half-step and the PV MFMAs can no longer be issued under the exps.)
   auto half_step = [&](f32x16& cur, f32x16& nxt, auto mode_tag, const bf16x8 (&kf)[NDS], auto&& loads) __attribute__((always_inline)) {
     constexpr int MODE = decltype(mode_tag)::value;
-    if constexpr (!(LN3D_ATTN_ABL & 32)) loads();
+    loads();
     if constexpr (MODE == 0) qk_tile(nxt, kf, negm);
     if constexpr (MODE == 2) { f32x16 z; _Pragma("unroll") for (int r = 0; r < 16; ++r) z[r] = 0.f; qk_tile(nxt, kf, z); }
     float ps0 = 0.f, ps1 = 0.f, ps2 = 0.f, ps3 = 0.f;
@@ -502,8 +484,8 @@ __global__ __launch_bounds__(512, 2) void attn_stream_kernel(AttnP p) {
       union { uint32_t u[4]; bf16x8 v; } cv;
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {
-        const float e0 = (LN3D_ATTN_ABL & 1) ? cur[8 * s + 2 * jj] : __builtin_amdgcn_exp2f(cur[8 * s + 2 * jj]);
-        const float e1 = (LN3D_ATTN_ABL & 1) ? cur[8 * s + 2 * jj + 1] : __builtin_amdgcn_exp2f(cur[8 * s + 2 * jj + 1]);
+        const float e0 = __builtin_amdgcn_exp2f(cur[8 * s + 2 * jj]);
+        const float e1 = __builtin_amdgcn_exp2f(cur[8 * s + 2 * jj + 1]);
         if (jj & 1) { ps2 += e0; ps3 += e1; } else { ps0 += e0; ps1 += e1; }
         cv.u[jj] = pack2bf(e0, e1);
       }
@@ -513,11 +495,8 @@ __global__ __launch_bounds__(512, 2) void attn_stream_kernel(AttnP p) {
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) {
-        if constexpr (LN3D_ATTN_ABL & 2) { asm volatile("" :: "v"(vf[s * NDT + dt]), "v"(pb[s])); } else
-        oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[s * NDT + dt], pb[s], oacc[dt], 0, 0, 0);
-      }
-    if constexpr (MODE == 0 && !(LN3D_ATTN_ABL & 8)) {
+      for (int dt = 0; dt < NDT; ++dt) oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[s * NDT + dt], pb[s], oacc[dt], 0, 0, 0);
+    if constexpr (MODE == 0) {
       // deferred re-base (wave-uniform, rare after the first tiles): scores of the next tile outgrow the reference by > 2^8
       const float mx = tile_max(nxt);
       if (!__all(mx <= 8.0f)) {
@@ -570,19 +549,16 @@ __global__ __launch_bounds__(512, 2) void attn_stream_kernel(AttnP p) {
   // refilled with stage g+7.  A step = two half-steps with STATIC accumulator names: (stA -> stB) on tile 0, (stB -> stA) on
   // tile 1.  The loop is unrolled over the 4 slots of a ring half (slot offsets are immediates); nkb is a multiple of 4, so a
   // query block ends at the end of a half and the two address sets swap there.
-  if constexpr (LN3D_ATTN_ABL & 64) { store_o(qb0); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); return; }   // bench: prologue + one store only
   // The wait is always "at most 10 requests outstanding": they are younger than stage g+1 whether or not the 4 requests of a
   // query DMA (issued at the first step of a query block) are among them, and the queries are older than anything a boundary
   // 6 or more steps later allows to be outstanding; only a 4-step query block (256 keys) has to ask for them by count.
   auto top_of_step = [&](auto slot_tag, bool first, bool boundary, bool more, int qb) __attribute__((always_inline)) {
     constexpr int SL = decltype(slot_tag)::value;
-    if constexpr (!(LN3D_ATTN_ABL & 4)) {
-      if (boundary && nkb < 8) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
+    if (boundary && nkb < 8) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
     if (first && more) dma_q(qb + 1);
-    if constexpr (!(LN3D_ATTN_ABL & 16)) issue_stage(std::integral_constant<int, SL + 7>{});
+    issue_stage(std::integral_constant<int, SL + 7>{});
   };
   auto swap_halves = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -647,17 +623,6 @@ __global__ __launch_bounds__(512, 2) void attn_stream_kernel(AttnP p) {
 // Per 32-key tile and wave: 10 MFMAs (4 S^T, 4 PV, 2 row-sum) against 16 v_exp + 8 v_cvt_pk + 8 ds_read_b128.
 // Counted waits: vmcnt counts LDS-DMA loads and global stores in issue order (gfx9 has one counter for both); every wait below
 // is "at most W younger requests outstanding", W derived in top_of_step from what was issued behind the request it needs.
-#ifndef LN3D_KRES_ORDER   // 0: S^T chain spread between the PV MFMAs, 1: S^T chain back to back, 2: PV of keys 0-15 first (r3: 54.8 / 50.3 / 51.3 us)
-#define LN3D_KRES_ORDER 1
-#endif
-#ifndef LN3D_KRES_PIN     // 1: pin the order of the pieces with sched_barrier; 0: hipcc's own interleave of the same pieces (r3: 50.3 vs 49.0 us)
-#define LN3D_KRES_PIN 0
-#endif
-#ifndef LN3D_KRES_ABL   // tools/attn_bench.hip builds with -DLN3D_KRES_ABL=bits (wrong results by construction): 1 no v_exp, 2 no MFMA,
-#define LN3D_KRES_ABL 0  // 4 no barrier / DMA wait, 8 no fragment reads, 16 no DMA issue in the stream, 32 hipcc's own instruction order
-#endif
-__device__ __forceinline__ f32x16 abl_nomfma(const bf16x8& a, const bf16x8& b, const f32x16& c) { asm volatile("" :: "v"(a), "v"(b)); return c; }
-template <bool PRIO, bool ST_INORDER>
 __global__ __launch_bounds__(512, 2) void attn_kres_kernel(AttnP p) {
   constexpr int DH = 64, NDS = 4, NDT = 2, QB = 256;
   constexpr int KREG = 768 * 128;                         // resident K rows (128 B each)
@@ -668,7 +633,7 @@ __global__ __launch_bounds__(512, 2) void attn_kres_kernel(AttnP p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
-  if constexpr (PRIO) { if (wid >= 4) __builtin_amdgcn_s_setprio(1); }   // the later-dispatched half loses every arbitration otherwise
+  if (wid >= 4) __builtin_amdgcn_s_setprio(1);           // the later-dispatched half loses every arbitration otherwise
 
   const int nqb = (p.Nq + QB - 1) / QB;
   const int BH = p.B * p.H;
@@ -830,101 +795,37 @@ __global__ __launch_bounds__(512, 2) void attn_kres_kernel(AttnP p) {
   // MODE 0: next tile with C = -m ; 2: next tile opens the NEXT query block (C = 0, qf holds its queries) ; 3: none.
   auto half_step = [&](f32x16& cur, f32x16& nxt, auto mode_tag, auto&& loads) __attribute__((always_inline)) {
     constexpr int MODE = decltype(mode_tag)::value;
-    // The instruction order is pinned (sched_barrier between the pieces): an in-order wave issues ~7 VALU under one 32-cycle
-    // MFMA, and the four S^T MFMAs are one dependent chain, so they alternate with the independent PV / row-sum MFMAs and the
-    // exps sit where an MFMA is in flight.  hipcc's own order put the first S^T MFMA (and a wait for all 8 reads) first.
-#define SB_ do { if constexpr (LN3D_KRES_PIN && !(LN3D_KRES_ABL & 32)) __builtin_amdgcn_sched_barrier(0); } while (0)
-#define EXP_(x_) ((LN3D_KRES_ABL & 1) ? (x_) : __builtin_amdgcn_exp2f(x_))
-#define MFMA_(a_, b_, c_) ((LN3D_KRES_ABL & 2) ? abl_nomfma(a_, b_, c_) : __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_, b_, c_, 0, 0, 0))
+    // Piece order: the S^T chain of the next tile back to back (accumulator forwarding), every exp block under MFMAs already
+    // issued (r3: 50.3 us, against 54.8 with the chain spread between the PV MFMAs and 51.3 with the PV of keys 0-15 first).
+    // hipcc interleaves the pieces itself: pinning this order with sched_barrier measured 50.3 vs 49.0 us (r3).
     f32x16 zc;
     if constexpr (MODE == 2) { _Pragma("unroll") for (int r = 0; r < 16; ++r) zc[r] = 0.f; }
-    if constexpr (!(LN3D_KRES_ABL & 8)) loads();         // K rows of the next tile (4 reads), then V^T columns of this one (4)
-    SB_;
+    loads();                                             // K rows of the next tile (4 reads), then V^T columns of this one (4)
     bf16x8 pb[2];
     auto probs = [&](auto s_tag) __attribute__((always_inline)) {     // 8 exps + 4 packs: P of 16 keys as the PV B operand
       constexpr int S = decltype(s_tag)::value;
       union { uint32_t u[4]; bf16x8 v; } cv;
 #pragma unroll
-      for (int jj = 0; jj < 4; ++jj) cv.u[jj] = pack2bf(EXP_(cur[8 * S + 2 * jj]), EXP_(cur[8 * S + 2 * jj + 1]));
+      for (int jj = 0; jj < 4; ++jj) cv.u[jj] = pack2bf(__builtin_amdgcn_exp2f(cur[8 * S + 2 * jj]), __builtin_amdgcn_exp2f(cur[8 * S + 2 * jj + 1]));
       pb[S] = cv.v;
     };
     auto pv = [&](auto s_tag) __attribute__((always_inline)) {        // 2 PV MFMAs + 1 row-sum MFMA of 16 keys
       constexpr int S = decltype(s_tag)::value;
-      oacc[0] = MFMA_(vf[2 * S], pb[S], oacc[0]);
-      oacc[1] = MFMA_(vf[2 * S + 1], pb[S], oacc[1]);
-      lacc = MFMA_(ones, pb[S], lacc);
+      oacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[2 * S], pb[S], oacc[0], 0, 0, 0);
+      oacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[2 * S + 1], pb[S], oacc[1], 0, 0, 0);
+      lacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, pb[S], lacc, 0, 0, 0);
     };
     using S0 = std::integral_constant<int, 0>; using S1 = std::integral_constant<int, 1>;
-    if constexpr (LN3D_KRES_ORDER == 0) {
-      // S^T chain spread between the independent MFMAs
-      float e[8];
-      probs(S0{});
-      SB_;
-      if constexpr (MODE != 3) nxt = MFMA_(kf[0], qf[0], MODE == 2 ? zc : negm);
-      SB_;
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) e[jj] = EXP_(cur[8 + jj]);
-      SB_;
-      if constexpr (MODE != 3) nxt = MFMA_(kf[1], qf[1], nxt);
-      SB_;
-      {
-#pragma unroll
-        for (int jj = 4; jj < 8; ++jj) e[jj] = EXP_(cur[8 + jj]);
-        union { uint32_t u[4]; bf16x8 v; } cv;
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) cv.u[jj] = pack2bf(e[2 * jj], e[2 * jj + 1]);
-        pb[1] = cv.v;
-      }
-      SB_;
-      oacc[0] = MFMA_(vf[0], pb[0], oacc[0]);
-      SB_;
-      if constexpr (MODE != 3) nxt = MFMA_(kf[2], qf[2], nxt);
-      SB_;
-      oacc[1] = MFMA_(vf[1], pb[0], oacc[1]);
-      SB_;
-      lacc = MFMA_(ones, pb[0], lacc);
-      SB_;
-      if constexpr (MODE != 3) nxt = MFMA_(kf[3], qf[3], nxt);
-      SB_;
-      pv(S1{});
-      SB_;
-    } else if constexpr (LN3D_KRES_ORDER == 1) {
-      // S^T chain back to back (accumulator forwarding), every exp block under MFMAs already issued
-      probs(S0{});
-      SB_;
-      if constexpr (MODE != 3) {
-        nxt = MFMA_(kf[0], qf[0], MODE == 2 ? zc : negm);
-        nxt = MFMA_(kf[1], qf[1], nxt);
-        nxt = MFMA_(kf[2], qf[2], nxt);
-        nxt = MFMA_(kf[3], qf[3], nxt);
-      }
-      SB_;
-      probs(S1{});
-      SB_;
-      pv(S0{});
-      pv(S1{});
-      SB_;
-    } else {
-      // PV of the first 16 keys first (needs only V^T), the S^T chain back to back behind it
-      probs(S0{});
-      SB_;
-      pv(S0{});
-      SB_;
-      probs(S1{});
-      SB_;
-      if constexpr (MODE != 3) {
-        nxt = MFMA_(kf[0], qf[0], MODE == 2 ? zc : negm);
-        nxt = MFMA_(kf[1], qf[1], nxt);
-        nxt = MFMA_(kf[2], qf[2], nxt);
-        nxt = MFMA_(kf[3], qf[3], nxt);
-      }
-      SB_;
-      pv(S1{});
-      SB_;
+    probs(S0{});
+    if constexpr (MODE != 3) {
+      nxt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[0], qf[0], MODE == 2 ? zc : negm, 0, 0, 0);
+      nxt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[1], qf[1], nxt, 0, 0, 0);
+      nxt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[2], qf[2], nxt, 0, 0, 0);
+      nxt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[3], qf[3], nxt, 0, 0, 0);
     }
-#undef SB_
-#undef EXP_
-#undef MFMA_
+    probs(S1{});
+    pv(S0{});
+    pv(S1{});
   };
 
   using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
@@ -951,7 +852,8 @@ __global__ __launch_bounds__(512, 2) void attn_kres_kernel(AttnP p) {
   //   later query blocks: V(g+1), V(g+2)                                   -> 2
   //   first query block : K(g+3), V(g+1), K(g+4), V(g+2) while they exist  -> 4 ; 3 / 2 in its last group (K blocks run out)
   //   + 4 while the next block's query DMA (issued at step 0) is younger   : steps 1..3 of a block's first group
-  //   + 4 while the previous block's O stores (end of its last step) are younger : steps 0..2 of a later block's first group
+  // The previous block's O stores (end of its last step) are younger than stage g in steps 0..2 of a later block's first group but
+  // are left out of W (r3 A/B): the wait then only lasts longer than it has to.
   auto wait_w = [&](int w) __attribute__((always_inline)) {
     switch (w) {
       case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
@@ -963,16 +865,14 @@ __global__ __launch_bounds__(512, 2) void attn_kres_kernel(AttnP p) {
       default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
     }
   };
-  auto top_of_step = [&](auto slot_tag, bool first, bool lastgrp, bool p1, bool more, bool stq, int qb) __attribute__((always_inline)) {
+  auto top_of_step = [&](auto slot_tag, bool first, bool lastgrp, bool p1, bool more, int qb) __attribute__((always_inline)) {
     constexpr int SL = decltype(slot_tag)::value;
     int w = p1 ? (lastgrp ? (SL == 0 ? 3 : 2) : 4) : 2;
     if (first && more && SL >= 1) w += 4;
-    if (ST_INORDER && first && stq && SL <= 2) w += 4;
-    if constexpr (!(LN3D_KRES_ABL & 4)) { wait_w(w); __builtin_amdgcn_s_barrier(); }
-    if constexpr (!(LN3D_KRES_ABL & 16)) {
-      if (p1 && kb_k < nkb) issue_k();
-      issue_v(std::integral_constant<int, SL + 3>{});
-    }
+    wait_w(w);
+    __builtin_amdgcn_s_barrier();
+    if (p1 && kb_k < nkb) issue_k();
+    issue_v(std::integral_constant<int, SL + 3>{});
     if (SL == 0 && first && more) dma_q(qb + 1);
   };
   auto advance_k = [&](bool wrap) __attribute__((always_inline)) {      // inside step 3 of a group: K block g+1 opens the next group
@@ -985,20 +885,20 @@ __global__ __launch_bounds__(512, 2) void attn_kres_kernel(AttnP p) {
 #define HS_B(SL_, MODE_) half_step(stB, stA, MODE_{}, [&]() __attribute__((always_inline)) {                                             \
     if constexpr (MODE_::value != 3) load_kf(std::integral_constant<int, (SL_ == 3 ? 0 : (SL_ + 1) * 8192)>{});                          \
     load_vf(std::integral_constant<int, SL_>{}, I1{}); })
-#define STEP(SL_, LASTG_) { top_of_step(std::integral_constant<int, SL_>{}, first, LASTG_, p1, more, stq, qb); HS_A(SL_, I0); HS_B(SL_, I0); }
+#define STEP(SL_, LASTG_) { top_of_step(std::integral_constant<int, SL_>{}, first, LASTG_, p1, more, qb); HS_A(SL_, I0); HS_B(SL_, I0); }
   for (int qb = qb0; qb < qb1; ++qb) {
-    const bool more = qb + 1 < qb1, p1 = qb == qb0, stq = qb != qb0;
+    const bool more = qb + 1 < qb1, p1 = qb == qb0;
     bool first = true;
     for (int grp = 1; grp < ngrp; ++grp) {
       STEP(0, false); STEP(1, false); STEP(2, false);
-      top_of_step(I3{}, first, false, p1, more, stq, qb);
+      top_of_step(I3{}, first, false, p1, more, qb);
       HS_A(3, I0);
       advance_k(false);
       HS_B(3, I0);
       first = false;
     }
     STEP(0, true); STEP(1, true); STEP(2, true);
-    top_of_step(I3{}, first, true, p1, more, stq, qb);
+    top_of_step(I3{}, first, true, p1, more, qb);
     HS_A(3, I0);
     advance_k(true);
     if (more) {
@@ -1026,7 +926,6 @@ __global__ __launch_bounds__(512, 2) void attn_kres_kernel(AttnP p) {
 #pragma unroll
   for (int w = 0; w < 8; ++w) redo |= *reinterpret_cast<volatile uint32_t*>(smem + WST + w * 4096);
   redo = __builtin_amdgcn_readfirstlane(redo);
-  if constexpr (LN3D_KRES_ABL != 0) redo = 0;              // ablated builds produce garbage sums: time the fast path only
   while (redo) {
     const int blk = __builtin_ctz(redo);
     redo &= redo - 1;
@@ -1153,16 +1052,6 @@ __global__ __launch_bounds__(256, 3) void attn_short_kernel(AttnP p) {
   const int kkey_r = (l31 >> 1) & 7, k_off = l31 * KROWB;
   const int vkey_r = (l31 >> 1) & 7, v_off = KTILE + l31 * 128;
   const int b = bh / p.H, h = bh - b * p.H;
-  if constexpr (LN3D_ATTN_ABL & 8) {                   // bench-only: loads + stores, no compute
-#pragma unroll
-    for (int it = 0; it < QT; ++it)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int q = blockIdx.x * (128 * QT) + (QT * wid + it) * 32 + 8 * i + (lane >> 3);
-        if (q < p.Nq) *reinterpret_cast<uint4*>(p.O + ((int64_t)b * p.Nq + q) * p.ldo + h * DH + (lane & 7) * 8) = qraw[it][i];
-      }
-    return;
-  }
 #pragma unroll 1
   for (int it = 0; it < QT; ++it) {
     const int q0 = blockIdx.x * (128 * QT) + (QT * wid + it) * 32;
@@ -1272,10 +1161,8 @@ __global__ __launch_bounds__(256, 3) void attn_short_kernel(AttnP p) {
   }
 }
 
-// r5: the attention kernels have no environment switches left - one kernel per shape class (the r1 - r4 A/B switches LN3D_ATTN_V /
-// _KRES / _SHORT / _QT / _SPLIT and the instantiations they selected are gone; their measurements are in profiles/r2 - r4_attn*.md).
-extern "C" void ln3d_attn_reload_env(void) {}
-
+// The attention kernels have no switches - one kernel per shape class (the r1 - r4 A/B switches LN3D_ATTN_V / _KRES / _SHORT /
+// _QT / _SPLIT and the instantiations they selected are gone; their measurements are in profiles/r2 - r4_attn*.md).
 static int launch_attn_short(const AttnP& p, hipStream_t s) {
   // one query tile per wave (128 queries per workgroup): twice the workgroups, so load, compute and store phases of
   // different workgroups overlap on a CU (the kernel is a latency-bound stream of Q in / O out)
@@ -1285,7 +1172,7 @@ static int launch_attn_short(const AttnP& p, hipStream_t s) {
 
 template <int DH, int OCC, int DT = DH>
 static int launch_attn(const AttnP& p, hipStream_t s) {
-  constexpr int NST = DH == 64 ? 4 : (DH == 80 ? 3 : LN3D_ATTN_NST128);
+  constexpr int NST = DH == 64 ? 4 : 3;
   constexpr int LDS = DH == 80 ? NST * (KVB * 176 + 96 * 128) : NST * (KVB * DH * 2 + DH * 128);
   static AttrOnce attr_once;
   if (attr_once.need()) {
@@ -1313,19 +1200,15 @@ static int launch_attn_stream(AttnP p, hipStream_t s) {
   return ln3d_check_launch();
 }
 
-template <bool PRIO, bool ST_INORDER>
-static int launch_attn_kres_t(const AttnP& p, hipStream_t s) {
+static int launch_attn_kres(AttnP p, hipStream_t s) {
   constexpr int LDS = 768 * 128 + 4 * 8192 + 8 * 4096;   // all 160 KiB of the CU
   static AttrOnce attr_once;
   if (attr_once.need()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_kres_kernel<PRIO, ST_INORDER>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_kres_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
   }
-  hipLaunchKernelGGL((attn_kres_kernel<PRIO, ST_INORDER>), dim3(p.B * p.H * p.nsplit), dim3(512), LDS, s, p);
-  return ln3d_check_launch();
-}
-static int launch_attn_kres(AttnP p, hipStream_t s) {
   p.nsplit = 1;                                            // every workgroup walks all query blocks of its head: K is fetched once
-  return launch_attn_kres_t<true, false>(p, s);            // static priority for waves 4-7, O stores not counted in the vmcnt waits (r3 A/B)
+  hipLaunchKernelGGL(attn_kres_kernel, dim3(p.B * p.H * p.nsplit), dim3(512), LDS, s, p);
+  return ln3d_check_launch();
 }
 
 extern "C" int ln3d_attention_bf16(const ln3d_attn_args* a, void* stream) {

@@ -564,16 +564,6 @@ __device__ __forceinline__ void staged_epilogue(const GemmP& p, f32x16 (&acc)[NI
 }
 
 
-#ifndef LN3D_RING_D1
-#define LN3D_RING_D1 0       // DMA pieces of a stage issued right behind the barrier (0 = half of them); the rest in the next two substeps
-#endif
-#ifndef LN3D_RING_PRE
-#define LN3D_RING_PRE 1     // bench builds only: 0 = no residual prefetch under the last K stage (the r4 epilogue)
-#endif
-#ifndef LN3D_RING_ABL
-#define LN3D_RING_ABL 0     // bench builds only: 1 = skip the epilogue, 2 = two K stages only, 4 = no DMA in the steady state, 8 = per-stage s_memtime stamps into out2
-#endif
-
 // ------------------------------------------------------------------------------------------------------------------
 // LDS-DMA ring kernel for the large GEMMs: NW waves as (NW/WGT) x WGT, wave tile 32*NI features x 32*NJ tokens.
 //  * Operand tiles go HBM/L2 -> LDS with global_load_lds_dwordx4 (no VGPR staging); K stages of 64 so that an LDS row is a
@@ -623,7 +613,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && NI * NJ <= 6) ? 2 : NW / 4) vo
   // DMA instruction = 8 rows x 128 B -> 1 KB of the slot (W row groups first, then X row groups).  Every wave owns NPWW row
   // groups of the W tile and NPWX of the X tile, so the operand (and with it the wave-uniform base pointer) of instruction q is
   // known at compile time: the source is base (SGPR pair) + a 32-bit lane offset - one VGPR per instruction.
-  constexpr int ABL = LN3D_RING_ABL;
   constexpr int NPWW = BF / 8 / NW, NPWX = BT / 8 / NW;
   static_assert(BF / 8 % NW == 0 && BT / 8 % NW == 0 && NPWW + NPWX == NPW, "row groups of both operands divide evenly over the waves");
   const int r8 = lane >> 3;
@@ -663,7 +652,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && NI * NJ <= 6) ? 2 : NW / 4) vo
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   bf16x8 a0[NI], b0[NJ], a1[NI], b1[NJ];
-  const int ns = (ABL & 2) ? 2 : p.K / 64;
+  const int ns = p.K / 64;
 
   // CROSS_ATTN: the K rows of this tile's sample and 4 heads go into the LDS above the ring now (40 KB at 77 keys), long
   // before the epilogue needs them.  Row r of head hh at XK + hh*XKH + r*128, 16-byte chunk c at c ^ ((r >> 1) & 7).
@@ -693,10 +682,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && NI * NJ <= 6) ? 2 : NW / 4) vo
   for (int j = 0; j < NJ; ++j) b0[j] = Y_RDB(0, 0, j);
 
 #define Y_MMA(FA, FB, n) acc[(n) / NJ][(n) % NJ] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(FA[(n) / NJ], FB[(n) % NJ], acc[(n) / NJ][(n) % NJ], 0, 0, 0)
-  // D1 of a stage's NPW DMA instructions are issued in the last substep of stage s (right behind the barrier that retires
-  // their slot), the other NPW - D1 in the first two substeps of stage s+1 (LATE slots apart): the texture path accepts a
-  // 1 KB piece every ~16 cycles and a wave that finds its queue full stalls with its MFMAs behind it.
-  constexpr int D1 = LN3D_RING_D1 > 0 ? (LN3D_RING_D1 < NPW ? LN3D_RING_D1 : NPW) : (NPW + 1) / 2;
+  // D1 (half, rounded up) of a stage's NPW DMA instructions are issued in the last substep of stage s (right behind the
+  // barrier that retires their slot), the other NPW - D1 in the first two substeps of stage s+1 (LATE slots apart): the texture
+  // path accepts a 1 KB piece every ~16 cycles and a wave that finds its queue full stalls with its MFMAs behind it.
+  constexpr int D1 = (NPW + 1) / 2;
   constexpr int NLATE = NPW - D1;
   // substep: multiply (CA, CB) while (s2, ks2) is read into (NA, NB); LATE0 >= 0: late DMA pieces [LATE0, LATE1) of stage sd
 #define Y_PHASE(CA, CB, NA, NB, s2, ks2, LATE, sd, L0, L1)                                                \
@@ -713,22 +702,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && NI * NJ <= 6) ? 2 : NW / 4) vo
   // The stage's one barrier sits behind the FIRST MFMA of the last substep: every wave has read the last fragments of slot
   // s & 1 (lgkmcnt(0): they were issued at least two MFMAs earlier) and its own DMAs of stage s+1 have landed (vmcnt(0): the
   // only ones in flight); the fragment reads of stage s+1 and the first D1 DMAs of stage s+2 fill the remaining NM-1 slots.
-#define Y_SYNC(s)                                                                                         \
-  {                                                                                                       \
-    uint64_t tA_ = 0, tB_ = 0;                                                                            \
-    if constexpr ((ABL & 8) != 0) tA_ = __builtin_amdgcn_s_memtime();                                     \
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                      \
-    __builtin_amdgcn_s_waitcnt(0xC07F);                                                                   \
-    if constexpr ((ABL & 8) != 0) tB_ = __builtin_amdgcn_s_memtime();                                     \
-    __builtin_amdgcn_s_barrier();                                                                         \
-    if constexpr ((ABL & 8) != 0) {       /* bench builds: per-wave stamps (before the waits, before / behind the barrier) -> out2 */ \
-      const uint64_t tC_ = __builtin_amdgcn_s_memtime();                                                  \
-      if (lane == 0 && (s) < 64) {                                                                        \
-        uint32_t* tl_ = (uint32_t*)p.out2 + (((int64_t)blockIdx.x * NW + wid) * 64 + (s)) * 4;            \
-        tl_[0] = (uint32_t)tA_; tl_[1] = (uint32_t)tB_; tl_[2] = (uint32_t)tC_;                           \
-      }                                                                                                   \
-    }                                                                                                     \
-  }
   static_assert(NM - 1 >= NR, "one fragment read per MFMA slot behind the barrier");
   constexpr int LH = D1 + (NLATE + 1) / 2;             // late pieces [D1, LH) in the first substep, [LH, NPW) in the second
 #define Y_STAGE(s, PREV, FILL, MORE)                                                                      \
@@ -738,7 +711,11 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && NI * NJ <= 6) ? 2 : NW / 4) vo
     Y_PHASE(a0, b0, a1, b1, s, 3, false, 0, 0, 0);                                                        \
     _Pragma("unroll") for (int n = 0; n < NM; ++n) {                                                      \
       Y_MMA(a1, b1, n);                                                                                   \
-      if (MORE && n == 0) Y_SYNC(s);                                                                      \
+      if (MORE && n == 0) {                                                                               \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                  \
+        __builtin_amdgcn_s_waitcnt(0xC07F);                                                               \
+        __builtin_amdgcn_s_barrier();                                                                     \
+      }                                                                                                   \
       if (MORE) {                                                                                         \
         if (n >= 1 && n - 1 < NI) a0[n - 1] = Y_RDA((s) + 1, 0, n - 1);                                   \
         else if (n >= 1 && n - 1 < NR) b0[n - 1 - NI] = Y_RDB((s) + 1, 0, n - 1 - NI);                    \
@@ -754,9 +731,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && NI * NJ <= 6) ? 2 : NW / 4) vo
   // hipcc answer the loop head's fragment dependency with lgkmcnt(0) on EVERY iteration (mixed event types cannot be counted).
   __builtin_amdgcn_s_waitcnt(0xC07F);
   int s = 0;
-  if constexpr ((ABL & 4) != 0) {                        // bench builds: no DMA in the steady state
-    for (; s + 1 < ns; ++s) Y_STAGE(s, false, false, true);
-  } else if (ns >= 3) {
+  if (ns >= 3) {
     Y_STAGE(0, false, true, true);
     for (s = 1; s + 2 < ns; ++s) Y_STAGE(s, true, true, true);
     Y_STAGE(s, true, false, true);
@@ -767,7 +742,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && NI * NJ <= 6) ? 2 : NW / 4) vo
   }
   // GATE_RES, interior tile: block 0's residual quads (8 rows x 16 B per lane) and its bias / gate rows are requested here, one K stage
   // before the accumulators are final - the epilogue then starts on data that has arrived instead of on an L2 / fabric round trip
-  constexpr bool kPre = LN3D_RING_PRE && EPI == LN3D_EPI_GATE_RES && NW <= 8 && NI % 2 == 0 && NI * NJ <= 6 && !(ABL & 1);
+  constexpr bool kPre = EPI == LN3D_EPI_GATE_RES && NW <= 8 && NI % 2 == 0 && NI * NJ <= 6;
   float4 xpre[8];
   RunEpi<EPI> re_pre;
   bool have_pre = false;
@@ -785,7 +760,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && NI * NJ <= 6) ? 2 : NW / 4) vo
   }
   Y_STAGE(s, false, false, false);
 
-  if constexpr ((ABL & 1) != 0) { if (acc[0][0][0] != 12345.f) return; }
   if constexpr (EPI == LN3D_EPI_CROSS_ATTN) {
     // acc[i][j] = q^T of head (f0/64 + wf): features (rows) x the wave's 96 tokens (columns, lane & 31 within block j).
     // Same swapped products and lane-local softmax as csrc/attention.hip; q is consumed straight from the accumulators
@@ -1159,8 +1133,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_p4_kernel(GemmP p) {
     tile_of(has_next ? vbn : vb, ftn, ttn);
     const char* Wn = reinterpret_cast<const char*>(p.W) + (int64_t)ftn * BF * ldw2;
     const char* Xn = reinterpret_cast<const char*>(p.X) + (int64_t)ttn * BT * ldx2;
-    uint64_t tm0 = 0, tm1 = 0, tm2 = 0, tm3 = 0;
-    if constexpr ((LN3D_RING_ABL & 8) != 0) tm0 = __builtin_amdgcn_s_memtime();
     // first fragments of this tile (its stage 0 landed and was published by the previous tile's last rendezvous / the prologue): read
     // here rather than under the last stage, so that 32 VGPRs are not live across the epilogue (they spilled)
 #pragma unroll
@@ -1169,7 +1141,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_p4_kernel(GemmP p) {
     for (int j = 0; j < NJ; ++j) b0[j] = P_RDB(0, 0, j);
     // stages 0 .. 4 and ns - 3 .. ns - 1 are compile-time positions: each carries 3 of the previous tile's 24 parked stores
     P_STAGE(0, false, Wc, Xc, Wc + 2 * 128, Xc + 2 * 128, 0, true, true);                                          // s = 0: C = 0
-    if constexpr ((LN3D_RING_ABL & 8) != 0) tm1 = __builtin_amdgcn_s_memtime();
     P_STAGE(1, true, Wc + 2 * 128, Xc + 2 * 128, Wc + 3 * 128, Xc + 3 * 128, 1, false, true);
     P_STAGE(0, true, Wc + 3 * 128, Xc + 3 * 128, Wc + 4 * 128, Xc + 4 * 128, 2, false, true);
     P_STAGE(1, true, Wc + 4 * 128, Xc + 4 * 128, Wc + 5 * 128, Xc + 5 * 128, 3, false, true);
@@ -1184,7 +1155,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_p4_kernel(GemmP p) {
 #pragma unroll
     for (int d = D1; d < NPW; ++d) P_ISSUE(Wn + 128, Xn + 128, 1, d);                                        // rest of the next tile's stage 1
     if (p.bias && wid == 0) lds_dma16_s(p.bias + ftn * BF, boff, lds0 + BIASB + (par ^ 1) * 1024);
-    if constexpr ((LN3D_RING_ABL & 8) != 0) tm2 = __builtin_amdgcn_s_memtime();
 
     // ---- epilogue: accumulators -> parked bf16 tile (registers only).  Bias is always added from the LDS image (zeros when the
     // launch has none: a runtime test inside the unrolled block made hipcc round-trip all 256 accumulators through AGPR writes)
@@ -1222,14 +1192,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_p4_kernel(GemmP p) {
       }
       pbase = nbase;
       have = true;
-    }
-    if constexpr ((LN3D_RING_ABL & 8) != 0) {        // bench builds: per-wave stamps of every tile -> out2: [block][wave][tile k][4] = start, first stage done, loop done, epilogue done
-      tm3 = __builtin_amdgcn_s_memtime();
-      const int k = (vb - (int)blockIdx.x) / G;
-      if (lane == 0 && k < 16 && p.out2) {
-        uint32_t* tl = (uint32_t*)p.out2 + (((int64_t)blockIdx.x * 4 + wid) * 16 + k) * 4;
-        tl[0] = (uint32_t)tm0; tl[1] = (uint32_t)tm1; tl[2] = (uint32_t)tm2; tl[3] = (uint32_t)tm3;
-      }
     }
     if (!has_next) break;
     vb = vbn; ft = ftn; tt = ttn; Wc = Wn; Xc = Xn; par ^= 1;
@@ -1366,10 +1328,7 @@ static int pick_cfg(int M, int N, bool head_aligned = false, hipStream_t s = nul
   // r6: the persistent one-wave-per-SIMD kernel (cfg 16) for the bf16 / erf-GELU epilogues when every CU gets >= 2 whole 256 x 256 tiles
   // and the last round is >= 85 % full (DiT-L/2 fc1: 768 tiles = 3 rounds; I23D fc1: 12).  Sustained (3000-launch loops, profiles/r6_gemm.md):
   // fc1 + GELU 102.8 -> 99.0 us, plain 94.0 -> 87.2, I23D fc1 + GELU 411.6 -> 398.0.  run_cfg falls back to cfg 7 when p4_ok() refuses.
-#ifndef LN3D_P4_AUTO
-#define LN3D_P4_AUTO 1      // bench builds: 0 = never pick cfg 16 by itself (same-box A/B of the whole line)
-#endif
-  if (LN3D_P4_AUTO && (epi == LN3D_EPI_BF16 || epi == LN3D_EPI_GELU_ERF) && (M % 256) == 0 && (N % 256) == 0 && (K % 128) == 0 && K >= 512) {
+  if ((epi == LN3D_EPI_BF16 || epi == LN3D_EPI_GELU_ERF) && (M % 256) == 0 && (N % 256) == 0 && (K % 128) == 0 && K >= 512) {
     const int64_t t = (int64_t)(N / 256) * (M / 256), rounds = (t + cus - 1) / cus;
     if (t >= 2 * (int64_t)cus && t * 100 >= rounds * cus * 85) best = 16;
   }

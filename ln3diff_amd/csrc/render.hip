@@ -51,19 +51,12 @@
 #define MAX_GROUPS ((LN3D_RENDER_SCRATCH_FLOATS - GRP_OFF) / GRP_WORDS)
 static_assert(MAX_GROUPS >= 1024, "room for the per-call range records");
 
-// 4 wavefronts per workgroup, 3 per SIMD.  r6 re-measured 8-wave workgroups at 4 per SIMD (-DRENDER_WPB=8 -DRENDER_OCC=4): with the r6 gather and
+// 4 wavefronts per workgroup, 3 per SIMD.  r6 re-measured 8-wave workgroups at 4 per SIMD: with the r6 gather and
 // the decoder behind the gather the kernel fits 128 VGPRs with 6 spilled loop invariants (r4: 28 spills, 8 % slower) and the isolated loop gains
 // 2 - 4 % (0.630 -> 0.62 ms per 256^2 view, 2.37 -> 2.25 at 512^2) - but inside the pipelines it is level on configs[1] (+0.2 %) and 0.8 % BEHIND on
 // configs[2] (768 views of 32 plane sets per launch), so the no-spill form ships (profiles/r6_render_occ4.log, r6_render_insitu.log).
-#ifndef RENDER_OCC
-#define RENDER_OCC 3
-#endif
-#ifndef RENDER_WPB
-#define RENDER_WPB 4          // wavefronts (= rays in flight) per workgroup of render_kernel; they share one LDS copy of the decoder image
-#endif
-#ifndef LN3D_RENDER_ABL   // bench-only ablations (tools/render_bench.hip): 1 = no decoder MLP, 2 = no texel loads, 4 = no compositing
-#define LN3D_RENDER_ABL 0
-#endif
+constexpr int RENDER_OCC = 3;
+constexpr int RENDER_WPB = 4;         // wavefronts (= rays in flight) per workgroup of render_kernel; they share one LDS copy of the decoder image
 
 __device__ __forceinline__ uint32_t enc_f(float f) {
   uint32_t u = __float_as_uint(f);
@@ -245,15 +238,10 @@ __device__ __forceinline__ float softplus20_hw(float x) {
 }
 __device__ __forceinline__ float exp_neg_hw(float t) { return __builtin_amdgcn_exp2f(t * -1.4426950408889634f); }   // exp(-t)
 
-// -DLN3D_RENDER_OPSEL_REPRO (tools/r6_opsel_repro.sh, never the library): without the copy - the reproducer of profiles/r6_render_opsel.md
-__device__ __forceinline__ float even_reg(float x) {
-#ifdef LN3D_RENDER_OPSEL_REPRO
-  return x;
-#else
+__device__ __forceinline__ float even_reg(float x) {     // a copy into a fresh register: the gather in shade64 says why
   float r;
   asm("v_mov_b32 %0, %1" : "=v"(r) : "v"(x));
   return r;
-#endif
 }
 
 __device__ __forceinline__ void shade64(const RenderP& p, const float* __restrict__ planes, char* wl, const char* cimg,
@@ -335,12 +323,8 @@ __device__ __forceinline__ void shade64(const RenderP& p, const float* __restric
     }
 #pragma unroll
     for (int k = 0; k < 12; ++k) {
-      if constexpr (!(LN3D_RENDER_ABL & 2))
-      {
-        const f32x4 tv = *reinterpret_cast<__attribute__((address_space(1))) const f32x4*>(pbase + ((uint32_t)off[k] + c4b));
-        t[k] = make_float4(tv.x, tv.y, tv.z, tv.w);
-      }
-      else t[k] = make_float4((float)k, (float)off[k], 1.f, 2.f);
+      const f32x4 tv = *reinterpret_cast<__attribute__((address_space(1))) const f32x4*>(pbase + ((uint32_t)off[k] + c4b));
+      t[k] = make_float4(tv.x, tv.y, tv.z, tv.w);
     }
   };
   // the tap weights are read where they are used (behind whatever was placed under the loads): 12 registers less across that code
@@ -392,8 +376,7 @@ __device__ __forceinline__ void shade64(const RenderP& p, const float* __restric
     *reinterpret_cast<uint2*>(wrow + it * 1024 + ((it & 1) ? 0 : 64)) = lv;
   };
   // ---- the 32 -> 64 -> 4 decoder of one 32-point tile in four pieces (hidden tile jt = 0, 1: layer 1 + softplus, then its two k-steps of
-  // layer 2): the LN3D_RENDER_SEQ=0 bench build places the pieces of point tile 0 between the load issue and the load use of gather
-  // iterations 4 - 7; the shipped build runs them back to back behind the gather
+  // layer 2), run back to back behind the gather
   const int l31 = lane & 31, hi = lane >> 5;
   const uint32_t cb = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)cimg;
   auto mlp_l1 = [&](int pt, int jt, f32x16& hacc) {
@@ -451,49 +434,30 @@ __device__ __forceinline__ void shade64(const RenderP& p, const float* __restric
       if (hi == pt) o[k] = v;
     }
   };
-  constexpr bool kMlp = !(LN3D_RENDER_ABL & 1);
   float4 tA[12];
   // one iteration (8 points) at a time: double-buffering the 12 loads measured slower at 2 waves/SIMD (r2: 0.863 vs 0.838 ms per 256^2 view),
   // and r6's ablations say why more loads in flight do not help: the texel loads are an L1-path THROUGHPUT term (profiles/r6_render_abl.log)
-  // LN3D_RENDER_SEQ 1 (shipped): the decoder of both point tiles behind the whole gather.  0 (bench builds) = the decoder of tile 0 in four
-  // pieces under the texel loads of gather iterations 4 - 7: built first this round, bit-identical, and measured NO faster - isolated 0.636 vs
-  // 0.630 ms per 256^2 view, 0.212 vs 0.198 at 128^2, 2.34 vs 2.37 at 512^2; in the pipelines configs[1] level, configs[2] 0.5 % behind - at 23 more
-  // VGPRs: the decoder is 0.05 ms of the kernel and the texel loads it would hide under are an L1-path throughput term
-  // (profiles/r6_render_abl.log, r6_render_insitu.log).
-#ifndef LN3D_RENDER_SEQ
-#define LN3D_RENDER_SEQ 1
-#endif
+  // The decoder of both point tiles runs behind the whole gather.  r6 also built the decoder of tile 0 in four pieces under the texel loads of
+  // gather iterations 4 - 7: bit-identical, and measured NO faster - isolated 0.636 vs 0.630 ms per 256^2 view, 0.212 vs 0.198 at 128^2,
+  // 2.34 vs 2.37 at 512^2; in the pipelines configs[1] level, configs[2] 0.5 % behind - at 23 more VGPRs: the decoder is 0.05 ms of the kernel
+  // and the texel loads it would hide under are an L1-path throughput term (profiles/r6_render_abl.log, r6_render_insitu.log).
 #pragma unroll 1
-  for (int it = 0; it < (LN3D_RENDER_SEQ ? 8 : 4); ++it) {
+  for (int it = 0; it < 8; ++it) {
     fetch(it, tA);
     reduce(it, tA);
   }
   wave_sync();
-  // LN3D_RENDER_SEQ 0 only: points 0 - 31 are complete and their decoder runs UNDER the texel loads of points 32 - 63 (a piece per gather
-  // iteration, between the issue of the iteration's 12 loads and their first use).  Same arithmetic in the same order per point: bit-identical.
   f32x16 hacc, oacc;
-#define SB0_ __builtin_amdgcn_sched_barrier(0)
-  if constexpr (LN3D_RENDER_SEQ) {
-    if constexpr (kMlp) { mlp_l1(0, 0, hacc); mlp_l2(0, hacc, oacc); SB0_; mlp_l1(0, 1, hacc); mlp_l2(1, hacc, oacc); mlp_out(0, oacc); }
-  } else {
-    fetch(4, tA); SB0_; if constexpr (kMlp) mlp_l1(0, 0, hacc); SB0_; reduce(4, tA); SB0_;
-    fetch(5, tA); SB0_; if constexpr (kMlp) mlp_l2(0, hacc, oacc); SB0_; reduce(5, tA); SB0_;
-    fetch(6, tA); SB0_; if constexpr (kMlp) mlp_l1(0, 1, hacc); SB0_; reduce(6, tA); SB0_;
-    fetch(7, tA); SB0_; if constexpr (kMlp) mlp_l2(1, hacc, oacc); SB0_; reduce(7, tA); SB0_;
-    if constexpr (kMlp) mlp_out(0, oacc);
-    wave_sync();
-  }
-  if constexpr (kMlp) {
-    mlp_l1(1, 0, hacc); mlp_l2(0, hacc, oacc);
-    SB0_;                                              // keep the two hidden tiles apart: one set of fragments live at a time
-    mlp_l1(1, 1, hacc); mlp_l2(1, hacc, oacc);
-    mlp_out(1, oacc);
-    const float4 b1 = *reinterpret_cast<const float4*>(cimg + DEC_B1);
-    o[0] += b1.x; o[1] += b1.y; o[2] += b1.z; o[3] += b1.w;
-  } else {
-    o[0] = sx; o[1] = sy; o[2] = sz; o[3] = sx + sy;
-  }
-#undef SB0_
+  mlp_l1(0, 0, hacc); mlp_l2(0, hacc, oacc);
+  __builtin_amdgcn_sched_barrier(0);                   // keep the two hidden tiles apart: one set of fragments live at a time
+  mlp_l1(0, 1, hacc); mlp_l2(1, hacc, oacc);
+  mlp_out(0, oacc);
+  mlp_l1(1, 0, hacc); mlp_l2(0, hacc, oacc);
+  __builtin_amdgcn_sched_barrier(0);
+  mlp_l1(1, 1, hacc); mlp_l2(1, hacc, oacc);
+  mlp_out(1, oacc);
+  const float4 b1 = *reinterpret_cast<const float4*>(cimg + DEC_B1);
+  o[0] += b1.x; o[1] += b1.y; o[2] += b1.z; o[3] += b1.w;
   wave_sync();   // the wave's LDS may be overwritten by the caller / next pass
   sigma = inb ? o[0] : sg_fill;
   rgb[0] = inb ? (1.0f / (1.0f + __expf(-o[1]))) * 1.002f - 0.001f : 0.f;
@@ -547,10 +511,7 @@ __device__ __forceinline__ const char* stage_decoder(char* lds_bytes, const floa
   return cimg;
 }
 #define RENDER_LDS_BYTES (4 * WAVE_LDS_BYTES + DEC_BYTES)
-#ifndef RENDER_LDS_PAD
-#define RENDER_LDS_PAD 0        // bench builds: extra dynamic LDS per workgroup (> 80 KB leaves ONE workgroup per CU: profiles/r6_render_slp.md)
-#endif
-#define RENDER_K_LDS_BYTES (RENDER_WPB * WAVE_LDS_BYTES + DEC_BYTES + RENDER_LDS_PAD)
+constexpr int RENDER_K_LDS_BYTES = RENDER_WPB * WAVE_LDS_BYTES + DEC_BYTES;
 
 __device__ __forceinline__ void flush_depth_range(uint32_t* scal_u, int grp, float dmin_l, float dmax_l, int lane) {
   if (grp < 0) return;

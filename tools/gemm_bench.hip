@@ -1,10 +1,10 @@
 // Stand-alone bench + self-check of csrc/gemm_bf16.hip (no torch import: a fresh GPU box spends 1-2 minutes on that).
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize [-DLN3D_RING_VAR=n] [-DLN3D_RING_ABL=n] tools/gemm_bench.hip -o build/gemm_bench
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize tools/gemm_bench.hip ln3diff_amd/csrc/runtime.hip -o build/gemm_bench
 //   build/gemm_bench [rounds] [case-substring] [launches per round = 20]
 // Every case: outputs hashed (FNV-1a over the raw bytes: variants that keep the summation order must agree bit for bit),
 // 4096 sampled outputs checked against an fp32 dot product of the same bf16 operands (plain / GELU / gate+residual epilogues),
 // then `rounds` timing rounds of 20 launches each (HIP events on the launch stream); min and median over the rounds.
-// Environment: LN3D_GEMM_TILE (force a tile), LN3D_GEMM_ABL (bits 8-11 = prefetch distance of the PREFETCH variant).
+// Environment: LN3D_GEMM_TILE (force a tile).
 #include "../ln3diff_amd/csrc/gemm_bf16.hip"
 #include <algorithm>
 #include <cmath>
@@ -112,7 +112,6 @@ int main(int argc, char** argv) {
   };
   hipStream_t st; CK(hipStreamCreate(&st));
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-  printf("LN3D_RING_D1=%d LN3D_RING_ABL=%d \n", LN3D_RING_D1, LN3D_RING_ABL);
   for (const Case& c : cases) {
     if (!strstr(c.name, filt)) continue;
     if (c.tile) setenv("LN3D_GEMM_TILE", c.tile, 1); else unsetenv("LN3D_GEMM_TILE");
@@ -138,8 +137,6 @@ int main(int argc, char** argv) {
       o0b = (size_t)M * N * 2; o1b = o2b = (size_t)B * H * 128 * 64 * 2; a.bias = nullptr;
       a.tokens = c.tokens; a.heads = H; a.head_dim = 64; a.ctx_keys = 77; a.ctx_pad = 128; a.ctx_scale = 0.125f;
     } else o0b = (size_t)M * N * (c.epi == LN3D_EPI_F32 ? 4 : 2);
-    const bool timeline = (LN3D_RING_ABL & 8) && (c.epi == LN3D_EPI_BF16 || c.epi == LN3D_EPI_GELU_ERF);
-    if (timeline) o2b = (size_t)8192 * 12 * 64 * 4 * 4;       // [block][wave][stage][4] stamps
     CK(hipMalloc(&o0, o0b)); if (o1b) CK(hipMalloc(&o1, o1b)); if (o2b) CK(hipMalloc(&o2, o2b));
     CK(hipMemsetAsync(o0, 0, o0b, st));
     if (c.epi == LN3D_EPI_CROSS_ATTN) { fill_bf16<<<1024, 256, 0, st>>>((bf16_t*)o1, o1b / 2, 16, 1.0f); fill_bf16<<<1024, 256, 0, st>>>((bf16_t*)o2, o2b / 2, 17, 1.0f); }
@@ -176,52 +173,6 @@ int main(int argc, char** argv) {
         maxerr = std::max(maxerr, err);
       }
       CK(hipFree(mi)); CK(hipFree(ni)); CK(hipFree(ref));
-    }
-    if (timeline && c.tile && !strcmp(c.tile, "x16")) {
-      CK(hipMemsetAsync(o2, 0, o2b, st));
-      for (int w = 0; w < 50; ++w) ln3d_gemm_bf16(&a, st);            // sustained clock first
-      CK(hipMemsetAsync(o2, 0, o2b, st));
-      CK(hipEventRecord(e0, st)); ln3d_gemm_bf16(&a, st); CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
-      float ms1; CK(hipEventElapsedTime(&ms1, e0, e1));
-      std::vector<uint32_t> tl(o2b / 4); CK(hipMemcpy(tl.data(), o2, o2b, hipMemcpyDeviceToHost));
-      double first = 0, loop = 0, epi = 0, gap = 0, whole = 0; long nt = 0, ng = 0, nw = 0;
-      for (int b = 0; b < 256; ++b)
-        for (int w = 0; w < 4; ++w) {
-          const uint32_t* q = &tl[(((size_t)b * 4 + w) * 16) * 4];
-          int last = -1;
-          for (int k = 0; k < 16; ++k) {
-            if (q[k * 4 + 3] == 0) break;
-            first += (double)(uint32_t)(q[k * 4 + 1] - q[k * 4 + 0]); loop += (double)(uint32_t)(q[k * 4 + 2] - q[k * 4 + 0]); epi += (double)(uint32_t)(q[k * 4 + 3] - q[k * 4 + 2]); ++nt;
-            if (k > 0) { gap += (double)(uint32_t)(q[k * 4 + 0] - q[(k - 1) * 4 + 3]); ++ng; }
-            last = k;
-          }
-          if (last >= 0) { whole += (double)(uint32_t)(q[last * 4 + 3] - q[0]); ++nw; }
-        }
-      printf("  p4 timeline %-22s: 1 launch %.1f us | per tile per wave (ticks): first stage %.0f, whole K loop %.0f, epilogue %.0f, between tiles %.0f | first tile start -> last epilogue end %.0f ticks, %ld tiles\n",
-             c.name, ms1 * 1000.f, first / nt, loop / nt, epi / nt, ng ? gap / ng : 0.0, whole / nw, nt);
-    } else if (timeline) {
-      // one launch alone, timed, then the stamps: A = before the stage's waits, B = own DMAs landed + own reads retired, C = behind the barrier
-      CK(hipMemsetAsync(o2, 0, o2b, st));
-      CK(hipEventRecord(e0, st)); ln3d_gemm_bf16(&a, st); CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
-      float ms1; CK(hipEventElapsedTime(&ms1, e0, e1));
-      std::vector<uint32_t> tl(o2b / 4); CK(hipMemcpy(tl.data(), o2, o2b, hipMemcpyDeviceToHost));
-      const int nst = K / 64;
-      double wdma = 0, wbar = 0, seg = 0; long cnt = 0, cseg = 0; uint32_t tmin = 0xffffffffu, tmax = 0; double span = 0; long nspan = 0;
-      std::vector<double> segs;
-      for (int b = 0; b < 8192; ++b)
-        for (int w = 0; w < 12; ++w) {
-          const uint32_t* q = &tl[(((size_t)b * 12 + w) * 64) * 4];
-          if (q[2] == 0 && q[6] == 0) continue;
-          for (int s2 = 0; s2 + 1 < nst && s2 < 63; ++s2) {
-            const uint32_t A = q[s2 * 4], B = q[s2 * 4 + 1], C = q[s2 * 4 + 2];
-            if (C == 0) continue;
-            wdma += (double)(uint32_t)(B - A); wbar += (double)(uint32_t)(C - B); ++cnt;
-            if (s2 + 2 < nst && q[(s2 + 1) * 4 + 2] != 0) { const double d = (double)(uint32_t)(q[(s2 + 1) * 4] - C); seg += d; ++cseg; }
-          }
-          span += (double)(uint32_t)(q[(nst - 2) * 4 + 2] - q[2]); ++nspan;
-        }
-      printf("  timeline %-24s: 1 launch %.1f us | per stage per wave: wait own DMA+reads %.0f, barrier %.0f, work segment %.0f ticks (stages %ld) | first->last barrier of a tile %.0f ticks over %d stages\n",
-             c.name, ms1 * 1000.f, wdma / cnt, wbar / cnt, seg / cseg, cnt, span / nspan, nst - 2);
     }
     // ---- timing
     std::vector<float> ts;

@@ -3,11 +3,19 @@
 # (MI355X_MICROARCH.md's HBM section: KB units, FETCH x2 on gfx950); for the ray-marcher additionally the issue counters that say
 # what it is bound by (SQ_INSTS_VALU, SQ_ACTIVE_INST_VALU, SQ_VALU_MFMA_BUSY_CYCLES, SQ_WAVE_CYCLES, GRBM_GUI_ACTIVE, ...).  Every
 # entry carries the sha256 of the kernel source it was measured on.
+# Each rocprofv3 pass runs under its own time limit; the first pass that fails ends the script (its log is printed).
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/r6_pmc
-rm -rf $OUT; mkdir -p $OUT
-run() { n=$1; c=$2; shift 2; timeout 180 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$n.$(echo $c | tr ' ' '+') -- python $R/tools/pmc_one.py "$@" > /dev/null 2>&1; }
+LOGS=${OUT}_logs
+rm -rf $OUT $LOGS; mkdir -p $OUT $LOGS
+run() {
+  n=$1; c=$2; shift 2
+  tag=$n.$(echo $c | tr ' ' '+')
+  timeout -k 10 180 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$tag -- python $R/tools/pmc_one.py "$@" > $LOGS/$tag.log 2>&1
+  rc=$?
+  if [ $rc -ne 0 ]; then echo "r6_pmc.sh: $tag failed (exit $rc)"; tail -n 30 $LOGS/$tag.log; exit $rc; fi
+}
 for c in FETCH_SIZE WRITE_SIZE; do
   run gemm_fc1_gelu_12288x4096x1024 $c gemm 12288 4096 1024
   run gemm_fc1_gelu_49152x4096x1024 $c gemm 49152 4096 1024

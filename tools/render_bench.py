@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Timing of the fused tri-plane ray-marcher at the benchmarked resolutions (GPU box).  LN3D_LIB selects an alternative build of
-the library (bench-only ablation builds: -DLN3D_RENDER_ABL=n, see csrc/render.hip)."""
+"""Timing of the fused tri-plane ray-marcher at the benchmarked resolutions (GPU box).  LN3D_LIB selects another build of the
+library (an A/B against another commit's libln3d_hip.so)."""
 import os
 import sys
 import torch

@@ -1,5 +1,5 @@
 // Determinism probe for the decoder path of csrc/render.hip (GPU box): ln3d_query_points twice on the same inputs, outputs must be
-// bit-identical.   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DLN3D_RENDER_ABL=n] tools/render_det.hip -o build/render_det
+// bit-identical.   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/render_det.hip -o build/render_det
 #include "../ln3diff_amd/csrc/render.hip"
 #include <cstdio>
 #include <cstring>
