@@ -8,6 +8,9 @@ One "step" = one pass of the whole hot path over one batch of B samples per GPU:
   synthetic noise / conditioning / orbit cameras, resident in HBM before the timed region.
 N GPUs: one process per GPU, weak scaling (B samples per rank), RCCL broadcast of rank 0's weights at start-up,
 all_gather of the final latents inside the timed region; no collective inside the denoise loop.
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the result line.  --full adds what the headline does
+not need, each after the timed region: value_unfolded (extra steps without the CFG fold), golden_check (the timed run against the
+reference's fixtures), the roofline probes (with the fc1 GEMM timed inside the timed region) and the CPU baseline.
 """
 import argparse
 import json
@@ -52,12 +55,15 @@ def build_models(dev, arch, dec_arch, seed=0, fill=True, golden_weights=False):
     from ln3diff_amd.vit.vit_triplane import (
         RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout_withSD_D_ditDecoder as Dec)
     from ln3diff_amd.synth import fill_module_random_
-    dit = DiT_models[arch](input_size=32, num_classes=0, learn_sigma=False, in_channels=4, context_dim=768,
-                           roll_out=True, vit_blk=TextCondDiTBlock)
-    vit = DiT2_models[dec_arch](input_size=16, num_classes=0, learn_sigma=False, in_channels=dit.embed_dim,
-                                mixed_prediction=False, context_dim=None, roll_out=True, plane_n=3)
-    dec = Dec(vit_decoder=vit, triplane_decoder=Triplane(img_resolution=128), cls_token=False, vae_p=2,
-              ldm_z_channels=4, ldm_embed_dim=4)
+    # built on the device: torch's default init of ~1e9 weights takes seconds on the host, and every value it draws is replaced below
+    # (the fill, or rank 0's broadcast); the one computed tensor, pos_embed, is made on the host from numpy either way
+    with dev:
+        dit = DiT_models[arch](input_size=32, num_classes=0, learn_sigma=False, in_channels=4, context_dim=768,
+                               roll_out=True, vit_blk=TextCondDiTBlock)
+        vit = DiT2_models[dec_arch](input_size=16, num_classes=0, learn_sigma=False, in_channels=dit.embed_dim,
+                                    mixed_prediction=False, context_dim=None, roll_out=True, plane_n=3)
+        dec = Dec(vit_decoder=vit, triplane_decoder=Triplane(img_resolution=128), cls_token=False, vae_p=2,
+                  ldm_z_channels=4, ldm_embed_dim=4)
     dit, dec = dit.to(dev), dec.to(dev)
     if fill:
         if golden_weights:            # the (name, shape, seed) weights of tests/golden: lets the timed run be checked against a golden
@@ -360,8 +366,8 @@ def _cpu_view(res_target, g):
 def cpu_baseline(arch, steps_total, views, res, B, i23d=False):
     """CPU restatement (oracle/, validated against the reference's own Python in the build container) timed on this box's host
     cores on a bounded sample of the same workload and extrapolated linearly (per-step and per-view costs are constant, BASELINE.md
-    2): 1 warm-up + 5 timed network evaluations at B = 1 with CFG (network batch 2) - cut to 2 when a step exceeds 6 s, so the
-    default run stays within its few minutes -, the VAE decode scaled from the step by FLOPs, one view at 64^2 scaled to the
+    2): 1 warm-up + 5 timed network evaluations at B = 1 with CFG (network batch 2) - cut to 2 when a step exceeds 6 s, so a
+    --full run stays within its few minutes -, the VAE decode scaled from the step by FLOPs, one view at 64^2 scaled to the
     target resolution by rays."""
     from oracle import dit as odit, samplers as osamp
     cores, host, probe = _pick_threads()
@@ -537,13 +543,16 @@ def main():
     ap.add_argument("--res", type=int, default=None, help="render resolution (the metric: 256^2; unet: the launcher's 128)")
     ap.add_argument("--arch", default=None)
     ap.add_argument("--dec-arch", default="DiT2-L/2")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: value_unfolded, golden_check, the roofline probes "
+                         "and the CPU baseline (--unfolded-steps, --no-probes and --no-cpu-baseline narrow it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-probes", action="store_true")
     ap.add_argument("--ode-method", default="euler", choices=["euler", "heun", "dopri5"],
                     help="i23d workload: euler = configs[2] (50 fixed steps); dopri5 = the released sampler's default (torchdiffeq "
                          "semantics, atol 1e-6, rtol 1e-3: the number of network evaluations is decided by the solver and reported)")
     ap.add_argument("--unfolded-steps", type=int, default=2,
-                    help="extra steps after the timed region with the zero-context fold of the unconditional CFG half disabled "
+                    help="--full: extra steps after the timed region with the zero-context fold of the unconditional CFG half disabled "
                          "(prints value_unfolded; 0 = skip)")
     ap.add_argument("--dist", action="store_true",
                     help="go through torch.distributed.run + an RCCL process group even with --gpus 1 (the N-GPU code path on one GPU)")
@@ -562,6 +571,8 @@ def main():
     args.arch = args.arch or ("UNet-ShapeNet(320ch, attn 4,2,1)" if unet else "DiT-PixArt-L/2" if i23d else "DiT-L/2")
     if unet and args.dec_arch == "DiT2-L/2":
         args.dec_arch = "DiT2-B/2"                   # the second entry point's default decoder
+    if unet or not args.full:      # unet: the DiT probes / CFG fold / oracle baseline do not apply
+        args.no_probes, args.unfolded_steps, args.no_cpu_baseline = True, 0, True
 
     if (args.gpus > 1 or args.dist) and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)
@@ -669,8 +680,6 @@ def main():
         out = one_step()
     # dominant-kernel timing INSIDE the timed region: HIP events on the launch stream around the MLP fc1 GEMM of the middle
     # layer, every denoise step (an event pair costs ~1 us of stream time per 12 ms step)
-    if unet:
-        args.no_probes, args.unfolded_steps, args.no_cpu_baseline = True, 0, True     # the DiT probes / CFG fold / oracle baseline do not apply
     if rank == 0 and not args.no_probes:
         dit._fc1_probe = {'layer': dit.depth // 2, 'events': [], 'max': 4096}
     clk = ClockSampler() if (rank == 0 and not args.no_probes) else None
@@ -753,9 +762,10 @@ def main():
             "value_unfolded": value_unfolded,
             "finite": ok,
             "ranks_seen": seen, "collectives": parallel.collective_info(), "bcast_ms": round(bcast_ms, 2),
-            "golden_check": golden_check(out[0][0], i23d, args.arch, args.sample_steps if (not i23d or args.ode_method == "euler") else -1),
         }
-        if not i23d and rec["golden_check"].get("fixture") == "tests/golden/full_edm_ditl2_250.npz":
+        if args.full:
+            rec["golden_check"] = golden_check(out[0][0], i23d, args.arch, args.sample_steps if (not i23d or args.ode_method == "euler") else -1)
+        if args.full and not i23d and rec["golden_check"].get("fixture") == "tests/golden/full_edm_ditl2_250.npz":
             pc = picture_check(out[0][0], eng.rec_model, args.dec_arch)
             if pc:
                 rec["golden_check"].update(pc)

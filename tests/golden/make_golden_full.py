@@ -69,7 +69,7 @@ def sec_full_edm():
 
 def sec_full_edm_xl2():
     """r4: configs[3]'s denoiser through the WHOLE 250-step loop (r3 pinned DiT-XL/2 for 10 steps only): reference loop only, the
-    oracle is already checked against it on this network in make_golden_geom.py xl2_edm10.  bench.py --arch DiT-XL/2 compares the
+    oracle is already checked against it on this network in make_golden_geom.py xl2_edm10.  bench.py --full --arch DiT-XL/2 compares the
     latent of its timed run with `final` (same inputs: seed 41, synthetic weights 0)."""
     print('== DiT-XL/2 T23D (configs[3]): EulerEDM 250 + CFG 6.5, B=1 (reference sgm sampler)')
     from sgm.modules.diffusionmodules.sampling import EulerEDMSampler

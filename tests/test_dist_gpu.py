@@ -1,6 +1,7 @@
 """The N-rank code path on ONE GPU (r4): bench.py under torch.distributed.run with one rank creates an RCCL process group and runs
 every collective of a node run - all_reduce of ones, flat weight broadcast, all_gather of the latents, barriers, max-over-ranks
-timing - so that the first 8-GPU launch has no untested call left (the build container has no GPU and the test boxes have one)."""
+timing - so that the first 8-GPU launch has no untested call left (the build container has no GPU and the test boxes have one).
+Also what a plain run and a --full run of bench.py print."""
 import json
 import os
 import socket
@@ -59,3 +60,23 @@ def test_bench_mismatched_launch_fails_fast(hip_lib):
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode != 0
     assert "refusing to print a line" in (r.stderr + r.stdout)
+
+
+def test_bench_plain_run_is_lean_and_full_adds_the_rest(hip_lib):
+    """A plain run prints the headline without the figures that take runs of their own; --full adds them after the timed region
+    (the CPU baseline stays off here: minutes of host time whatever the size)."""
+    bench = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + [a for a in SMALL if a not in ("--no-cpu-baseline", "--no-probes")]
+    r = subprocess.run(bench, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _line(r.stdout)
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["finite"] is True and d["value_unfolded"] is None
+    extras = ("golden_check", "clock_timed_region", "roofline", "roofline_attention", "roofline_raymarch", "roofline_gate_residual",
+              "roofline_out_proj", "mfma_sustained_probe", "cpu_baseline")
+    assert not [k for k in extras if k in d]
+    r = subprocess.run(bench + ["--full", "--no-cpu-baseline", "--unfolded-steps", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _line(r.stdout)
+    assert d["value"] > 0 and d["value_unfolded"] > 0
+    assert d["golden_check"]["fixture"] is None                   # 3 sample steps: no reference fixture to compare with
+    assert [k for k in extras if k not in d] == ["cpu_baseline"]
+    assert d["roofline"]["achieved"] > 0 and d["roofline"]["launches_timed"] > 0
