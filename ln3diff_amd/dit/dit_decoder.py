@@ -10,8 +10,7 @@ import torch.nn as nn
 
 from .. import ops
 from .. import _cache
-from .dit_models_xformers import (DiTBlock, Workspace, bf16, f32, get_2d_sincos_pos_embed, self_attention_hip,
-                                  pad_head_columns)
+from .dit_models_xformers import DiTBlock, Workspace, bf16, f32, get_2d_sincos_pos_embed, pack_block, self_attention_hip
 
 
 class DiTBlock2(DiTBlock):
@@ -43,11 +42,8 @@ class DiT2(nn.Module):
             return self._packed
         P = {'device': device, 'pos': f32(self.pos_embed[0], device), 'blocks': []}
         for b in self.blocks:
-            q = {'ada_w': bf16(b.adaLN_modulation[1].weight, device), 'ada_b': f32(b.adaLN_modulation[1].bias, device),
-                 'qkv_w': bf16(b.attn.qkv.weight, device), 'qkv_b': f32(b.attn.qkv.bias, device),
-                 'proj_w': bf16(pad_head_columns(b.attn.proj.weight.detach(), self.num_heads, self.embed_dim // self.num_heads), device), 'proj_b': f32(b.attn.proj.bias, device),
-                 'fc1_w': bf16(b.mlp.mlp[0].weight, device), 'fc1_b': f32(b.mlp.mlp[1].bias, device),
-                 'fc2_w': bf16(b.mlp.mlp[2].weight, device), 'fc2_b': f32(b.mlp.mlp[3].bias, device)}
+            q = pack_block(b, self.num_heads, self.embed_dim // self.num_heads, device)
+            q['ada_w'], q['ada_b'] = bf16(b.adaLN_modulation[1].weight, device), f32(b.adaLN_modulation[1].bias, device)
             P['blocks'].append(q)
         self._packed = _cache.stamp(P, self)
         return P

@@ -14,10 +14,10 @@ import os
 import torch
 import torch.nn as nn
 
-from .. import ops, _cache
+from .. import ops
 from .dit_models_xformers import (CaptionEmbedder, ImageCondDiTBlock, ImageCondDiTBlockPixelArtRMSNorm, RMSNormP, T2IFinalLayer, bf16, f32,
-                                  self_attention_hip, pad_head_columns, attn_head_pad, attn_out_dim)
-from .dit_trilatent import DiT, DiT_TriLatent
+                                  self_attention_hip, pack_caption, attn_head_pad, attn_out_dim)
+from .dit_trilatent import DiT_TriLatent
 
 
 class DiT_I23D_PixelArt(DiT_TriLatent):
@@ -37,66 +37,22 @@ class DiT_I23D_PixelArt(DiT_TriLatent):
         self.attention_y_norm = RMSNormP(1024)
         self.pooling_ctx_dim = pooling_ctx_dim
 
+    _uc_first = False                  # the flow-matching engine's [c, uc] order: the unconditional samples trail
+
     def _append_proj(self):
         """CaptionEmbedder whose output tokens are appended to the self-attention sequence."""
         return self.dino_proj
 
-    def _ensure_packed(self, device):
-        if _cache.fresh(self._packed, device):
-            return
-        from .dit_models_xformers import Workspace
-        D = self.embed_dim
-        P = {'device': device}
-        self._pack_embedder(P, device)
-        P['t_w0'], P['t_b0'] = bf16(self.t_embedder.mlp[0].weight, device), f32(self.t_embedder.mlp[0].bias, device)
-        P['t_w2'], P['t_b2'] = bf16(self.t_embedder.mlp[2].weight, device), f32(self.t_embedder.mlp[2].bias, device)
-        if getattr(self, 'adaLN_modulation', None) is not None:          # PixArt: ONE shared adaLN + per-block tables
-            P['ada_w'], P['ada_b'] = bf16(self.adaLN_modulation[1].weight, device), f32(self.adaLN_modulation[1].bias, device)
-            P['sst'] = f32(torch.stack([b.scale_shift_table.reshape(-1) for b in self.blocks], 0), device)   # [depth, 6D]
-        else:                                                            # plain DiT_I23D: every block's own adaLN, one GEMM
-            P['ada_w'] = bf16(torch.cat([b.adaLN_modulation[1].weight for b in self.blocks], 0), device)    # [depth*6D, D]
-            P['ada_b'] = f32(torch.cat([b.adaLN_modulation[1].bias for b in self.blocks], 0), device)
+    def _pack_prompt(self, P, device):
         if hasattr(self, 'cap_embedder'):
             P['cap_ln_w'], P['cap_ln_b'] = f32(self.cap_embedder[0].weight, device), f32(self.cap_embedder[0].bias, device)
             P['cap_w'], P['cap_b'] = bf16(self.cap_embedder[1].weight, device), f32(self.cap_embedder[1].bias, device)
         if hasattr(self, 'attention_y_norm'):
             P['ynorm_w'] = f32(self.attention_y_norm.weight, device)
         if self._append_proj() is not None:
-            dp = self._append_proj().y_proj
-            P['d_w1'], P['d_b1'] = bf16(dp.fc1.weight, device), f32(dp.fc1.bias, device)
-            P['d_w2'], P['d_b2'] = bf16(dp.fc2.weight, device), f32(dp.fc2.bias, device)
-        blks = []
-        for b in self.blocks:
-            q = {}
-            q['n1'], q['n2'] = (f32(b.norm1.weight, device), f32(b.norm2.weight, device)) if hasattr(b, 'norm1') else (None, None)
-            q['qkv_w'], q['qkv_b'] = bf16(b.attn.qkv.weight, device), f32(b.attn.qkv.bias, device)
-            dh = self.embed_dim // self.num_heads
-            padw = lambda w: torch.nn.functional.pad(w.detach().float(), (0, attn_head_pad(dh) - dh))     # zero beyond the true head size
-            has_qk = getattr(b.attn, 'qk_norm', False)
-            q['qn'], q['kn'] = (f32(padw(b.attn.q_norm.weight), device), f32(padw(b.attn.k_norm.weight), device)) if has_qk else (None, None)
-            q['proj_w'], q['proj_b'] = bf16(pad_head_columns(b.attn.proj.weight.detach(), self.num_heads, self.embed_dim // self.num_heads), device), f32(b.attn.proj.bias, device)
-            q['cq_w'] = bf16(b.cross_attn.to_q.weight, device)
-            q['ckv_w'] = bf16(torch.cat([b.cross_attn.to_k.weight, b.cross_attn.to_v.weight], 0), device)
-            has_cqk = getattr(b.cross_attn, 'qk_norm', False)
-            q['cqn'], q['ckn'] = (f32(b.cross_attn.q_norm.weight, device), f32(b.cross_attn.k_norm.weight, device)) if has_cqk else (None, None)
-            if hasattr(b, 'attention_y_norm'):
-                q['ynorm'] = f32(b.attention_y_norm.weight, device)
-            q['co_w'], q['co_b'] = bf16(b.cross_attn.to_out[0].weight, device), f32(b.cross_attn.to_out[0].bias, device)
-            q['fc1_w'], q['fc1_b'] = bf16(b.mlp.mlp[0].weight, device), f32(b.mlp.mlp[1].bias, device)
-            q['fc2_w'], q['fc2_b'] = bf16(b.mlp.mlp[2].weight, device), f32(b.mlp.mlp[3].bias, device)
-            blks.append(q)
-        P['blocks'] = blks
-        P['fin_w'], P['fin_b'] = f32(self.final_layer.linear.weight, device), f32(self.final_layer.linear.bias, device)
+            pack_caption(P, 'd', self._append_proj(), device)
         P['fin_sst'] = f32(self.final_layer.scale_shift_table, device)          # [2, D]
-        P['zeros'] = torch.zeros(max(D, self.pooling_ctx_dim), device=device)
-        self._packed = _cache.stamp(P, self)
-        self._ws = Workspace(device)
-
-    def _pack_embedder(self, P, device):
-        D = self.embed_dim
-        P['pe_w'] = f32(self.x_embedder.proj.weight.reshape(D, -1), device)
-        P['pe_b'] = f32(self.x_embedder.proj.bias, device)
-        P['pos'] = f32(self.pos_embed[0], device)
+        P['zeros'] = torch.zeros(max(self.embed_dim, self.pooling_ctx_dim), device=device)
 
     def _cls_token(self, vec):
         """pooled token: LayerNorm(affine, eps 1e-5) -> Linear   (dit_i23d.py:211-217,245)"""
@@ -111,85 +67,25 @@ class DiT_I23D_PixelArt(DiT_TriLatent):
 
     def _appended_tokens(self, feats):
         """CaptionEmbedder (Linear -> tanh-GELU -> Linear) of [Bn, L, C] features -> bf16 [Bn, L, D]."""
-        P, ws, D = self._packed, self._ws, self.embed_dim
-        Bn, L, C = feats.shape
-        fin = ws.get('app_in', (Bn * L, C), torch.bfloat16)
-        ops.cast_bf16(feats.contiguous().float(), fin)
-        h1 = ws.get('app_h', (Bn * L, D), torch.bfloat16)
-        ops.gemm(fin, P['d_w1'], P['d_b1'], ops.EPI_GELU_TANH, h1)
-        out = torch.empty(Bn, L, D, device=feats.device, dtype=torch.bfloat16)
-        ops.gemm(h1, P['d_w2'], P['d_b2'], ops.EPI_BF16, out)
-        return out
-
-    def _cross_kv(self, ctx_bf16, Bn, Lk):
-        """every block's cross-attention K (k_norm applied) / V^T of a [Bn*Lk, C] bf16 context."""
-        P, H = self._packed, self.num_heads
-        lpad = (Lk + 63) // 64 * 64
-        dev = ctx_bf16.device
-        k_all = torch.zeros(self.depth, Bn, H, lpad, 64, dtype=torch.bfloat16, device=dev)
-        vt_all = torch.zeros(self.depth, Bn, H, 64, lpad, dtype=torch.bfloat16, device=dev)
-        for i, q in enumerate(P['blocks']):
-            ops.gemm(ctx_bf16, q['ckv_w'], None, ops.EPI_HEADS, k_all[i], vt_all[i], M=Bn * Lk, tokens=Lk, tok_pad=lpad,
-                     heads=H, head_dim=64, transpose_mask=0b10)
-            if q['ckn'] is not None:
-                ops.rmsnorm_heads(k_all[i], q['ckn'], Bn * H * lpad, 64)
-        return k_all, vt_all, lpad
-
-    def _fold_uc(self, cc, rows):
-        """Samples whose cross-attention context rows are all IDENTICAL - the zero image / text embeddings of the unconditional CFG
-        branch (pipeline._zero_uc; every K / V row of a sample is a row-wise function of its context row, so they are identical
-        too): softmax over identical scores is uniform whatever the query and the cross-attention sub-block is the constant
-        to_out(v) + b per (layer, sample).  For a TRAILING run of such samples (the flow-matching engine's [c, uc] order) the
-        constants are computed here, once per prompt, with the same kernels (bf16 V row -> to_out GEMM, fp32 accumulate); forward()
-        adds them in the gate / residual epilogue of the self-attention projection and runs to_q / attention / to_out on the leading
-        samples only (LN3D_NO_UC_FOLD=1: off).  `rows`: [Bn, L, C] raw context the K / V were made from."""
-        cc['fold'] = 0
-        Bn = cc['Bn']
-        if os.environ.get('LN3D_NO_UC_FOLD') or cc['Lc'] < 1 or Bn < 2:
-            return cc
-        same = (rows == rows[:, :1]).flatten(1).all(1).tolist()              # one host read per prompt
-        fold = 0
-        while fold < Bn and same[Bn - 1 - fold]:
-            fold += 1
-        if not 0 < fold < Bn:
-            return cc
-        P, H, D = self._packed, self.num_heads, self.embed_dim
-        const = torch.zeros(self.depth, Bn, D, dtype=torch.float32, device=rows.device)       # rows < Bn - fold stay 0
-        for i, q in enumerate(P['blocks']):
-            v_row = cc['vt'][i, Bn - fold:, :, :, 0].reshape(fold, H * 64).contiguous()        # V^T[b, h, d, key 0] = the attention output
-            ops.gemm(v_row, q['co_w'], q['co_b'], ops.EPI_F32, const[i, Bn - fold:])
-        cc['fold'], cc['const'] = fold, const
-        return cc
+        Bn, L, _ = feats.shape
+        return self._caption_mlp(feats, 'd', torch.empty(Bn, L, self.embed_dim, device=feats.device, dtype=torch.bfloat16))
 
     @torch.no_grad()
     def prepare_context(self, context):
         ca, vec = context['crossattn'], context['vector']
-        dev = ca.device
-        self._ensure_packed(dev)
-        P, ws = self._packed, self._ws
+        self._ensure_packed(ca.device)
         Bn, Lc, _ = ca.shape
-        D, H, C1 = self.embed_dim, self.num_heads, self.clip_ctx_dim
+        C1 = self.clip_ctx_dim
         want = C1 + self.dino_proj.y_proj.fc1.in_features
         if ca.shape[-1] != want or vec.shape[-1] != self.pooling_ctx_dim:
             raise ValueError(f"context['crossattn'] must be [B, L, {want}] (CLIP {C1} || DINO) and context['vector'] [B, {self.pooling_ctx_dim}]; "
                              f"got {tuple(ca.shape)} / {tuple(vec.shape)}")
         cls = self._cls_token(vec)
-        # CLIP tokens: RMSNorm once (dit_i23d.py:247); DINO tokens: tanh-GELU MLP
-        clip_n = ws.get('clip_n', (Bn * Lc, C1), torch.bfloat16)
-        ops.norm_modulate(ca[..., :C1].contiguous().float(), clip_n, Bn * Lc, C1, kind=1, eps=1e-5, weight=P['ynorm_w'])
-        dino_in = ws.get('dino_in', (Bn * Lc, ca.shape[-1] - C1), torch.bfloat16)
-        ops.cast_bf16(ca[..., C1:].contiguous().float(), dino_in)
-        d1 = ws.get('dino_h', (Bn * Lc, D), torch.bfloat16)
-        ops.gemm(dino_in, P['d_w1'], P['d_b1'], ops.EPI_GELU_TANH, d1)
-        dino = torch.empty(Bn, Lc, D, device=dev, dtype=torch.bfloat16)
-        ops.gemm(d1, P['d_w2'], P['d_b2'], ops.EPI_BF16, dino)
-        lpad = (Lc + 63) // 64 * 64
-        k_all = torch.zeros(self.depth, Bn, H, lpad, 64, dtype=torch.bfloat16, device=dev)
-        vt_all = torch.zeros(self.depth, Bn, H, 64, lpad, dtype=torch.bfloat16, device=dev)
-        for i, q in enumerate(P['blocks']):
-            ops.gemm(clip_n, q['ckv_w'], None, ops.EPI_HEADS, k_all[i], vt_all[i], M=Bn * Lc, tokens=Lc, tok_pad=lpad,
-                     heads=H, head_dim=64, transpose_mask=0b10)
-            ops.rmsnorm_heads(k_all[i], q['ckn'], Bn * H * lpad, 64)
+        # CLIP tokens: the model's attention_y_norm once for every layer (dit_i23d.py:247); DINO tokens: tanh-GELU MLP
+        clip_n = self._ws.get('clip_n', (Bn * Lc, C1), torch.bfloat16)
+        ops.norm_modulate(ca[..., :C1].contiguous().float(), clip_n, Bn * Lc, C1, kind=1, eps=1e-5, weight=self._packed['ynorm_w'])
+        dino = self._appended_tokens(ca[..., C1:])
+        k_all, vt_all, lpad = self._cross_kv(clip_n, Bn, Lc)
         return self._fold_uc({'k': k_all, 'vt': vt_all, 'Lc': Lc, 'lpad': lpad, 'Bn': Bn, 'cls': cls, 'dino': dino}, ca[..., :C1])
 
     @torch.no_grad()
@@ -271,14 +167,7 @@ class DiT_I23D_PixelArt(DiT_TriLatent):
             ops.gemm(oc, q['co_w'], q['co_b'], ops.EPI_GATE_RES, xt, M=Mc)
             ops.norm_modulate(xt, hb, M, D, kind=nk, eps=neps, weight=q['n2'], shift=mi[:, 3 * D:], scale=mi[:, 4 * D:],
                               mod_rows=N, mod_ld=ld)
-            if probe is not None and i == probe['layer'] and len(probe['events']) < probe['max']:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)      # bench.py measurement hook
-                e0.record()
-                ops.gemm(hb, q['fc1_w'], q['fc1_b'], ops.EPI_GELU_ERF, f1)
-                e1.record()
-                probe['events'].append((e0, e1))
-            else:
-                ops.gemm(hb, q['fc1_w'], q['fc1_b'], ops.EPI_GELU_ERF, f1)
+            self._fc1(probe, i, hb, q, f1)
             ops.gemm(f1, q['fc2_w'], q['fc2_b'], ops.EPI_GATE_RES, xt, gate=mi[:, 5 * D:], gate_rows=N, gate_ld=ld)
         return self._output(xt, tsum, Bn, N)
 
@@ -398,46 +287,21 @@ class DiT_I23D(DiT_I23D_PixelArt):
 
     def _cls_token(self, vec):
         """clip_text_proj(context['vector']): Linear -> tanh-GELU -> Linear, fp32 out (dit_i23d.py:112)"""
-        P, ws, D = self._packed, self._ws, self.embed_dim
-        Bn = vec.shape[0]
-        vin = ws.get('cls_in', (Bn, vec.shape[-1]), torch.bfloat16)
-        ops.cast_bf16(vec.contiguous().float(), vin)
-        h1 = ws.get('cls_h', (Bn, D), torch.bfloat16)
-        ops.gemm(vin, P['c_w1'], P['c_b1'], ops.EPI_GELU_TANH, h1)
-        cls = torch.empty(Bn, D, device=vec.device, dtype=torch.float32)
-        ops.gemm(h1, P['c_w2'], P['c_b2'], ops.EPI_F32, cls)
-        return cls
-
-    def _pack_embedder(self, P, device):
-        super()._pack_embedder(P, device)
-        cp = self.clip_text_proj.y_proj
-        P['c_w1'], P['c_b1'] = bf16(cp.fc1.weight, device), f32(cp.fc1.bias, device)
-        P['c_w2'], P['c_b2'] = bf16(cp.fc2.weight, device), f32(cp.fc2.bias, device)
+        return self._caption_mlp(vec, 'c', torch.empty(vec.shape[0], self.embed_dim, device=vec.device, dtype=torch.float32))
 
     @torch.no_grad()
     def prepare_context(self, context):
         ca, vec = context['crossattn'], context['vector']
-        dev = ca.device
-        self._ensure_packed(dev)
-        P, ws = self._packed, self._ws
+        self._ensure_packed(ca.device)
         Bn, Lc, _ = ca.shape
-        D, H, C1 = self.embed_dim, self.num_heads, self.clip_ctx_dim
+        C1 = self.clip_ctx_dim
         want = C1 + self.dino_proj.y_proj.fc1.in_features
         if ca.shape[-1] != want or vec.shape[-1] != self.pooling_ctx_dim:
             raise ValueError(f"context['crossattn'] must be [B, L, {want}] (CLIP {C1} || DINO) and context['vector'] [B, {self.pooling_ctx_dim}]; "
                              f"got {tuple(ca.shape)} / {tuple(vec.shape)}")
         cls = self._cls_token(vec)
         dino = self._appended_tokens(ca[..., C1:])
-        lpad = (Lc + 63) // 64 * 64
-        k_all = torch.zeros(self.depth, Bn, H, lpad, 64, dtype=torch.bfloat16, device=dev)
-        vt_all = torch.zeros(self.depth, Bn, H, 64, lpad, dtype=torch.bfloat16, device=dev)
-        clip = ca[..., :C1].contiguous().float()
-        cn = ws.get('clip_n', (Bn * Lc, C1), torch.bfloat16)
-        for i, q in enumerate(P['blocks']):
-            ops.norm_modulate(clip, cn, Bn * Lc, C1, kind=1, eps=1e-5, weight=q['ynorm'])            # the BLOCK's attention_y_norm
-            ops.gemm(cn, q['ckv_w'], None, ops.EPI_HEADS, k_all[i], vt_all[i], M=Bn * Lc, tokens=Lc, tok_pad=lpad, heads=H, head_dim=64,
-                     transpose_mask=0b10)
-            ops.rmsnorm_heads(k_all[i], q['ckn'], Bn * H * lpad, 64)
+        k_all, vt_all, lpad = self._cross_kv(ca[..., :C1], Bn, Lc, block_norm=True)      # the BLOCK's attention_y_norm
         return self._fold_uc({'k': k_all, 'vt': vt_all, 'Lc': Lc, 'lpad': lpad, 'Bn': Bn, 'cls': cls, 'dino': dino}, ca[..., :C1])
 
 
@@ -532,19 +396,10 @@ class DiT_TriLatent_PixelArt(DiT_I23D_PixelArt):
                              f"got {tuple(ca.shape)} / {tuple(vec.shape)}")
         dev = ca.device
         self._ensure_packed(dev)
-        P, ws = self._packed, self._ws
-        Bn, Lc, Cd = ca.shape
-        D, H = self.embed_dim, self.num_heads
+        Bn, Lc, _ = ca.shape
+        D = self.embed_dim
         cls = self._cls_token(vec)
-        lpad = (Lc + 63) // 64 * 64
-        k_all = torch.zeros(self.depth, Bn, H, lpad, 64, dtype=torch.bfloat16, device=dev)
-        vt_all = torch.zeros(self.depth, Bn, H, 64, lpad, dtype=torch.bfloat16, device=dev)
-        caf = ca.contiguous().float()
-        cn = ws.get('ctx_n', (Bn * Lc, Cd), torch.bfloat16)
-        for i, q in enumerate(P['blocks']):
-            ops.norm_modulate(caf, cn, Bn * Lc, Cd, kind=1, eps=1e-5, weight=q['ynorm'])       # the BLOCK's attention_y_norm
-            ops.gemm(cn, q['ckv_w'], None, ops.EPI_HEADS, k_all[i], vt_all[i], M=Bn * Lc, tokens=Lc, tok_pad=lpad, heads=H, head_dim=64,
-                     transpose_mask=0b10)
+        k_all, vt_all, lpad = self._cross_kv(ca, Bn, Lc, block_norm=True)               # the BLOCK's attention_y_norm
         return self._fold_uc({'k': k_all, 'vt': vt_all, 'Lc': Lc, 'lpad': lpad, 'Bn': Bn, 'cls': cls,
                               'dino': torch.zeros(Bn, 0, D, device=dev, dtype=torch.bfloat16)}, ca)
 

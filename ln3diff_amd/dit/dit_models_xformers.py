@@ -226,6 +226,36 @@ class Workspace:
         return t
 
 
+def pack_caption(P, pfx, emb, device):
+    """CaptionEmbedder MLP weights -> P[pfx + '_w1' / '_b1' / '_w2' / '_b2'] (bf16 GEMM operands, fp32 biases)."""
+    mlp = emb.y_proj
+    P[pfx + '_w1'], P[pfx + '_b1'] = bf16(mlp.fc1.weight, device), f32(mlp.fc1.bias, device)
+    P[pfx + '_w2'], P[pfx + '_b2'] = bf16(mlp.fc2.weight, device), f32(mlp.fc2.bias, device)
+
+
+def pack_block(b, H, Dh, device):
+    """One block's GEMM operands and norm weights.  What is packed follows the submodules the block has: pre-norm weights
+    (None for the affine-free LayerNorm), qk-norms of the self- and cross-attention (None without), the cross-attention and
+    the block's own attention_y_norm when present."""
+    q = {}
+    q['n1'], q['n2'] = (f32(b.norm1.weight, device), f32(b.norm2.weight, device)) if hasattr(b, 'norm1') else (None, None)
+    q['qkv_w'], q['qkv_b'] = bf16(b.attn.qkv.weight, device), f32(b.attn.qkv.bias, device)
+    padw = lambda w: torch.nn.functional.pad(w.detach().float(), (0, attn_head_pad(Dh) - Dh))     # zero beyond the true head size
+    q['qn'], q['kn'] = (f32(padw(b.attn.q_norm.weight), device), f32(padw(b.attn.k_norm.weight), device)) if b.attn.qk_norm else (None, None)
+    q['proj_w'], q['proj_b'] = bf16(pad_head_columns(b.attn.proj.weight.detach(), H, Dh), device), f32(b.attn.proj.bias, device)
+    if hasattr(b, 'cross_attn'):
+        ca = b.cross_attn
+        q['cq_w'] = bf16(ca.to_q.weight, device)
+        q['ckv_w'] = bf16(torch.cat([ca.to_k.weight, ca.to_v.weight], 0), device)
+        q['cqn'], q['ckn'] = (f32(ca.q_norm.weight, device), f32(ca.k_norm.weight, device)) if ca.qk_norm else (None, None)
+        q['co_w'], q['co_b'] = bf16(ca.to_out[0].weight, device), f32(ca.to_out[0].bias, device)
+    if hasattr(b, 'attention_y_norm'):
+        q['ynorm'] = f32(b.attention_y_norm.weight, device)
+    q['fc1_w'], q['fc1_b'] = bf16(b.mlp.mlp[0].weight, device), f32(b.mlp.mlp[1].bias, device)
+    q['fc2_w'], q['fc2_b'] = bf16(b.mlp.mlp[2].weight, device), f32(b.mlp.mlp[3].bias, device)
+    return q
+
+
 def attn_head_pad(Dh):
     """Head size the attention kernel runs at: 64, 80 and 128 natively; smaller heads (the U-Net's 32 / 40) zero-padded to 64, 65 - 80
     (DiT-XL/2: 72, the U-Net's 80) stored 80 wide (r6: the K / V^T stream of such a launch is what bounds it, 80 wide is 5/8 of the

@@ -23,7 +23,7 @@ import torch.nn as nn
 from .. import ops, _cache
 from .dit_models_xformers import (CaptionEmbedder, DiTBlock, FinalLayer, PatchEmbed, T2IFinalLayer,  # noqa: F401
                                   TextCondDiTBlock, TimestepEmbedder, Workspace, bf16, f32,
-                                  get_2d_sincos_pos_embed, self_attention_hip, pad_head_columns)
+                                  get_2d_sincos_pos_embed, self_attention_hip, pack_block, pack_caption)
 
 
 class DiT(nn.Module):
@@ -86,23 +86,6 @@ class DiT(nn.Module):
         _cache.bump()
         return super()._apply(fn, *a, **k)
 
-    def flat_weights(self):
-        """All packed device tensors (for the one-buffer RCCL broadcast in ln3diff_amd.parallel)."""
-        self._ensure_packed(next(self.parameters()).device)
-        out = []
-
-        def walk(o):
-            if isinstance(o, torch.Tensor):
-                out.append(o)
-            elif isinstance(o, dict):
-                for v in o.values():
-                    walk(v)
-            elif isinstance(o, (list, tuple)):
-                for v in o:
-                    walk(v)
-        walk(self._packed)
-        return out
-
 
 class DiT_TriLatent(DiT):
     def __init__(self, input_size=32, patch_size=2, in_channels=4, hidden_size=1152, depth=28, num_heads=16,
@@ -125,34 +108,112 @@ class DiT_TriLatent(DiT):
     def _ensure_packed(self, device):
         if _cache.fresh(self._packed, device):
             return
+        H = self.num_heads
+        P = {'device': device}
+        self._pack_embedder(P, device)
+        P['t_w0'], P['t_b0'] = bf16(self.t_embedder.mlp[0].weight, device), f32(self.t_embedder.mlp[0].bias, device)
+        P['t_w2'], P['t_b2'] = bf16(self.t_embedder.mlp[2].weight, device), f32(self.t_embedder.mlp[2].bias, device)
+        if getattr(self, 'clip_text_proj', None) is not None:
+            pack_caption(P, 'c', self.clip_text_proj, device)
+        shared = getattr(self, 'adaLN_modulation', None)
+        if shared is not None:                                           # PixArt: ONE shared adaLN + per-block tables
+            ada = [shared[1]]
+            P['sst'] = f32(torch.stack([b.scale_shift_table.reshape(-1) for b in self.blocks], 0), device)   # [depth, 6D]
+        else:                                     # every block's own adaLN (and a FinalLayer's), one GEMM: [depth*6D (+2D), D]
+            ada = [m.adaLN_modulation[1] for m in (*self.blocks, self.final_layer) if m.adaLN_modulation is not None]
+        P['ada_w'], P['ada_b'] = bf16(torch.cat([a.weight for a in ada], 0), device), f32(torch.cat([a.bias for a in ada], 0), device)
+        self._pack_prompt(P, device)
+        P['blocks'] = [pack_block(b, H, self.embed_dim // H, device) for b in self.blocks]
+        P['fin_w'], P['fin_b'] = f32(self.final_layer.linear.weight, device), f32(self.final_layer.linear.bias, device)
+        self._packed = _cache.stamp(P, self)
+        self._ws = Workspace(device)
+
+    def _pack_embedder(self, P, device):
         D = self.embed_dim
-        P = _cache.stamp({'device': device}, self)
         P['pe_w'] = f32(self.x_embedder.proj.weight.reshape(D, -1), device)
         P['pe_b'] = f32(self.x_embedder.proj.bias, device)
         P['pos'] = f32(self.pos_embed[0], device)
-        P['t_w0'], P['t_b0'] = bf16(self.t_embedder.mlp[0].weight, device), f32(self.t_embedder.mlp[0].bias, device)
-        P['t_w2'], P['t_b2'] = bf16(self.t_embedder.mlp[2].weight, device), f32(self.t_embedder.mlp[2].bias, device)
-        cp = self.clip_text_proj.y_proj
-        P['c_w1'], P['c_b1'] = bf16(cp.fc1.weight, device), f32(cp.fc1.bias, device)
-        P['c_w2'], P['c_b2'] = bf16(cp.fc2.weight, device), f32(cp.fc2.bias, device)
-        ada_w = [b.adaLN_modulation[1].weight for b in self.blocks] + [self.final_layer.adaLN_modulation[1].weight]
-        ada_b = [b.adaLN_modulation[1].bias for b in self.blocks] + [self.final_layer.adaLN_modulation[1].bias]
-        P['ada_w'], P['ada_b'] = bf16(torch.cat(ada_w, 0), device), f32(torch.cat(ada_b, 0), device)
-        blks = []
-        for b in self.blocks:
-            q = {}
-            q['qkv_w'], q['qkv_b'] = bf16(b.attn.qkv.weight, device), f32(b.attn.qkv.bias, device)
-            q['proj_w'], q['proj_b'] = bf16(pad_head_columns(b.attn.proj.weight.detach(), self.num_heads, self.embed_dim // self.num_heads), device), f32(b.attn.proj.bias, device)
-            q['cq_w'] = bf16(b.cross_attn.to_q.weight, device)
-            q['ckv_w'] = bf16(torch.cat([b.cross_attn.to_k.weight, b.cross_attn.to_v.weight], 0), device)
-            q['co_w'], q['co_b'] = bf16(b.cross_attn.to_out[0].weight, device), f32(b.cross_attn.to_out[0].bias, device)
-            q['fc1_w'], q['fc1_b'] = bf16(b.mlp.mlp[0].weight, device), f32(b.mlp.mlp[1].bias, device)
-            q['fc2_w'], q['fc2_b'] = bf16(b.mlp.mlp[2].weight, device), f32(b.mlp.mlp[3].bias, device)
-            blks.append(q)
-        P['blocks'] = blks
-        P['fin_w'], P['fin_b'] = f32(self.final_layer.linear.weight, device), f32(self.final_layer.linear.bias, device)
-        self._packed = P
-        self._ws = Workspace(device)
+
+    def _pack_prompt(self, P, device):
+        """model-level weights of the prompt-side preparation beyond the caption MLP (none here)"""
+
+    # ------------------------------------------------------------------ context helpers shared by every denoiser of the family
+    def _caption_mlp(self, x, pfx, out):
+        """CaptionEmbedder (Linear -> tanh-GELU -> Linear) with the packed weights P[pfx + '_w1' ...] of x [..., C] -> out [..., D]:
+        bf16 tokens or fp32 rows, by out's dtype."""
+        P, ws = self._packed, self._ws
+        R = x.numel() // x.shape[-1]
+        xb = ws.get('cap_in', (R, x.shape[-1]), torch.bfloat16)
+        ops.cast_bf16(x.contiguous().float(), xb)
+        h1 = ws.get('cap_h', (R, self.embed_dim), torch.bfloat16)
+        ops.gemm(xb, P[pfx + '_w1'], P[pfx + '_b1'], ops.EPI_GELU_TANH, h1)
+        ops.gemm(h1, P[pfx + '_w2'], P[pfx + '_b2'], ops.EPI_BF16 if out.dtype == torch.bfloat16 else ops.EPI_F32, out)
+        return out
+
+    def _cross_kv(self, ctx, Bn, Lk, block_norm=False):
+        """Every block's cross-attention K / V^T (and the block's k-norm, if it has one) of the context: ctx [Bn*Lk, C] bf16, or with
+        block_norm the raw context [Bn, Lk, C], normalised by each block's own attention_y_norm in front of that block's GEMM."""
+        P, H = self._packed, self.num_heads
+        lpad = (Lk + 63) // 64 * 64
+        dev = ctx.device
+        k_all = torch.zeros(self.depth, Bn, H, lpad, 64, dtype=torch.bfloat16, device=dev)
+        vt_all = torch.zeros(self.depth, Bn, H, 64, lpad, dtype=torch.bfloat16, device=dev)
+        if block_norm:
+            raw, C = ctx.contiguous().float(), ctx.shape[-1]
+            ctx = self._ws.get('ctx_n', (Bn * Lk, C), torch.bfloat16)
+        for i, q in enumerate(P['blocks']):
+            if block_norm:
+                ops.norm_modulate(raw, ctx, Bn * Lk, C, kind=1, eps=1e-5, weight=q['ynorm'])
+            ops.gemm(ctx, q['ckv_w'], None, ops.EPI_HEADS, k_all[i], vt_all[i], M=Bn * Lk, tokens=Lk, tok_pad=lpad, heads=H,
+                     head_dim=64, transpose_mask=0b10)
+            if q['ckn'] is not None:
+                ops.rmsnorm_heads(k_all[i], q['ckn'], Bn * H * lpad, 64)
+        return k_all, vt_all, lpad
+
+    _uc_first = True                   # the unconditional CFG samples lead the batch: VanillaCFG's [uc, c] order
+
+    def _fold_uc(self, cc, rows):
+        """Samples whose cross-attention context rows are all IDENTICAL - the zero embeddings of the unconditional CFG branch
+        (force_uc_zero_embeddings, sgm_DiffusionEngine.py:448-452; pipeline._zero_uc; every K / V row of a sample is a row-wise
+        function of its context row, so they are identical too): every key of such a sample is the same vector, softmax over
+        identical scores is uniform whatever the query, and the cross-attention sub-block is the constant to_out(v) + b per
+        (layer, sample).  For a run of such samples at the unconditional end of the batch (leading when _uc_first, else trailing:
+        the flow-matching engine's [c, uc]) the constants are computed here, once per prompt, with the same kernels (bf16 V row ->
+        to_out GEMM, fp32 accumulate); forward() adds them in the gate / residual epilogue of the self-attention projection and runs
+        to_q / attention / to_out on the other samples only (LN3D_NO_UC_FOLD=1: off).  `rows`: [Bn, L, C] raw context the K / V
+        were made from.  A batch that is uniform throughout is not folded (with one context row, every batch is)."""
+        cc['fold'] = 0
+        Bn = cc['Bn']
+        if os.environ.get('LN3D_NO_UC_FOLD') or cc['Lc'] < 2 or Bn < 2:
+            return cc
+        same = (rows == rows[:, :1]).flatten(1).all(1).tolist()              # one host read per prompt
+        if not self._uc_first:
+            same.reverse()
+        fold = 0
+        while fold < Bn and same[fold]:
+            fold += 1
+        if not 0 < fold < Bn:
+            return cc
+        P, H, D = self._packed, self.num_heads, self.embed_dim
+        uc = slice(0, fold) if self._uc_first else slice(Bn - fold, Bn)
+        const = torch.zeros(self.depth, Bn, D, dtype=torch.float32, device=rows.device)       # the other samples' rows stay 0
+        for i, q in enumerate(P['blocks']):
+            v_row = cc['vt'][i, uc, :, :, 0].reshape(fold, H * 64).contiguous()        # V^T[b, h, d, key 0] = the attention output
+            ops.gemm(v_row, q['co_w'], q['co_b'], ops.EPI_F32, const[i, uc])
+        cc['fold'], cc['const'] = fold, const
+        return cc
+
+    def _fc1(self, probe, i, hb, q, f1):
+        """Block i's MLP fc1 GEMM (erf-GELU epilogue).  `probe`: bench.py's `_fc1_probe` measurement hook {'layer', 'events', 'max'}:
+        HIP events on the launch stream around this one GEMM of that layer, inside the real step."""
+        if probe is not None and i == probe['layer'] and len(probe['events']) < probe['max']:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            ops.gemm(hb, q['fc1_w'], q['fc1_b'], ops.EPI_GELU_ERF, f1)
+            e1.record()
+            probe['events'].append((e0, e1))
+        else:
+            ops.gemm(hb, q['fc1_w'], q['fc1_b'], ops.EPI_GELU_ERF, f1)
 
     # ------------------------------------------------------------------ context (constant per prompt)
     def prepare_context(self, context):
@@ -160,52 +221,18 @@ class DiT_TriLatent(DiT):
         samplers call this once per run instead of once per step (the reference recomputes them 250x)."""
         if isinstance(context, dict):
             context = context['crossattn']
-        dev = context.device
-        self._ensure_packed(dev)
-        P, ws = self._packed, self._ws
-        Bn, Lc, Cd = context.shape
-        D, H = self.embed_dim, self.num_heads
-        lpad = (Lc + 63) // 64 * 64
-        cb = ws.get('ctx_bf', (Bn * Lc, Cd), torch.bfloat16)
-        ops.cast_bf16(context.contiguous().float(), cb)
-        h1 = ws.get('ctx_h1', (Bn * Lc, D), torch.bfloat16)
-        ops.gemm(cb, P['c_w1'], P['c_b1'], ops.EPI_GELU_TANH, h1)
-        cp = ws.get('ctx_p', (Bn * Lc, D), torch.bfloat16)
-        ops.gemm(h1, P['c_w2'], P['c_b2'], ops.EPI_BF16, cp)
-        dh = 64
-        k_all = torch.zeros(self.depth, Bn, H, lpad, dh, dtype=torch.bfloat16, device=dev)
-        vt_all = torch.zeros(self.depth, Bn, H, dh, lpad, dtype=torch.bfloat16, device=dev)
-        for i, q in enumerate(P['blocks']):
-            ops.gemm(cp, q['ckv_w'], None, ops.EPI_HEADS, k_all[i], vt_all[i], M=Bn * Lc, tokens=Lc, tok_pad=lpad,
-                     heads=H, head_dim=dh, transpose_mask=0b10)
+        self._ensure_packed(context.device)
+        Bn, Lc, _ = context.shape
+        cp = self._caption_mlp(context, 'c', self._ws.get('ctx_p', (Bn * Lc, self.embed_dim), torch.bfloat16))
+        k_all, vt_all, lpad = self._cross_kv(cp, Bn, Lc)
         # K copy whose 64 head dims are stored in the 16-group order [0-3, 8-11, 4-7, 12-15]: the order in which the query
         # projection's accumulators hand q to the MFMA when cross-attention runs inside that GEMM (LN3D_EPI_CROSS_ATTN)
-        kp_all = k_all[..., ops.vt_key_order(dh, dev)].contiguous()
-        cc = {'k': k_all, 'kp': kp_all, 'vt': vt_all, 'Lc': Lc, 'lpad': lpad, 'Bn': Bn, 'fold': 0}
-        # Samples whose context rows are all IDENTICAL - the zero embeddings of the unconditional CFG branch (force_uc_zero_embeddings,
-        # sgm_DiffusionEngine.py:448-452; the caption MLP turns them into 77 copies of one row): every key of such a sample is the same
-        # vector, softmax over identical scores is uniform whatever the query, and the cross-attention sub-block is the constant
-        # to_out(v) + b per (layer, sample).  For a leading run of such samples ([uc, c] order) the constants are computed here, once
-        # per prompt, with the same kernels (bf16 V row -> to_out GEMM, fp32 accumulate), and forward() adds them in the epilogue of
-        # the preceding GEMM instead of running to_q / attention / to_out on those rows (LN3D_NO_UC_FOLD=1: off).
-        if not os.environ.get('LN3D_NO_UC_FOLD') and Lc > 1 and Bn > 1:
-            same = (context == context[:, :1]).flatten(1).all(1)                 # [Bn]: one host read per prompt
-            fold = 0
-            for v in same.tolist():
-                if not v:
-                    break
-                fold += 1
-            if 0 < fold < Bn:
-                const = torch.zeros(self.depth, Bn, D, dtype=torch.float32, device=dev)      # rows >= fold stay 0
-                for i, q in enumerate(P['blocks']):
-                    v_row = vt_all[i, :fold, :, :, 0].reshape(fold, H * dh).contiguous()     # V^T[b, h, d, key 0] = the attention output
-                    ops.gemm(v_row, q['co_w'], q['co_b'], ops.EPI_F32, const[i, :fold])
-                cc['fold'], cc['const'] = fold, const
-        return cc
+        kp_all = k_all[..., ops.vt_key_order(64, context.device)].contiguous()
+        return self._fold_uc({'k': k_all, 'kp': kp_all, 'vt': vt_all, 'Lc': Lc, 'lpad': lpad, 'Bn': Bn}, context)
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
-    def _modulation(self, timesteps, mod, tag):
+    def _timestep_modulation(self, timesteps, mod, tag):
         """t -> sincos(256) -> MLP -> SiLU -> adaLN Linear of every block + final layer, all rows of `timesteps` at once."""
         P, ws, D = self._packed, self._ws, self.embed_dim
         R = timesteps.shape[0]
@@ -236,7 +263,7 @@ class DiT_TriLatent(DiT):
         if n * rows * nmod * 4 > self.MODCACHE_MAX_BYTES:
             return None
         mod_all = self._ws.get('mod_all', (n * rows, nmod), torch.float32)
-        self._modulation(t_table[:, :rows].reshape(-1).to(dev), mod_all, 'ma')
+        self._timestep_modulation(t_table[:, :rows].reshape(-1).to(dev), mod_all, 'ma')
         return {'mod': mod_all, 'rows': rows}
 
     def forward(self, x, timesteps=None, context=None, y=None, get_attr='', context_cache=None, in_scale=None,
@@ -270,7 +297,7 @@ class DiT_TriLatent(DiT):
             ld = nmod if rows == Bn else 0                     # one shared row per step: every sample reads row 0
         else:
             mod = ws.get('mod', (Bn, nmod), torch.float32)
-            self._modulation(timesteps, mod, 'm')
+            self._timestep_modulation(timesteps, mod, 'm')
 
         # -- tokens
         xt = ws.get('x', (M, D), torch.float32)
@@ -320,16 +347,7 @@ class DiT_TriLatent(DiT):
                 ops.attention(qc, cc['k'][i][fold:], cc['vt'][i][fold:], oc[r0:], Bn - fold, H, N, N, cc['Lc'], cc['lpad'], 64)
             ops.gemm(oc[r0:], q['co_w'], q['co_b'], ops.EPI_GATE_RES, xt[r0:])
             ops.norm_modulate(xt, hb, M, D, kind=0, eps=1e-6, shift=sh_m, scale=sc_m, mod_rows=N, mod_ld=ld)
-            fc1 = lambda: ops.gemm(hb, q['fc1_w'], q['fc1_b'], ops.EPI_GELU_ERF, f1)
-            if probe is not None and i == probe['layer'] and len(probe['events']) < probe['max']:
-                # measurement hook (bench.py): HIP events on the launch stream around this one GEMM, inside the real step
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fc1()
-                e1.record()
-                probe['events'].append((e0, e1))
-            else:
-                fc1()
+            self._fc1(probe, i, hb, q, f1)
             ops.gemm(f1, q['fc2_w'], q['fc2_b'], ops.EPI_GATE_RES, xt, gate=g_m, gate_rows=N, gate_ld=ld)
 
         of = depth * 6 * D
