@@ -1,4 +1,4 @@
-"""ctypes binding of libln3d_hip.so (the C ABI of include/ln3d.h and include/ln3d_encoder.h).
+"""ctypes binding of libln3d_hip.so (the C ABI of include/ln3d.h, include/ln3d_encoder.h and include/ln3d_shapenet.h).
 
 There is NO fallback: if the library is missing or a kernel launch fails the product raises.
 """
@@ -20,6 +20,9 @@ SYMBOLS = [
     "ln3d_mix_prediction",
     # include/ln3d_encoder.h (the multi-view VAE encoder)
     "ln3d_im2col3x3_pad01", "ln3d_frame_mean", "ln3d_mv_posterior",
+    # include/ln3d_shapenet.h (the ShapeNet VAE decoder class)
+    "ln3d_triplane_axis_attention", "ln3d_sr_unpatchify", "ln3d_resize_bilinear_cl", "ln3d_resize_add_lrelu", "ln3d_rollout_means",
+    "ln3d_im2col3x3_rollout",
 ]
 
 EPI_F32, EPI_BF16, EPI_GELU_ERF, EPI_GELU_TANH, EPI_SILU, EPI_GATE_RES, EPI_HEADS, EPI_F32_SILU, EPI_QUICK_GELU, EPI_CROSS_ATTN = range(10)

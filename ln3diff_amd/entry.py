@@ -34,11 +34,16 @@ _IGNORED_DEFAULTS = dict(lr=5e-5, batch_size=1, microbatch=-1, ema_rate='0.9999'
 # refused (with the reason) when set to something this build does not implement - silently dropping them would change what is
 # sampled.  (name: (default, {allowed values} or None = any, engines it matters for, message))
 _RELEASED_DECODER = 'vit.vit_triplane.RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout_withSD_D_ditDecoder'
+# the ShapeNet launchers' decoder (sample_shapenet_{car,chair,plane}_t23d.sh): a DINOv2 ViT-B decoder + roll-out SR convs, selected
+# with the U-Net denoiser (--create_dit false) under the guided_diffusion engines; only with this class are --cfg / --ray_start /
+# --ray_end read (vit/vit_triplane_shapenet.py)
+_SHAPENET_DECODER = 'vit.vit_triplane.RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn'
 _CHECKED = {
     'mixed_prediction': (False, None, ('edm', 'flow', 'gd'), None),      # see validate(): the U-Net denoiser (--create_dit false) has it
     'predict_v': (False, None, ('gd',), None),            # see validate(): only the guided_diffusion engines read them
     'pred_type': ('eps', None, ('gd',), None),            # (guided_diffusion/script_util.py:36-37,84,682-686: predict_v -> ModelMeanType.V)
-    'ae_classname': (_RELEASED_DECODER, {_RELEASED_DECODER}, ('edm', 'flow', 'gd'), "only the released decoder class is built"),
+    'ae_classname': (_RELEASED_DECODER, {_RELEASED_DECODER, _SHAPENET_DECODER}, ('edm', 'flow', 'gd'),
+                     "only the released decoder class is built (and, with --create_dit false, the ShapeNet launchers' one)"),
     'vae_p': (2, {2}, ('edm', 'flow', 'gd'), "the decoder tokeniser is built for vae_p = 2"),
     'denoise_out_channels': (4, None, ('edm', 'flow', 'gd'), None),
     'decoder_in_chans': (32, {32}, ('edm', 'flow', 'gd'), "tri-plane feature width 32 (OSGDecoder 32 -> 64 -> 4)"),
@@ -82,7 +87,8 @@ def create_argparser(objaverse=True):
         # those launchers pass neither flag, so run verbatim they select the U-Net with a 12-channel latent, as in the reference
         create_dit=objaverse, num_channels=320, num_res_blocks=2, channel_mult='', attention_resolutions='4,2,1', num_heads=8,
         num_head_channels=-1, num_heads_upsample=-1, use_scale_shift_norm=True, use_spatial_transformer=True, transformer_depth=1,
-        dropout=0.0, mixing_logit_init=-6.0)
+        dropout=0.0, mixing_logit_init=-6.0,
+        ray_start=0.6, ray_end=1.8)          # nsr/script_util.py triplane_decoder_defaults; read by the ShapeNet decoder class only
     d.update(_IGNORED_DEFAULTS)
     d.update({k: v[0] for k, v in _CHECKED.items()})
     ap = argparse.ArgumentParser(allow_abbrev=False)
@@ -137,6 +143,15 @@ def validate(args):
         val = getattr(args, name)
         if allowed is not None and kind in kinds and val not in allowed:
             raise SystemExit(f"--{name} {val}: {why} (supported: {sorted(allowed, key=str)})")
+    if args.ae_classname == _SHAPENET_DECODER:
+        if kind != 'gd' or not unet:
+            raise SystemExit(f"--ae_classname {args.ae_classname}: the ShapeNet decoder class goes with the U-Net denoiser "
+                             "(--create_dit false) under --trainer_name adm / ddpm / vpsde_crossattn, as its launchers run it")
+        from .vit.vit_triplane_shapenet import shapenet_rendering_kwargs
+        try:
+            shapenet_rendering_kwargs(args.cfg, args.ray_start, args.ray_end)
+        except ValueError as e:
+            raise SystemExit(str(e))
     if args.denoise_out_channels != args.denoise_in_channels:
         raise SystemExit(f"--denoise_out_channels {args.denoise_out_channels} != --denoise_in_channels {args.denoise_in_channels}: the "
                          "samplers update the latent in place with the network output (learn_sigma False)")
@@ -169,9 +184,8 @@ def build_models(args, dev, rank):
     common = dict(input_size=args.diffusion_input_size, num_classes=0, learn_sigma=args.learn_sigma,
                   in_channels=args.denoise_in_channels, roll_out=args.roll_out)
     if not args.create_dit:
-        # guided_diffusion/script_util.py:255-451 create_model, U-Net branch (the ShapeNet / FFHQ launchers): the released VAE decoder of
-        # those launchers (ViT-B decoder + 32-channel renderer + NearestConvSR) is not built - the latent is decoded by the released
-        # Objaverse decoder class like every other denoiser's here
+        # guided_diffusion/script_util.py:255-451 create_model, U-Net branch (the ShapeNet / FFHQ launchers): their latent is decoded by
+        # the ShapeNet decoder class when --ae_classname names it (below), otherwise by the released Objaverse decoder class
         from .guided_diffusion.unet import create_unet
         dit = create_unet(args.diffusion_input_size, args.num_channels, args.num_res_blocks, channel_mult=args.channel_mult,
                           learn_sigma=args.learn_sigma, attention_resolutions=args.attention_resolutions, num_heads=args.num_heads,
@@ -190,10 +204,19 @@ def build_models(args, dev, rank):
         dit = I23D[args.dit_model_arch](context_dim=ctx_dim, pooling_ctx_dim=768, **common)
     else:
         dit = T23D[args.dit_model_arch](context_dim=args.context_dim, vit_blk=TextCondDiTBlock, **common)
-    vit = DiT2_models[args.arch_dit_decoder](input_size=16, num_classes=0, learn_sigma=False, in_channels=dit.embed_dim,
-                                             mixed_prediction=False, context_dim=None, roll_out=True, plane_n=3)
-    dec = Dec(vit_decoder=vit, triplane_decoder=Triplane(img_resolution=args.image_size), cls_token=False, vae_p=2, ldm_z_channels=4,
-              ldm_embed_dim=4)
+    if args.ae_classname == _SHAPENET_DECODER:
+        # --arch_decoder vitb (DINOv2 ViT-B/14), --decoder_output_dim 32, --out_chans 96, --decoder_in_chans 32; --cfg / --ray_start /
+        # --ray_end give the renderer preset (nsr/script_util.py:679-700)
+        from .vit.vit_triplane_shapenet import RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn as ShapeNetDec, dinov2_vitb14, \
+            shapenet_rendering_kwargs
+        tp = Triplane(img_resolution=args.image_size, rendering_kwargs=shapenet_rendering_kwargs(args.cfg, args.ray_start, args.ray_end),
+                      decoder_in_chans=args.decoder_in_chans, decoder_output_dim=args.decoder_output_dim)
+        dec = ShapeNetDec(dinov2_vitb14(), tp, cls_token=False, vae_p=2, ldm_z_channels=4, ldm_embed_dim=4)
+    else:
+        vit = DiT2_models[args.arch_dit_decoder](input_size=16, num_classes=0, learn_sigma=False, in_channels=dit.embed_dim,
+                                                 mixed_prediction=False, context_dim=None, roll_out=True, plane_n=3)
+        dec = Dec(vit_decoder=vit, triplane_decoder=Triplane(img_resolution=args.image_size), cls_token=False, vae_p=2, ldm_z_channels=4,
+                  ldm_embed_dim=4)
     dit, dec = dit.to(dev), dec.to(dev)
     got = {'dit': None, 'decoder': None}                  # which file gave each component its weights
     if rank == 0:

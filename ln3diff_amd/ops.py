@@ -372,3 +372,62 @@ def mv_posterior(h, qw, qb, eps, B, F, E=4):
                                       _p(out['mean']), _p(out['logvar']), _p(out['z']), _p(out['latent_tok']), _p(out['log_q']),
                                       _p(out['entropy']), B, F, HW, E, _stream()), "mv_posterior")
     return out
+
+
+# ---------------------------------------------------------------- ShapeNet VAE decoder class (include/ln3d_shapenet.h, csrc/shapenet_ops.hip)
+def _need(cond, msg):
+    if not cond:
+        raise ValueError(msg)
+
+
+def triplane_axis_attention(qkv, out, B, p, H, scale=None):
+    """qkv f32 [B*3*p*p, >= 3*H*64] ([q | k | v] columns) -> out bf16 [B*3*p*p, H*64]: plane i's query at (y, x) attends to row y of
+    plane (i+1) % 3 and column x of plane (i+2) % 3 (Conv3DCrossAttentionBlockXformerMHANested)."""
+    _chk_dev(qkv, out)
+    rows, D = B * 3 * p * p, H * 64
+    _need(qkv.dtype == torch.float32 and qkv.stride(-1) == 1 and qkv.shape[0] == rows and qkv.shape[1] >= 3 * D,
+          "triplane_axis_attention: qkv must be f32 [B*3*p*p, >= 3*H*64] with unit column stride")
+    _need(out.dtype == torch.bfloat16 and out.is_contiguous() and out.numel() == rows * D, "triplane_axis_attention: out bf16 [rows, H*64]")
+    L.check(L.lib().ln3d_triplane_axis_attention(_p(qkv), C.c_int64(qkv.stride(0)), _p(out), B, p, H, C.c_float(scale or 64 ** -0.5),
+                                                 _stream()), "triplane_axis_attention")
+
+
+def sr_unpatchify(pred, planes, mixed, B, S, P, Cc):
+    _chk_dev(pred, planes, mixed)
+    n = B * 3 * S * P * S * P * Cc
+    _need(pred.dtype == torch.float32 and pred.is_contiguous() and pred.numel() == n, "sr_unpatchify: pred f32 [B, 3*S*S, P*P*C]")
+    _need(planes.dtype == torch.float32 and planes.is_contiguous() and planes.numel() == n, "sr_unpatchify: planes f32 [B, 3, R, R, C]")
+    _need(mixed.dtype == torch.bfloat16 and mixed.is_contiguous() and mixed.numel() == n, "sr_unpatchify: mixed bf16 [B, 3, R, R, C]")
+    L.check(L.lib().ln3d_sr_unpatchify(_p(pred), _p(planes), _p(mixed), B, S, P, Cc, _stream()), "sr_unpatchify")
+
+
+def resize_bilinear_cl(x, y, N, h, w, Ho, Wo, Cc, transpose=False):
+    _chk_dev(x, y)
+    _need(x.dtype == torch.float32 and x.is_contiguous() and x.numel() == N * h * w * Cc, "resize_bilinear_cl: x f32 [N, h, w, C]")
+    _need(y.dtype == torch.bfloat16 and y.is_contiguous() and y.numel() == N * Ho * Wo * Cc, "resize_bilinear_cl: y bf16 [N, Ho, Wo, C]")
+    L.check(L.lib().ln3d_resize_bilinear_cl(_p(x), _p(y), N, h, w, Ho, Wo, Cc, int(bool(transpose)), _stream()), "resize_bilinear_cl")
+
+
+def resize_add_lrelu(base, t, out, N, h, w, Ho, Wo, Cc, slope=0.01):
+    _chk_dev(base, t, out)
+    _need(base.dtype == torch.float32 and base.is_contiguous() and base.numel() == N * h * w * Cc, "resize_add_lrelu: base f32 [N, h, w, C]")
+    for z in (t, out):
+        _need(z.dtype == torch.float32 and z.is_contiguous() and z.numel() == N * Ho * Wo * Cc, "resize_add_lrelu: t / out f32 [N, Ho, Wo, C]")
+    L.check(L.lib().ln3d_resize_add_lrelu(_p(base), _p(t), _p(out), N, h, w, Ho, Wo, Cc, C.c_float(slope), _stream()), "resize_add_lrelu")
+
+
+def rollout_means(x, rowmean, colmean, N, H, W, Cc):
+    _chk_dev(x, rowmean, colmean)
+    _need(x.is_contiguous() and x.numel() == N * H * W * Cc and rowmean.numel() == N * H * Cc and colmean.numel() == N * W * Cc,
+          "rollout_means: x [N, H, W, C], rowmean [N, H, C], colmean [N, W, C] (f32, contiguous)")
+    L.check(L.lib().ln3d_rollout_means(_p(x), _p(rowmean), _p(colmean), N, H, W, Cc, _stream()), "rollout_means")
+
+
+def im2col3x3_rollout(x, rowmean, colmean, col, plane, H, W, Cc, Kpad):
+    """x f32 [3, H, W, C] (one object), rowmean [3, H, C], colmean [3, W, C] -> col bf16 [H*W, Kpad] of plane `plane`'s roll-out conv."""
+    _chk_dev(x, rowmean, colmean, col)
+    _need(x.dtype == torch.float32 and x.is_contiguous() and x.numel() == 3 * H * W * Cc, "im2col3x3_rollout: x f32 [3, H, W, C]")
+    _need(rowmean.is_contiguous() and rowmean.numel() == 3 * H * Cc and colmean.is_contiguous() and colmean.numel() == 3 * W * Cc,
+          "im2col3x3_rollout: rowmean [3, H, C] / colmean [3, W, C]")
+    _need(col.dtype == torch.bfloat16 and col.is_contiguous() and col.numel() == H * W * Kpad, "im2col3x3_rollout: col bf16 [H*W, Kpad]")
+    L.check(L.lib().ln3d_im2col3x3_rollout(_p(x), _p(rowmean), _p(colmean), _p(col), plane, H, W, Cc, Kpad, _stream()), "im2col3x3_rollout")

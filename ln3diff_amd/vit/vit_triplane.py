@@ -362,3 +362,12 @@ class RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout
         pts = torch.stack(torch.meshgrid(ax, ax, ax, indexing='ij'), dim=-1).reshape(1, -1, 3).expand(N, -1, -1)
         f = self.forward_points(pcl, pts)
         return {k: v.reshape(N, grid_size, grid_size, grid_size, -1) for k, v in f.items()}
+
+
+def __getattr__(name):
+    """The ShapeNet launchers' decoder class (--ae_classname vit.vit_triplane.RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn)
+    lives in vit_triplane_shapenet, which imports this module; it is re-exported here lazily."""
+    if name == 'RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn':
+        from . import vit_triplane_shapenet
+        return vit_triplane_shapenet.RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

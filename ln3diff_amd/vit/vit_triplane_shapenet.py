@@ -1,0 +1,467 @@
+"""The ShapeNet VAE decoder class (latent [B,12,32,32] -> planes [B,96,256,256] -> renders / grids) on the HIP path.
+
+Mirrors `RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn` of the reference (vit/vit_triplane.py:802-1121, with the parts of its
+base ViTTriplaneDecomposed :130 that the decode path reaches), same class name and state-dict keys, so that the ShapeNet launchers'
+`--ae_classname vit.vit_triplane.RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn` and their checkpoints load.
+
+Network (launchers: --arch_decoder vitb, DINOv2 ViT-B/14 from torch.hub, --out_chans 96, --decoder_in_chans 32):
+  ldm_upsample   PatchEmbedTriplane 12 -> 3 x 768 tokens (ln3d_patch_embed_triplane) + pos_embed [1, 768, 768]
+  vit_decoder    12 DINOv2 blocks in 6 pairs (TriplaneFusionBlockv4_nested_init_from_dino, vit/vision_transformer.py:2062), tokens
+                 viewed as B x 3 planes x 256.  Block 0 of a pair: per-plane self-attention + MLP.  Block 1: its `attn` is a whole
+                 Conv3DCrossAttentionBlockXformerMHANested (norm1 + wq / w_kv / proj) whose output includes its own input, so
+                 x <- x + ls1 * (n + CA(norm1'(n))), n = norm1(x); the cross-plane attention lets plane i's token (y, x) attend to row y
+                 of plane i+1 and column x of plane i+2 (ln3d_triplane_axis_attention).  UViT long skips feed pairs 3 - 5:
+                 x <- x + skip_linear([x, skip]).
+  decoder_pred   Linear 768 -> 4*4*128, unpatchify_triplane p = 4 -> [B, 3*128, 64, 64]
+  conv_sr        RodinConv3D4X_lite_mlp_as_residual_lite (vision_transformer.py:1202 and its base :1047):
+                   res = bilinear_256(short_cut(x viewed [B, 3, L, 128] across the plane groups))
+                   x0  = res + lrelu(groupconv3x3(bilinear_256(x^T)))                  (x^T: the reference's permute(0, 1, 3, 2))
+                   x   = x0 + lrelu(rollout_groupconv3x3(x0))     (plane i reads [x_i | row means of i+1 | column means of i+2])
+Everything runs channel-last; the convolutions are im2col gathers + the MFMA GEMM, one object plane at a time.
+
+Not built: the encoder side (`ldm_downsample` is applied by vae_reparameterization, the ShapeNet VAE encoder itself is not part of
+this package), Triplane.superresolution (every launcher passes --sr_training False; `sr_w_code = w_avg` is carried in the dict and
+nothing reads it).  Batches decode each object independently; the reference's batched cross-plane attention re-orders query rows
+across objects when B > 1, so only B = 1 agrees with it element for element.
+"""
+import torch
+import torch.nn as nn
+
+from .. import ops, _cache
+from ..dit.dit_models_xformers import Workspace, bf16, f32
+from ..nsr.triplane import Triplane
+from .vit_triplane import PatchEmbedTriplane, DiagonalGaussianDistribution, \
+    RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout_withSD_D_ditDecoder as _Objv
+
+# nsr/script_util.py rendering_options_defaults with the defaults of encoder_and_nsr_defaults() + loss_defaults() (c_scale 1,
+# density_reg 0, density_reg_p_dist 0.004, reg_type 'l1'), and the --cfg presets of the ShapeNet launchers (:679-700).  The
+# ray limits come from --ray_start / --ray_end, box_warp = ray_end - ray_start.
+_RENDERING_BASE = dict(image_resolution=256, disparity_space_sampling=False, clamp_mode='softplus', c_gen_conditioning_zero=True, c_scale=1,
+                       superresolution_noise_mode='none', density_reg=0.0, density_reg_p_dist=0.004, reg_type='l1', decoder_lr_mul=1,
+                       decoder_activation='sigmoid', sr_antialias=True, return_triplane_features=False, return_sampling_details_flag=False,
+                       superresolution_module='utils.torch_utils.components.NearestConvSR')
+SHAPENET_CFGS = {
+    'shapenet_tuneray_aug_resolution_64_64_nearestSR': dict(depth_resolution=64, depth_resolution_importance=64, white_back=True,
+                                                            avg_camera_radius=1.2, avg_camera_pivot=[0, 0, 0],
+                                                            superresolution_module='utils.torch_utils.components.NearestConvSR'),
+}
+
+
+def shapenet_rendering_kwargs(cfg, ray_start, ray_end):
+    """rendering_kwargs of a ShapeNet launcher's --cfg / --ray_start / --ray_end; an unknown --cfg raises ValueError."""
+    if cfg not in SHAPENET_CFGS:
+        raise ValueError(f"--cfg {cfg}: the ShapeNet decoder class is built with the presets {sorted(SHAPENET_CFGS)}")
+    rk = dict(_RENDERING_BASE)
+    rk.update(SHAPENET_CFGS[cfg])
+    rk.update(ray_start=float(ray_start), ray_end=float(ray_end), box_warp=float(ray_end) - float(ray_start))
+    return rk
+
+
+# ----------------------------------------------------------------------------- parameter containers (DINOv2 / reference key layout)
+class _Gamma(nn.Module):
+    def __init__(self, D):
+        super().__init__()
+        self.gamma = nn.Parameter(torch.ones(D))
+
+
+class _Attn(nn.Module):
+    def __init__(self, D, heads):
+        super().__init__()
+        self.num_heads = heads
+        self.qkv, self.proj = nn.Linear(D, 3 * D), nn.Linear(D, D)
+
+
+class _Mlp(nn.Module):
+    def __init__(self, D, I):
+        super().__init__()
+        self.fc1, self.fc2 = nn.Linear(D, I), nn.Linear(I, D)
+
+
+class _DinoBlock(nn.Module):                  # dinov2 NestedTensorBlock: norm1, attn, ls1, norm2, mlp, ls2
+    def __init__(self, D, heads):
+        super().__init__()
+        self.norm1, self.attn, self.ls1 = nn.LayerNorm(D, eps=1e-6), _Attn(D, heads), _Gamma(D)
+        self.norm2, self.mlp, self.ls2 = nn.LayerNorm(D, eps=1e-6), _Mlp(D, 4 * D), _Gamma(D)
+
+
+class _PatchEmbed(nn.Module):
+    def __init__(self, D, P):
+        super().__init__()
+        self.proj = nn.Conv2d(3, D, P, P)
+
+
+class DinoVisionTransformer(nn.Module):
+    """Container of torch.hub facebookresearch/dinov2 `dinov2_vit{s,b,l}14` (no registers), the module the reference's ShapeNet
+    launchers pass as `vit_decoder` (nsr/script_util.py:1383-1392).  Only its blocks, norm and (replaced) pos_embed are used."""
+
+    def __init__(self, embed_dim=768, depth=12, num_heads=12, patch_size=14, img_size=518):
+        super().__init__()
+        self.embed_dim, self.num_heads, self.patch_size = embed_dim, num_heads, patch_size
+        self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
+        self.pos_embed = nn.Parameter(torch.zeros(1, (img_size // patch_size) ** 2 + 1, embed_dim))
+        self.mask_token = nn.Parameter(torch.zeros(1, embed_dim))
+        self.patch_embed = _PatchEmbed(embed_dim, patch_size)
+        self.blocks = nn.ModuleList([_DinoBlock(embed_dim, num_heads) for _ in range(depth)])
+        self.norm = nn.LayerNorm(embed_dim, eps=1e-6)
+
+
+def dinov2_vitb14(**kw):
+    return DinoVisionTransformer(768, 12, 12, **kw)
+
+
+class _XYGridAttn(nn.Module):                # xformer_Conv3D_Aware_CrossAttention_xygrid
+    def __init__(self, D, heads):
+        super().__init__()
+        self.num_heads = heads
+        self.wq, self.w_kv, self.proj = nn.Linear(D, D), nn.Linear(D, 2 * D), nn.Linear(D, D)
+
+
+class Conv3DCrossAttentionBlockXformerMHANested(nn.Module):
+    def __init__(self, dim, num_heads, **_):
+        super().__init__()
+        self.norm1 = nn.LayerNorm(dim, eps=1e-6)
+        self.attn = _XYGridAttn(dim, num_heads)
+
+
+class TriplaneFusionBlockv4_nested_init_from_dino(nn.Module):
+    """Two DINOv2 blocks; the second block's attention is replaced by the cross-plane block, initialised from its qkv / proj."""
+
+    def __init__(self, vit_blks, num_heads, embed_dim, use_fusion_blk=True, **_):
+        super().__init__()
+        assert use_fusion_blk and len(vit_blks) == 2
+        self.num_branches = 3
+        self.vit_blks = vit_blks
+        ca = Conv3DCrossAttentionBlockXformerMHANested(embed_dim, num_heads)
+        qkv = vit_blks[1].attn.qkv
+        with torch.no_grad():
+            ca.attn.proj.load_state_dict(vit_blks[1].attn.proj.state_dict())
+            ca.attn.wq.weight.copy_(qkv.weight[:embed_dim])
+            ca.attn.w_kv.weight.copy_(qkv.weight[embed_dim:])
+            ca.attn.wq.bias.copy_(qkv.bias[:embed_dim])
+            ca.attn.w_kv.bias.copy_(qkv.bias[embed_dim:])
+        del self.vit_blks[1].attn
+        self.vit_blks[1].attn = ca
+
+
+class _RollOutInplaneConv(nn.Module):         # RodinRollOut_GroupConv_noConv3D
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.roll_out_inplane_conv = nn.Conv2d(cin, cout, 3, padding=1, groups=3)
+
+
+class _RollOutConv3D(nn.Module):              # RodinRollOutConv3D_GroupConv
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.roll_out_convs = nn.Conv2d(3 * cin, cout, 3, padding=1, groups=3)
+
+
+class RodinConv3D4X_lite_mlp_as_residual_lite(nn.Module):
+    def __init__(self, in_chans, out_chans, input_resolution=256, interp_mode='bilinear'):
+        super().__init__()
+        assert interp_mode == 'bilinear' and in_chans != out_chans
+        self.input_resolution, self.out_chans, self.interp_mode = input_resolution, out_chans, interp_mode
+        self.conv3D_0 = _RollOutInplaneConv(in_chans, out_chans)
+        self.conv3D_1 = _RollOutConv3D(out_chans, out_chans)
+        self.short_cut = nn.Linear(in_chans // 3, out_chans // 3)
+
+
+# ----------------------------------------------------------------------------- the decoder class
+class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(nn.Module):
+    def __init__(self, vit_decoder: DinoVisionTransformer, triplane_decoder: Triplane, cls_token=False, use_fusion_blk=True,
+                 fusion_blk_depth=2, fusion_blk=TriplaneFusionBlockv4_nested_init_from_dino, channel_multiplier=4, ldm_z_channels=4,
+                 ldm_embed_dim=4, vae_p=2, **kwargs):
+        super().__init__()
+        assert not cls_token and vae_p == 2 and fusion_blk_depth == 2
+        self.cls_token, self.vae_p, self.token_size, self.plane_n = cls_token, vae_p, 16, 3
+        self.ldm_z_channels, self.ldm_embed_dim, self.channel_multiplier = ldm_z_channels, ldm_embed_dim, channel_multiplier
+        self.superresolution = nn.ModuleDict({})
+        self.vit_decoder, self.triplane_decoder = vit_decoder, triplane_decoder
+        self.patch_size = vit_decoder.patch_size
+        D = vit_decoder.embed_dim
+        out_chans = getattr(triplane_decoder, "out_chans", 3 * triplane_decoder.decoder_in_chans)     # --out_chans 96
+        self.unpatchify_out_chans = out_chans
+        self.decoder_pred = nn.Linear(D, 4 ** 2 * int(out_chans // 3 * channel_multiplier))
+        self.vit_decoder.pos_embed = nn.Parameter(torch.zeros(1, 3 * self.token_size ** 2, D))
+        blks = vit_decoder.blocks
+        assert len(blks) == 12, 'ViT-B by default'
+        nh = blks[0].attn.num_heads
+        self.vit_decoder.blocks = nn.ModuleList([fusion_blk(blks[i:i + fusion_blk_depth], nh, D, use_fusion_blk)
+                                                 for i in range(0, len(blks), fusion_blk_depth)])
+        self.register_buffer('w_avg', torch.zeros([512]))
+        self.rendering_kwargs = triplane_decoder.rendering_kwargs
+        self.superresolution.update(dict(
+            ldm_downsample=nn.Linear(384, vae_p * vae_p * 3 * ldm_z_channels * 2),
+            ldm_upsample=PatchEmbedTriplane(vae_p * self.token_size, vae_p, 3 * ldm_embed_dim, D),
+            quant_conv=nn.Conv2d(2 * 3 * ldm_z_channels, 2 * ldm_embed_dim * 3, kernel_size=1, groups=3),
+            conv_sr=RodinConv3D4X_lite_mlp_as_residual_lite(int(out_chans * channel_multiplier), int(out_chans))))
+        self.reparameterization_soft_clamp = True
+        for blk in self.vit_decoder.blocks[len(self.vit_decoder.blocks) // 2:]:       # create_uvit_arch
+            blk.skip_linear = nn.Linear(2 * D, D)
+            nn.init.constant_(blk.skip_linear.weight, 0)
+            nn.init.constant_(blk.skip_linear.bias, 0)
+        self._packed = None
+        self._ws = None
+        _cache.watch(self)
+
+    def _apply(self, fn, *a, **k):
+        _cache.bump()
+        return super()._apply(fn, *a, **k)
+
+    # the posterior (encoder side) and the renderer seams are the Objaverse class's: same quant_conv / soft clamp / tri-plane gather
+    _quant_packed = _Objv._quant_packed
+    _posterior = _Objv._posterior
+    vae_encode = _Objv.vae_encode
+    triplane_renderer = _Objv.triplane_renderer
+    forward_points = _Objv.forward_points
+
+    # ------------------------------------------------------------------ packing
+    def _ensure_packed(self, dev):
+        if _cache.fresh(self._packed, dev):
+            return
+        vd, sr = self.vit_decoder, self.superresolution
+        D = vd.embed_dim
+        P = {'device': dev, 'D': D, 'H': vd.blocks[0].vit_blks[0].attn.num_heads}
+        P['pe_w'], P['pe_b'] = f32(sr['ldm_upsample'].proj.weight, dev), f32(sr['ldm_upsample'].proj.bias, dev)
+        P['pos'] = f32(vd.pos_embed.reshape(-1), dev)
+        ln = lambda m: (f32(m.weight, dev), f32(m.bias, dev))
+
+        def mlp_part(b):
+            return {'n2': ln(b.norm2), 'fc1_w': bf16(b.mlp.fc1.weight, dev), 'fc1_b': f32(b.mlp.fc1.bias, dev),
+                    'fc2_w': bf16(b.mlp.fc2.weight, dev), 'fc2_b': f32(b.mlp.fc2.bias, dev), 'ls2': f32(b.ls2.gamma, dev)}
+        P['pairs'] = []
+        for fb in vd.blocks:
+            b0, b1 = fb.vit_blks[0], fb.vit_blks[1]
+            q0 = {'n1': ln(b0.norm1), 'qkv_w': bf16(b0.attn.qkv.weight, dev), 'qkv_b': f32(b0.attn.qkv.bias, dev),
+                  'o_w': bf16(b0.attn.proj.weight, dev), 'o_b': f32(b0.attn.proj.bias, dev), 'ls1': f32(b0.ls1.gamma, dev), **mlp_part(b0)}
+            ca = b1.attn
+            g1 = b1.ls1.gamma.detach().float()
+            q1 = {'n1': ln(b1.norm1), 'n1g': (f32(b1.norm1.weight.detach().float() * g1, dev), f32(b1.norm1.bias.detach().float() * g1, dev)),
+                  'ca_n': ln(ca.norm1), 'qkv_w': bf16(torch.cat([ca.attn.wq.weight, ca.attn.w_kv.weight], 0), dev),
+                  'qkv_b': f32(torch.cat([ca.attn.wq.bias, ca.attn.w_kv.bias], 0), dev),
+                  'o_w': bf16(ca.attn.proj.weight, dev), 'o_b': f32(ca.attn.proj.bias, dev), 'ls1': f32(g1, dev), **mlp_part(b1)}
+            q = {'b0': q0, 'b1': q1}
+            if hasattr(fb, 'skip_linear'):
+                w = fb.skip_linear.weight
+                q['skip_wx'], q['skip_ws'] = bf16(w[:, :D], dev), bf16(w[:, D:], dev)
+                q['skip_b'] = f32(fb.skip_linear.bias, dev)
+            P['pairs'].append(q)
+        P['norm'] = ln(vd.norm)
+        P['dp_w'], P['dp_b'] = bf16(self.decoder_pred.weight, dev), f32(self.decoder_pred.bias, dev)
+        cs = sr['conv_sr']
+        P['sc_w'], P['sc_b'] = bf16(cs.short_cut.weight, dev), f32(cs.short_cut.bias, dev)
+
+        def group_conv(conv):                    # [Cout, Cin/3, 3, 3] groups = 3 -> per group [Cout/3, Kpad] in (ky, kx, c) order
+            w = conv.weight.detach().float()
+            g = w.shape[0] // 3
+            k = 9 * w.shape[1]
+            kpad = (k + 63) // 64 * 64
+            out = []
+            for d in range(3):
+                m = torch.zeros(g, kpad)
+                m[:, :k] = w[d * g:(d + 1) * g].permute(0, 2, 3, 1).reshape(g, k).cpu()
+                out.append((bf16(m, dev), f32(conv.bias[d * g:(d + 1) * g], dev)))
+            return out, kpad
+        P['c0'], P['c0_kpad'] = group_conv(cs.conv3D_0.roll_out_inplane_conv)
+        P['c1'], P['c1_kpad'] = group_conv(cs.conv3D_1.roll_out_convs)
+        P['zeros'] = torch.zeros(D, device=dev)
+        self._packed = _cache.stamp(P, self)
+        self._ws = Workspace(dev)
+
+    # ------------------------------------------------------------------ ViT pieces
+    def _mlp(self, x, q, M, D):
+        ws, P = self._ws, self._packed
+        h = ws.get('h', (M, D), torch.bfloat16)
+        ops.norm_modulate(x, h, M, D, kind=0, eps=1e-6, weight=q['n2'][0], shift=q['n2'][1], scale=P['zeros'], mod_rows=M, mod_ld=0)
+        f1 = ws.get('f1', (M, q['fc1_w'].shape[0]), torch.bfloat16)
+        ops.gemm(h, q['fc1_w'], q['fc1_b'], ops.EPI_GELU_ERF, f1)
+        ops.gemm(f1, q['fc2_w'], q['fc2_b'], ops.EPI_GATE_RES, x, gate=q['ls2'], gate_rows=M, gate_ld=0)
+
+    def _plane_block(self, x, q, B, N, D, H):
+        """DINOv2 block over each plane's N tokens (objects x planes = B*3 attention batches)."""
+        ws, P = self._ws, self._packed
+        M, Dh = B * 3 * N, D // H
+        npad = (N + 63) // 64 * 64
+        h = ws.get('h', (M, D), torch.bfloat16)
+        ops.norm_modulate(x, h, M, D, kind=0, eps=1e-6, weight=q['n1'][0], shift=q['n1'][1], scale=P['zeros'], mod_rows=M, mod_ld=0)
+        qq = ws.get('q', (B * 3, H, npad, Dh), torch.bfloat16, zero=True)
+        kk = ws.get('k', (B * 3, H, npad, Dh), torch.bfloat16, zero=True)
+        vt = ws.get('vt', (B * 3, H, Dh, npad), torch.bfloat16, zero=True)
+        o = ws.get('o', (M, D), torch.bfloat16)
+        ops.gemm(h, q['qkv_w'], q['qkv_b'], ops.EPI_HEADS, qq, kk, vt, M=M, tokens=N, tok_pad=npad, heads=H, head_dim=Dh, transpose_mask=0b100)
+        ops.attention(qq, kk, vt, o, B * 3, H, N, npad, N, npad, Dh, scale=Dh ** -0.5)
+        ops.gemm(o, q['o_w'], q['o_b'], ops.EPI_GATE_RES, x, gate=q['ls1'], gate_rows=M, gate_ld=0)
+        self._mlp(x, q, M, D)
+
+    def _cross_block(self, x, q, B, N, D, H):
+        """DINOv2 block whose attention is the nested cross-plane block: x += ls1 * (n + proj(axis_attn(norm1'(n)))), n = norm1(x)."""
+        ws, P = self._ws, self._packed
+        M = B * 3 * N
+        n = ws.get('n', (M, D), torch.float32)
+        r = ws.get('r', (M, D), torch.float32)
+        ops.layernorm_f32(x, q['n1'][0], q['n1'][1], n, M, D, 1e-6)
+        ops.layernorm_f32(x, q['n1g'][0], q['n1g'][1], r, M, D, 1e-6)           # ls1 * n: the inner block's residual, gated
+        h = ws.get('h', (M, D), torch.bfloat16)
+        ops.norm_modulate(n, h, M, D, kind=0, eps=1e-6, weight=q['ca_n'][0], shift=q['ca_n'][1], scale=P['zeros'], mod_rows=M, mod_ld=0)
+        qkv = ws.get('ca_qkv', (M, 3 * D), torch.float32)
+        ops.gemm(h, q['qkv_w'], q['qkv_b'], ops.EPI_F32, qkv)
+        o = ws.get('o', (M, D), torch.bfloat16)
+        ops.triplane_axis_attention(qkv, o, B, int(round(N ** 0.5)), H, scale=(D // H) ** -0.5)
+        ops.gemm(o, q['o_w'], q['o_b'], ops.EPI_GATE_RES, x, gate=q['ls1'], gate_rows=1, gate_ld=0, res_bias=r, res_bias_ld=D)
+        self._mlp(x, q, M, D)
+
+    # ------------------------------------------------------------------ reference-named stages
+    @torch.no_grad()
+    def vit_decode_backbone(self, latent, img_size=None):
+        if isinstance(latent, dict):
+            latent = latent['latent_normalized_2Ddiffusion']
+        if not latent.is_cuda:
+            raise RuntimeError("ln3diff_amd decoder runs on the HIP device only (no CPU fallback)")
+        self._ensure_packed(latent.device)
+        B = latent.shape[0]
+        D, S = self._packed['D'], self.vae_p * self.token_size
+        L = 3 * self.token_size ** 2
+        raw = self._ws.get('pe_raw', (B * L, D), torch.float32)
+        ops.patch_embed_triplane(latent.contiguous().float(), self._packed['pe_w'], self._packed['pe_b'],
+                                 self._ws.get('pe_silu', (B * L, D), torch.bfloat16), raw, B, self.ldm_embed_dim, S, self.vae_p, D)
+        return self.forward_vit_decoder(raw.view(B, L, D), img_size)
+
+    @torch.no_grad()
+    def forward_vit_decoder(self, x, img_size=None):
+        """x [B, 3*256, D] (ldm_upsample output) -> + pos_embed -> 6 block pairs with UViT skips -> norm; returns f32 [B, 3*256, D]."""
+        if not x.is_cuda:
+            raise RuntimeError("ln3diff_amd decoder runs on the HIP device only (no CPU fallback)")
+        self._ensure_packed(x.device)
+        P, ws = self._packed, self._ws
+        B, L, D = x.shape
+        H, N, M = P['H'], L // 3, B * L
+        h = ws.get('x', (M, D), torch.float32)
+        ops.add_table_rows(x.contiguous().float(), P['pos'], h, 1, B, L * D)
+        pairs = P['pairs']
+        skips = []
+
+        def push():
+            s = ws.get(f'skip{len(skips)}', (M, D), torch.bfloat16)
+            ops.cast_bf16(h, s)
+            skips.append(s)
+        push()
+        for j, q in enumerate(pairs):
+            if j >= len(pairs) // 2:
+                xb = ws.get('skip_x', (M, D), torch.bfloat16)
+                ops.cast_bf16(h, xb)
+                ops.gemm(xb, q['skip_wx'], q['skip_b'], ops.EPI_GATE_RES, h)
+                ops.gemm(skips.pop(), q['skip_ws'], None, ops.EPI_GATE_RES, h)
+            self._plane_block(h, q['b0'], B, N, D, H)
+            self._cross_block(h, q['b1'], B, N, D, H)
+            if j < len(pairs) // 2 - 1:
+                push()
+        out = torch.empty(B, L, D, device=x.device, dtype=torch.float32)
+        ops.layernorm_f32(h, P['norm'][0], P['norm'][1], out, M, D, 1e-6)
+        return out
+
+    @torch.no_grad()
+    def vit_decode_postprocess(self, latent_from_vit, ret_dict: dict, want_nchw=True, return_stages=False):
+        """decoder_pred -> unpatchify_triplane (p = 4) -> conv_sr.  Adds 'planes_channel_last' [B, 3, R, R, 32] (the renderer's layout),
+        'latent_after_vit' [B, 96, R, R] (want_nchw), 'sr_w_code' and 'cls_token' (None) to ret_dict; return_stages also adds
+        'decoder_pred' [B, 768, 2048] and the low-resolution planes 'planes_lowres' [B, 3, 64, 64, 128] (channel-last)."""
+        P, ws = self._packed, self._ws
+        B, L, D = latent_from_vit.shape
+        dev = latent_from_vit.device
+        cs = self.superresolution['conv_sr']
+        S, p, Cm = self.token_size, 4, P['dp_w'].shape[0] // 16
+        r, R, Co = S * p, cs.input_resolution, cs.out_chans // 3
+        N = B * 3
+        xb = ws.get('tok_bf', (B * L, D), torch.bfloat16)
+        ops.cast_bf16(latent_from_vit.contiguous(), xb)
+        pred = ws.get('pred', (B * L, 16 * Cm), torch.float32)
+        ops.gemm(xb, P['dp_w'], P['dp_b'], ops.EPI_F32, pred)
+        lo = ws.get('lo', (N, r, r, Cm), torch.float32)
+        mixed = ws.get('mixed', (N * r * r, Cm), torch.bfloat16)
+        ops.sr_unpatchify(pred, lo, mixed, B, S, p, Cm)
+        res = ws.get('res', (N, r, r, Co), torch.float32)
+        ops.gemm(mixed, P['sc_w'], P['sc_b'], ops.EPI_F32, res)
+        up = ws.get('up', (N, R, R, Cm), torch.bfloat16)
+        ops.resize_bilinear_cl(lo, up, N, r, r, R, R, Cm, transpose=True)
+        t = ws.get('t', (N, R * R, Co), torch.float32)
+        col = ws.get('col0', (R * R, P['c0_kpad']), torch.bfloat16)
+        for n in range(N):
+            w, b = P['c0'][n % 3]
+            ops.im2col3x3(up[n], col, 1, R, R, Cm, 1, P['c0_kpad'])
+            ops.gemm(col, w, b, ops.EPI_F32, t[n])
+        x0 = ws.get('x0', (B, 3, R, R, Co), torch.float32)
+        ops.resize_add_lrelu(res, t, x0, N, r, r, R, R, Co, 0.01)
+        rowm = ws.get('rowm', (B, 3, R, Co), torch.float32)
+        colm = ws.get('colm', (B, 3, R, Co), torch.float32)
+        ops.rollout_means(x0, rowm, colm, N, R, R, Co)
+        col = ws.get('col1', (R * R, P['c1_kpad']), torch.bfloat16)
+        for b in range(B):
+            for i in range(3):
+                w, bias = P['c1'][i]
+                ops.im2col3x3_rollout(x0[b], rowm[b], colm[b], col, i, R, R, Co, P['c1_kpad'])
+                ops.gemm(col, w, bias, ops.EPI_F32, t[b * 3 + i])
+        planes_cl = torch.empty(B, 3, R, R, Co, device=dev, dtype=torch.float32)
+        ops.resize_add_lrelu(x0, t, planes_cl, N, R, R, R, R, Co, 0.01)
+        ret_dict.update(dict(cls_token=None, planes_channel_last=planes_cl,
+                             sr_w_code=self.w_avg.reshape(1, 1, -1).expand(B, 1, self.w_avg.numel())))
+        if want_nchw:
+            nchw = torch.empty(B, 3 * Co, R, R, device=dev, dtype=torch.float32)
+            ops.planes_to_nchw(planes_cl, nchw, B, Co, R, R)
+            ret_dict['latent_after_vit'] = nchw
+        if return_stages:
+            ret_dict['decoder_pred'] = pred.view(B, L, -1).clone()
+            ret_dict['planes_lowres'] = lo.view(B, 3, r, r, Cm).clone()
+        return ret_dict
+
+    @torch.no_grad()
+    def vae_reparameterization(self, latent, sample_posterior, eps=None):
+        """latent: ViT encoder tokens [B, 256, 384] -> ldm_downsample -> unpatchify3D (p = 2) -> quant_conv posterior (mode, or
+        mean + std * eps with eps [B, 4, 3, 1024]; sampling without eps draws it like the reference, on the CPU generator)."""
+        if not latent.is_cuda:
+            raise RuntimeError("ln3diff_amd decoder runs on the HIP device only (no CPU fallback)")
+        dev = latent.device
+        ld = self.superresolution['ldm_downsample']
+        q = self.__dict__.get('_down')
+        if not _cache.fresh(q, dev):
+            q = _cache.stamp({'device': dev, 'w': bf16(ld.weight, dev), 'b': f32(ld.bias, dev)}, self)
+            self.__dict__['_down'] = q
+        B, T, Ce = latent.shape
+        xb = torch.empty(B * T, Ce, device=dev, dtype=torch.bfloat16)
+        ops.cast_bf16(latent.contiguous().float(), xb)
+        y = torch.empty(B * T, ld.weight.shape[0], device=dev, dtype=torch.float32)
+        ops.gemm(xb, q['w'], q['b'], ops.EPI_F32, y)
+        t, p, Cz = self.token_size, self.vae_p, 2 * self.ldm_z_channels
+        # unpatchify3D 'nhwpqdc->ndhpwqc' then B 3 C H W -> B 3C H W: a layout copy for the posterior kernel's NCHW input
+        h = y.view(B, t, t, p, p, 3, Cz).permute(0, 5, 6, 1, 3, 2, 4).reshape(B, 3 * Cz, t * p, t * p)
+        HW = (t * p) ** 2
+        if sample_posterior and eps is None:
+            eps = torch.randn(B, self.ldm_embed_dim, 3, HW)
+        r = self._posterior(h, eps if sample_posterior else None, 1)
+        return dict(normal_entropy=r['entropy'], latent_normalized=r['latent_tok'],
+                    latent_normalized_2Ddiffusion=r['z'].view(B, -1, t * p, t * p), log_q_2Ddiffusion=r['log_q'].view(B, -1, t * p, t * p),
+                    log_q=r['log_q'], posterior=DiagonalGaussianDistribution(r['mean'], r['logvar']))
+
+    @torch.no_grad()
+    def vit_decode(self, latent, img_size, sample_posterior=True, eps=None, **kwargs):
+        ret_dict = self.vae_reparameterization(latent, sample_posterior, eps=eps)
+        tok = self.vit_decode_backbone(ret_dict, img_size)
+        return self.vit_decode_postprocess(tok, ret_dict)
+
+    @torch.no_grad()
+    def triplane_decode(self, vit_decode_out, c, return_raw_only=False, **kwargs):
+        """The reference passes ws = sr_w_code, which only Triplane.superresolution reads (not built: --sr_training False)."""
+        return _Objv.triplane_decode(self, vit_decode_out, c, return_raw_only=return_raw_only, **kwargs)
+
+    @torch.no_grad()
+    def triplane_decode_grid(self, vit_decode_out, grid_size, aabb=None, **kwargs):
+        """vit_triplane.py:290-337: the grid spans sampler_bbox_min / max when the preset has them, else +- box_warp / 2 (ShapeNet)."""
+        pcl = vit_decode_out.get('planes_channel_last')
+        if pcl is None:
+            pcl = Triplane.to_channel_last(vit_decode_out['latent_after_vit'])
+        N = pcl.shape[0]
+        rk = self.rendering_kwargs
+        if aabb is not None:
+            raise NotImplementedError("triplane_decode_grid: a per-object aabb is not supported; the preset's box is used")
+        lo, hi = (rk['sampler_bbox_min'], rk['sampler_bbox_max']) if 'sampler_bbox_min' in rk else (-rk['box_warp'] / 2, rk['box_warp'] / 2)
+        ax = torch.linspace(lo, hi, grid_size, device=pcl.device)
+        pts = torch.stack(torch.meshgrid(ax, ax, ax, indexing='ij'), dim=-1).reshape(1, -1, 3).expand(N, -1, -1)
+        f = self.forward_points(pcl, pts)
+        return {k: v.reshape(N, grid_size, grid_size, grid_size, -1) for k, v in f.items()}
