@@ -1,4 +1,4 @@
-"""ctypes binding of libln3d_hip.so (the C ABI of include/ln3d.h, include/ln3d_encoder.h and include/ln3d_shapenet.h).
+"""ctypes binding of libln3d_hip.so (the C ABI of include/ln3d.h, include/ln3d_encoder.h, include/ln3d_shapenet.h and include/ln3d_mx.h).
 
 There is NO fallback: if the library is missing or a kernel launch fails the product raises.
 """
@@ -23,6 +23,8 @@ SYMBOLS = [
     # include/ln3d_shapenet.h (the ShapeNet VAE decoder class)
     "ln3d_triplane_axis_attention", "ln3d_sr_unpatchify", "ln3d_resize_bilinear_cl", "ln3d_resize_add_lrelu", "ln3d_rollout_means",
     "ln3d_im2col3x3_rollout",
+    # include/ln3d_mx.h (the opt-in MX-FP8 GEMMs of the T23D DiT)
+    "ln3d_quantize_mx", "ln3d_gemm_mxfp8", "ln3d_norm_modulate_mx",
 ]
 
 EPI_F32, EPI_BF16, EPI_GELU_ERF, EPI_GELU_TANH, EPI_SILU, EPI_GATE_RES, EPI_HEADS, EPI_F32_SILU, EPI_QUICK_GELU, EPI_CROSS_ATTN = range(10)
@@ -41,6 +43,15 @@ class GemmArgs(C.Structure):
                 ("transpose_mask", i32), ("ctx_keys", i32), ("ctx_pad", i32), ("ctx_scale", f32), ("head_dim_pad", i32),
                 ("head_norm0", vp), ("head_norm1", vp), ("head_norm_eps", f32),
                 ("res_bias", vp), ("res_bias_ld", i64)]
+
+
+class MxGemmArgs(C.Structure):          # ln3d_gemm_mx_args (include/ln3d_mx.h)
+    _fields_ = [("Xq", vp), ("Xs", vp), ("ldx", i64), ("ldxs", i64),
+                ("Wq", vp), ("Ws", vp), ("ldw", i64), ("ldws", i64), ("bias", vp),
+                ("M", i32), ("N", i32), ("K", i32), ("epilogue", i32),
+                ("out0", vp), ("out1", vp), ("out2", vp), ("ldo", i64), ("out_scale", vp), ("ldos", i64),
+                ("gate", vp), ("gate_rows", i32), ("gate_ld", i64),
+                ("tokens", i32), ("tok_pad", i32), ("heads", i32), ("head_dim", i32), ("transpose_mask", i32), ("head_dim_pad", i32)]
 
 
 class AttnArgs(C.Structure):

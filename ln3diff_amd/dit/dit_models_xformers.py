@@ -256,6 +256,15 @@ def pack_block(b, H, Dh, device):
     return q
 
 
+def pack_block_mx(q, b, device):
+    """MX-FP8 operands of one block (DiT_TriLatent.set_matmul_precision('mxfp8')): qkv_w, fc1_w and fc2_w of a pack_block dict are replaced
+    by ops.MX copies quantized on the device from the fp32 master weights, in pack_block's column order; their bf16 copies are dropped so
+    that only the active precision's operands stay resident."""
+    for key, w in (('qkv_w', b.attn.qkv.weight), ('fc1_w', b.mlp.mlp[0].weight), ('fc2_w', b.mlp.mlp[2].weight)):
+        q[key] = ops.quantize_mx(f32(w, device))
+    return q
+
+
 def attn_head_pad(Dh):
     """Head size the attention kernel runs at: 64, 80 and 128 natively; smaller heads (the U-Net's 32 / 40) zero-padded to 64, 65 - 80
     (DiT-XL/2: 72, the U-Net's 80) stored 80 wide (r6: the K / V^T stream of such a launch is what bounds it, 80 wide is 5/8 of the
@@ -280,7 +289,8 @@ def pad_head_columns(w, H, Dh):
 
 
 def self_attention_hip(ws, tag, h_bf16, B, N, D, H, qkv_w, qkv_b, qn=None, kn=None, nq=None):
-    """h [B*N, D] bf16 -> attention output bf16 [B*nq, H*attn_out_dim] (nq <= N query rows kept).  For head sizes other than
+    """h [B*N, D] bf16, or an ops.MX with qkv_w one too (the MX-FP8 QKV GEMM) -> attention output bf16 [B*nq, H*attn_out_dim] (nq <= N
+    query rows kept).  For head sizes other than
     64/128 the QKV epilogue writes into 128-wide zero-initialised heads (exact: the extra dims contribute 0 to q.k); the kernel
     skips the padding for the sizes it knows (DiT-XL/2's 72: compact output, unpadded proj weight), otherwise it produces 0 output
     columns, which meet zero columns of the padded proj weight."""
@@ -293,9 +303,14 @@ def self_attention_hip(ws, tag, h_bf16, B, N, D, H, qkv_w, qkv_b, qn=None, kn=No
     vt = ws.get(tag + 'vt', (B, H, Dp, npad), torch.bfloat16, zero=True)
     Do = attn_out_dim(Dh)
     o = ws.get(tag + 'o', (B * nq, H * Do), torch.bfloat16)
-    fused = qn is not None and ops.heads_norm_fusable(B * N, qkv_w.shape[0], N, Dh, Dp)
-    ops.gemm(h_bf16, qkv_w, qkv_b, ops.EPI_HEADS, q, k, vt, M=B * N, tokens=N, tok_pad=npad, heads=H, head_dim=Dh,
-             transpose_mask=0b100, head_dim_pad=Dp, head_norm0=qn if fused else None, head_norm1=kn if fused else None)
+    if isinstance(h_bf16, ops.MX):
+        fused = False                  # the MX GEMM's head split has no fused qk-norm
+        ops.gemm_mx(h_bf16, qkv_w, qkv_b, ops.EPI_HEADS, q, k, vt, M=B * N, tokens=N, tok_pad=npad, heads=H, head_dim=Dh,
+                    transpose_mask=0b100, head_dim_pad=Dp)
+    else:
+        fused = qn is not None and ops.heads_norm_fusable(B * N, qkv_w.shape[0], N, Dh, Dp)
+        ops.gemm(h_bf16, qkv_w, qkv_b, ops.EPI_HEADS, q, k, vt, M=B * N, tokens=N, tok_pad=npad, heads=H, head_dim=Dh,
+                 transpose_mask=0b100, head_dim_pad=Dp, head_norm0=qn if fused else None, head_norm1=kn if fused else None)
     if qn is not None and not fused:
         ops.rmsnorm_heads(q, qn, B * H * npad, Dp, true_dim=Dh)      # qn / kn: [Dp] (zero beyond Dh when padded)
         ops.rmsnorm_heads(k, kn, B * H * npad, Dp, true_dim=Dh)

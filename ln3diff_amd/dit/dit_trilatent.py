@@ -14,6 +14,8 @@ returning float32 [B, C*3, H, W]); the forward pass is a fixed sequence of HIP l
                 -> fc2 GEMM (gate*out + residual epilogue)
   final       : LN+modulate+Linear(D->p*p*C)+unpatchify in one kernel.
 The residual stream, LN statistics, softmax and all accumulators are fp32; GEMM operands are bf16.
+set_matmul_precision('mxfp8') (opt-in; no reference counterpart) runs the QKV, fc1 and fc2 GEMMs of every block on MX-FP8 operands
+(include/ln3d_mx.h): the two LN+modulate kernels write MXFP8, fc1's GELU epilogue writes MXFP8 for fc2; everything else stays bf16.
 """
 import os
 
@@ -23,7 +25,7 @@ import torch.nn as nn
 from .. import ops, _cache
 from .dit_models_xformers import (CaptionEmbedder, DiTBlock, FinalLayer, PatchEmbed, T2IFinalLayer,  # noqa: F401
                                   TextCondDiTBlock, TimestepEmbedder, Workspace, bf16, f32,
-                                  get_2d_sincos_pos_embed, self_attention_hip, pack_block, pack_caption)
+                                  get_2d_sincos_pos_embed, self_attention_hip, pack_block, pack_block_mx, pack_caption)
 
 
 class DiT(nn.Module):
@@ -104,6 +106,28 @@ class DiT_TriLatent(DiT):
         pe = get_2d_sincos_pos_embed(D, (self.plane_n, L)).reshape(self.plane_n * L, D)
         self.pos_embed = nn.Parameter(torch.from_numpy(pe).float().unsqueeze(0), requires_grad=False)
 
+    # ------------------------------------------------------------------ matmul precision
+    MATMUL_PRECISIONS = ('bf16', 'mxfp8')
+    _matmul_precision = 'bf16'
+
+    def set_matmul_precision(self, precision):
+        """'bf16' (default: the reference's numerics up to bf16 GEMM operands) or 'mxfp8': the QKV, fc1 and fc2 GEMMs of every block
+        on OCP MXFP8 operands (e4m3 elements, one E8M0 scale per 32 values along K), quantized on the device from the fp32 master
+        weights when the model is packed.  Only the active precision's operands are kept; a change drops the packed copies."""
+        if precision not in self.MATMUL_PRECISIONS:
+            raise ValueError(f"matmul precision {precision!r}: expected one of {self.MATMUL_PRECISIONS}")
+        if precision != 'bf16' and type(self).forward is not DiT_TriLatent.forward:
+            raise ValueError(f"{type(self).__name__}: the {precision} path is built for the T23D DiT_TriLatent forward only")
+        if precision != self._matmul_precision:
+            self._matmul_precision = precision
+            self._packed = None
+            self._ws = None
+        return self
+
+    @property
+    def matmul_precision(self):
+        return self._matmul_precision
+
     # ------------------------------------------------------------------ packing
     def _ensure_packed(self, device):
         if _cache.fresh(self._packed, device):
@@ -124,6 +148,9 @@ class DiT_TriLatent(DiT):
         P['ada_w'], P['ada_b'] = bf16(torch.cat([a.weight for a in ada], 0), device), f32(torch.cat([a.bias for a in ada], 0), device)
         self._pack_prompt(P, device)
         P['blocks'] = [pack_block(b, H, self.embed_dim // H, device) for b in self.blocks]
+        P['precision'] = self._matmul_precision
+        if P['precision'] == 'mxfp8':
+            P['blocks'] = [pack_block_mx(q, b, device) for q, b in zip(P['blocks'], self.blocks)]
         P['fin_w'], P['fin_b'] = f32(self.final_layer.linear.weight, device), f32(self.final_layer.linear.bias, device)
         self._packed = _cache.stamp(P, self)
         self._ws = Workspace(device)
@@ -204,14 +231,21 @@ class DiT_TriLatent(DiT):
         return cc
 
     def _fc1(self, probe, i, hb, q, f1):
-        """Block i's MLP fc1 GEMM (erf-GELU epilogue).  `probe`: bench.py's `_fc1_probe` measurement hook {'layer', 'events', 'max'}:
-        HIP events on the launch stream around this one GEMM of that layer, inside the real step."""
+        """Block i's MLP fc1 GEMM (erf-GELU epilogue; MX-FP8 in and out when hb is an ops.MX).  `probe`: bench.py's `_fc1_probe`
+        measurement hook {'layer', 'events', 'max'}: HIP events on the launch stream around this one GEMM of that layer, inside the real step."""
         if probe is not None and i == probe['layer'] and len(probe['events']) < probe['max']:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            ops.gemm(hb, q['fc1_w'], q['fc1_b'], ops.EPI_GELU_ERF, f1)
+            self._fc1_launch(hb, q, f1)
             e1.record()
             probe['events'].append((e0, e1))
+        else:
+            self._fc1_launch(hb, q, f1)
+
+    @staticmethod
+    def _fc1_launch(hb, q, f1):
+        if isinstance(hb, ops.MX):
+            ops.gemm_mx(hb, q['fc1_w'], q['fc1_b'], ops.EPI_GELU_ERF, f1.q, out_scale=f1.s)
         else:
             ops.gemm(hb, q['fc1_w'], q['fc1_b'], ops.EPI_GELU_ERF, f1)
 
@@ -306,7 +340,21 @@ class DiT_TriLatent(DiT):
         xb = ws.get('xb', (M, D), torch.bfloat16)
         qc = ws.get('qc', (Bn, H, N, 64), torch.bfloat16)
         oc = ws.get('oc', (M, H * 64), torch.bfloat16)
-        f1 = ws.get('f1', (M, P['blocks'][0]['fc1_w'].shape[0]), torch.bfloat16)
+        mx = P['precision'] == 'mxfp8'
+        if mx:                                                 # MXFP8 operands of QKV / fc1 (LN+modulate output) and fc2 (GELU output)
+            F = P['blocks'][0]['fc1_w'].q.shape[0]
+            hq = ops.MX(ws.get('hq', (M, D), torch.uint8), ws.get('hqs', (M, D // 32), torch.uint8))
+            f1 = ops.MX(ws.get('f1q', (M, F), torch.uint8), ws.get('f1s', (M, F // 32), torch.uint8))
+        else:
+            f1 = ws.get('f1', (M, P['blocks'][0]['fc1_w'].shape[0]), torch.bfloat16)
+
+        def norm_mod(rows, shift, scale):
+            """LN + adaLN modulate of xt[:rows] -> the QKV / fc1 operand (bf16, or MXFP8 in mxfp8 mode)"""
+            if mx:
+                ops.norm_modulate_mx(xt[:rows], hq.rows(0, rows), rows, D, kind=0, eps=1e-6, shift=shift, scale=scale, mod_rows=N, mod_ld=ld)
+                return hq.rows(0, rows)
+            ops.norm_modulate(xt[:rows], hb[:rows], rows, D, kind=0, eps=1e-6, shift=shift, scale=scale, mod_rows=N, mod_ld=ld)
+            return hb[:rows]
 
         probe = getattr(self, '_fc1_probe', None)
         fused_cross = N % 192 == 0 and (H * 64) % 256 == 0 and cc['Lc'] <= 96 and 'kp' in cc
@@ -326,15 +374,13 @@ class DiT_TriLatent(DiT):
             sh_m, sc_m, g_m = mod[:, o6 + 3 * D:], mod[:, o6 + 4 * D:], mod[:, o6 + 5 * D:]
             if i == 0 and dedup0:
                 Mh = half * N
-                ops.norm_modulate(xt[:Mh], hb[:Mh], Mh, D, kind=0, eps=1e-6, shift=sh_a, scale=sc_a, mod_rows=N, mod_ld=ld)
-                ao = self_attention_hip(ws, 'sa0_', hb[:Mh], half, N, D, H, q['qkv_w'], q['qkv_b'])
+                ao = self_attention_hip(ws, 'sa0_', norm_mod(Mh, sh_a, sc_a), half, N, D, H, q['qkv_w'], q['qkv_b'])
                 # first half: with the fold these are the unconditional rows (+ their constant cross-attention, no bf16 copy needed)
                 ops.gemm(ao, q['proj_w'], q['proj_b'], ops.EPI_GATE_RES, xt[:Mh], None if fold else xb[:Mh], gate=g_a, gate_rows=N,
                          gate_ld=ld, res_bias=cc['const'][i] if fold else None, res_bias_ld=D)
                 ops.gemm(ao, q['proj_w'], q['proj_b'], ops.EPI_GATE_RES, xt[Mh:], xb[Mh:], gate=g_a, gate_rows=N, gate_ld=ld)
             else:
-                ops.norm_modulate(xt, hb, M, D, kind=0, eps=1e-6, shift=sh_a, scale=sc_a, mod_rows=N, mod_ld=ld)
-                ao = self_attention_hip(ws, 'sa_', hb, Bn, N, D, H, q['qkv_w'], q['qkv_b'])
+                ao = self_attention_hip(ws, 'sa_', norm_mod(M, sh_a, sc_a), Bn, N, D, H, q['qkv_w'], q['qkv_b'])
                 # samples [0, fold) have a constant cross-attention output (prepare_context): it rides on this epilogue as a per-sample row
                 ops.gemm(ao, q['proj_w'], q['proj_b'], ops.EPI_GATE_RES, xt, xb, gate=g_a, gate_rows=N, gate_ld=ld,
                          res_bias=cc['const'][i] if fold else None, res_bias_ld=D)
@@ -346,9 +392,11 @@ class DiT_TriLatent(DiT):
                 ops.gemm(xb[r0:], q['cq_w'], None, ops.EPI_HEADS, qc, M=M - r0, tokens=N, tok_pad=N, heads=H, head_dim=64)
                 ops.attention(qc, cc['k'][i][fold:], cc['vt'][i][fold:], oc[r0:], Bn - fold, H, N, N, cc['Lc'], cc['lpad'], 64)
             ops.gemm(oc[r0:], q['co_w'], q['co_b'], ops.EPI_GATE_RES, xt[r0:])
-            ops.norm_modulate(xt, hb, M, D, kind=0, eps=1e-6, shift=sh_m, scale=sc_m, mod_rows=N, mod_ld=ld)
-            self._fc1(probe, i, hb, q, f1)
-            ops.gemm(f1, q['fc2_w'], q['fc2_b'], ops.EPI_GATE_RES, xt, gate=g_m, gate_rows=N, gate_ld=ld)
+            self._fc1(probe, i, norm_mod(M, sh_m, sc_m), q, f1)
+            if mx:
+                ops.gemm_mx(f1, q['fc2_w'], q['fc2_b'], ops.EPI_GATE_RES, xt, gate=g_m, gate_rows=N, gate_ld=ld)
+            else:
+                ops.gemm(f1, q['fc2_w'], q['fc2_b'], ops.EPI_GATE_RES, xt, gate=g_m, gate_rows=N, gate_ld=ld)
 
         of = depth * 6 * D
         out = torch.empty(Bn, self.out_channels * 3, S, S, dtype=torch.float32, device=dev)

@@ -54,6 +54,9 @@ _CHECKED = {
 }
 
 
+DIT_PRECISIONS = ('bf16', 'mxfp8')
+
+
 def str2bool(v):
     if isinstance(v, bool):
         return v
@@ -88,7 +91,8 @@ def create_argparser(objaverse=True):
         create_dit=objaverse, num_channels=320, num_res_blocks=2, channel_mult='', attention_resolutions='4,2,1', num_heads=8,
         num_head_channels=-1, num_heads_upsample=-1, use_scale_shift_norm=True, use_spatial_transformer=True, transformer_depth=1,
         dropout=0.0, mixing_logit_init=-6.0,
-        ray_start=0.6, ray_end=1.8)          # nsr/script_util.py triplane_decoder_defaults; read by the ShapeNet decoder class only
+        ray_start=0.6, ray_end=1.8,          # nsr/script_util.py triplane_decoder_defaults; read by the ShapeNet decoder class only
+        dit_precision='bf16')                # matmul precision of the T23D DiT (no reference counterpart): bf16 or the opt-in mxfp8
     d.update(_IGNORED_DEFAULTS)
     d.update({k: v[0] for k, v in _CHECKED.items()})
     ap = argparse.ArgumentParser(allow_abbrev=False)
@@ -127,6 +131,14 @@ def validate(args):
                          "(--dit_model_arch DiT-PixelArt-L/2): the flow-matching engine calls forward_with_cfg(x, t, context=..., "
                          "cfg_scale=...), which the plain T23D DiT_TriLatent does not define (in the reference neither: "
                          "dit/dit_models_xformers.py:915 takes class labels)")
+    prec = getattr(args, 'dit_precision', 'bf16')
+    if prec not in DIT_PRECISIONS:
+        raise SystemExit(f"--dit_precision {prec}: expected one of {list(DIT_PRECISIONS)}")
+    if prec != 'bf16' and (unet or args.i23d or pixart_t23d):
+        which = ("the U-Net denoiser (--create_dit false)" if unet else "the I23D denoisers (--i23d true)" if args.i23d else
+                 "the PixArt-style T23D denoiser (DiT-PixelArt-*)")
+        raise SystemExit(f"--dit_precision {prec}: the MX-FP8 path is built for the T23D DiT_TriLatent denoiser "
+                         f"(--dit_model_arch DiT-B/2, DiT-L/2, DiT-XL/2, DiT-B/1) only; {which} has bf16 GEMMs only")
     if pixart_t23d and kind != 'flow':
         raise SystemExit("--dit_model_arch DiT-PixelArt-* (DiT_TriLatent_PixelArt) is the flow-matching T23D denoiser: use "
                          "--trainer_name flow_matching")
@@ -416,13 +428,16 @@ def run(args, objaverse=None):
 
     if kind == 'edm':
         eng = T23DPipeline(dit, ae, num_steps=args.sample_steps, cfg_scale=args.unconditional_guidance_scale,
-                           triplane_scaling_divider=args.triplane_scaling_divider, img_size=args.image_size)
+                           triplane_scaling_divider=args.triplane_scaling_divider, img_size=args.image_size,
+                           dit_precision=getattr(args, 'dit_precision', 'bf16'))
     elif kind == 'flow':
         # --ode_method defaults to dopri5 like the reference's sample_ode (torchdiffeq dopri5, atol 1e-6, rtol 1e-3;
         # transport/transport.py:377); the benchmark configurations ("50 steps") pass --ode_method euler
         eng = FlowMatchingEngine(dit, ae, triplane_scaling_divider=args.triplane_scaling_divider, img_size=args.image_size,
                                  sampling_method=args.ode_method)
     else:
+        if getattr(args, 'dit_precision', 'bf16') != 'bf16':          # a DiT_TriLatent denoiser under the guided_diffusion engines (validate() refuses the rest)
+            dit.set_matmul_precision(args.dit_precision)
         from .guided_diffusion import gaussian_diffusion as gd
         from .guided_diffusion.respace import SpacedDiffusion, space_timesteps
         spec = args.timestep_respacing or str(args.diffusion_steps)

@@ -54,6 +54,58 @@ def gemm(x, w, bias, epilogue, out0, out1=None, out2=None, *, M=None, ldo=None, 
     L.check(L.lib().ln3d_gemm_bf16(C.byref(a), _stream()), "gemm")
 
 
+class MX:
+    """An MXFP8 matrix [R, K] (include/ln3d_mx.h): q e4m3 bytes [R, K] (torch.uint8) and s E8M0 scale bytes [R, K / 32] (torch.uint8),
+    both row-major and contiguous."""
+    __slots__ = ('q', 's')
+
+    def __init__(self, q, s):
+        self.q, self.s = q, s
+
+    @staticmethod
+    def empty(R, K, device):
+        return MX(torch.empty(R, K, dtype=torch.uint8, device=device), torch.empty(R, K // 32, dtype=torch.uint8, device=device))
+
+    def rows(self, r0, r1=None):
+        """row slice [r0, r1) (views)"""
+        return MX(self.q[r0:r1], self.s[r0:r1])
+
+
+def quantize_mx(x, out=None):
+    """x [R, K] f32 or bf16 (row stride = x.stride(0)) -> MX (one E8M0 scale per 32 values, OCP e4m3 elements)."""
+    _chk_dev(x)
+    assert x.dtype in (torch.float32, torch.bfloat16) and x.dim() == 2 and x.stride(1) == 1
+    R, K = x.shape
+    out = out if out is not None else MX.empty(R, K, x.device)
+    L.check(L.lib().ln3d_quantize_mx(_p(x), int(x.dtype == torch.bfloat16), C.c_int64(x.stride(0)), int(R), int(K), _p(out.q),
+                                     C.c_int64(out.q.stride(0)), _p(out.s), C.c_int64(out.s.stride(0)), _stream()), "quantize_mx")
+    return out
+
+
+def gemm_mx(x, w, bias, epilogue, out0, out1=None, out2=None, *, M=None, ldo=None, out_scale=None, gate=None, gate_rows=1, gate_ld=0,
+            tokens=0, tok_pad=0, heads=0, head_dim=0, transpose_mask=0, head_dim_pad=0):
+    """out = epi(deq(x)[M,K] @ deq(w)[N,K]^T + bias) on the MX-FP8 MFMA.  x, w: MX.  epilogue: EPI_F32, EPI_HEADS, EPI_GATE_RES or
+    EPI_GELU_ERF, whose output is MXFP8 (out0 uint8 e4m3 [M, ldo], out_scale uint8 [M, N / 32])."""
+    _chk_dev(x.q, w.q, out0)
+    a = L.MxGemmArgs()
+    K = w.q.shape[1]
+    if x.q.shape[-1] != K:
+        raise ValueError(f"gemm_mx: activation has {x.q.shape[-1]} input features, the weight expects {K}")
+    a.Xq, a.Xs, a.ldx, a.ldxs = _p(x.q), _p(x.s), x.q.stride(0), x.s.stride(0)
+    a.Wq, a.Ws, a.ldw, a.ldws = _p(w.q), _p(w.s), w.q.stride(0), w.s.stride(0)
+    a.bias = _p(bias)
+    a.M = int(M if M is not None else x.q.shape[0])
+    a.N, a.K = w.q.shape[0], K
+    a.epilogue = epilogue
+    a.out0, a.out1, a.out2 = _p(out0), _p(out1), _p(out2)
+    a.ldo = int(ldo if ldo is not None else w.q.shape[0])
+    a.out_scale = _p(out_scale)
+    a.ldos = int(out_scale.stride(0)) if out_scale is not None else 0
+    a.gate, a.gate_rows, a.gate_ld = _p(gate), gate_rows, gate_ld
+    a.tokens, a.tok_pad, a.heads, a.head_dim, a.transpose_mask, a.head_dim_pad = tokens, tok_pad, heads, head_dim, transpose_mask, head_dim_pad
+    L.check(L.lib().ln3d_gemm_mxfp8(C.byref(a), _stream()), "gemm_mx")
+
+
 def heads_norm_fusable(M, N, tokens, head_dim, head_dim_pad=0):
     """True when ln3d_gemm_bf16's HEADS epilogue applies qk_norm itself for this problem - the library's own answer (it depends on
     the tile configuration it picks), not a copy of its heuristic."""
@@ -86,6 +138,15 @@ def norm_modulate(x, y, rows, D, kind=0, eps=1e-6, weight=None, shift=None, scal
     a.shift, a.scale, a.mod_rows, a.mod_ld = _p(shift), _p(scale), mod_rows, mod_ld
     a.shift_table, a.scale_table, a.rows_in, a.rows_out = _p(shift_table), _p(scale_table), rows_in, rows_out
     L.check(L.lib().ln3d_norm_modulate(C.byref(a), _stream()), "norm_modulate")
+
+
+def norm_modulate_mx(x, y, rows, D, kind=0, eps=1e-6, weight=None, shift=None, scale=None, mod_rows=1, mod_ld=0):
+    """norm_modulate with an MXFP8 output: y MX [rows, D] (contiguous)."""
+    _chk_dev(x, y.q)
+    a = L.NormArgs()
+    a.x, a.y, a.rows, a.D, a.kind, a.eps, a.weight = _p(x), _p(y.q), rows, D, kind, eps, _p(weight)
+    a.shift, a.scale, a.mod_rows, a.mod_ld = _p(shift), _p(scale), mod_rows, mod_ld
+    L.check(L.lib().ln3d_norm_modulate_mx(C.byref(a), _p(y.s), _stream()), "norm_modulate_mx")
 
 
 def timestep_embedding(t, out, B, dim=256):

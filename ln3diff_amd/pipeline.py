@@ -106,9 +106,11 @@ class T23DPipeline:
     """Text -> 3D: EulerEDM (LegacyDDPM sigmas) + VanillaCFG over DiT_TriLatent, then decode + render."""
 
     def __init__(self, dit, decoder, num_steps=250, cfg_scale=6.5, conditioner=None, triplane_scaling_divider=TRIPLANE_SCALING_DIVIDER,
-                 img_size=128):
+                 img_size=128, dit_precision=None):
         from .nsr.script_util import AE
         self.dit, self.decoder, self.conditioner = dit, decoder, conditioner
+        if dit_precision is not None:             # 'bf16' | 'mxfp8': DiT_TriLatent.set_matmul_precision (None: leave the model as it is)
+            dit.set_matmul_precision(dit_precision)
         self.rec_model = decoder if isinstance(decoder, AE) else AE(None, decoder, img_size)
         self.sampler = EulerEDMSampler(num_steps=num_steps, guider=VanillaCFG(cfg_scale))
         self.denoiser = DiscreteDenoiser()
