@@ -326,8 +326,9 @@ int ln3d_mesh_emit(const float* sigma, int G, float thr, const int64_t* offsets_
 /* ---------------------------------------------------------------- conv decoder pieces (channel-last f32/bf16)
  * GroupNorm(32, eps 1e-6, affine) + optional swish over x f32 [N, HW, C] -> bf16 (ldm model.py:45-51)        */
 #define LN3D_GN_PIXELS_PER_CHUNK 256
-/* stats_scratch: [N*groups*2 * (1 + ceil(HW / LN3D_GN_PIXELS_PER_CHUNK))] floats - the sums, then one partial pair per pixel chunk
- * (reduced in chunk order: the result is bitwise reproducible) */
+/* stats_scratch: [N*groups*2 * (1 + ceil(HW / LN3D_GN_PIXELS_PER_CHUNK))] floats - (mean, biased variance) per (sample, group), then one
+ * (mean, M2) pair per pixel chunk, summed about a pivot (the group's first element in the chunk) and merged in chunk order with
+ * Chan's formula (no E[x^2] - mean^2 cancellation; bitwise reproducible) */
 int ln3d_groupnorm_swish(const float* x, const float* w, const float* b, void* y_bf16, float* stats_scratch,
                          int N, int HW, int C, int groups, float eps, int swish, void* stream);
 /* im2col for 3x3 pad 1 convs on channel-last bf16 [N,H,W,C] with optional nearest 2x upsample of the input

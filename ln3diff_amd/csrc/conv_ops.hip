@@ -7,22 +7,27 @@
 #include "../../include/ln3d_encoder.h"
 
 // ------------------------------------------------------------------ GroupNorm (+swish) on f32 [N, HW, C] -> bf16
+// Statistics from centred quantities: every chunk sums x - pivot (the group's first element in the chunk) and stores (mean, M2); the
+// chunks are merged in order with Chan's formula.  E[x^2] - mean^2 in fp32 (before) lost the variance when |mean| >> std: ~3e-3 of it
+// at |mean| / std = 100, 20-30 % at 1000 (gn_any_kernel had the same flaw, fixed in r6 with two passes; here x is still read once).
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* x, float* stats, int HW, int C, int groups, int pix_per_block) {
   // grid (chunks, N); thread t -> channel t % C, pixel phase t / C
   const int n = blockIdx.y;
   const int c = threadIdx.x % C, ph = threadIdx.x / C, nph = 256 / C;
+  const int cpg = C / groups;
   const int p0 = blockIdx.x * pix_per_block;
   const int p1 = min(p0 + pix_per_block, HW);
+  const float* xc = x + ((int64_t)n * HW + p0) * C;            // pixel p0 of sample n (p0 < HW: chunks = ceil(HW / pix_per_block))
+  const float pivot = xc[(c / cpg) * cpg];
   float s = 0.f, q = 0.f;
   if (ph < nph)
     for (int p = p0 + ph; p < p1; p += nph) {
-      const float v = x[((int64_t)n * HW + p) * C + c];
-      s += v; q += v * v;
+      const float d = x[((int64_t)n * HW + p) * C + c] - pivot;
+      s += d; q += d * d;
     }
   __shared__ float sh[2][256];
   sh[0][threadIdx.x] = s; sh[1][threadIdx.x] = q;
   __syncthreads();
-  const int cpg = C / groups;
   if (threadIdx.x < groups) {
     float ts = 0.f, tq = 0.f;
     for (int pp = 0; pp < nph; ++pp)
@@ -30,20 +35,30 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* x, float* st
         ts += sh[0][pp * C + threadIdx.x * cpg + cc];
         tq += sh[1][pp * C + threadIdx.x * cpg + cc];
       }
-    // per-chunk partial sums; gn_reduce_kernel adds them in chunk order (fp32 atomics here made the planes differ from run to run)
+    const float dm = ts / (float)((p1 - p0) * cpg);
+    // per-chunk (mean, M2); gn_reduce_kernel merges them in chunk order (fp32 atomics here made the planes differ from run to run)
     float* part = stats + 2 * (int64_t)gridDim.y * groups + (((int64_t)n * gridDim.x + blockIdx.x) * groups + threadIdx.x) * 2;
-    part[0] = ts; part[1] = tq;
+    part[0] = xc[threadIdx.x * cpg] + dm;
+    part[1] = fmaxf(tq - ts * dm, 0.f);
   }
 }
 
-__global__ void gn_reduce_kernel(float* stats, int N, int groups, int chunks) {
+// Chan et al.'s pairwise update, chunk by chunk; the count of chunk k is min(ppb, HW - k * ppb) * cpg.  -> stats[2 i] = mean,
+// stats[2 i + 1] = biased variance of (sample, group) i
+__global__ void gn_reduce_kernel(float* stats, int N, int groups, int chunks, int HW, int cpg, int ppb) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;          // (n, group)
   if (i >= N * groups) return;
   const int n = i / groups, g = i % groups;
   const float* part = stats + 2 * (int64_t)N * groups + ((int64_t)n * chunks * groups + g) * 2;
-  float ts = 0.f, tq = 0.f;
-  for (int c = 0; c < chunks; ++c) { ts += part[(int64_t)c * groups * 2]; tq += part[(int64_t)c * groups * 2 + 1]; }
-  stats[2 * i] = ts; stats[2 * i + 1] = tq;
+  float na = 0.f, mean = 0.f, m2 = 0.f;
+  for (int c = 0; c < chunks; ++c) {
+    const float nb = (float)(min(ppb, HW - c * ppb) * cpg), nab = na + nb;
+    const float delta = part[(int64_t)c * groups * 2] - mean;
+    mean += delta * (nb / nab);
+    m2 += part[(int64_t)c * groups * 2 + 1] + delta * delta * (na * (nb / nab));
+    na = nab;
+  }
+  stats[2 * i] = mean; stats[2 * i + 1] = m2 / na;
 }
 
 __global__ void gn_apply_kernel(const float* x, const float* stats, const float* w, const float* b, bf16_t* y, int64_t total4,
@@ -54,14 +69,13 @@ __global__ void gn_apply_kernel(const float* x, const float* stats, const float*
   const int c = (int)(i % C);
   const int64_t n = i / ((int64_t)HW * C);
   const int cpg = C / groups;
-  const float cnt = (float)HW * cpg;
   const float4 v = *reinterpret_cast<const float4*>(x + i);
   float in[4] = {v.x, v.y, v.z, v.w}, out[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int g = (c + k) / cpg;
-    const float mean = stats[(n * groups + g) * 2] / cnt;
-    const float var = fmaxf(stats[(n * groups + g) * 2 + 1] / cnt - mean * mean, 0.f);
+    const float mean = stats[(n * groups + g) * 2];
+    const float var = stats[(n * groups + g) * 2 + 1];
     float t = (in[k] - mean) * rsqrtf(var + eps) * w[c + k] + b[c + k];
     if (swish) t = t / (1.0f + __expf(-t));
     out[k] = t;
@@ -72,12 +86,13 @@ __global__ void gn_apply_kernel(const float* x, const float* stats, const float*
 
 extern "C" int ln3d_groupnorm_swish(const float* x, const float* w, const float* b, void* y, float* stats_scratch, int N, int HW,
                                     int C, int groups, float eps, int swish, void* stream) {
-  if (!x || !w || !b || !y || !stats_scratch || C % groups || 256 % C || C % 4) return LN3D_ERR_BAD_ARG;
+  if (!x || !w || !b || !y || !stats_scratch || N <= 0 || HW <= 0 || C <= 0 || groups <= 0) return LN3D_ERR_BAD_ARG;
+  if (C % groups || 256 % C || C % 4) return LN3D_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   const int ppb = LN3D_GN_PIXELS_PER_CHUNK;
   const int chunks = (HW + ppb - 1) / ppb;
   hipLaunchKernelGGL(gn_stats_kernel, dim3(chunks, N), dim3(256), 0, s, x, stats_scratch, HW, C, groups, ppb);
-  hipLaunchKernelGGL(gn_reduce_kernel, dim3((N * groups + 255) / 256), dim3(256), 0, s, stats_scratch, N, groups, chunks);
+  hipLaunchKernelGGL(gn_reduce_kernel, dim3((N * groups + 255) / 256), dim3(256), 0, s, stats_scratch, N, groups, chunks, HW, C / groups, ppb);
   const int64_t total4 = (int64_t)N * HW * C / 4;
   hipLaunchKernelGGL(gn_apply_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, x, stats_scratch, w, b, (bf16_t*)y, total4, HW,
                      C, groups, eps, swish);
@@ -105,7 +120,8 @@ __global__ void im2col3x3_kernel(const bf16_t* x, bf16_t* col, int H, int W, int
   *reinterpret_cast<uint4*>(col + row * Kpad + kk) = v;
 }
 extern "C" int ln3d_im2col3x3(const void* x, void* col, int N, int H, int W, int C, int upsample, int Kpad, void* stream) {
-  if (!x || !col || C % 8 || Kpad % 8 || Kpad < 9 * C || (upsample != 1 && upsample != 2)) return LN3D_ERR_BAD_ARG;
+  if (!x || !col || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || Kpad % 8 || Kpad < 9 * C || (upsample != 1 && upsample != 2))
+    return LN3D_ERR_BAD_ARG;
   const int64_t rows = (int64_t)N * H * upsample * W * upsample;
   const int64_t total8 = rows * (Kpad / 8);
   hipLaunchKernelGGL(im2col3x3_kernel, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
@@ -130,7 +146,7 @@ __global__ void cl_to_nchw_kernel(const float* src, float* dst, int C, int HW) {
   }
 }
 extern "C" int ln3d_planes_to_nchw(const float* src, float* dst, int NP, int C, int H, int W, void* stream) {
-  if (!src || !dst || C != 32) return LN3D_ERR_BAD_ARG;
+  if (!src || !dst || NP <= 0 || H <= 0 || W <= 0 || C != 32) return LN3D_ERR_BAD_ARG;
   const int HW = H * W;
   hipLaunchKernelGGL(cl_to_nchw_kernel, dim3((HW + 31) / 32, NP * 3), dim3(256), 0, (hipStream_t)stream, src, dst, C, HW);
   return ln3d_check_launch();

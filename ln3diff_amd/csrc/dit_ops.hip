@@ -257,7 +257,7 @@ __global__ void timestep_embedding_kernel(const float* t, bf16_t* out, int B, in
   out[(int64_t)b * dim + half + k] = f2bf(sinf(arg));
 }
 extern "C" int ln3d_timestep_embedding(const float* t, void* out, int B, int dim, void* stream) {
-  if (!t || !out || dim % 2) return LN3D_ERR_BAD_ARG;
+  if (!t || !out || B <= 0 || dim <= 0 || dim % 2) return LN3D_ERR_BAD_ARG;
   const int n = B * dim / 2;
   hipLaunchKernelGGL(timestep_embedding_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, t, (bf16_t*)out, B, dim);
   return ln3d_check_launch();
@@ -287,7 +287,7 @@ __global__ void cast_f32_bf16_kernel(const float4* x, uint2* y, int64_t n4) {
   }
 }
 extern "C" int ln3d_cast_f32_bf16(const float* x, void* y, int64_t n, void* stream) {
-  if (!x || !y || n % 4) return LN3D_ERR_BAD_ARG;
+  if (!x || !y || n <= 0 || n % 4) return LN3D_ERR_BAD_ARG;
   const int64_t n4 = n / 4;
   int64_t blocks = (n4 + 255) / 256; if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float4*)x, (uint2*)y, n4);
@@ -373,7 +373,8 @@ __global__ __launch_bounds__(256) void patch_embed_triplane_kernel(const float* 
 }
 extern "C" int ln3d_patch_embed_triplane(const float* latent, const float* w, const float* bias, void* out_silu_bf16,
                                          float* out_raw, int B, int Cg, int S, int p, int D, void* stream) {
-  if (!latent || !w || !bias || !out_silu_bf16 || Cg * p * p > 64 || S % p) return LN3D_ERR_BAD_ARG;
+  if (!latent || !w || !bias || !out_silu_bf16 || B <= 0 || Cg <= 0 || S <= 0 || p <= 0 || D <= 0) return LN3D_ERR_BAD_ARG;
+  if (Cg * p * p > 64 || S % p) return LN3D_ERR_BAD_ARG;
   const int L = (S / p) * (S / p);
   hipLaunchKernelGGL(patch_embed_triplane_kernel, dim3(B * 3 * L), dim3(256), 0, (hipStream_t)stream, latent, w, bias,
                      (bf16_t*)out_silu_bf16, out_raw, Cg, S, p, D);
@@ -386,7 +387,7 @@ __global__ void tile_rows_kernel(const float4* x, float4* y, int64_t per4, int64
   if (i < total4) y[i] = x[i % per4];
 }
 extern "C" int ln3d_tile_rows(const float* x, float* y, int64_t per, int reps, void* stream) {
-  if (!x || !y || per % 4) return LN3D_ERR_BAD_ARG;
+  if (!x || !y || per <= 0 || reps <= 0 || per % 4) return LN3D_ERR_BAD_ARG;
   const int64_t total4 = per / 4 * reps;
   hipLaunchKernelGGL(tile_rows_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)x,
                      (float4*)y, per / 4, total4);
@@ -653,7 +654,7 @@ __global__ void add_table_rows_kernel(const float* t0, const float* tables, floa
   out[i] = tables[l * W + w] + t0[b * W + w];
 }
 extern "C" int ln3d_add_table_rows(const float* t0, const float* tables, float* out, int layers, int B, int64_t W, void* stream) {
-  if (!t0 || !tables || !out) return LN3D_ERR_BAD_ARG;
+  if (!t0 || !tables || !out || layers <= 0 || B <= 0 || W <= 0) return LN3D_ERR_BAD_ARG;
   const int64_t total = (int64_t)layers * B * W;
   hipLaunchKernelGGL(add_table_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t0, tables, out, B, W, total);
   return ln3d_check_launch();

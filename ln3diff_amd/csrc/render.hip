@@ -1122,7 +1122,7 @@ __global__ void planes_to_cl_kernel(const float* src, float* dst, int C, int HW,
   }
 }
 extern "C" int ln3d_planes_to_channel_last(const float* src, float* dst, int NP, int C, int H, int W, void* stream) {
-  if (!src || !dst || C != 32) return LN3D_ERR_BAD_ARG;
+  if (!src || !dst || NP <= 0 || H <= 0 || W <= 0 || C != 32) return LN3D_ERR_BAD_ARG;
   const int HW = H * W;
   hipLaunchKernelGGL(planes_to_cl_kernel, dim3((HW + 31) / 32, NP * 3), dim3(256), 0, (hipStream_t)stream, src, dst, C, HW, (int64_t)NP * 3 * C * HW);
   return ln3d_check_launch();

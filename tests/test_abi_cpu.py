@@ -57,6 +57,31 @@ NULL_CALLS = {
 }
 NOT_A_KERNEL = {'ln3d_abi_version', 'ln3d_gemm_heads_norm_fusable', 'ln3d_device_cus'}      # pure host queries
 
+# Sizes <= 0 are bad arguments too, not zero-sized grids: every buffer below is a fake, never dereferenced address, so on a correct
+# library nothing is launched
+P = C.c_void_p(0x10000)
+ZERO_CALLS = [
+    ('ln3d_tile_rows', (P, P, I64(4), 0, N)),
+    ('ln3d_tile_rows', (P, P, I64(0), 3, N)),
+    ('ln3d_add_table_rows', (P, P, P, 0, 1, I64(4), N)),
+    ('ln3d_add_table_rows', (P, P, P, 1, 0, I64(4), N)),
+    ('ln3d_add_table_rows', (P, P, P, 1, 1, I64(0), N)),
+    ('ln3d_timestep_embedding', (P, P, 0, 256, N)),
+    ('ln3d_cast_f32_bf16', (P, P, I64(0), N)),
+    ('ln3d_groupnorm_swish', (P, P, P, P, P, 0, 64, 64, 32, F(1e-6), 1, N)),
+    ('ln3d_groupnorm_swish', (P, P, P, P, P, 1, 0, 64, 32, F(1e-6), 1, N)),
+    ('ln3d_groupnorm_swish', (P, P, P, P, P, 1, 64, 64, 0, F(1e-6), 1, N)),
+    ('ln3d_im2col3x3', (P, P, 0, 8, 8, 64, 1, 576, N)),
+    ('ln3d_im2col3x3', (P, P, 1, 0, 8, 64, 1, 576, N)),
+    ('ln3d_im2col3x3', (P, P, 1, 8, 0, 64, 1, 576, N)),
+    ('ln3d_planes_to_channel_last', (P, P, 0, 32, 8, 8, N)),
+    ('ln3d_planes_to_channel_last', (P, P, 1, 32, 0, 8, N)),
+    ('ln3d_planes_to_nchw', (P, P, 0, 32, 8, 8, N)),
+    ('ln3d_planes_to_nchw', (P, P, 1, 32, 8, 0, N)),
+    ('ln3d_patch_embed_triplane', (P, P, P, P, P, 0, 4, 32, 2, 128, N)),
+    ('ln3d_patch_embed_triplane', (P, P, P, P, P, 1, 4, 32, 0, 128, N)),
+]
+
 
 def test_every_entry_point_rejects_missing_buffers(hip_lib):
     hdr = open(os.path.join(ROOT, 'include', 'ln3d.h')).read()
@@ -90,3 +115,8 @@ def test_gate_residual_row_arguments_are_validated(hip_lib):
     for extra in bad:
         a = GemmArgs(**dict(base, **extra))
         assert hip_lib.ln3d_gemm_bf16(C.byref(a), None) == -1, extra
+
+
+def test_zero_sizes_are_bad_arguments(hip_lib):
+    for name, args in ZERO_CALLS:
+        assert getattr(hip_lib, name)(*args) == -1, (name, args)              # LN3D_ERR_BAD_ARG, before any launch
