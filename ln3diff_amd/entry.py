@@ -38,12 +38,17 @@ _RELEASED_DECODER = 'vit.vit_triplane.RodinSR_256_fusionv6_ConvQuant_liteSR_dino
 # with the U-Net denoiser (--create_dit false) under the guided_diffusion engines; only with this class are --cfg / --ray_start /
 # --ray_end read (vit/vit_triplane_shapenet.py)
 _SHAPENET_DECODER = 'vit.vit_triplane.RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn'
+# the FFHQ launcher's decoder (sample_ffhq_t23d.sh): a DINOv2 ViT-B decoder of TriplaneFusionBlockv3 blocks + two roll-out SR convs, a
+# [B, 12, 16, 16] latent (--overwrite_diff_inp_size 16); selected like the ShapeNet one, --cfg ffhq gives its renderer preset and
+# --vae_p is not read (the launcher leaves it at create_3DAE_model's default 1, which the class is built with)
+_FFHQ_DECODER = ('vit.vit_triplane.VAE_LDM_V4_vit3D_v3_conv3D_depth2_xformer_mha_PEinit_2d_sincos_uvit_RodinRollOutConv_4x4_lite_mlp_'
+                 'unshuffle_4XC_final')
 _CHECKED = {
     'mixed_prediction': (False, None, ('edm', 'flow', 'gd'), None),      # see validate(): the U-Net denoiser (--create_dit false) has it
     'predict_v': (False, None, ('gd',), None),            # see validate(): only the guided_diffusion engines read them
     'pred_type': ('eps', None, ('gd',), None),            # (guided_diffusion/script_util.py:36-37,84,682-686: predict_v -> ModelMeanType.V)
-    'ae_classname': (_RELEASED_DECODER, {_RELEASED_DECODER, _SHAPENET_DECODER}, ('edm', 'flow', 'gd'),
-                     "only the released decoder class is built (and, with --create_dit false, the ShapeNet launchers' one)"),
+    'ae_classname': (_RELEASED_DECODER, {_RELEASED_DECODER, _SHAPENET_DECODER, _FFHQ_DECODER}, ('edm', 'flow', 'gd'),
+                     "only the released decoder class is built (and, with --create_dit false, the ShapeNet and FFHQ launchers' ones)"),
     'vae_p': (2, {2}, ('edm', 'flow', 'gd'), "the decoder tokeniser is built for vae_p = 2"),
     'denoise_out_channels': (4, None, ('edm', 'flow', 'gd'), None),
     'decoder_in_chans': (32, {32}, ('edm', 'flow', 'gd'), "tri-plane feature width 32 (OSGDecoder 32 -> 64 -> 4)"),
@@ -164,6 +169,20 @@ def validate(args):
             shapenet_rendering_kwargs(args.cfg, args.ray_start, args.ray_end)
         except ValueError as e:
             raise SystemExit(str(e))
+    if args.ae_classname == _FFHQ_DECODER:
+        if kind != 'gd' or not unet:
+            raise SystemExit(f"--ae_classname {args.ae_classname}: the FFHQ decoder class goes with the U-Net denoiser "
+                             "(--create_dit false) under --trainer_name adm / ddpm / vpsde_crossattn, as its launcher runs it")
+        from .vit.vit_triplane_ffhq import ffhq_rendering_kwargs
+        try:
+            ffhq_rendering_kwargs(args.cfg)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        S = int(args.overwrite_diff_inp_size) if args.overwrite_diff_inp_size else args.diffusion_input_size
+        if S != 16 or args.denoise_in_channels != 12:
+            raise SystemExit(f"--ae_classname {args.ae_classname}: the FFHQ decoder class decodes a [B, 12, 16, 16] latent; pass "
+                             "--denoise_in_channels 12 --denoise_out_channels 12 and --overwrite_diff_inp_size 16, as its launcher does "
+                             f"(got {args.denoise_in_channels} channels at {S} x {S})")
     if args.denoise_out_channels != args.denoise_in_channels:
         raise SystemExit(f"--denoise_out_channels {args.denoise_out_channels} != --denoise_in_channels {args.denoise_in_channels}: the "
                          "samplers update the latent in place with the network output (learn_sigma False)")
@@ -224,6 +243,13 @@ def build_models(args, dev, rank):
         tp = Triplane(img_resolution=args.image_size, rendering_kwargs=shapenet_rendering_kwargs(args.cfg, args.ray_start, args.ray_end),
                       decoder_in_chans=args.decoder_in_chans, decoder_output_dim=args.decoder_output_dim)
         dec = ShapeNetDec(dinov2_vitb14(), tp, cls_token=False, vae_p=2, ldm_z_channels=4, ldm_embed_dim=4)
+    elif args.ae_classname == _FFHQ_DECODER:
+        # --arch_decoder vitb, --decoder_output_dim 32, --out_chans 96, --decoder_in_chans 32; vae_p / ldm_z_channels / ldm_embed_dim at
+        # create_3DAE_model's defaults (nsr/script_util.py:1203-1205), which the launcher does not override
+        from .vit import vit_triplane_ffhq as ffhq
+        tp = Triplane(img_resolution=args.image_size, rendering_kwargs=ffhq.ffhq_rendering_kwargs(args.cfg),
+                      decoder_in_chans=args.decoder_in_chans, decoder_output_dim=args.decoder_output_dim)
+        dec = getattr(ffhq, ffhq.CLASS_NAME)(ffhq.dinov2_vitb14(), tp, cls_token=False, vae_p=1, ldm_z_channels=4, ldm_embed_dim=4)
     else:
         vit = DiT2_models[args.arch_dit_decoder](input_size=16, num_classes=0, learn_sigma=False, in_channels=dit.embed_dim,
                                                  mixed_prediction=False, context_dim=None, roll_out=True, plane_n=3)

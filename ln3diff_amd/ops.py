@@ -481,6 +481,8 @@ def rollout_means(x, rowmean, colmean, N, H, W, Cc):
     _chk_dev(x, rowmean, colmean)
     _need(x.is_contiguous() and x.numel() == N * H * W * Cc and rowmean.numel() == N * H * Cc and colmean.numel() == N * W * Cc,
           "rollout_means: x [N, H, W, C], rowmean [N, H, C], colmean [N, W, C] (f32, contiguous)")
+    if x.dtype == torch.bfloat16:                # include/ln3d_ffhq.h: the same means of bf16 planes
+        return L.check(L.lib().ln3d_rollout_means_bf16(_p(x), _p(rowmean), _p(colmean), N, H, W, Cc, _stream()), "rollout_means_bf16")
     L.check(L.lib().ln3d_rollout_means(_p(x), _p(rowmean), _p(colmean), N, H, W, Cc, _stream()), "rollout_means")
 
 
@@ -492,3 +494,20 @@ def im2col3x3_rollout(x, rowmean, colmean, col, plane, H, W, Cc, Kpad):
           "im2col3x3_rollout: rowmean [3, H, C] / colmean [3, W, C]")
     _need(col.dtype == torch.bfloat16 and col.is_contiguous() and col.numel() == H * W * Kpad, "im2col3x3_rollout: col bf16 [H*W, Kpad]")
     L.check(L.lib().ln3d_im2col3x3_rollout(_p(x), _p(rowmean), _p(colmean), _p(col), plane, H, W, Cc, Kpad, _stream()), "im2col3x3_rollout")
+
+
+def conv3x3_rollout(x, rowmean, colmean, w, bias, base, out, H, W, Cc, Cout, slope=0.01):
+    """Fused roll-out 3x3 conv of one object (include/ln3d_ffhq.h): x f32 / bf16 [3, H, W, C], rowmean [3, H, C], colmean [3, W, C],
+    w bf16 [3, Cout, 27C], bias f32 [3, Cout], base f32 [3, h, w, Cout] (resized when h, w differ from H, W) -> out f32 [3, H, W, Cout]
+    = base + leaky_relu(conv + bias)."""
+    _chk_dev(x, rowmean, colmean, w, bias, base, out)
+    _need(x.dtype in (torch.float32, torch.bfloat16) and x.is_contiguous() and x.numel() == 3 * H * W * Cc, "conv3x3_rollout: x f32 / bf16 [3, H, W, C]")
+    for z, n, what in ((rowmean, 3 * H * Cc, "rowmean f32 [3, H, C]"), (colmean, 3 * W * Cc, "colmean f32 [3, W, C]"), (bias, 3 * Cout, "bias f32 [3, Cout]"),
+                       (out, 3 * H * W * Cout, "out f32 [3, H, W, Cout]")):
+        _need(z.dtype == torch.float32 and z.is_contiguous() and z.numel() == n, "conv3x3_rollout: " + what)
+    _need(w.dtype == torch.bfloat16 and w.is_contiguous() and w.numel() == 3 * Cout * 27 * Cc, "conv3x3_rollout: w bf16 [3, Cout, 27C]")
+    _need(base.dtype == torch.float32 and base.is_contiguous() and base.dim() == 4 and base.shape[0] == 3 and base.shape[3] == Cout,
+          "conv3x3_rollout: base f32 [3, h, w, Cout]")
+    _need(out.data_ptr() != x.data_ptr(), "conv3x3_rollout: out must not be x")
+    L.check(L.lib().ln3d_conv3x3_rollout_bf16(_p(x), int(x.dtype == torch.bfloat16), _p(rowmean), _p(colmean), _p(w), _p(bias), _p(base),
+                                              base.shape[1], base.shape[2], _p(out), H, W, Cc, Cout, C.c_float(slope), _stream()), "conv3x3_rollout")

@@ -366,8 +366,12 @@ class RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout
 
 def __getattr__(name):
     """The ShapeNet launchers' decoder class (--ae_classname vit.vit_triplane.RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn)
-    lives in vit_triplane_shapenet, which imports this module; it is re-exported here lazily."""
+    lives in vit_triplane_shapenet, which imports this module; it is re-exported here lazily.  So is the FFHQ launcher's
+    (vit_triplane_ffhq)."""
     if name == 'RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn':
         from . import vit_triplane_shapenet
         return vit_triplane_shapenet.RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn
+    if name == 'VAE_LDM_V4_vit3D_v3_conv3D_depth2_xformer_mha_PEinit_2d_sincos_uvit_RodinRollOutConv_4x4_lite_mlp_unshuffle_4XC_final':
+        from . import vit_triplane_ffhq
+        return getattr(vit_triplane_ffhq, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
