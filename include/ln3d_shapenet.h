@@ -18,7 +18,7 @@ extern "C" {
  *   qkv f32 [B*3*p*p, ld]: q at columns [0, D), k at [D, 2D), v at [2D, 3D) (the fused [wq ; w_kv] projection), D = H * 64
  *   out bf16 [B*3*p*p, D], head h at columns h*64 ..
  * Each object only reads its own tokens (the reference's batched path re-orders rows across objects when B > 1; B = 1 agrees).
- * 1 <= p <= 32, Dh = 64. */
+ * 1 <= p <= 32, Dh = 64; B * 3 * p * p * H < 2^31 (else LN3D_ERR_UNSUPPORTED). */
 int ln3d_triplane_axis_attention(const float* qkv, int64_t ld, void* out_bf16, int B, int p, int H, float scale, void* stream);
 
 /* decoder_pred output -> the two low-resolution inputs of conv_sr (unpatchify_triplane with patch P, then the short_cut's view):

@@ -1276,7 +1276,7 @@ __global__ void rmsnorm_heads_kernel(bf16_t* x, const float* w, int64_t rows, in
 }
 
 extern "C" int ln3d_rmsnorm_heads_bf16(void* x, const float* w, int64_t rows, int Dh, int true_dim, float eps, void* stream) {
-  if (!x || !w || (Dh != 64 && Dh != 80 && Dh != 128) || true_dim < 0 || true_dim > Dh) return LN3D_ERR_BAD_ARG;
+  if (!x || !w || rows <= 0 || (Dh != 64 && Dh != 80 && Dh != 128) || true_dim < 0 || true_dim > Dh) return LN3D_ERR_BAD_ARG;
   if (true_dim == 0) true_dim = Dh;
   const int per = Dh <= 64 ? 16 : 32;
   const int64_t threads = rows * per;

@@ -338,7 +338,8 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(const float* x, const 
 }
 extern "C" int ln3d_patch_embed(const float* x, const float* in_scale, const float* w, const float* bias, const float* pos,
                                 float* tokens, int Bx, int Bn, int C, int S, int p, int D, void* stream) {
-  if (!x || !w || !bias || !pos || !tokens || C * p * p > 64 || S % p) return LN3D_ERR_BAD_ARG;
+  if (!x || !w || !bias || !pos || !tokens || Bx <= 0 || Bn <= 0 || C <= 0 || S <= 0 || p <= 0 || D <= 0) return LN3D_ERR_BAD_ARG;
+  if (C * p * p > 64 || S % p) return LN3D_ERR_BAD_ARG;
   const int L = (S / p) * (S / p);
   hipLaunchKernelGGL(patch_embed_kernel, dim3((Bn * 3 * L + PE_TPB - 1) / PE_TPB), dim3(256), 0, (hipStream_t)stream, x, in_scale, w, bias, pos,
                      tokens, Bx, Bn, C, S, p, D);
@@ -472,7 +473,8 @@ __global__ __launch_bounds__(256) void final_layer_kernel(FinalP q) {
 extern "C" int ln3d_final_layer(const float* tokens, const float* shift, const float* scale, int64_t mod_ld,
                                 const float* shift_table, const float* scale_table, const float* w, const float* bias,
                                 float* out, int Bn, int C, int S, int p, int D, void* stream) {
-  if (!tokens || !shift || !scale || !w || !bias || !out || D % 128 || D > 128 * MAXV) return LN3D_ERR_BAD_ARG;
+  if (!tokens || !shift || !scale || !w || !bias || !out || D <= 0 || D % 128 || D > 128 * MAXV) return LN3D_ERR_BAD_ARG;
+  if (Bn <= 0 || C <= 0 || S <= 0 || p <= 0 || S % p) return LN3D_ERR_BAD_ARG;
   FinalP q{tokens, shift, scale, mod_ld, shift_table, scale_table, w, bias, out, Bn, C, S, p, D};
   const int64_t ntok = (int64_t)Bn * 3 * (S / p) * (S / p);
   hipLaunchKernelGGL(final_layer_kernel, dim3((unsigned)((ntok + 4 * FL_TPW - 1) / (4 * FL_TPW))), dim3(256), 0, (hipStream_t)stream, q);

@@ -10,8 +10,8 @@
 // One wavefront per (query token, head): lane j < 2p scores key j, the softmax is two wave reductions, lane d sums the value column d.
 __global__ __launch_bounds__(64) void axis_attention_kernel(const float* qkv, int64_t ld, bf16_t* out, int p, int H, float scale) {
   const int lane = threadIdx.x;
-  const int h = blockIdx.x;
-  const int64_t row = blockIdx.y;                    // (b*3 + i)*N + y*p + x
+  const int h = blockIdx.x % H;                      // grid: row * H + h, heads fastest
+  const int64_t row = blockIdx.x / H;                // (b*3 + i)*N + y*p + x
   const int N = p * p, D = H * 64;
   const int64_t bi = row / N;
   const int n = (int)(row - bi * N);
@@ -45,7 +45,10 @@ __global__ __launch_bounds__(64) void axis_attention_kernel(const float* qkv, in
 extern "C" int ln3d_triplane_axis_attention(const float* qkv, int64_t ld, void* out, int B, int p, int H, float scale, void* stream) {
   if (!qkv || !out || B <= 0 || p < 1 || p > 32 || H <= 0 || ld < 3 * 64 * (int64_t)H) return LN3D_ERR_BAD_ARG;
   const int64_t rows = (int64_t)B * 3 * p * p;
-  hipLaunchKernelGGL(axis_attention_kernel, dim3(H, (unsigned)rows), dim3(64), 0, (hipStream_t)stream, qkv, ld, (bf16_t*)out, p, H, scale);
+  // one block per (row, head) on gridDim.x (up to 2^31 - 1): with the rows on gridDim.y (limit 65536) B * 3 * p * p passed the limit
+  // from B = 22 at p = 32
+  if (rows * H > 0x7fffffff) return LN3D_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(axis_attention_kernel, dim3((unsigned)(rows * H)), dim3(64), 0, (hipStream_t)stream, qkv, ld, (bf16_t*)out, p, H, scale);
   return ln3d_check_launch();
 }
 

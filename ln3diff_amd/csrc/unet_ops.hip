@@ -87,7 +87,8 @@ __global__ void im2col3x3_strided_kernel(const bf16_t* x, bf16_t* col, int H, in
   *reinterpret_cast<uint4*>(col + row * Kpad + kk) = v;
 }
 extern "C" int ln3d_im2col3x3_strided(const void* x, void* col, int N, int H, int W, int C, int stride, int Kpad, void* stream) {
-  if (!x || !col || C % 8 || Kpad % 8 || Kpad < 9 * C || stride < 1 || stride > 2 || N <= 0) return LN3D_ERR_BAD_ARG;
+  if (!x || !col || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || Kpad % 8 || Kpad < 9 * C || stride < 1 || stride > 2)
+    return LN3D_ERR_BAD_ARG;
   const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;          // floor((H + 2 - 3) / stride) + 1
   const int64_t total8 = (int64_t)N * Ho * Wo * (Kpad / 8);
   hipLaunchKernelGGL(im2col3x3_strided_kernel, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,

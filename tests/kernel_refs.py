@@ -1,4 +1,5 @@
-"""Float64 restatements of the glue kernels of include/ln3d.h and per-element bounds for their outputs.
+"""Float64 restatements of the glue kernels of include/ln3d.h and of the stage headers (ln3d_shapenet.h, ln3d_encoder.h, ln3d_ffhq.h)
+and per-element bounds for their outputs.
 
 Every reference is computed in double from the same fp32 / bf16 inputs the kernel received, from the operation's definition (the
 reference source lines each kernel's comment cites) or torch.nn.functional in double.  Besides the value, the fp32-sensitive
@@ -271,3 +272,228 @@ def patch_embed_triplane(latent, w, bias, p, D):
     raw = regroup(F.conv2d(lat, w64, b64, stride=p, groups=3))
     mag = regroup(F.conv2d(lat.abs(), w64.abs(), b64.abs(), stride=p, groups=3))
     return raw, mag
+
+
+# ================================================================ stage kernels (U-Net, VAE decoders, encoder, DiT boundary)
+def _f32(v):
+    """the fp32 value of a Python scalar argument, as the kernel receives it"""
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+# ---------------------------------------------------------------- softmax attention
+def attention_floor(score_mag, n_dot, Nk):
+    """Per-row floor of the attention bound, in fp32 ulps (2^-23) of sum_j p_j |v_j|.
+    A score is a sequential fp32 sum whose n_dot roundings (one per fma, or a product and an add rounding per term where the products
+    are not exact, and one for the multiplication by the softmax scale) each cost at most 2^-24 of the summed magnitudes:
+    |ds_j| <= n_dot * 2^-24 * score_mag, score_mag = |scale| * max_j sum_d |q_d k_jd|.  An absolute score error is a relative error
+    of exp(s_j - max); it reaches the output through the numerator and through the normaliser: 2 * max_j |ds_j| relative to
+    sum p |v|.  The rest, in units of 2^-24: Nk for the sequential value sum; Nk / 64 + 6 for the normaliser (strided partial sums
+    and a 6-level butterfly); 4 ln(Nk) for the exp argument (s - max and its product with log2(e) are each rounded, an absolute
+    2^-24 |s_j - max| per rounding on a term of weight p_j, and sum_j p_j |s_j - max| <= ln Nk; numerator and normaliser); 12 for the
+    exp itself, the reciprocal or division and the final product (2 ulps each at most).  In ulps (two units each):
+      floor = n_dot * score_mag + (Nk + Nk / 64 + 4 ln(max(Nk, 2)) + 18) / 2"""
+    return n_dot * score_mag + (Nk + Nk / 64.0 + 4.0 * math.log(max(Nk, 2)) + 18.0) / 2.0
+
+
+def attention_small(q, k, v, scale):
+    """q [B, Nq, H, Dh], k / v [B, Nk, H, Dh] bf16 (views) -> (ref [B, Nq, H, Dh], sum_j p_j |v_j| of the same shape, floor
+    [B, Nq, H, 1] in fp32 ulps of that sum: attention_floor with n_dot = Dh + 1, the bf16 x bf16 products being exact in fp32).
+    CrossAttention (attention_compat.py:161-202) / QKVAttentionLegacy (unet.py:359-389): softmax(scale * q k^T) v."""
+    q, k, v = _d(q), _d(k), _d(v)
+    sc = _f32(scale)
+    s = torch.einsum("bqhd,bkhd->bhqk", q, k) * sc
+    smag = torch.einsum("bqhd,bkhd->bhqk", q.abs(), k.abs()).amax(-1) * abs(sc)               # [B, H, Nq]
+    p = torch.softmax(s, -1)
+    out = torch.einsum("bhqk,bkhd->bqhd", p, v)
+    mag = torch.einsum("bhqk,bkhd->bqhd", p, v.abs())
+    floor = attention_floor(smag, q.shape[-1] + 1, k.shape[1]).permute(0, 2, 1)[..., None]
+    return out, mag, floor
+
+
+def triplane_axis_attention(qkv, B, p, H, scale):
+    """qkv f32 [B*3*p*p, >= 3*H*64] -> (ref [rows, H*64], sum p |v|, floor [rows, H*64]).  Conv3DCrossAttentionBlockXformerMHANested:
+    the query of plane i at (y, x) attends to tokens (y, j) of plane (i+1) % 3 and tokens (j, x) of plane (i+2) % 3, j < p, in
+    one softmax over the 2p keys.  floor: attention_floor with n_dot = 2 * 64 + 1 (fp32 x fp32 products are rounded, so a term costs
+    a product and an add rounding where the compiler does not contract them into an fma)."""
+    D = H * 64
+    t = _d(qkv)
+    sc = _f32(scale)
+    q, k, v = (t[:, i * D:(i + 1) * D].reshape(B, 3, p, p, H, 64) for i in range(3))
+    nxt = [1, 2, 0]
+    prv = [2, 0, 1]
+    k1, v1, k2, v2 = k[:, nxt], v[:, nxt], k[:, prv], v[:, prv]
+
+    def scores(qq, ka, kb):
+        return torch.cat([torch.einsum("biyxhd,biyjhd->biyxhj", qq, ka), torch.einsum("biyxhd,bijxhd->biyxhj", qq, kb)], -1)
+    s = scores(q, k1, k2) * sc
+    smag = scores(q.abs(), k1.abs(), k2.abs()).amax(-1) * abs(sc)
+    pr = torch.softmax(s, -1)
+
+    def av(va, vb):
+        return torch.einsum("biyxhj,biyjhd->biyxhd", pr[..., :p], va) + torch.einsum("biyxhj,bijxhd->biyxhd", pr[..., p:], vb)
+    out, mag = av(v1, v2), av(v1.abs(), v2.abs())
+    floor = attention_floor(smag, 2 * 64 + 1, 2 * p)[..., None].expand_as(out)
+    rows = B * 3 * p * p
+    return out.reshape(rows, D), mag.reshape(rows, D), floor.reshape(rows, D)
+
+
+# ---------------------------------------------------------------- GEGLU, mixed prediction
+def geglu(x, inner):
+    """x f32 [rows, 2 * inner] = [a | gate] -> (a * gelu(gate), scale) with the exact erf GELU (attention_compat.py:45-53).
+    gelu(g) = 0.5 g (1 + erf(g / sqrt 2)): its terms are 1 and |erf|, which cancel for g << 0, so
+    scale = |a| * 0.5 |g| * (1 + |erf(g / sqrt 2)|)."""
+    v = _d(x)
+    a, g = v[:, :inner], v[:, inner:]
+    e = torch.erf(g / math.sqrt(2.0))
+    return a * 0.5 * g * (1 + e), a.abs() * 0.5 * g.abs() * (1 + e.abs())
+
+
+def mix_prediction(eps, x, logit, sqrt_one_minus_ab):
+    """eps, x f32 [N, C, HW], logit f32 [C] -> (ref, scale): (1 - s_c) * sqrt(1 - ab) * x + s_c * eps, s = sigmoid(logit)
+    (continuous_diffusion_utils.py:748-754).  1 - s has the terms 1 and s; the fp32 sigmoid carries a relative error of about
+    (|logit| / 2 + 3) ulps (the exp argument's rounding is an absolute error of the exponent), which the s-dependent terms are
+    weighted with: scale = |c x| + s (|c x| + |eps|) (1 + |logit| / 8), to be used with 8 ulps."""
+    e, xx, lg = _d(eps), _d(x), _d(logit)[None, :, None]
+    c = _f32(sqrt_one_minus_ab)
+    s = torch.sigmoid(lg)
+    return (1 - s) * (c * xx) + s * e, (c * xx).abs() + s * ((c * xx).abs() + e.abs()) * (1 + lg.abs() / 8)
+
+
+# ---------------------------------------------------------------- bilinear resize
+def bilinear_taps(n_in, n_out):
+    """(i0, i1, l1, src) of every output index along one axis, computed in fp32 as ATen's upsample_bilinear2d does with
+    align_corners=False: scale = in / out, src = max(scale * (o + 0.5) - 0.5, 0), i0 = min(int(src), in - 1), i1 = min(i0 + 1, in - 1),
+    l1 = src - i0.  The taps are part of the operation's definition: for a non-dyadic ratio a float64 source index differs from this
+    by about src * 2^-24, far over a few ulps of the result."""
+    scale = torch.tensor(float(n_in), dtype=torch.float32) / torch.tensor(float(n_out), dtype=torch.float32)
+    o = torch.arange(n_out, dtype=torch.float32)
+    src = (scale * (o + 0.5) - 0.5).clamp(min=0)
+    i0 = src.to(torch.int64).clamp(max=n_in - 1)
+    i1 = (i0 + 1).clamp(max=n_in - 1)
+    l1 = src - i0.to(torch.float32)
+    return i0, i1, l1.double(), src.double()
+
+
+def resize_bilinear(x, Ho, Wo):
+    """x f32 [N, h, w, C] channel-last -> (ref [N, Ho, Wo, C], scale): the four fp32 taps of bilinear_taps blended in float64.
+    scale = the four weighted magnitudes + (src_y + src_x) * amax / 4, amax the largest |x| within two pixels of the first tap: a
+    kernel that contracts scale * (o + 0.5) - 0.5 into one fma rounds src once where ATen rounds twice, an absolute 2^-24 src on
+    l1 (and, where src sits on an integer, the neighbouring cell); with the 4 ulps of the blend this term admits 1 ulp of src."""
+    v = _d(x)
+    N, h, w, C = v.shape
+    y0, y1, ly, sy = bilinear_taps(h, Ho)
+    x0, x1, lx, sx = bilinear_taps(w, Wo)
+    ly, lx = ly[None, :, None, None], lx[None, None, :, None]
+
+    def tap(t, yi, xi):
+        return t[:, yi][:, :, xi]
+    ref = (1 - ly) * ((1 - lx) * tap(v, y0, x0) + lx * tap(v, y0, x1)) + ly * ((1 - lx) * tap(v, y1, x0) + lx * tap(v, y1, x1))
+    a = v.abs()
+    mag = (1 - ly) * ((1 - lx) * tap(a, y0, x0) + lx * tap(a, y0, x1)) + ly * ((1 - lx) * tap(a, y1, x0) + lx * tap(a, y1, x1))
+    amax = F.max_pool2d(a.permute(0, 3, 1, 2), 5, 1, 2).permute(0, 2, 3, 1)
+    slack = (sy[None, :, None, None] + sx[None, None, :, None]) * tap(amax, y0, x0) / 4
+    return ref, mag + slack
+
+
+def resize_add_lrelu(base, t, Ho, Wo, slope):
+    """(resize(base) + leaky_relu(t, slope), scale): the residual step of RodinConv3D4X_lite_mlp_as_residual"""
+    r, mag = resize_bilinear(base, Ho, Wo)
+    tt = _d(t)
+    act = torch.where(tt >= 0, tt, tt * _f32(slope))
+    return r + act, mag + act.abs()
+
+
+# ---------------------------------------------------------------- sequential means
+def mean_over(x, dim):
+    """(mean over dim, sum |x| / n): an n-term sequential fp32 sum is within (n - 1) * 2^-24 * sum |x| and the division rounds once
+    more, so the bound is (n - 1) / 2 + 1 fp32 ulps of sum |x| / n (mean_ulps)."""
+    v = _d(x)
+    return v.mean(dim), v.abs().mean(dim)
+
+
+def mean_ulps(n):
+    return (n - 1) / 2.0 + 1.0
+
+
+# ---------------------------------------------------------------- multi-view posterior
+def mv_posterior(h, qw, qb, eps, B, F_, E=4):
+    """h f32 [B*F, 6E, HW] (any strides), qw [6E, 2E], qb [6E], eps [B, E, 3, HW] or None -> dict name -> (ref, scale) for mean, logvar,
+    z, latent_tok, log_q, entropy, and 'ulps' (vit_triplane.py:912-933, 1152-1199; distributions.py:44-88, soft_clamp).
+    With U = F / 2 + 5 fp32 ulps for a moment (pooling: (F - 1) / 2 + 1; eight fma and the bias: 4.5) of magnitude
+    m_mag = sum |qw| avg|h| + |qb|, every output is held to ulps = U + 4 of:
+      mean     m_mag
+      logvar   s_lv = m_mag + |logvar|     (20 tanh(. / 20): slope <= 1, and tanh, the division and the product within 4 ulps)
+      z, tok   m_mag + |mean| + |std eps| (1 + s_lv)      (std = exp(logvar / 2): an absolute logvar error is a relative one of std)
+      entropy  s_lv + 0.5 (log 2 pi + 1)
+      log_q    |ns| (|z| + |mean|) / var + ns^2 (1.5 s_lv + 2) + s_lv + 0.5 log 2 pi + |logvar|
+               (ns = (z - mean) / var: z - mean cancels when |mean| >> std |eps|, term magnitude (|z| + |mean|) / var; var carries the
+               whole logvar error, the std inside z half of it: 1.5 s_lv per ns, and ns is squared)."""
+    hh = _d(h).reshape(B, F_, 6 * E, -1)
+    HW = hh.shape[-1]
+    avg, amag = hh.mean(1), hh.abs().mean(1)                                          # [B, 6E, HW]
+    w, b = _d(qw), _d(qb)
+    G = 2 * E
+    mom = torch.einsum("goj,bgjp->bgop", w.reshape(3, G, G), avg.reshape(B, 3, G, HW)).reshape(B, 6 * E, HW) + b[None, :, None]
+    mmag = torch.einsum("goj,bgjp->bgop", w.abs().reshape(3, G, G), amag.reshape(B, 3, G, HW)).reshape(B, 6 * E, HW) + b.abs()[None, :, None]
+    mom, mmag = mom.reshape(B, 2 * E, 3, HW), mmag.reshape(B, 2 * E, 3, HW)
+    mean, m_mag = mom[:, :E], mmag[:, :E]
+    lv = 20.0 * torch.tanh(mom[:, E:] / 20.0)
+    s_lv = mmag[:, E:] + lv.abs()
+    std, var = torch.exp(0.5 * lv), torch.exp(lv)
+    se = std * _d(eps) if eps is not None else torch.zeros_like(mean)
+    z = mean + se
+    z_mag = m_mag + mean.abs() + se.abs() * (1 + s_lv)
+    ns = se / var
+    c = 0.5 * math.log(2 * math.pi)
+    log_q = -0.5 * ns * ns - c - lv
+    lq_mag = ns.abs() * (z.abs() + mean.abs()) / var + ns * ns * (1.5 * s_lv + 2) + s_lv + c + lv.abs()
+    tok = lambda t: t.permute(0, 2, 3, 1).reshape(B, 3 * HW, E)                          # noqa: E731
+    return dict(mean=(mean, m_mag), logvar=(lv, s_lv), z=(z, z_mag), latent_tok=(tok(z), tok(z_mag)), log_q=(log_q, lq_mag),
+                entropy=(lv + c + 0.5, s_lv + c + 0.5), ulps=F_ / 2.0 + 9.0)
+
+
+# ---------------------------------------------------------------- DiT boundary
+def patch_embed(x, in_scale, w, bias, pos, Bn, p):
+    """x f32 [Bx, C*3, S, S] (channel c*3 + n: plane n), in_scale [Bn] or None, w [D, C, p, p], bias [D], pos [3L, D] ->
+    (tokens [Bn, 3L, D], sum of |terms|): token n*L + ph*G + pw = bias + pos + conv_{kernel = stride = p}(s_b * x[b % Bx, plane n]).
+    A chain of C*p*p fma, the input scale and the two adds: C*p*p / 2 + 2 fp32 ulps of the terms."""
+    xx, ww, bb, pp = _d(x), _d(w), _d(bias), _d(pos)
+    Bx, C3, S, _ = xx.shape
+    C = C3 // 3
+    xb = xx[torch.arange(Bn) % Bx]
+    if in_scale is not None:
+        xb = xb * _d(in_scale)[:, None, None, None]
+    xb = xb.reshape(Bn, C, 3, S, S)
+    D = ww.shape[0]
+    out, mag = [], []
+    for n in range(3):
+        out.append(F.conv2d(xb[:, :, n], ww, bb, stride=p).flatten(2).transpose(1, 2))               # [Bn, L, D]
+        mag.append(F.conv2d(xb[:, :, n].abs(), ww.abs(), bb.abs(), stride=p).flatten(2).transpose(1, 2))
+    return torch.cat(out, 1) + pp[None], torch.cat(mag, 1) + pp.abs()[None]
+
+
+def final_layer(tokens, shift, scale, shift_table, scale_table, w, bias, Bn, C, S, p):
+    """tokens f32 [Bn*3L, D], shift / scale [Bn, D], tables [D] or None, w [p*p*C, D], bias [p*p*C] -> (out [Bn, C*3, S, S], scale):
+    LayerNorm(eps 1e-6, no affine) * (1 + scale + table) + shift + table, the linear, and the unpatchify
+    out[b, c*3 + n, p*ph + i, p*pw + j] = y[b, n*L + ph*G + pw, (i*p + j)*C + c]  (dit_models_xformers.py FinalLayer / unpatchify).
+    Bound: D / 128 + 8 fp32 ulps of sum_d |w_od| mag_d + |bias| (mag: norm_modulate's; a lane sums D / 64 fma, then a 6-level
+    butterfly: (D / 64 + 6) / 2 ulps; the normalised row itself within 4; the bias)."""
+    D = tokens.shape[-1]
+    G = S // p
+    L = G * G
+    t, mag = norm_modulate(tokens, 0, 1e-6, shift=shift, scale=scale, mod_rows=3 * L, shift_table=shift_table, scale_table=scale_table)
+    ww, bb = _d(w), _d(bias)
+    y, ymag = t @ ww.t() + bb, mag @ ww.abs().t() + bb.abs()
+
+    def unpatch(v):
+        return v.reshape(Bn, 3, G, G, p, p, C).permute(0, 6, 1, 2, 4, 3, 5).reshape(Bn, C * 3, S, S)
+    return unpatch(y), unpatch(ymag)
+
+
+def rmsnorm_heads(x, w, eps, true_dim=0):
+    """x bf16 [rows, Dh], w f32 [Dh] -> (ref, |ref|): x * rsqrt(sum x^2 / true_dim + eps) * w (dit/norm.py RMSNorm on each head;
+    heads stored zero-padded to Dh are normalised by their true width)."""
+    v = _d(x)
+    td = true_dim or v.shape[-1]
+    t = v * ((v * v).sum(-1, keepdim=True) / td + _f32(eps)).rsqrt() * _d(w)
+    return t, t.abs()

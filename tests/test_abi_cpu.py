@@ -1,6 +1,7 @@
-"""C-ABI contract without a GPU: every entry point of include/ln3d.h rejects missing buffers with LN3D_ERR_BAD_ARG BEFORE it touches
-the device (argument validation is not a compute call; nothing is launched here).  The table must cover every `int ln3d_*(...)`
-declared in the header, so a new export without validation shows up as a failing test."""
+"""C-ABI contract without a GPU: every entry point of include/ln3d.h and of the stage headers (ln3d_shapenet.h, ln3d_encoder.h,
+ln3d_ffhq.h, ln3d_mx.h) rejects missing buffers with LN3D_ERR_BAD_ARG BEFORE it touches the device (argument validation is not a
+compute call; nothing is launched here).  The tables must cover every `int ln3d_*(...)` declared in each header, so a new export
+without validation shows up as a failing test."""
 import ctypes as C
 import os
 import re
@@ -55,6 +56,31 @@ NULL_CALLS = {
     'ln3d_cl_to_nchw_f32': (N, N, 1, 12, 64, N),
     'ln3d_mix_prediction': (N, N, N, F(0.5), 1, 12, 64, N),
 }
+# the stage headers, walked the same way
+STAGE_NULL_CALLS = {
+    'ln3d_shapenet.h': {
+        'ln3d_triplane_axis_attention': (N, I64(192), N, 1, 4, 1, F(0.125), N),
+        'ln3d_sr_unpatchify': (N, N, N, 1, 2, 2, 4, N),
+        'ln3d_resize_bilinear_cl': (N, N, 1, 4, 4, 8, 8, 4, 0, N),
+        'ln3d_resize_add_lrelu': (N, N, N, 1, 4, 4, 8, 8, 4, F(0.01), N),
+        'ln3d_rollout_means': (N, N, N, 1, 4, 4, 4, N),
+        'ln3d_im2col3x3_rollout': (N, N, N, N, 0, 4, 4, 4, 108, N),
+    },
+    'ln3d_encoder.h': {
+        'ln3d_im2col3x3_pad01': (N, N, 1, 8, 8, 8, 72, N),
+        'ln3d_frame_mean': (N, N, 1, 1, 4, 24, N),
+        'ln3d_mv_posterior': (N, I64(96), I64(1), I64(4), N, N, N, N, N, N, N, N, N, 1, 1, 4, 4, N),
+    },
+    'ln3d_ffhq.h': {
+        'ln3d_conv3x3_rollout_bf16': (N, 0, N, N, N, N, N, 8, 8, N, 8, 8, 16, 32, F(0.01), N),
+        'ln3d_rollout_means_bf16': (N, N, N, 1, 4, 4, 4, N),
+    },
+    'ln3d_mx.h': {
+        'ln3d_quantize_mx': (N, 0, I64(32), 1, 32, N, I64(32), N, I64(1), N),
+        'ln3d_gemm_mxfp8': (N, N),
+        'ln3d_norm_modulate_mx': (N, N, N),
+    },
+}
 NOT_A_KERNEL = {'ln3d_abi_version', 'ln3d_gemm_heads_norm_fusable', 'ln3d_device_cus'}      # pure host queries
 
 # Sizes <= 0 are bad arguments too, not zero-sized grids: every buffer below is a fake, never dereferenced address, so on a correct
@@ -83,6 +109,44 @@ ZERO_CALLS = [
 ]
 
 
+def _sizes_zeroed(name, args, positions):
+    """one row per size argument at `positions` of the otherwise valid call `args`, set to 0 and to -1 (keeping its C type)"""
+    for i in positions:
+        for bad in (0, -1):
+            a = list(args)
+            a[i] = type(a[i])(bad) if not isinstance(a[i], int) else bad
+            yield (name, tuple(a))
+
+
+# every size argument of the U-Net, VAE-decoder, encoder and DiT-boundary glue kernels (tests/test_stage_kernels_gpu.py)
+for _name, _args, _pos in [
+    ('ln3d_attention_small', (P, P, P, P, 1, 1, 16, 16, 40, I64(40), I64(40), I64(40), F(0.1), N), (4, 5, 6, 7, 8)),
+    ('ln3d_triplane_axis_attention', (P, I64(192), P, 1, 4, 1, F(0.125), N), (3, 4, 5)),
+    ('ln3d_geglu', (P, P, I64(1), 64, N), (2, 3)),
+    ('ln3d_mix_prediction', (P, P, P, F(0.5), 1, 12, 64, N), (4, 5, 6)),
+    ('ln3d_im2col3x3_strided', (P, P, 1, 8, 8, 64, 2, 576, N), (2, 3, 4, 5, 6)),
+    ('ln3d_im2col3x3_pad01', (P, P, 1, 8, 8, 8, 72, N), (2, 3, 4, 5)),
+    ('ln3d_im2col3x3_rollout', (P, P, P, P, 0, 4, 4, 4, 108, N), (5, 6, 7)),
+    ('ln3d_nchw_to_cl_bf16', (P, P, 1, 12, 64, 16, N), (2, 3, 4)),
+    ('ln3d_cl_to_nchw_f32', (P, P, 1, 12, 64, N), (2, 3, 4)),
+    ('ln3d_sr_unpatchify', (P, P, P, 1, 2, 2, 4, N), (3, 4, 5, 6)),
+    ('ln3d_resize_bilinear_cl', (P, P, 1, 4, 4, 8, 8, 4, 0, N), (2, 3, 4, 5, 6, 7)),
+    ('ln3d_resize_add_lrelu', (P, P, P, 1, 4, 4, 8, 8, 4, F(0.01), N), (3, 4, 5, 6, 7, 8)),
+    ('ln3d_rollout_means', (P, P, P, 1, 4, 4, 4, N), (3, 4, 5, 6)),
+    ('ln3d_rollout_means_bf16', (P, P, P, 1, 4, 4, 4, N), (3, 4, 5, 6)),
+    ('ln3d_frame_mean', (P, P, 1, 1, 4, 24, N), (2, 3, 4, 5)),
+    ('ln3d_mv_posterior', (P, I64(96), I64(1), I64(4), P, P, P, P, P, P, P, P, P, 1, 1, 4, 4, N), (13, 14, 15, 16)),
+    ('ln3d_patch_embed', (P, P, P, P, P, P, 1, 1, 4, 32, 2, 128, N), (6, 7, 8, 9, 10, 11)),
+    ('ln3d_final_layer', (P, P, P, I64(256), P, P, P, P, P, 1, 4, 32, 2, 128, N), (9, 10, 11, 12, 13)),
+    ('ln3d_rmsnorm_heads_bf16', (P, P, I64(1), 64, 64, F(1e-5), N), (2, 3)),
+]:
+    ZERO_CALLS += list(_sizes_zeroed(_name, _args, _pos))
+ZERO_CALLS += [
+    ('ln3d_final_layer', (P, P, P, I64(256), P, P, P, P, P, 1, 4, 33, 2, 128, N)),           # S % p != 0
+    ('ln3d_patch_embed', (P, P, P, P, P, P, 1, 1, 4, 33, 2, 128, N)),
+]
+
+
 def test_every_entry_point_rejects_missing_buffers(hip_lib):
     hdr = open(os.path.join(ROOT, 'include', 'ln3d.h')).read()
     declared = set(re.findall(r'^int (ln3d_[a-z0-9_]+)\(', hdr, re.M))
@@ -91,6 +155,16 @@ def test_every_entry_point_rejects_missing_buffers(hip_lib):
         rc = getattr(hip_lib, name)(*args)
         assert rc == -1, (name, rc)                                       # LN3D_ERR_BAD_ARG
     assert b'bad argument' in hip_lib.ln3d_strerror(-1)
+
+
+def test_every_stage_entry_point_rejects_missing_buffers(hip_lib):
+    for header, calls in STAGE_NULL_CALLS.items():
+        hdr = open(os.path.join(ROOT, 'include', header)).read()
+        declared = set(re.findall(r'^int (ln3d_[a-z0-9_]+)\(', hdr, re.M))
+        assert declared == set(calls), (header, declared ^ set(calls))
+        for name, args in calls.items():
+            rc = getattr(hip_lib, name)(*args)
+            assert rc == -1, (header, name, rc)                               # LN3D_ERR_BAD_ARG
 
 
 def test_host_queries(hip_lib):
