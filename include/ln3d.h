@@ -246,6 +246,8 @@ int ln3d_planes_to_nchw(const float* planes_nhwc, float* planes_nchw, int NP, in
 
 typedef struct {
   const float* planes; int H, W;        /* channel-last tri-planes                                 */
+                                        /* H, W >= 1 and H * W <= 5 592 405 (2 364 x 2 364): the gather addresses a tri-plane with
+                                         * 32-bit byte offsets (3 * H * W * 128 < 2^31); larger: LN3D_ERR_BAD_ARG.  box_warp > 0, finite */
   const int32_t* plane_index;           /* [V] which tri-plane each view renders                     */
   const float* cams;                    /* [V,25] cam2world(16) + intrinsics(9)                      */
   int V, res;                           /* rays per view = res*res                                   */
@@ -303,6 +305,7 @@ typedef struct {
 int ln3d_render_triplane(const ln3d_render_args* a, void* stream);
 
 /* triplane_decode_grid / forward_points (vit/vit_triplane.py:2009-2112): points f32 [P,3] -> sigma[P], rgb[P,3].
+ * H, W and box_warp: the limits of ln3d_render_args.
  * scalars: caller-owned scratch of >= 4096 floats (the decoder's fragment image is built into it) */
 int ln3d_query_points(const float* planes, int H, int W, const float* points, int64_t P,
                       const float* dec_w0, const float* dec_b0, const float* dec_w1, const float* dec_b1,

@@ -1009,14 +1009,23 @@ __global__ __launch_bounds__(256, 1) void render_generic_kernel(RenderP p) {
   flush_depth_range(p.scal_u, cur_grp, dmin_l, dmax_l, lane);
 }
 
+// what shade64 indexes with and divides by: plane sizes (its tap offsets are 32-bit BYTE offsets inside one tri-plane) and box_warp
+static bool planes_ok(int H, int W, float box_warp) {
+  if (H <= 0 || W <= 0 || (int64_t)H * W > (int64_t)0x7fffffff / (3 * 32 * 4)) return false;
+  return box_warp > 0.f && box_warp <= 3.0e38f;          // false for NaN and +inf as well
+}
+
 extern "C" int ln3d_render_triplane(const ln3d_render_args* a, void* stream) {
   if (!a || !a->planes || !a->plane_index || !a->jitter || !a->u_fine || !a->rgb || !a->depth || !a->wsum ||
       !a->ray_limits || !a->scalars || !a->dec_w0 || !a->dec_b0 || !a->dec_w1 || !a->dec_b1)
     return LN3D_ERR_BAD_ARG;
-  if (a->V <= 0 || (a->res <= 0 && a->rays_per_view <= 0)) return LN3D_ERR_BAD_ARG;
+  if (a->V <= 0 || a->rays_per_view < 0 || (a->res <= 0 && a->rays_per_view <= 0)) return LN3D_ERR_BAD_ARG;
   if (!a->cams && !(a->ray_o && a->ray_d)) return LN3D_ERR_BAD_ARG;       // cameras, or explicit rays
   if ((a->ray_o != nullptr) != (a->ray_d != nullptr)) return LN3D_ERR_BAD_ARG;
+  if (!a->ray_o && (a->res <= 0 || a->res > 32768)) return LN3D_ERR_BAD_ARG;                               // make_ray divides by res; M = res * res is an int
   if (a->rays_per_view > 0 && !a->ray_o && a->rays_per_view != a->res * a->res) return LN3D_ERR_BAD_ARG;   // camera rays are a res x res image
+  if (!planes_ok(a->H, a->W, a->box_warp)) return LN3D_ERR_BAD_ARG;
+  if (a->depth_resolution < 0 || a->depth_resolution_importance < 0) return LN3D_ERR_UNSUPPORTED;          // 0 = 64, the header's default
   const int S = a->depth_resolution > 0 ? a->depth_resolution : NS, NI = a->depth_resolution_importance > 0 ? a->depth_resolution_importance : NS;
   if (S < 4 || S > GEN_MAXS || NI < 1 || NI > GEN_MAXS) return LN3D_ERR_UNSUPPORTED;
   if (a->ray_mode != 0 && !(a->ray_end > a->ray_start)) return LN3D_ERR_BAD_ARG;
@@ -1088,6 +1097,7 @@ extern "C" int ln3d_query_points(const float* planes, int H, int W, const float*
                                  const float* dec_b0, const float* dec_w1, const float* dec_b1, float box_warp, float* sigma,
                                  float* rgb, float* scalars, void* stream) {
   if (!planes || !points || !sigma || !rgb || !scalars || P <= 0) return LN3D_ERR_BAD_ARG;
+  if (!dec_w0 || !dec_b0 || !dec_w1 || !dec_b1 || !planes_ok(H, W, box_warp)) return LN3D_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   RenderP p{};
   p.planes = planes; p.H = H; p.W = W; p.coord_scale = (float)(2.0 / (double)box_warp);

@@ -147,6 +147,58 @@ ZERO_CALLS += [
 ]
 
 
+# ---- the ray-marcher: every size or scale csrc/render.hip indexes with or divides by.  (field, value) rows on an otherwise valid
+# ln3d_render_args (fake, never dereferenced addresses) and the code each must return before any launch.
+def _render_args(**kw):
+    from ln3diff_amd._lib import RenderArgs
+    a = RenderArgs()
+    for k in ('planes', 'plane_index', 'cams', 'dec_w0', 'dec_b0', 'dec_w1', 'dec_b1', 'jitter', 'u_fine', 'rgb', 'depth', 'wsum', 'ray_limits',
+              'scalars'):
+        setattr(a, k, 0x10000)
+    a.H, a.W, a.V, a.res, a.box_warp, a.bbox_min, a.bbox_max = 8, 8, 1, 4, 0.9, -0.45, 0.45
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+BAD_ARG, UNSUPPORTED = -1, -3
+RENDER_ROWS = [
+    (dict(H=0), BAD_ARG), (dict(H=-1), BAD_ARG), (dict(W=0), BAD_ARG), (dict(W=-8), BAD_ARG),
+    (dict(H=1 << 15, W=1 << 15), BAD_ARG),                                        # 32-bit tap offsets
+    (dict(box_warp=0.0), BAD_ARG), (dict(box_warp=-0.9), BAD_ARG), (dict(box_warp=float('nan')), BAD_ARG), (dict(box_warp=float('inf')), BAD_ARG),
+    (dict(V=0), BAD_ARG), (dict(V=-1), BAD_ARG),
+    (dict(res=0), BAD_ARG), (dict(res=-2), BAD_ARG), (dict(res=-2, rays_per_view=4), BAD_ARG), (dict(res=0, rays_per_view=16), BAD_ARG),
+    (dict(res=1 << 16), BAD_ARG),                                                 # res * res is an int
+    (dict(rays_per_view=-1), BAD_ARG), (dict(rays_per_view=15), BAD_ARG),         # camera rays are a res x res image
+    (dict(cams=None), BAD_ARG), (dict(ray_o=0x10000), BAD_ARG), (dict(ray_d=0x10000), BAD_ARG),
+    (dict(cams=None, ray_o=0x10000, ray_d=0x10000, res=0, rays_per_view=0), BAD_ARG),
+    (dict(cams=None, ray_o=0x10000, ray_d=0x10000, res=0, rays_per_view=-5), BAD_ARG),
+    (dict(depth_resolution=3), UNSUPPORTED), (dict(depth_resolution=129), UNSUPPORTED), (dict(depth_resolution=-64), UNSUPPORTED),
+    (dict(depth_resolution_importance=129), UNSUPPORTED), (dict(depth_resolution_importance=-1), UNSUPPORTED),
+    (dict(ray_mode=1, ray_start=1.0, ray_end=1.0), BAD_ARG), (dict(ray_mode=1, ray_start=1.8, ray_end=0.6), BAD_ARG),
+    (dict(ray_mode=1, ray_start=0.6, ray_end=float('nan')), BAD_ARG),
+    (dict(V=2000, views_per_call=1), BAD_ARG),                                    # more call groups than the scratch holds
+]
+QUERY_OK = (P, 8, 8, P, I64(4), P, P, P, P, F(0.9), P, P, P, N)
+QUERY_ROWS = [{1: 0}, {1: -1}, {2: 0}, {2: -3}, {1: 1 << 15, 2: 1 << 15}, {4: I64(0)}, {4: I64(-1)}, {9: F(0.0)}, {9: F(-1.0)},
+              {9: F(float('nan'))}, {9: F(float('inf'))}, {5: N}, {6: N}, {7: N}, {8: N}, {10: N}, {11: N}, {12: N}]
+
+
+def test_render_and_query_arguments_are_validated(hip_lib):
+    """H, W <= 0 and box_warp <= 0 or non-finite were accepted by both entry points (H = 0 clamps tap coordinates to -1, box_warp = 0
+    makes coord_scale infinite), so were res < 0 with rays_per_view = res^2, rays_per_view < 0, negative sample counts (silently 64)
+    and, in ln3d_query_points, missing decoder weights (dereferenced by the init kernel)."""
+    from ln3diff_amd._lib import RENDER_MAX_CALLS
+    assert RENDER_MAX_CALLS < 2000
+    for kw, code in RENDER_ROWS:
+        assert hip_lib.ln3d_render_triplane(C.byref(_render_args(**kw)), None) == code, (kw, code)
+    for row in QUERY_ROWS:
+        a = list(QUERY_OK)
+        for i, v in row.items():
+            a[i] = v
+        assert hip_lib.ln3d_query_points(*a) == BAD_ARG, row
+
+
 def test_every_entry_point_rejects_missing_buffers(hip_lib):
     hdr = open(os.path.join(ROOT, 'include', 'ln3d.h')).read()
     declared = set(re.findall(r'^int (ln3d_[a-z0-9_]+)\(', hdr, re.M))
