@@ -1,4 +1,5 @@
-"""ctypes binding of libln3d_hip.so (the C ABI of include/ln3d.h, include/ln3d_encoder.h, include/ln3d_shapenet.h, include/ln3d_mx.h and include/ln3d_ffhq.h).
+"""ctypes binding of libln3d_hip.so (the C ABI of include/ln3d.h, include/ln3d_encoder.h, include/ln3d_shapenet.h, include/ln3d_mx.h, include/ln3d_ffhq.h
+and include/ln3d_planes16.h).
 
 There is NO fallback: if the library is missing or a kernel launch fails the product raises.
 """
@@ -27,6 +28,8 @@ SYMBOLS = [
     "ln3d_quantize_mx", "ln3d_gemm_mxfp8", "ln3d_norm_modulate_mx",
     # include/ln3d_ffhq.h (the FFHQ VAE decoder class)
     "ln3d_conv3x3_rollout_bf16", "ln3d_rollout_means_bf16",
+    # include/ln3d_planes16.h (the opt-in fp16 tri-plane texels of the ray-marcher and the point query)
+    "ln3d_planes_to_channel_last_f16", "ln3d_planes_f32_to_f16", "ln3d_render_triplane_f16", "ln3d_query_points_f16",
 ]
 
 EPI_F32, EPI_BF16, EPI_GELU_ERF, EPI_GELU_TANH, EPI_SILU, EPI_GATE_RES, EPI_HEADS, EPI_F32_SILU, EPI_QUICK_GELU, EPI_CROSS_ATTN = range(10)

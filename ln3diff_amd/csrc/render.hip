@@ -25,6 +25,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "../../include/ln3d.h"
+#include "../../include/ln3d_planes16.h"
 
 #define NS 64            // samples per pass (coarse == fine == 64, Objaverse preset)
 #define WAVE_LDS_BYTES 8192           // per wave: 64 points x (64 B hi + 64 B lo) feature rows; reused for cdf / merge arrays
@@ -75,7 +76,7 @@ __device__ __forceinline__ float softplus_fast(float x) {   // torch softplus(be
 }
 
 struct RenderP {
-  const float* planes; int H, W;
+  const void* planes; int H, W;                    // channel-last texels, f32 or binary16 (the kernels' template argument)
   const int32_t* plane_index; const float* cams; int V, res;
   const float* jitter; const float* u_fine;
   float coord_scale, bbox_min, bbox_max; int white_back;
@@ -244,7 +245,16 @@ __device__ __forceinline__ float even_reg(float x) {     // a copy into a fresh 
   return r;
 }
 
-__device__ __forceinline__ void shade64(const RenderP& p, const float* __restrict__ planes, char* wl, const char* cimg,
+// Texel storage type TX of the planes: float (a 128-byte texel, 16 bytes per lane and tap) or _Float16 (include/ln3d_planes16.h: a 64-byte
+// texel, 8 bytes per lane and tap - the two x-neighbours of a bilinear footprint share one 128-byte line whenever x0 is even).  Only the
+// tap byte offsets, the loads (fetch) and the widening inside the tap sums (reduce) differ; the arithmetic is fp32 in the same order.
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+template <typename TX> struct TexelRegs;
+template <> struct TexelRegs<float> { typedef float4 quad; };
+template <> struct TexelRegs<_Float16> { typedef f16x4 quad; };
+
+template <typename TX>
+__device__ __forceinline__ void shade64(const RenderP& p, const TX* __restrict__ planes, char* wl, const char* cimg,
                                         float px, float py, float pz, int lane, float rgb[3], float& sigma) {
   const int g = lane >> 3, c4 = lane & 7;
   const bool inb = px >= p.bbox_min && px <= p.bbox_max && py >= p.bbox_min && py <= p.bbox_max && pz >= p.bbox_min &&
@@ -265,6 +275,8 @@ __device__ __forceinline__ void shade64(const RenderP& p, const float* __restric
   // 8 times - the address / weight arithmetic was 200 of the 252 VALU instructions of a gather iteration (profiles/r2_render_pmc.md).
   int toff[12];
   float tw[12];
+  constexpr int TB = (int)sizeof(TX);                        // bytes per texel channel
+  typedef typename TexelRegs<TX>::quad tquad;                // this lane's 4 channels of one tap
 #pragma unroll
   for (int pl = 0; pl < 3; ++pl) {
     const float gx = pl == 0 ? sx : (pl == 1 ? sy : sz);     // (x,y) (y,z) (z,x)
@@ -283,8 +295,8 @@ __device__ __forceinline__ void shade64(const RenderP& p, const float* __restric
     tw[4 * pl + 0] = (xin0 && yin0) ? w_nw : 0.f; tw[4 * pl + 1] = (xin1 && yin0) ? w_ne : 0.f;
     tw[4 * pl + 2] = (xin0 && yin1) ? w_sw : 0.f; tw[4 * pl + 3] = (xin1 && yin1) ? w_se : 0.f;
     const int pb = pl * plane_stride;
-    toff[4 * pl + 0] = (pb + (yc0 * p.W + xc0) * 32) * 4; toff[4 * pl + 1] = (pb + (yc0 * p.W + xc1) * 32) * 4;
-    toff[4 * pl + 2] = (pb + (yc1 * p.W + xc0) * 32) * 4; toff[4 * pl + 3] = (pb + (yc1 * p.W + xc1) * 32) * 4;
+    toff[4 * pl + 0] = (pb + (yc0 * p.W + xc0) * 32) * TB; toff[4 * pl + 1] = (pb + (yc0 * p.W + xc1) * 32) * TB;
+    toff[4 * pl + 2] = (pb + (yc1 * p.W + xc0) * 32) * TB; toff[4 * pl + 3] = (pb + (yc1 * p.W + xc1) * 32) * TB;
   }
   // ---- r6: the setup hand-off goes through the wave's feature tile instead of 24 ds_bpermute per 8-point iteration.  Row s of the tile
   // (128 B, free until the features of point s land in it - in the very iteration that consumes its setup, behind the reads: a
@@ -312,9 +324,9 @@ __device__ __forceinline__ void shade64(const RenderP& p, const float* __restric
   const uint64_t pl64 = reinterpret_cast<uint64_t>(planes);
   gchar_t* const pbase = reinterpret_cast<gchar_t*>(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(pl64 >> 32)) << 32) |
                                                    (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pl64));
-  const uint32_t c4b = c4 * 16;
+  const uint32_t c4b = c4 * (4 * TB);
   const lds_i4* const srow = reinterpret_cast<const lds_i4*>((uintptr_t)wb) + g * 8;      // this lane group's setup row of iteration 0
-  auto fetch = [&](int it, float4 (&t)[12]) {
+  auto fetch = [&](int it, tquad (&t)[12]) {
     int off[12];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -323,13 +335,19 @@ __device__ __forceinline__ void shade64(const RenderP& p, const float* __restric
     }
 #pragma unroll
     for (int k = 0; k < 12; ++k) {
-      const f32x4 tv = *reinterpret_cast<__attribute__((address_space(1))) const f32x4*>(pbase + ((uint32_t)off[k] + c4b));
-      t[k] = make_float4(tv.x, tv.y, tv.z, tv.w);
+      if constexpr (sizeof(TX) == 4) {
+        const f32x4 tv = *reinterpret_cast<__attribute__((address_space(1))) const f32x4*>(pbase + ((uint32_t)off[k] + c4b));
+        t[k] = make_float4(tv.x, tv.y, tv.z, tv.w);
+      } else {                                              // global_load_dwordx2: the lane's 4 binary16 channels
+        t[k] = *reinterpret_cast<__attribute__((address_space(1))) const f16x4*>(pbase + ((uint32_t)off[k] + c4b));
+      }
     }
   };
   // the tap weights are read where they are used (behind whatever was placed under the loads): 12 registers less across that code
   char* const wrow = wl + g * 128 + (c4 & 1) * 8 + (((c4 >> 1) ^ (g >> 1)) << 4);
-  auto reduce = [&](int it, const float4 (&t)[12]) {
+  float neg_zero = -0.0f;
+  if constexpr (sizeof(TX) == 2) asm("s_mov_b32 %0, 0x80000000" : "=s"(neg_zero));        // see the binary16 branch of reduce
+  auto reduce = [&](int it, const tquad (&t)[12]) {
     float a[12];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -347,13 +365,30 @@ __device__ __forceinline__ void shade64(const RenderP& p, const float* __restric
     ln3d_f32x2 accA = {0.f, 0.f}, accB = {0.f, 0.f};
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) {
-      const ln3d_f32x2 w0 = {a[4 * pl], a[4 * pl]};
-      ln3d_f32x2 sA = ln3d_f32x2{t[4 * pl].x, t[4 * pl].y} * w0, sB = ln3d_f32x2{t[4 * pl].z, t[4 * pl].w} * w0;
+      ln3d_f32x2 sA, sB;
+      if constexpr (sizeof(TX) == 4) {
+        const ln3d_f32x2 w0 = {a[4 * pl], a[4 * pl]};
+        sA = ln3d_f32x2{t[4 * pl].x, t[4 * pl].y} * w0; sB = ln3d_f32x2{t[4 * pl].z, t[4 * pl].w} * w0;
 #pragma unroll
-      for (int k = 1; k < 4; ++k) {
-        const ln3d_f32x2 wk = {a[4 * pl + k], a[4 * pl + k]};
-        sA = __builtin_elementwise_fma(ln3d_f32x2{t[4 * pl + k].x, t[4 * pl + k].y}, wk, sA);
-        sB = __builtin_elementwise_fma(ln3d_f32x2{t[4 * pl + k].z, t[4 * pl + k].w}, wk, sB);
+        for (int k = 1; k < 4; ++k) {
+          const ln3d_f32x2 wk = {a[4 * pl + k], a[4 * pl + k]};
+          sA = __builtin_elementwise_fma(ln3d_f32x2{t[4 * pl + k].x, t[4 * pl + k].y}, wk, sA);
+          sB = __builtin_elementwise_fma(ln3d_f32x2{t[4 * pl + k].z, t[4 * pl + k].w}, wk, sB);
+        }
+      } else {
+        // binary16 texels: the widening rides on the multiply-add (v_fma_mix_f32: binary16 texel x fp32 weight + fp32 sum, one rounding
+        // of the exact fp32 result - what v_pk_fma_f32 returns for the widened value), one instruction per channel and tap where the fp32
+        // texels take one packed instruction per channel PAIR.  The first tap adds -0.0, which returns the product with its sign: the
+        // bits of the fp32 path's multiply (the constant is opaque to hipcc, which otherwise folds the add away and widens with a
+        // separate v_cvt_f32_f16 per channel: 12 more instructions per iteration).  No fp16 arithmetic anywhere.
+        float s[4];
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) {
+          s[ch] = __builtin_fmaf((float)t[4 * pl][ch], a[4 * pl], neg_zero);
+#pragma unroll
+          for (int k = 1; k < 4; ++k) s[ch] = __builtin_fmaf((float)t[4 * pl + k][ch], a[4 * pl + k], s[ch]);
+        }
+        sA = ln3d_f32x2{s[0], s[1]}; sB = ln3d_f32x2{s[2], s[3]};
       }
       accA += sA; accB += sB;
     }
@@ -434,7 +469,7 @@ __device__ __forceinline__ void shade64(const RenderP& p, const float* __restric
       if (hi == pt) o[k] = v;
     }
   };
-  float4 tA[12];
+  tquad tA[12];
   // one iteration (8 points) at a time: double-buffering the 12 loads measured slower at 2 waves/SIMD (r2: 0.863 vs 0.838 ms per 256^2 view),
   // and r6's ablations say why more loads in flight do not help: the texel loads are an L1-path THROUGHPUT term (profiles/r6_render_abl.log)
   // The decoder of both point tiles runs behind the whole gather.  r6 also built the decoder of tile 0 in four pieces under the texel loads of
@@ -523,6 +558,7 @@ __device__ __forceinline__ void flush_depth_range(uint32_t* scal_u, int grp, flo
   }
 }
 
+template <typename TX>
 __global__ __launch_bounds__(64 * RENDER_WPB, RENDER_OCC) void render_kernel(RenderP p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -553,7 +589,7 @@ __global__ __launch_bounds__(64 * RENDER_WPB, RENDER_OCC) void render_kernel(Ren
     const uint32_t* gr = p.scal_u + (int64_t)grp * GRP_WORDS;
     float t0 = p.ray_limits[2 * ray], t1 = p.ray_limits[2 * ray + 1];
     if (gr[4] != 0u && !(t1 > t0)) { t0 = dec_f(gr[0]); t1 = dec_f(gr[1]); }    // renderer.py:151-155 (sic)
-    const float* planes = p.planes + (int64_t)p.plane_index[v] * 3 * p.H * p.W * 32;
+    const TX* planes = reinterpret_cast<const TX*>(p.planes) + (int64_t)p.plane_index[v] * 3 * p.H * p.W * 32;     // stride in texel elements
 
     // ---- coarse depths: linspace + jitter * delta
     const float step = (float)lane / (float)(NS - 1);
@@ -806,6 +842,7 @@ __device__ __forceinline__ void march_lds(const float* a, int PS, int n, int lan
   acc_r = wave_total(r); acc_g = wave_total(g); acc_b = wave_total(b); acc_d = wave_total(d); acc_w = wave_total(w);
 }
 
+template <typename TX>
 __global__ __launch_bounds__(256, 1) void render_generic_kernel(RenderP p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -845,7 +882,7 @@ __global__ __launch_bounds__(256, 1) void render_generic_kernel(RenderP p) {
       t0 = p.ray_limits[2 * ray]; t1 = p.ray_limits[2 * ray + 1];
       if (gr[4] != 0u && !(t1 > t0)) { t0 = dec_f(gr[0]); t1 = dec_f(gr[1]); }    // renderer.py:151-155 (sic)
     }
-    const float* planes = p.planes + (int64_t)p.plane_index[v] * 3 * p.H * p.W * 32;
+    const TX* planes = reinterpret_cast<const TX*>(p.planes) + (int64_t)p.plane_index[v] * 3 * p.H * p.W * 32;     // stride in texel elements
     // sentinels: depths past the sample count compare as +inf in the rank counts and searches
     wf[G_ZC + lane] = 3.0e38f; wf[G_ZC + 64 + lane] = 3.0e38f; wf[G_ZF + lane] = 3.0e38f; wf[G_ZF + 64 + lane] = 3.0e38f;
     wave_sync();
@@ -1010,12 +1047,13 @@ __global__ __launch_bounds__(256, 1) void render_generic_kernel(RenderP p) {
 }
 
 // what shade64 indexes with and divides by: plane sizes (its tap offsets are 32-bit BYTE offsets inside one tri-plane) and box_warp
-static bool planes_ok(int H, int W, float box_warp) {
-  if (H <= 0 || W <= 0 || (int64_t)H * W > (int64_t)0x7fffffff / (3 * 32 * 4)) return false;
+static bool planes_ok(int H, int W, float box_warp, int texel_bytes = 4) {
+  if (H <= 0 || W <= 0 || (int64_t)H * W > (int64_t)0x7fffffff / (3 * 32 * texel_bytes)) return false;
   return box_warp > 0.f && box_warp <= 3.0e38f;          // false for NaN and +inf as well
 }
 
-extern "C" int ln3d_render_triplane(const ln3d_render_args* a, void* stream) {
+template <typename TX>
+static int render_triplane_t(const ln3d_render_args* a, void* stream) {
   if (!a || !a->planes || !a->plane_index || !a->jitter || !a->u_fine || !a->rgb || !a->depth || !a->wsum ||
       !a->ray_limits || !a->scalars || !a->dec_w0 || !a->dec_b0 || !a->dec_w1 || !a->dec_b1)
     return LN3D_ERR_BAD_ARG;
@@ -1024,7 +1062,7 @@ extern "C" int ln3d_render_triplane(const ln3d_render_args* a, void* stream) {
   if ((a->ray_o != nullptr) != (a->ray_d != nullptr)) return LN3D_ERR_BAD_ARG;
   if (!a->ray_o && (a->res <= 0 || a->res > 32768)) return LN3D_ERR_BAD_ARG;                               // make_ray divides by res; M = res * res is an int
   if (a->rays_per_view > 0 && !a->ray_o && a->rays_per_view != a->res * a->res) return LN3D_ERR_BAD_ARG;   // camera rays are a res x res image
-  if (!planes_ok(a->H, a->W, a->box_warp)) return LN3D_ERR_BAD_ARG;
+  if (!planes_ok(a->H, a->W, a->box_warp, (int)sizeof(TX))) return LN3D_ERR_BAD_ARG;
   if (a->depth_resolution < 0 || a->depth_resolution_importance < 0) return LN3D_ERR_UNSUPPORTED;          // 0 = 64, the header's default
   const int S = a->depth_resolution > 0 ? a->depth_resolution : NS, NI = a->depth_resolution_importance > 0 ? a->depth_resolution_importance : NS;
   if (S < 4 || S > GEN_MAXS || NI < 1 || NI > GEN_MAXS) return LN3D_ERR_UNSUPPORTED;
@@ -1055,26 +1093,29 @@ extern "C" int ln3d_render_triplane(const ln3d_render_args* a, void* stream) {
   if (fast) {
     static AttrOnce attr_once;
     if (attr_once.need()) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&render_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, RENDER_K_LDS_BYTES);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&render_kernel<TX>), hipFuncAttributeMaxDynamicSharedMemorySize, RENDER_K_LDS_BYTES);
     }
     int64_t blocks = (nrays + RENDER_WPB - 1) / RENDER_WPB;
     const int64_t cap = 256 * 8 * 4 / RENDER_WPB;
     if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(render_kernel, dim3((unsigned)blocks), dim3(64 * RENDER_WPB), RENDER_K_LDS_BYTES, s, p);
+    hipLaunchKernelGGL(render_kernel<TX>, dim3((unsigned)blocks), dim3(64 * RENDER_WPB), RENDER_K_LDS_BYTES, s, p);
   } else {
     static AttrOnce attr_once;
     if (attr_once.need()) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&render_generic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, GEN_LDS_BYTES);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&render_generic_kernel<TX>), hipFuncAttributeMaxDynamicSharedMemorySize, GEN_LDS_BYTES);
     }
     int64_t blocks = (nrays + 3) / 4;
     if (blocks > 256 * 4) blocks = 256 * 4;
-    hipLaunchKernelGGL(render_generic_kernel, dim3((unsigned)blocks), dim3(256), GEN_LDS_BYTES, s, p);
+    hipLaunchKernelGGL(render_generic_kernel<TX>, dim3((unsigned)blocks), dim3(256), GEN_LDS_BYTES, s, p);
   }
   hipLaunchKernelGGL(render_finalize_kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, s, a->depth, p.scal_u, nrays, (int64_t)p.vpc * p.M);
   return ln3d_check_launch();
 }
+extern "C" int ln3d_render_triplane(const ln3d_render_args* a, void* stream) { return render_triplane_t<float>(a, stream); }
+extern "C" int ln3d_render_triplane_f16(const ln3d_render_args* a, void* stream) { return render_triplane_t<_Float16>(a, stream); }
 
 // ------------------------------------------------------------------ point query (sigma / rgb grid), no bbox filter
+template <typename TX>
 __global__ __launch_bounds__(256) void query_points_kernel(RenderP p, const float* pts, int64_t P, float* sigma, float* rgb) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -1088,16 +1129,17 @@ __global__ __launch_bounds__(256) void query_points_kernel(RenderP p, const floa
     if (!ok) i = P - 1;
     const float x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
     float c[3], sg;
-    shade64(p, p.planes, wl, cimg, x, y, z, lane, c, sg);
+    shade64(p, reinterpret_cast<const TX*>(p.planes), wl, cimg, x, y, z, lane, c, sg);
     if (ok) { sigma[i] = sg; rgb[3 * i] = c[0]; rgb[3 * i + 1] = c[1]; rgb[3 * i + 2] = c[2]; }
   }
 }
 
-extern "C" int ln3d_query_points(const float* planes, int H, int W, const float* points, int64_t P, const float* dec_w0,
-                                 const float* dec_b0, const float* dec_w1, const float* dec_b1, float box_warp, float* sigma,
-                                 float* rgb, float* scalars, void* stream) {
+template <typename TX>
+static int query_points_t(const void* planes, int H, int W, const float* points, int64_t P, const float* dec_w0,
+                          const float* dec_b0, const float* dec_w1, const float* dec_b1, float box_warp, float* sigma,
+                          float* rgb, float* scalars, void* stream) {
   if (!planes || !points || !sigma || !rgb || !scalars || P <= 0) return LN3D_ERR_BAD_ARG;
-  if (!dec_w0 || !dec_b0 || !dec_w1 || !dec_b1 || !planes_ok(H, W, box_warp)) return LN3D_ERR_BAD_ARG;
+  if (!dec_w0 || !dec_b0 || !dec_w1 || !dec_b1 || !planes_ok(H, W, box_warp, (int)sizeof(TX))) return LN3D_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   RenderP p{};
   p.planes = planes; p.H = H; p.W = W; p.coord_scale = (float)(2.0 / (double)box_warp);
@@ -1105,13 +1147,23 @@ extern "C" int ln3d_query_points(const float* planes, int H, int W, const float*
   p.scal_u = reinterpret_cast<uint32_t*>(scalars) + GRP_OFF; p.dec = scalars + DEC_OFF; p.vpc = 1;
   static AttrOnce attr_once;
   if (attr_once.need()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&query_points_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, RENDER_LDS_BYTES);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&query_points_kernel<TX>), hipFuncAttributeMaxDynamicSharedMemorySize, RENDER_LDS_BYTES);
   }
   hipLaunchKernelGGL(render_init_kernel, dim3(8), dim3(256), 0, s, p.scal_u, 0, scalars + DEC_OFF, dec_w0, dec_b0, dec_w1, dec_b1);
   int64_t blocks = ((P + 63) / 64 + 3) / 4;
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(query_points_kernel, dim3((unsigned)blocks), dim3(256), RENDER_LDS_BYTES, s, p, points, P, sigma, rgb);
+  hipLaunchKernelGGL(query_points_kernel<TX>, dim3((unsigned)blocks), dim3(256), RENDER_LDS_BYTES, s, p, points, P, sigma, rgb);
   return ln3d_check_launch();
+}
+extern "C" int ln3d_query_points(const float* planes, int H, int W, const float* points, int64_t P, const float* dec_w0,
+                                 const float* dec_b0, const float* dec_w1, const float* dec_b1, float box_warp, float* sigma,
+                                 float* rgb, float* scalars, void* stream) {
+  return query_points_t<float>(planes, H, W, points, P, dec_w0, dec_b0, dec_w1, dec_b1, box_warp, sigma, rgb, scalars, stream);
+}
+extern "C" int ln3d_query_points_f16(const void* planes, int H, int W, const float* points, int64_t P, const float* dec_w0,
+                                     const float* dec_b0, const float* dec_w1, const float* dec_b1, float box_warp, float* sigma,
+                                     float* rgb, float* scalars, void* stream) {
+  return query_points_t<_Float16>(planes, H, W, points, P, dec_w0, dec_b0, dec_w1, dec_b1, box_warp, sigma, rgb, scalars, stream);
 }
 
 // ------------------------------------------------------------------ [NP, 3*C, H, W] -> [NP, 3, H, W, C]
@@ -1135,5 +1187,50 @@ extern "C" int ln3d_planes_to_channel_last(const float* src, float* dst, int NP,
   if (!src || !dst || NP <= 0 || H <= 0 || W <= 0 || C != 32) return LN3D_ERR_BAD_ARG;
   const int HW = H * W;
   hipLaunchKernelGGL(planes_to_cl_kernel, dim3((HW + 31) / 32, NP * 3), dim3(256), 0, (hipStream_t)stream, src, dst, C, HW, (int64_t)NP * 3 * C * HW);
+  return ln3d_check_launch();
+}
+
+// ------------------------------------------------------------------ f32 -> binary16 texels (include/ln3d_planes16.h)
+// round to nearest even; everything beyond +-65504 (the infinities included) saturates to +-65504; a NaN stays a NaN
+__device__ __forceinline__ uint16_t f32_to_f16_sat(float x) {
+  const float c = x != x ? x : fminf(fmaxf(x, -65504.0f), 65504.0f);
+  const _Float16 h = (_Float16)c;
+  return __builtin_bit_cast(uint16_t, h);
+}
+// the tile transpose of planes_to_cl_kernel; a thread writes two channels (4 bytes) of one texel
+__global__ void planes_to_cl_f16_kernel(const float* src, uint32_t* dst, int C, int HW) {
+  __shared__ float tile[32][33];
+  const int pn = blockIdx.y;
+  const int hw0 = blockIdx.x * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
+  for (int c = ty; c < C; c += 8) {
+    const int hw = hw0 + tx;
+    tile[c][tx] = hw < HW ? src[((int64_t)pn * C + c) * HW + hw] : 0.f;
+  }
+  __syncthreads();
+  const int cx = threadIdx.x & 15, ry = threadIdx.x >> 4;   // 16 channel pairs x 16 texels
+  for (int r = ry; r < 32; r += 16) {
+    const int hw = hw0 + r;
+    if (hw < HW && 2 * cx < C)
+      dst[((int64_t)pn * HW + hw) * (C / 2) + cx] = (uint32_t)f32_to_f16_sat(tile[2 * cx][r]) | ((uint32_t)f32_to_f16_sat(tile[2 * cx + 1][r]) << 16);
+  }
+}
+extern "C" int ln3d_planes_to_channel_last_f16(const float* src, void* dst, int NP, int C, int H, int W, void* stream) {
+  if (!src || !dst || NP <= 0 || H <= 0 || W <= 0 || C != 32) return LN3D_ERR_BAD_ARG;
+  if ((int64_t)H * W > 0x7fffffff - 31 || (int64_t)NP * 3 > 65535) return LN3D_ERR_BAD_ARG;     // HW + 31 is an int, NP * 3 the grid's y extent
+  const int HW = H * W;
+  hipLaunchKernelGGL(planes_to_cl_f16_kernel, dim3((HW + 31) / 32, NP * 3), dim3(256), 0, (hipStream_t)stream, src, reinterpret_cast<uint32_t*>(dst), C, HW);
+  return ln3d_check_launch();
+}
+
+__global__ __launch_bounds__(256) void planes_f32_to_f16_kernel(const float* src, uint16_t* dst, int64_t n) {
+  const int64_t nt = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += nt) dst[i] = f32_to_f16_sat(src[i]);
+}
+extern "C" int ln3d_planes_f32_to_f16(const float* src, void* dst, int64_t n, void* stream) {
+  if (!src || !dst || n <= 0) return LN3D_ERR_BAD_ARG;
+  int64_t blocks = (n + 255) / 256;
+  if (blocks > 256 * 32) blocks = 256 * 32;
+  hipLaunchKernelGGL(planes_f32_to_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, reinterpret_cast<uint16_t*>(dst), n);
   return ln3d_check_launch();
 }

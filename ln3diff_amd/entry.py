@@ -60,6 +60,7 @@ _CHECKED = {
 
 
 DIT_PRECISIONS = ('bf16', 'mxfp8')
+PLANE_PRECISIONS = ('fp32', 'fp16')
 
 
 def str2bool(v):
@@ -97,7 +98,8 @@ def create_argparser(objaverse=True):
         num_head_channels=-1, num_heads_upsample=-1, use_scale_shift_norm=True, use_spatial_transformer=True, transformer_depth=1,
         dropout=0.0, mixing_logit_init=-6.0,
         ray_start=0.6, ray_end=1.8,          # nsr/script_util.py triplane_decoder_defaults; read by the ShapeNet decoder class only
-        dit_precision='bf16')                # matmul precision of the T23D DiT (no reference counterpart): bf16 or the opt-in mxfp8
+        dit_precision='bf16',                # matmul precision of the T23D DiT (no reference counterpart): bf16 or the opt-in mxfp8
+        plane_precision='fp32')              # texel storage of the renderer's tri-planes (no reference counterpart): fp32 or the opt-in fp16
     d.update(_IGNORED_DEFAULTS)
     d.update({k: v[0] for k, v in _CHECKED.items()})
     ap = argparse.ArgumentParser(allow_abbrev=False)
@@ -144,6 +146,9 @@ def validate(args):
                  "the PixArt-style T23D denoiser (DiT-PixelArt-*)")
         raise SystemExit(f"--dit_precision {prec}: the MX-FP8 path is built for the T23D DiT_TriLatent denoiser "
                          f"(--dit_model_arch DiT-B/2, DiT-L/2, DiT-XL/2, DiT-B/1) only; {which} has bf16 GEMMs only")
+    plane_prec = getattr(args, 'plane_precision', 'fp32')
+    if plane_prec not in PLANE_PRECISIONS:
+        raise SystemExit(f"--plane_precision {plane_prec}: expected one of {list(PLANE_PRECISIONS)}")
     if pixart_t23d and kind != 'flow':
         raise SystemExit("--dit_model_arch DiT-PixelArt-* (DiT_TriLatent_PixelArt) is the flow-matching T23D denoiser: use "
                          "--trainer_name flow_matching")
@@ -423,6 +428,7 @@ def run(args, objaverse=None):
     torch.cuda.set_device(dev)
     os.makedirs(args.logdir, exist_ok=True)
     dit, ae, dec, weights_from = build_models(args, dev, rank)
+    dec.triplane_decoder.set_plane_precision(getattr(args, 'plane_precision', 'fp32'))      # renders and the mesh grid alike (Triplane.cast_planes)
     parallel.broadcast_flat([p.data for p in dit.parameters()] + [p.data for p in dec.parameters()] + list(dec.buffers()), src=0)
 
     # conditioning is produced ONCE, on rank 0 (checkpoint loads, image / prompt encoding), and broadcast; a failure there is

@@ -61,8 +61,7 @@ def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0,
     vtx = (verts / (grid_size - 1) * 2 - 1) * 0.45                       # g-objaverse scale
     pcl = dec_out.get('planes_channel_last')
     if pcl is None:
-        from .nsr.triplane import Triplane
-        pcl = Triplane.to_channel_last(dec_out['latent_after_vit'])
+        pcl = decoder.triplane_decoder.to_channel_last(dec_out['latent_after_vit'])        # f32, or f16 under set_plane_precision('fp16')
     pcl = pcl[sample_index:sample_index + 1]
     col = decoder.forward_points(pcl, vtx[None])['rgb'][0] if vtx.shape[0] else vtx
     colors = (col.clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()

@@ -7,6 +7,9 @@ image_depth, weights_samples, image_mask, ...) and `OSGDecoder` (state-dict keys
 samples, box_warp 0.9, bbox +-0.45, white background, auto ray limits).  ray generation, sampling, gather, MLP
 and compositing all run inside `ln3d_render_triplane` (csrc/render.hip) - nothing of the reference's
 [V,3,M*S,32] feature tensor or its sort/gather intermediates is ever materialised.
+
+set_plane_precision('fp16') (opt-in; no reference counterpart) stores the channel-last tri-plane texels the kernels gather as IEEE
+binary16 (include/ln3d_planes16.h): half the bytes per tap and per tri-plane, the same fp32 arithmetic behind the load.
 """
 import torch
 import torch.nn as nn
@@ -90,19 +93,46 @@ class Triplane(nn.Module):
                               for t in (n[0].weight, n[0].bias, n[2].weight[:4], n[2].bias[:4]))
         return self._dec
 
-    @staticmethod
-    def to_channel_last(planes):
-        """[NP, 96, H, W] (reference '(n c) h w') -> [NP, 3, H, W, 32] f32 for the gather kernel."""
+    # ------------------------------------------------------------------ plane (texel) precision
+    PLANE_PRECISIONS = ('fp32', 'fp16')
+    _plane_precision = 'fp32'
+
+    def set_plane_precision(self, precision):
+        """'fp32' (default: the reference's planes) or 'fp16': the channel-last texels that the ray-marcher and the point query gather
+        are stored as IEEE binary16, rounded to nearest even and saturated at +-65504 (include/ln3d_planes16.h).  A storage format only:
+        the kernels widen every texel to fp32 and run the same arithmetic.  f32 planes handed to forward / query_points are converted
+        once per call while 'fp16' is active; f16 planes are rendered as they are under either setting."""
+        if precision not in self.PLANE_PRECISIONS:
+            raise ValueError(f"plane precision {precision!r}: expected one of {self.PLANE_PRECISIONS}")
+        self._plane_precision = precision
+        return self
+
+    @property
+    def plane_precision(self):
+        return self._plane_precision
+
+    def to_channel_last(self, planes):
+        """[NP, 96, H, W] (reference '(n c) h w') -> [NP, 3, H, W, 32] for the gather kernel, in the active plane precision."""
         NP, C3, H, W = planes.shape
-        out = torch.empty(NP, 3, H, W, C3 // 3, device=planes.device, dtype=torch.float32)
-        ops.planes_to_channel_last(planes.contiguous().float(), out, NP, C3 // 3, H, W)
+        fp16 = self._plane_precision == 'fp16'
+        out = torch.empty(NP, 3, H, W, C3 // 3, device=planes.device, dtype=torch.float16 if fp16 else torch.float32)
+        (ops.planes_to_channel_last_f16 if fp16 else ops.planes_to_channel_last)(planes.contiguous().float(), out, NP, C3 // 3, H, W)
         return out
+
+    def cast_planes(self, planes_channel_last):
+        """channel-last texels as the kernels will read them: f32 planes become f16 ones while the plane precision is 'fp16' (the
+        converter's rounding, element for element); everything else passes."""
+        if self._plane_precision == 'fp16' and planes_channel_last.dtype == torch.float32:
+            out = torch.empty(planes_channel_last.shape, device=planes_channel_last.device, dtype=torch.float16)
+            ops.planes_f32_to_f16(planes_channel_last.contiguous(), out)
+            return out
+        return planes_channel_last
 
     @torch.no_grad()
     def forward(self, planes=None, c=None, neural_rendering_resolution=None, jitter=None, u_fine=None,
                 planes_channel_last=None, plane_index=None, return_debug=False, views_per_call=0, **_):
         """planes [V,96,H,W] (one tri-plane per camera row, as the reference) or
-        planes_channel_last [NP,3,H,W,32] + plane_index [V] (many views of few tri-planes).
+        planes_channel_last [NP,3,H,W,32] f32 or f16 + plane_index [V] (many views of few tri-planes).
         views_per_call: the reference reduces the ray-limit fix-up and the depth clamp range over everything ONE forward() call
         renders; 0 = this call is one such call (reference semantics of Triplane.forward), k = every k consecutive views are
         (the drivers, which call the reference once per camera, pass 1)."""
@@ -116,6 +146,7 @@ class Triplane(nn.Module):
         if planes_channel_last is None:
             planes_channel_last = self.to_channel_last(planes)
             plane_index = torch.arange(V, device=dev, dtype=torch.int32)
+        planes_channel_last = self.cast_planes(planes_channel_last)
         H, W = planes_channel_last.shape[2], planes_channel_last.shape[3]
         if jitter is None:
             jitter, u_fine = draw_render_noise(V, M, S, device=dev, n_importance=NI)
@@ -159,7 +190,7 @@ class Triplane(nn.Module):
 
     @torch.no_grad()
     def query_points(self, planes_channel_last_one, points):
-        """points [P,3] against ONE tri-plane [3,H,W,32] -> {'sigma':[P,1],'rgb':[P,3]} (no bbox filter:
+        """points [P,3] against ONE tri-plane [3,H,W,32] (f32 or f16) -> {'sigma':[P,1],'rgb':[P,3]} (no bbox filter:
         renderer._run_model as used by forward_points, vit/vit_triplane.py:2026-2041)."""
         dev = points.device
         P = points.shape[0]
@@ -167,6 +198,6 @@ class Triplane(nn.Module):
         sigma = torch.empty(P, 1, device=dev)
         rgb = torch.empty(P, 3, device=dev)
         scal = torch.empty(RENDER_SCRATCH_FLOATS, device=dev)
-        ops.query_points(planes_channel_last_one.contiguous(), H, W, points.contiguous().float(), self._decoder_dev(dev),
+        ops.query_points(self.cast_planes(planes_channel_last_one).contiguous(), H, W, points.contiguous().float(), self._decoder_dev(dev),
                          self.rendering_kwargs['box_warp'], sigma, rgb, scal)
         return {'sigma': sigma, 'rgb': rgb}

@@ -194,6 +194,29 @@ def planes_to_channel_last(src, dst, NP, Cc, H, W):
     L.check(L.lib().ln3d_planes_to_channel_last(_p(src), _p(dst), NP, Cc, H, W, _stream()), "planes_to_channel_last")
 
 
+def planes_to_channel_last_f16(src, dst, NP, Cc, H, W):
+    """src [NP, 3 * Cc, H, W] f32 -> dst [NP, 3, H, W, Cc] torch.float16: round to nearest even, saturating at +-65504 (include/ln3d_planes16.h)."""
+    if src.dtype != torch.float32 or dst.dtype != torch.float16:
+        raise TypeError(f"planes_to_channel_last_f16: f32 source and f16 destination expected, got {src.dtype} -> {dst.dtype}")
+    L.check(L.lib().ln3d_planes_to_channel_last_f16(_p(src), _p(dst), NP, Cc, H, W, _stream()), "planes_to_channel_last_f16")
+
+
+def planes_f32_to_f16(src, dst):
+    """contiguous f32 planes (any layout) -> torch.float16, element for element, by the rule of planes_to_channel_last_f16."""
+    if src.dtype != torch.float32 or dst.dtype != torch.float16:
+        raise TypeError(f"planes_f32_to_f16: f32 source and f16 destination expected, got {src.dtype} -> {dst.dtype}")
+    L.check(L.lib().ln3d_planes_f32_to_f16(_p(src), _p(dst), C.c_int64(src.numel()), _stream()), "planes_f32_to_f16")
+
+
+def _plane_entry(planes, what):
+    """the entry point for this texel type: f32 planes -> include/ln3d.h, f16 planes -> include/ln3d_planes16.h; nothing else exists"""
+    if planes.dtype == torch.float32:
+        return getattr(L.lib(), "ln3d_" + what)
+    if planes.dtype == torch.float16:
+        return getattr(L.lib(), "ln3d_" + what + "_f16")
+    raise TypeError(f"{what}: tri-plane texels are torch.float32 or torch.float16, got {planes.dtype}")
+
+
 def planes_to_nchw(src, dst, NP, Cc, H, W):
     L.check(L.lib().ln3d_planes_to_nchw(_p(src), _p(dst), NP, Cc, H, W, _stream()), "planes_to_nchw")
 
@@ -204,8 +227,10 @@ def render_triplane(planes_cl, H, W, plane_index, cams, res, dec, jitter, u_fine
                     rays_per_view=0, visibility=None, depth_resolution=0, depth_resolution_importance=0, ray_start='auto', ray_end='auto',
                     filter_out_of_bbox=True, weights=None, all_coords=None, feature_volume=None):
     """cams [V,25] (rays generated in-kernel) or explicit ray_o / ray_d [V, M, 3] (then cams may be None; rays_per_view = M).
+    planes_cl: channel-last texels, torch.float32 or torch.float16 (ln3d_render_triplane_f16); any other dtype is a TypeError.
     views_per_call: how many consecutive views form one reference forward() call for the call-wide reductions (ray-limit fix-up,
     depth clamp range); 0 = all of them (include/ln3d.h).  ray_start / ray_end: both 'auto' or both numbers."""
+    entry = _plane_entry(planes_cl, "render_triplane")
     a = L.RenderArgs()
     a.planes, a.H, a.W, a.plane_index, a.cams = _p(planes_cl), H, W, _p(plane_index), _p(cams)
     a.V, a.res = (cams.shape[0] if cams is not None else n_views), res
@@ -226,12 +251,13 @@ def render_triplane(planes_cl, H, W, plane_index, cams, res, dec, jitter, u_fine
         a.ray_mode, a.ray_start, a.ray_end = 1, float(ray_start), float(ray_end)
     a.no_bbox_filter = 0 if filter_out_of_bbox else 1
     a.weights, a.all_coords, a.feature_volume = _p(weights), _p(all_coords), _p(feature_volume)
-    L.check(L.lib().ln3d_render_triplane(C.byref(a), _stream()), "render_triplane")
+    L.check(entry(C.byref(a), _stream()), "render_triplane")
 
 
 def query_points(planes_cl, H, W, points, dec, box_warp, sigma, rgb, scalars):
-    """scalars: caller-owned f32 scratch of _lib.RENDER_SCRATCH_FLOATS (no allocation inside the library)."""
-    L.check(L.lib().ln3d_query_points(_p(planes_cl), H, W, _p(points), C.c_int64(points.shape[0]), *(_p(t) for t in dec),
+    """scalars: caller-owned f32 scratch of _lib.RENDER_SCRATCH_FLOATS (no allocation inside the library).  planes_cl: torch.float32 or
+    torch.float16 texels (ln3d_query_points_f16)."""
+    L.check(_plane_entry(planes_cl, "query_points")(_p(planes_cl), H, W, _p(points), C.c_int64(points.shape[0]), *(_p(t) for t in dec),
                                       C.c_float(box_warp), _p(sigma), _p(rgb), _p(scalars), _stream()), "query_points")
 
 

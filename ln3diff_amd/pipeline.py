@@ -22,13 +22,30 @@ TRIPLANE_SCALING_DIVIDER = 0.96806      # the released Objaverse runs (shell_scr
 
 @torch.no_grad()
 def render_video_given_triplane(planes, rec_model, cams, triplane_scaling_divider=TRIPLANE_SCALING_DIVIDER, latent_name='latent_normalized_2Ddiffusion',
-                                export_mesh=False, mesh_size=192, mesh_thres=10, mesh_path=None, resolution=None, jitter=None, u_fine=None):
+                                export_mesh=False, mesh_size=192, mesh_thres=10, mesh_path=None, resolution=None, jitter=None, u_fine=None,
+                                plane_precision=None):
     """planes: sampled latent [B, 12, 32, 32] (scaled IN PLACE like the reference, :188); rec_model: `AE`; cams [V, 25] rendered
-    for every sample.  Returns {'latent_after_vit' (if produced), 'image_raw' [B,V,3,R,R], 'image_depth', 'weights_samples',
+    for every sample.  plane_precision: 'fp32' | 'fp16' = the renderer's Triplane.set_plane_precision FOR THIS CALL (the renderer's own
+    setting is restored on the way out; None: render with the setting it has); under 'fp16' the decoded planes are converted once and
+    the mesh and every view read the f16 texels.  Returns {'latent_after_vit' (if produced), 'image_raw' [B,V,3,R,R], 'image_depth', 'weights_samples',
     'image_mask', 'mesh': [(verts, faces, colors)] when export_mesh}."""
     planes *= triplane_scaling_divider
     ddpm_latent = {latent_name: planes}
     ddpm_latent.update(rec_model(latent=ddpm_latent, behaviour='decode_after_vae_no_render'))
+    tp = rec_model.decoder.triplane_decoder
+    before = tp.plane_precision
+    if plane_precision is not None:
+        tp.set_plane_precision(plane_precision)
+    try:
+        return _render_video_decoded(ddpm_latent, planes, rec_model, cams, export_mesh, mesh_size, mesh_thres, mesh_path, resolution, jitter, u_fine)
+    finally:
+        tp.set_plane_precision(before)
+
+
+def _render_video_decoded(ddpm_latent, planes, rec_model, cams, export_mesh, mesh_size, mesh_thres, mesh_path, resolution, jitter, u_fine):
+    tp = rec_model.decoder.triplane_decoder
+    if ddpm_latent.get('planes_channel_last') is not None:
+        ddpm_latent['planes_channel_last'] = tp.cast_planes(ddpm_latent['planes_channel_last'])
     out = {}
     if export_mesh:
         from .mesh import mesh_from_grid
@@ -230,14 +247,18 @@ class FlowMatchingEngine:
         return samples, render_video_given_triplane(samples.clone(), self.rec_model, camera[:24], self.triplane_scaling_divider,
                                                     export_mesh=export_mesh, resolution=resolution, **render_kw)
 
+    @torch.no_grad()
+    def render_video_given_triplane(self, planes, cams, **kw):
+        return render_video_given_triplane(planes, self.rec_model, cams, self.triplane_scaling_divider, **kw)
+
     # FlowMatchingEngine.eval_i23d_and_export (:684-760): image -> conditioner -> sample -> mesh + video
     @torch.no_grad()
     def eval_i23d_and_export(self, inp_img, camera, num_steps=250, seed=42, mesh_size=192, mesh_thres=10, unconditional_guidance_scale=4.0,
-                             num_samples=1, export_mesh=True, resolution=None, mesh_path=None):
+                             num_samples=1, export_mesh=True, resolution=None, mesh_path=None, plane_precision=None):
         assert self.conditioner is not None, "construct the engine with conditioner=I23DConditioner(...)"
         cond = self.conditioner(inp_img)
         samples, out = self.eval_cldm(cond, camera, num_samples, unconditional_guidance_scale, num_steps, seed, export_mesh,
-                                      resolution, mesh_size=mesh_size, mesh_thres=mesh_thres, mesh_path=mesh_path)
+                                      resolution, mesh_size=mesh_size, mesh_thres=mesh_thres, mesh_path=mesh_path, plane_precision=plane_precision)
         return samples, out
 
 
@@ -297,13 +318,17 @@ class GuidedDiffusionEngine:
                                                    export_mesh=export_mesh, resolution=resolution, **render_kw)
 
     @torch.no_grad()
+    def render_video_given_triplane(self, planes, cams, **kw):
+        return render_video_given_triplane(planes, self.rec_model, cams, self.triplane_scaling_divider, **kw)
+
+    @torch.no_grad()
     def eval_ddpm_sample(self, camera, **kw):
         return self.eval_cldm(None, camera, **kw)
 
 
 @torch.no_grad()
 def reconstruct(rec_model, img, cams, latent_dir=None, ins_names=None, sample_posterior=True, eps=None, export_mesh=False, mesh_size=192,
-                mesh_thres=10, mesh_path=None, resolution=None, jitter=None, u_fine=None):
+                mesh_thres=10, mesh_path=None, resolution=None, jitter=None, u_fine=None, plane_precision=None):
     """Posed views -> tri-plane latent -> renders (and meshes): TrainLoop.eval_novelview_loop(save_latent=True) of the VAE
     reconstruction launcher (vae_xl_reconstruction.sh; nsr/train_nv_util.py:1176-1213).  rec_model: `AE` with the released encoder;
     img [B*F, 10, 256, 256] (F = rec_model.encoder.num_frames views per object); cams [V, 25] rendered for every object.
@@ -332,6 +357,7 @@ def reconstruct(rec_model, img, cams, latent_dir=None, ins_names=None, sample_po
             os.makedirs(os.path.join(latent_dir, name), exist_ok=True)
             np.save(os.path.join(latent_dir, name, 'latent.npy'), zc[b])
     out = render_video_given_triplane(z.clone(), rec_model, cams, triplane_scaling_divider=1.0, export_mesh=export_mesh, mesh_size=mesh_size,
-                                      mesh_thres=mesh_thres, mesh_path=mesh_path, resolution=resolution, jitter=jitter, u_fine=u_fine)
+                                      mesh_thres=mesh_thres, mesh_path=mesh_path, resolution=resolution, jitter=jitter, u_fine=u_fine,
+                                      plane_precision=plane_precision)
     out['latent'] = lat
     return out

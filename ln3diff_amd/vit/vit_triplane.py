@@ -341,9 +341,9 @@ class RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout
         if isinstance(latent, dict):
             pcl = latent.get('planes_channel_last')
             if pcl is None:
-                pcl = Triplane.to_channel_last(latent['latent_after_vit'])
+                pcl = self.triplane_decoder.to_channel_last(latent['latent_after_vit'])
         else:
-            pcl = Triplane.to_channel_last(latent)
+            pcl = self.triplane_decoder.to_channel_last(latent)
         return self.forward_points(pcl, coordinates)
 
     @torch.no_grad()
@@ -355,7 +355,7 @@ class RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout
     def triplane_decode_grid(self, vit_decode_out, grid_size, aabb=None, **kwargs):
         pcl = vit_decode_out.get('planes_channel_last')
         if pcl is None:
-            pcl = Triplane.to_channel_last(vit_decode_out['latent_after_vit'])
+            pcl = self.triplane_decoder.to_channel_last(vit_decode_out['latent_after_vit'])
         N = pcl.shape[0]
         lo, hi = self.rendering_kwargs['sampler_bbox_min'], self.rendering_kwargs['sampler_bbox_max']
         ax = torch.linspace(lo, hi, grid_size, device=pcl.device)

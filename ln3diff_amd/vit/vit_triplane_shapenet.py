@@ -455,7 +455,7 @@ class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(nn.Module):
         """vit_triplane.py:290-337: the grid spans sampler_bbox_min / max when the preset has them, else +- box_warp / 2 (ShapeNet)."""
         pcl = vit_decode_out.get('planes_channel_last')
         if pcl is None:
-            pcl = Triplane.to_channel_last(vit_decode_out['latent_after_vit'])
+            pcl = self.triplane_decoder.to_channel_last(vit_decode_out['latent_after_vit'])
         N = pcl.shape[0]
         rk = self.rendering_kwargs
         if aabb is not None:
