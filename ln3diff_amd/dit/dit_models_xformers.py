@@ -318,6 +318,50 @@ def self_attention_hip(ws, tag, h_bf16, B, N, D, H, qkv_w, qkv_b, qn=None, kn=No
     return o
 
 
+# ----------------------------------------------------------------------------- the pre-LN ViT block (CLIP / OpenCLIP / DINOv2 towers, DINO decoders)
+def gate_res_gemm(a, w, bias, x, **gate):
+    """x += gate * (a @ w^T + bias): one GEMM with the gated-residual epilogue."""
+    ops.gemm(a, w, bias, ops.EPI_GATE_RES, x, **gate)
+
+
+def _layer_scale(g, M):
+    """GEMM gate arguments of a LayerScale gamma [D] (one row for all M tokens); the epilogue reads gate_rows only with a gate."""
+    return {} if g is None else dict(gate=g, gate_rows=M, gate_ld=0)
+
+
+def vit_mlp_hip(ws, x, q, zeros, eps, act, res_gemm=gate_res_gemm):
+    """MLP half of vit_block_hip: x += ls2 * fc2(act(fc1(LN(x)))); q: 'n2' (weight, bias), 'fc1_w' / 'fc1_b', 'fc2_w' / 'fc2_b', 'ls2'."""
+    M, D = x.shape
+    h = ws.get('h', (M, D), torch.bfloat16)
+    ops.norm_modulate(x, h, M, D, kind=0, eps=eps, weight=q['n2'][0], shift=q['n2'][1], scale=zeros, mod_rows=M, mod_ld=0)
+    f1 = ws.get('f1', (M, q['fc1_w'].shape[0]), torch.bfloat16)
+    ops.gemm(h, q['fc1_w'], q['fc1_b'], act, f1)
+    res_gemm(f1, q['fc2_w'], q['fc2_b'], x, **_layer_scale(q.get('ls2'), M))
+
+
+def vit_block_hip(ws, x, q, B, T, H, zeros, eps, act, causal=False, res_gemm=gate_res_gemm):
+    """One pre-LN transformer block in place on the fp32 residual stream x [B*T, D]:
+      x += ls1 * proj(attention(qkv(LN(x))));  x += ls2 * fc2(act(fc1(LN(x)))).
+    q holds the packed operands: 'n1' / 'n2' (weight, bias) f32, 'qkv_w' / 'fc1_w' bf16, 'o_w' / 'fc2_w' whatever `res_gemm` takes
+    (bf16 for the default), the f32 biases 'qkv_b' / 'o_b' / 'fc1_b' / 'fc2_b' and, optionally, the LayerScale gammas 'ls1' / 'ls2'.
+    `zeros` [D] is the norm's (absent) modulation scale, `act` the fc1 GEMM's activation epilogue, `res_gemm(a, w, bias, x, **gate)` the
+    projection onto the residual stream.  Scratch is the caller's Workspace: 'h' 'q' 'k' 'vt' 'o' 'f1' (q / k / vt zero-initialised:
+    their padding rows T..tpad are never written)."""
+    M, D = x.shape
+    Dh = D // H
+    tpad = (T + 63) // 64 * 64
+    h = ws.get('h', (M, D), torch.bfloat16)
+    ops.norm_modulate(x, h, M, D, kind=0, eps=eps, weight=q['n1'][0], shift=q['n1'][1], scale=zeros, mod_rows=M, mod_ld=0)
+    qq = ws.get('q', (B, H, tpad, Dh), torch.bfloat16, zero=True)
+    kk = ws.get('k', (B, H, tpad, Dh), torch.bfloat16, zero=True)
+    vt = ws.get('vt', (B, H, Dh, tpad), torch.bfloat16, zero=True)
+    o = ws.get('o', (M, D), torch.bfloat16)
+    ops.gemm(h, q['qkv_w'], q['qkv_b'], ops.EPI_HEADS, qq, kk, vt, M=M, tokens=T, tok_pad=tpad, heads=H, head_dim=Dh, transpose_mask=0b100)
+    ops.attention(qq, kk, vt, o, B, H, T, tpad, T, tpad, Dh, scale=Dh ** -0.5, causal=causal)
+    res_gemm(o, q['o_w'], q['o_b'], x, **_layer_scale(q.get('ls1'), M))
+    vit_mlp_hip(ws, x, q, zeros, eps, act, res_gemm)
+
+
 def sincos_timestep_freqs(dim=256, max_period=10000.0):
     half = dim // 2
     return torch.exp(-math.log(max_period) * torch.arange(half, dtype=torch.float32) / half)

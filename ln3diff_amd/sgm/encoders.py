@@ -6,16 +6,15 @@ sgm/configs/txt2img-clipl-compat.yaml: layer="last", always_return_pooled=True):
 state-dict keys are the hub checkpoint's (`transformer.text_model.*`), so released weights load without renaming.
 forward(text | token ids) -> (last_hidden_state [B,77,768] f32, pooler_output [B,768] f32) = cond['crossattn'], cond['vector'].
 
-The arithmetic runs on the same kernels as the DiT: LayerNorm(+affine) -> fused QKV GEMM with head-split epilogue ->
-attention kernel with the causal flag -> out-proj GEMM with residual epilogue -> LayerNorm -> fc1 GEMM + quick-GELU
-epilogue -> fc2 GEMM with residual epilogue; final LayerNorm in fp32.  The tokenizer is third-party data (BPE vocabulary +
+The arithmetic runs on the same kernels as the DiT, every layer through the shared pre-LN block (dit_models_xformers.vit_block_hip)
+with the causal flag and the quick-GELU epilogue; final LayerNorm in fp32.  The tokenizer is third-party data (BPE vocabulary +
 merges files): `forward(text)` uses transformers.CLIPTokenizer when those files are available locally, otherwise pass ids.
 """
 import torch
 import torch.nn as nn
 
 from .. import ops, _cache
-from ..dit.dit_models_xformers import Workspace, bf16, f32
+from ..dit.dit_models_xformers import Workspace, bf16, f32, vit_block_hip
 
 
 class _Attn(nn.Module):
@@ -125,8 +124,8 @@ class FrozenCLIPEmbedder(nn.Module):
         for l in tm.encoder.layers:
             a = l.self_attn
             P['layers'].append({
-                'ln1w': f32(l.layer_norm1.weight, dev), 'ln1b': f32(l.layer_norm1.bias, dev),
-                'ln2w': f32(l.layer_norm2.weight, dev), 'ln2b': f32(l.layer_norm2.bias, dev),
+                'n1': (f32(l.layer_norm1.weight, dev), f32(l.layer_norm1.bias, dev)),
+                'n2': (f32(l.layer_norm2.weight, dev), f32(l.layer_norm2.bias, dev)),
                 'qkv_w': bf16(torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0), dev),
                 'qkv_b': f32(torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], 0), dev),
                 'o_w': bf16(a.out_proj.weight, dev), 'o_b': f32(a.out_proj.bias, dev),
@@ -148,27 +147,13 @@ class FrozenCLIPEmbedder(nn.Module):
         B, T = ids.shape
         D = P['tok'].shape[1]
         H = tm.heads
-        Dh = D // H
-        assert Dh in (64, 128), "attention kernel head sizes"
-        M, tpad = B * T, (T + 63) // 64 * 64
+        assert D // H in (64, 128), "attention kernel head sizes"
+        M = B * T
         ids_dev = ids.to(device=dev, dtype=torch.int32).contiguous()
         x = ws.get('x', (M, D), torch.float32)
         ops.embed_tokens(ids_dev, P['tok'], P['pos'], x, B, T, D)
-        h = ws.get('h', (M, D), torch.bfloat16)
-        q = ws.get('q', (B, H, tpad, Dh), torch.bfloat16, zero=True)
-        k = ws.get('k', (B, H, tpad, Dh), torch.bfloat16, zero=True)
-        vt = ws.get('vt', (B, H, Dh, tpad), torch.bfloat16, zero=True)
-        o = ws.get('o', (M, D), torch.bfloat16)
-        f1 = ws.get('f1', (M, P['layers'][0]['fc1_w'].shape[0]), torch.bfloat16)
         for L in P['layers']:
-            ops.norm_modulate(x, h, M, D, kind=0, eps=tm.eps, weight=L['ln1w'], shift=L['ln1b'], scale=P['zeros'], mod_rows=M, mod_ld=0)
-            ops.gemm(h, L['qkv_w'], L['qkv_b'], ops.EPI_HEADS, q, k, vt, M=M, tokens=T, tok_pad=tpad, heads=H, head_dim=Dh,
-                     transpose_mask=0b100)
-            ops.attention(q, k, vt, o, B, H, T, tpad, T, tpad, Dh, scale=Dh ** -0.5, causal=True)
-            ops.gemm(o, L['o_w'], L['o_b'], ops.EPI_GATE_RES, x)
-            ops.norm_modulate(x, h, M, D, kind=0, eps=tm.eps, weight=L['ln2w'], shift=L['ln2b'], scale=P['zeros'], mod_rows=M, mod_ld=0)
-            ops.gemm(h, L['fc1_w'], L['fc1_b'], ops.EPI_QUICK_GELU, f1)
-            ops.gemm(f1, L['fc2_w'], L['fc2_b'], ops.EPI_GATE_RES, x)
+            vit_block_hip(ws, x, L, B, T, H, P['zeros'], tm.eps, ops.EPI_QUICK_GELU, causal=True)
         last = torch.empty(B, T, D, device=dev, dtype=torch.float32)
         ops.layernorm_f32(x, P['fw'], P['fb'], last, M, D, tm.eps)
         if tm.eos_token_id == 2:                                        # legacy hub config: position of the largest id

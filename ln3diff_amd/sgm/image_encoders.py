@@ -8,16 +8,15 @@ kernels with the ORIGINAL packages' state-dict key layouts (`model.visual.*` / `
 renaming; the arithmetic is pinned against the architecture-identical HuggingFace models (tests/golden/make_golden_vit.py),
 the key naming and the kornia resize of `preprocess` are not (inputs: 224x224, already resized; normalisation is done here).
 
-Kernel sequence per block (same as the text tower): LayerNorm(+affine) -> fused QKV GEMM with head-split epilogue ->
-attention kernel (257 / 261 tokens, Dh 64) -> out-proj GEMM with the residual epilogue (LayerScale gamma as its gate for
-DINOv2) -> LayerNorm -> fc1 GEMM + quick-GELU / erf-GELU epilogue -> fc2 GEMM with the residual epilogue.  The 14x14
-patch-embedding convolution is a patchify kernel + one GEMM (K = 588 padded to 640).
+Every block is the shared pre-LN block of the text tower (dit_models_xformers.vit_block_hip: 257 / 261 tokens, Dh 64), with the
+quick-GELU / erf-GELU epilogue and, for DINOv2, the LayerScale gammas as the gates of the two GEMMs that write the residual.  The
+14x14 patch-embedding convolution is a patchify kernel + one GEMM (K = 588 padded to 640).
 """
 import torch
 import torch.nn as nn
 
 from .. import ops, _cache
-from ..dit.dit_models_xformers import Workspace, bf16, f32
+from ..dit.dit_models_xformers import Workspace, bf16, f32, vit_block_hip
 
 
 # ----------------------------------------------------------------------------- parameter containers (original key layouts)
@@ -130,6 +129,7 @@ class _ViTRunner:
         self.layers = []
         for l in spec['layers']:
             q = {k: (bf16(v, dev) if k.endswith('_w') and v.dim() == 2 else f32(v, dev)) for k, v in l.items() if v is not None}
+            q['n1'], q['n2'] = (q.pop('n1_w'), q.pop('n1_b')), (q.pop('n2_w'), q.pop('n2_b'))      # vit_block_hip's operand names
             self.layers.append(q)
 
     @torch.no_grad()
@@ -139,8 +139,8 @@ class _ViTRunner:
         assert tuple(img.shape[1:]) == (self.chans, S, S), f"expects {self.chans} x {S} x {S} inputs (resize first)"
         G = S // P
         Lp, T = G * G, 1 + R + G * G
-        M, tpad, Dh = B * T, (T + 63) // 64 * 64, D // H
-        assert Dh in (64, 128)
+        M = B * T
+        assert D // H in (64, 128)
         pm = ws.get('pm', (B * Lp, self.kpad), torch.bfloat16)
         ops.vit_patchify(img.contiguous().float(), pm, B, S, P, self.kpad, self.chans)
         pe = ws.get('pe', (B * Lp, D), torch.float32)
@@ -149,23 +149,9 @@ class _ViTRunner:
         ops.vit_assemble(pe, self.cls, self.reg, self.pos, x, B, Lp, R, D)
         if self.pre is not None:
             ops.layernorm_f32(x, self.pre[0], self.pre[1], x, M, D, s['eps'])
-        h = ws.get('h', (M, D), torch.bfloat16)
-        q = ws.get('q', (B, H, tpad, Dh), torch.bfloat16, zero=True)
-        k = ws.get('k', (B, H, tpad, Dh), torch.bfloat16, zero=True)
-        vt = ws.get('vt', (B, H, Dh, tpad), torch.bfloat16, zero=True)
-        o = ws.get('o', (M, D), torch.bfloat16)
-        f1 = ws.get('f1', (M, self.layers[0]['fc1_w'].shape[0]), torch.bfloat16)
         act = ops.EPI_QUICK_GELU if s['act'] == 'quick_gelu' else ops.EPI_GELU_ERF
-        for L in self.layers:
-            ops.norm_modulate(x, h, M, D, kind=0, eps=s['eps'], weight=L['n1_w'], shift=L['n1_b'], scale=self.zeros, mod_rows=M, mod_ld=0)
-            ops.gemm(h, L['qkv_w'], L['qkv_b'], ops.EPI_HEADS, q, k, vt, M=M, tokens=T, tok_pad=tpad, heads=H, head_dim=Dh,
-                     transpose_mask=0b100)
-            ops.attention(q, k, vt, o, B, H, T, tpad, T, tpad, Dh, scale=Dh ** -0.5)
-            g1, g2 = L.get('ls1'), L.get('ls2')                       # LayerScale = a per-feature gate on the branch output
-            ops.gemm(o, L['o_w'], L['o_b'], ops.EPI_GATE_RES, x, gate=g1, gate_rows=M, gate_ld=0)
-            ops.norm_modulate(x, h, M, D, kind=0, eps=s['eps'], weight=L['n2_w'], shift=L['n2_b'], scale=self.zeros, mod_rows=M, mod_ld=0)
-            ops.gemm(h, L['fc1_w'], L['fc1_b'], act, f1)
-            ops.gemm(f1, L['fc2_w'], L['fc2_b'], ops.EPI_GATE_RES, x, gate=g2, gate_rows=M, gate_ld=0)
+        for L in self.layers:                                         # 'ls1' / 'ls2' (DINOv2's LayerScale) gate the branch outputs
+            vit_block_hip(ws, x, L, B, T, H, self.zeros, s['eps'], act)
         y = torch.empty(B, T, D, device=dev, dtype=torch.float32)
         ops.layernorm_f32(x, self.post[0], self.post[1], y, M, D, s['eps'])
         return y, R

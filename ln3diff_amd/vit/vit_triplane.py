@@ -112,7 +112,101 @@ def _pack_conv1(conv, device):
     return {'w': bf16(conv.weight.detach().reshape(conv.weight.shape[0], -1), device), 'b': f32(conv.bias, device)}
 
 
-class RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout_withSD_D_ditDecoder(nn.Module):
+class _RendererSeams:
+    """The renderer side shared by the three decoder classes: tri-planes (a vit_decode_postprocess dict or [B, 96, H, W]) -> renders,
+    point queries and grids.  The class that inherits it provides `triplane_decoder` (nsr.triplane.Triplane) and `rendering_kwargs`."""
+    grid_ignores_aabb = False                  # triplane_decode_grid(aabb=...): raise, or (the Objaverse class) use the preset's box anyway
+
+    @torch.no_grad()
+    def triplane_decode(self, vit_decode_out, c, return_raw_only=False, **kwargs):
+        """The reference also passes ws = sr_w_code, which only Triplane.superresolution reads (not built: --sr_training False)."""
+        if isinstance(vit_decode_out, dict):
+            pcl = vit_decode_out.get('planes_channel_last')
+            planes = vit_decode_out.get('latent_after_vit')
+        else:
+            pcl, planes = None, vit_decode_out
+            vit_decode_out = dict(latent_normalized=planes)
+        if pcl is not None:
+            V = c.shape[0]
+            idx = kwargs.pop('plane_index', None)
+            if idx is None:
+                assert pcl.shape[0] in (V, 1)
+                idx = torch.arange(V, device=c.device, dtype=torch.int32) if pcl.shape[0] == V else \
+                    torch.zeros(V, device=c.device, dtype=torch.int32)
+            ret = self.triplane_decoder(c=c, planes_channel_last=pcl, plane_index=idx, **kwargs)
+        else:
+            ret = self.triplane_decoder(planes, c, **kwargs)
+        ret.update({'latent_after_vit': planes, **vit_decode_out})
+        return ret
+
+    @torch.no_grad()
+    def triplane_renderer(self, latent, coordinates, directions=None):
+        """decoder output at explicit points (vit/vit_triplane.py:377-388 -> renderer.run_model): latent = tri-planes
+        [B,96,H,W] / dict, coordinates [B,P,3] -> {'rgb': [B,P,3], 'sigma': [B,P,1]} (directions are unused by OSGDecoder)."""
+        if isinstance(latent, dict):
+            pcl = latent.get('planes_channel_last')
+            if pcl is None:
+                pcl = self.triplane_decoder.to_channel_last(latent['latent_after_vit'])
+        else:
+            pcl = self.triplane_decoder.to_channel_last(latent)
+        return self.forward_points(pcl, coordinates)
+
+    @torch.no_grad()
+    def forward_points(self, planes_channel_last, points, chunk_size=2 ** 16):
+        outs = [self.triplane_decoder.query_points(planes_channel_last[n], points[n]) for n in range(points.shape[0])]
+        return {k: torch.stack([o[k] for o in outs], 0) for k in outs[0]}
+
+    @torch.no_grad()
+    def triplane_decode_grid(self, vit_decode_out, grid_size, aabb=None, **kwargs):
+        """vit_triplane.py:290-337, :2052: the grid spans sampler_bbox_min / max when the preset has them, else +- box_warp / 2 (ShapeNet)."""
+        pcl = vit_decode_out.get('planes_channel_last')
+        if pcl is None:
+            pcl = self.triplane_decoder.to_channel_last(vit_decode_out['latent_after_vit'])
+        N = pcl.shape[0]
+        rk = self.rendering_kwargs
+        if aabb is not None and not self.grid_ignores_aabb:
+            raise NotImplementedError("triplane_decode_grid: a per-object aabb is not supported; the preset's box is used")
+        lo, hi = (rk['sampler_bbox_min'], rk['sampler_bbox_max']) if 'sampler_bbox_min' in rk else (-rk['box_warp'] / 2, rk['box_warp'] / 2)
+        ax = torch.linspace(lo, hi, grid_size, device=pcl.device)
+        pts = torch.stack(torch.meshgrid(ax, ax, ax, indexing='ij'), dim=-1).reshape(1, -1, 3).expand(N, -1, -1)
+        f = self.forward_points(pcl, pts)
+        return {k: v.reshape(N, grid_size, grid_size, grid_size, -1) for k, v in f.items()}
+
+
+class _PosteriorSeams:
+    """The quant_conv posterior of the encoder side (vit_triplane.py:912-933, :1152-1199).  The class that inherits it provides
+    `superresolution['quant_conv']` (grouped 1 x 1 conv) and `ldm_embed_dim`."""
+
+    def _quant_packed(self, dev):
+        q = self.__dict__.get('_quant')
+        if not _cache.fresh(q, dev):
+            qc = self.superresolution['quant_conv']
+            q = _cache.stamp({'device': dev, 'w': f32(qc.weight.reshape(qc.weight.shape[0], -1), dev), 'b': f32(qc.bias, dev)}, self)
+            self.__dict__['_quant'] = q
+        return q
+
+    def _posterior(self, h, eps, num_frames):
+        if not h.is_cuda:
+            raise RuntimeError("ln3diff_amd posterior runs on the HIP device only (no CPU fallback)")
+        if h.shape[0] % num_frames:
+            raise ValueError(f"posterior input batch {h.shape[0]} is not a multiple of num_frames={num_frames}")
+        q = self._quant_packed(h.device)
+        B = h.shape[0] // num_frames
+        if eps is not None:
+            eps = eps.to(h.device, torch.float32).reshape(B, self.ldm_embed_dim, 3, -1).contiguous()
+        return ops.mv_posterior(h, q['w'], q['b'], eps, B, num_frames, self.ldm_embed_dim)
+
+    @torch.no_grad()
+    def vae_encode(self, h, num_frames=1):
+        """h: encoder output [B, 2*3*ldm_z_channels, H, W] -> DiagonalGaussianDistribution(soft_clamp=True) over [B, C, 3, H*W].
+        num_frames > 1: h is the per-frame output [B*F, ...] (Encoder.forward_frames) and the frame mean is taken first."""
+        r = self._posterior(h, None, num_frames)
+        return DiagonalGaussianDistribution(r['mean'], r['logvar'])
+
+
+class RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout_withSD_D_ditDecoder(_RendererSeams, _PosteriorSeams, nn.Module):
+    grid_ignores_aabb = True
+
     def __init__(self, vit_decoder: DiT2, triplane_decoder: Triplane, cls_token=False, normalize_feat=True,
                  sr_ratio=2, vae_p=2, ldm_z_channels=4, ldm_embed_dim=4, token_size=16, **kwargs):
         super().__init__()
@@ -264,33 +358,7 @@ class RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout
             ret_dict['latent_after_vit'] = nchw
         return ret_dict
 
-    # ------------------------------------------------------------------ posterior (encoder side: vit_triplane.py:912-933, :1152-1199)
-    def _quant_packed(self, dev):
-        q = self.__dict__.get('_quant')
-        if not _cache.fresh(q, dev):
-            qc = self.superresolution['quant_conv']
-            q = _cache.stamp({'device': dev, 'w': f32(qc.weight.reshape(qc.weight.shape[0], -1), dev), 'b': f32(qc.bias, dev)}, self)
-            self.__dict__['_quant'] = q
-        return q
-
-    def _posterior(self, h, eps, num_frames):
-        if not h.is_cuda:
-            raise RuntimeError("ln3diff_amd posterior runs on the HIP device only (no CPU fallback)")
-        if h.shape[0] % num_frames:
-            raise ValueError(f"posterior input batch {h.shape[0]} is not a multiple of num_frames={num_frames}")
-        q = self._quant_packed(h.device)
-        B = h.shape[0] // num_frames
-        if eps is not None:
-            eps = eps.to(h.device, torch.float32).reshape(B, self.ldm_embed_dim, 3, -1).contiguous()
-        return ops.mv_posterior(h, q['w'], q['b'], eps, B, num_frames, self.ldm_embed_dim)
-
-    @torch.no_grad()
-    def vae_encode(self, h, num_frames=1):
-        """h: encoder output [B, 2*3*ldm_z_channels, H, W] -> DiagonalGaussianDistribution(soft_clamp=True) over [B, C, 3, H*W].
-        num_frames > 1: h is the per-frame output [B*F, ...] (Encoder.forward_frames) and the frame mean is taken first."""
-        r = self._posterior(h, None, num_frames)
-        return DiagonalGaussianDistribution(r['mean'], r['logvar'])
-
+    # ------------------------------------------------------------------ encoder side (the posterior itself: _PosteriorSeams)
     @torch.no_grad()
     def vae_reparameterization(self, latent, sample_posterior, eps=None, num_frames=1):
         """latent: encoder output [B, 24, 32, 32] (any strides with a uniform pixel stride; num_frames > 1: the per-frame output of
@@ -312,56 +380,6 @@ class RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout
         ret_dict = self.vae_reparameterization(latent, sample_posterior, eps=eps, num_frames=num_frames)
         tok = self.vit_decode_backbone(ret_dict, img_size)
         return self.vit_decode_postprocess(tok, ret_dict)
-
-    @torch.no_grad()
-    def triplane_decode(self, vit_decode_out, c, return_raw_only=False, **kwargs):
-        if isinstance(vit_decode_out, dict):
-            pcl = vit_decode_out.get('planes_channel_last')
-            planes = vit_decode_out.get('latent_after_vit')
-        else:
-            pcl, planes = None, vit_decode_out
-            vit_decode_out = dict(latent_normalized=planes)
-        if pcl is not None:
-            V = c.shape[0]
-            idx = kwargs.pop('plane_index', None)
-            if idx is None:
-                assert pcl.shape[0] in (V, 1)
-                idx = torch.arange(V, device=c.device, dtype=torch.int32) if pcl.shape[0] == V else \
-                    torch.zeros(V, device=c.device, dtype=torch.int32)
-            ret = self.triplane_decoder(c=c, planes_channel_last=pcl, plane_index=idx, **kwargs)
-        else:
-            ret = self.triplane_decoder(planes, c, **kwargs)
-        ret.update({'latent_after_vit': planes, **vit_decode_out})
-        return ret
-
-    @torch.no_grad()
-    def triplane_renderer(self, latent, coordinates, directions=None):
-        """decoder output at explicit points (vit/vit_triplane.py:377-388 -> renderer.run_model): latent = tri-planes
-        [B,96,H,W] / dict, coordinates [B,P,3] -> {'rgb': [B,P,3], 'sigma': [B,P,1]} (directions are unused by OSGDecoder)."""
-        if isinstance(latent, dict):
-            pcl = latent.get('planes_channel_last')
-            if pcl is None:
-                pcl = self.triplane_decoder.to_channel_last(latent['latent_after_vit'])
-        else:
-            pcl = self.triplane_decoder.to_channel_last(latent)
-        return self.forward_points(pcl, coordinates)
-
-    @torch.no_grad()
-    def forward_points(self, planes_channel_last, points, chunk_size=2 ** 16):
-        outs = [self.triplane_decoder.query_points(planes_channel_last[n], points[n]) for n in range(points.shape[0])]
-        return {k: torch.stack([o[k] for o in outs], 0) for k in outs[0]}
-
-    @torch.no_grad()
-    def triplane_decode_grid(self, vit_decode_out, grid_size, aabb=None, **kwargs):
-        pcl = vit_decode_out.get('planes_channel_last')
-        if pcl is None:
-            pcl = self.triplane_decoder.to_channel_last(vit_decode_out['latent_after_vit'])
-        N = pcl.shape[0]
-        lo, hi = self.rendering_kwargs['sampler_bbox_min'], self.rendering_kwargs['sampler_bbox_max']
-        ax = torch.linspace(lo, hi, grid_size, device=pcl.device)
-        pts = torch.stack(torch.meshgrid(ax, ax, ax, indexing='ij'), dim=-1).reshape(1, -1, 3).expand(N, -1, -1)
-        f = self.forward_points(pcl, pts)
-        return {k: v.reshape(N, grid_size, grid_size, grid_size, -1) for k, v in f.items()}
 
 
 def __getattr__(name):

@@ -23,6 +23,10 @@ L = h * h = 256 tokens per plane, z = 4: latent [B, 3z = 12, 16, 16] -> [B, 3L =
                    x   = x0 + lrelu(rollout_groupconv3x3(x0))     (plane i reads [x_i | row means of i+1 | column means of i+2])
                  each one launch of the fused implicit-GEMM kernel ln3d_conv3x3_rollout_bf16 per object (C = 128, then C = 32).
 
+The class derives from vit_triplane_shapenet._DinoTriplaneDecoderBase and supplies its `superresolution` entries, its packing, one
+fusion block (_group) and the two convolutions (_conv_sr); the per-plane DINOv2 block is dit_models_xformers.vit_block_hip with
+_res_gemm as its projection onto the residual stream.
+
 Not built: the encoder side (vae_reparameterization, vit_decode: ldm_downsample / quant_conv / quant_mlp / after_vit_conv exist as
 parameters so that checkpoints load strictly, their behaviour raises NotImplementedError), Triplane.superresolution (--sr_training
 False; `sr_w_code = w_avg` is carried in the dict and nothing reads it), background tri-planes.  pos_embed is created as zeros (the
@@ -33,11 +37,11 @@ element.
 import torch
 import torch.nn as nn
 
-from .. import ops, _cache
-from ..dit.dit_models_xformers import Workspace, bf16, f32
+from .. import ops
+from ..dit.dit_models_xformers import bf16, f32
 from ..nsr.triplane import Triplane
-from .vit_triplane_shapenet import (RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn as _ShapeNet, DinoVisionTransformer, dinov2_vitb14,  # noqa: F401
-                                    _XYGridAttn, _RollOutConv3D, _RENDERING_BASE)
+from .vit_triplane_shapenet import (_DinoTriplaneDecoderBase, DinoVisionTransformer, dinov2_vitb14,  # noqa: F401 (dinov2_vitb14: the launcher's)
+                                    _XYGridAttn, _RollOutConv3D, _RENDERING_BASE, _ln, _pack_dino)
 
 CLASS_NAME = 'VAE_LDM_V4_vit3D_v3_conv3D_depth2_xformer_mha_PEinit_2d_sincos_uvit_RodinRollOutConv_4x4_lite_mlp_unshuffle_4XC_final'
 
@@ -91,94 +95,45 @@ class RodinConv3D4X_lite_mlp_as_residual(nn.Module):
 
 
 # ----------------------------------------------------------------------------- the decoder class
-class VAE_LDM_V4_vit3D_v3_conv3D_depth2_xformer_mha_PEinit_2d_sincos_uvit_RodinRollOutConv_4x4_lite_mlp_unshuffle_4XC_final(nn.Module):
+def _pair(w, dev):                               # (bf16(w), bf16(w - bf16(w))): see _res_gemm
+    w = w.detach().float()
+    hi = w.to(torch.bfloat16)
+    return bf16(hi, dev), bf16(w - hi.float(), dev)
+
+
+class VAE_LDM_V4_vit3D_v3_conv3D_depth2_xformer_mha_PEinit_2d_sincos_uvit_RodinRollOutConv_4x4_lite_mlp_unshuffle_4XC_final(_DinoTriplaneDecoderBase):
     def __init__(self, vit_decoder: DinoVisionTransformer, triplane_decoder: Triplane, cls_token=False, use_fusion_blk=True,
                  fusion_blk_depth=2, channel_multiplier=4, fusion_blk=TriplaneFusionBlockv3, ldm_z_channels=4, ldm_embed_dim=4, vae_p=1,
                  **kwargs):
-        super().__init__()
-        assert not cls_token and fusion_blk_depth == 2
-        self.cls_token, self.vae_p, self.token_size, self.plane_n = cls_token, vae_p, 16, 3
-        self.ldm_z_channels, self.ldm_embed_dim, self.channel_multiplier = ldm_z_channels, ldm_embed_dim, channel_multiplier
-        self.superresolution = nn.ModuleDict({})
-        self.vit_decoder, self.triplane_decoder = vit_decoder, triplane_decoder
-        self.patch_size = vit_decoder.patch_size
-        D = vit_decoder.embed_dim
-        out_chans = getattr(triplane_decoder, "out_chans", 3 * triplane_decoder.decoder_in_chans)     # --out_chans 96
-        self.unpatchify_out_chans = out_chans
-        self.decoder_pred = nn.Linear(D, 4 ** 2 * int(out_chans // 3 * channel_multiplier))
-        self.vit_decoder.pos_embed = nn.Parameter(torch.zeros(1, 3 * self.token_size ** 2, D))
-        blks = vit_decoder.blocks
-        assert len(blks) == 12, 'ViT-B by default'
-        nh = blks[0].attn.num_heads
-        self.vit_decoder.blocks = nn.ModuleList([fusion_blk(blks[i:i + fusion_blk_depth], nh, D, use_fusion_blk)
-                                                 for i in range(0, len(blks), fusion_blk_depth)])
-        self.register_buffer('w_avg', torch.zeros([512]))
-        self.rendering_kwargs = triplane_decoder.rendering_kwargs
+        super().__init__(vit_decoder, triplane_decoder, cls_token, use_fusion_blk, fusion_blk_depth, fusion_blk, channel_multiplier,
+                         ldm_z_channels, ldm_embed_dim, vae_p)
+
+    def _sr_modules(self, D, out_chans):
+        vae_p, z, cm = self.vae_p, self.ldm_z_channels, self.channel_multiplier
         quant_mlp = nn.Module()                         # vision_transformer.Mlp(2z, out_features = 2 * embed): fc1 2z -> 2z, fc2
-        quant_mlp.fc1, quant_mlp.fc2 = nn.Linear(2 * ldm_z_channels, 2 * ldm_z_channels), nn.Linear(2 * ldm_z_channels, 2 * ldm_embed_dim)
-        self.superresolution.update(dict(
+        quant_mlp.fc1, quant_mlp.fc2 = nn.Linear(2 * z, 2 * z), nn.Linear(2 * z, 2 * self.ldm_embed_dim)
+        return dict(
             after_vit_conv=nn.Conv2d(2 * out_chans, 2 * out_chans, 3, padding=1),
             quant_conv=nn.Conv2d(2 * out_chans, 2 * out_chans, 1),
-            ldm_downsample=nn.Linear(384, vae_p * vae_p * 3 * ldm_z_channels * 2),
-            ldm_upsample=nn.Linear(vae_p * vae_p * ldm_z_channels, D),
+            ldm_downsample=nn.Linear(384, vae_p * vae_p * 3 * z * 2),
+            ldm_upsample=nn.Linear(vae_p * vae_p * z, D),
             quant_mlp=quant_mlp,
-            conv_sr=RodinConv3D4X_lite_mlp_as_residual(int(out_chans * channel_multiplier), int(out_chans))))
-        self.reparameterization_soft_clamp = True
-        for blk in self.vit_decoder.blocks[len(self.vit_decoder.blocks) // 2:]:       # create_uvit_arch
-            blk.skip_linear = nn.Linear(2 * D, D)
-            nn.init.constant_(blk.skip_linear.weight, 0)
-            nn.init.constant_(blk.skip_linear.bias, 0)
-        self._packed = None
-        self._ws = None
-        _cache.watch(self)
-
-    def _apply(self, fn, *a, **k):
-        _cache.bump()
-        return super()._apply(fn, *a, **k)
-
-    # the renderer seams are the ShapeNet class's
-    triplane_renderer = _ShapeNet.triplane_renderer
-    forward_points = _ShapeNet.forward_points
-    triplane_decode = _ShapeNet.triplane_decode
-    triplane_decode_grid = _ShapeNet.triplane_decode_grid
+            conv_sr=RodinConv3D4X_lite_mlp_as_residual(int(out_chans * cm), int(out_chans)))
 
     # ------------------------------------------------------------------ packing
-    def _ensure_packed(self, dev):
-        if _cache.fresh(self._packed, dev):
-            return
-        vd, sr = self.vit_decoder, self.superresolution
-        D = vd.embed_dim
-        P = {'device': dev, 'D': D, 'H': vd.blocks[0].vit_blks[0].attn.num_heads}
+    _res_w = staticmethod(_pair)             # with _res_gemm below
+
+    def _pack_group(self, fb, dev):
+        ca = fb.fusion
+        return {'vit': [_pack_dino(b, dev, self._res_w) for b in fb.vit_blks],
+                'ca_n': _ln(ca.norm1, dev), 'ca_qkv_w': bf16(torch.cat([ca.attn.wq.weight, ca.attn.w_kv.weight], 0), dev),
+                'ca_qkv_b': f32(torch.cat([ca.attn.wq.bias, ca.attn.w_kv.bias], 0), dev),
+                'ca_o_w': self._res_w(ca.attn.proj.weight, dev), 'ca_o_b': f32(ca.attn.proj.bias, dev)}
+
+    def _pack(self, P, dev):
+        sr = self.superresolution
         P['up_w32'], P['up_b'] = f32(sr['ldm_upsample'].weight, dev), f32(sr['ldm_upsample'].bias, dev)
-        P['pos'] = f32(vd.pos_embed.reshape(-1), dev)
-        ln = lambda m: (f32(m.weight, dev), f32(m.bias, dev))
-
-        def pair(w):                             # (bf16(w), bf16(w - bf16(w))): see _res_gemm
-            w = w.detach().float()
-            hi = w.to(torch.bfloat16)
-            return bf16(hi, dev), bf16(w - hi.float(), dev)
-
-        def dino(b):
-            return {'n1': ln(b.norm1), 'qkv_w': bf16(b.attn.qkv.weight, dev), 'qkv_b': f32(b.attn.qkv.bias, dev),
-                    'o_w': pair(b.attn.proj.weight), 'o_b': f32(b.attn.proj.bias, dev), 'ls1': f32(b.ls1.gamma, dev),
-                    'n2': ln(b.norm2), 'fc1_w': bf16(b.mlp.fc1.weight, dev), 'fc1_b': f32(b.mlp.fc1.bias, dev),
-                    'fc2_w': pair(b.mlp.fc2.weight), 'fc2_b': f32(b.mlp.fc2.bias, dev), 'ls2': f32(b.ls2.gamma, dev)}
-        P['blocks'] = []
-        for fb in vd.blocks:
-            ca = fb.fusion
-            q = {'vit': [dino(b) for b in fb.vit_blks],
-                 'ca_n': ln(ca.norm1), 'ca_qkv_w': bf16(torch.cat([ca.attn.wq.weight, ca.attn.w_kv.weight], 0), dev),
-                 'ca_qkv_b': f32(torch.cat([ca.attn.wq.bias, ca.attn.w_kv.bias], 0), dev),
-                 'ca_o_w': pair(ca.attn.proj.weight), 'ca_o_b': f32(ca.attn.proj.bias, dev)}
-            if hasattr(fb, 'skip_linear'):
-                w = fb.skip_linear.weight
-                q['skip_wx'], q['skip_ws'] = pair(w[:, :D]), pair(w[:, D:])
-                q['skip_b'] = f32(fb.skip_linear.bias, dev)
-            P['blocks'].append(q)
-        P['norm'] = ln(vd.norm)
-        P['dp_w'], P['dp_b'] = bf16(self.decoder_pred.weight, dev), f32(self.decoder_pred.bias, dev)
         cs = sr['conv_sr']
-        P['sc_w'], P['sc_b'] = bf16(cs.short_cut.weight, dev), f32(cs.short_cut.bias, dev)
 
         def rollout_conv(conv):                  # [Cout, 3C, 3, 3] groups = 3 -> [3, Cout/3, 27C] in (ky, kx, part, c) order
             w = conv.weight.detach().float()
@@ -186,9 +141,6 @@ class VAE_LDM_V4_vit3D_v3_conv3D_depth2_xformer_mha_PEinit_2d_sincos_uvit_RodinR
             return bf16(w.permute(0, 2, 3, 1).reshape(3, g, 9 * w.shape[1]), dev), f32(conv.bias.reshape(3, g), dev)
         P['c0'] = rollout_conv(cs.conv3D_0.roll_out_convs)
         P['c1'] = rollout_conv(cs.conv3D_1.roll_out_convs)
-        P['zeros'] = torch.zeros(D, device=dev)
-        self._packed = _cache.stamp(P, self)
-        self._ws = Workspace(dev)
 
     # ------------------------------------------------------------------ ViT pieces
     @staticmethod
@@ -197,38 +149,20 @@ class VAE_LDM_V4_vit3D_v3_conv3D_depth2_xformer_mha_PEinit_2d_sincos_uvit_RodinR
         launches of the GEMM.  The projections that write the residual stream (attention proj, fc2, the fusion proj, skip_linear) are
         carried this way: measured on the released size with synthetic weights, rounding every ViT weight to one bf16 accounts for
         4.1e-3 of the 4.9e-3 rel-L2 between a single-bf16 path and fp32 at the ViT output (all activation roundings together 2.7e-3),
-        and the rounding of these projections lands on the stream directly.  The ShapeNet class keeps single-bf16 weights."""
+        and the rounding of these projections lands on the stream directly.  The ShapeNet class keeps single-bf16 weights (the base
+        class's one-launch _res_gemm)."""
         ops.gemm(a, w[0], bias, ops.EPI_GATE_RES, x, **gate)
         ops.gemm(a, w[1], None, ops.EPI_GATE_RES, x, **gate)
 
-    def _mlp(self, x, q, M, D):
-        ws, P = self._ws, self._packed
-        h = ws.get('h', (M, D), torch.bfloat16)
-        ops.norm_modulate(x, h, M, D, kind=0, eps=1e-6, weight=q['n2'][0], shift=q['n2'][1], scale=P['zeros'], mod_rows=M, mod_ld=0)
-        f1 = ws.get('f1', (M, q['fc1_w'].shape[0]), torch.bfloat16)
-        ops.gemm(h, q['fc1_w'], q['fc1_b'], ops.EPI_GELU_ERF, f1)
-        self._res_gemm(f1, q['fc2_w'], q['fc2_b'], x, gate=q['ls2'], gate_rows=M, gate_ld=0)
+    def _group(self, x, q, B, N, H):
+        for qb in q['vit']:
+            self._plane_block(x, qb, B, N, H)
+        self._fusion(x, q, B, N, H)
 
-    def _plane_block(self, x, q, B, N, D, H):
-        """DINOv2 block over each plane's N tokens (objects x planes = B*3 attention batches), as the ShapeNet class's."""
-        ws, P = self._ws, self._packed
-        M, Dh = B * 3 * N, D // H
-        npad = (N + 63) // 64 * 64
-        h = ws.get('h', (M, D), torch.bfloat16)
-        ops.norm_modulate(x, h, M, D, kind=0, eps=1e-6, weight=q['n1'][0], shift=q['n1'][1], scale=P['zeros'], mod_rows=M, mod_ld=0)
-        qq = ws.get('q', (B * 3, H, npad, Dh), torch.bfloat16, zero=True)
-        kk = ws.get('k', (B * 3, H, npad, Dh), torch.bfloat16, zero=True)
-        vt = ws.get('vt', (B * 3, H, Dh, npad), torch.bfloat16, zero=True)
-        o = ws.get('o', (M, D), torch.bfloat16)
-        ops.gemm(h, q['qkv_w'], q['qkv_b'], ops.EPI_HEADS, qq, kk, vt, M=M, tokens=N, tok_pad=npad, heads=H, head_dim=Dh, transpose_mask=0b100)
-        ops.attention(qq, kk, vt, o, B * 3, H, N, npad, N, npad, Dh, scale=Dh ** -0.5)
-        self._res_gemm(o, q['o_w'], q['o_b'], x, gate=q['ls1'], gate_rows=M, gate_ld=0)
-        self._mlp(x, q, M, D)
-
-    def _fusion(self, x, q, B, N, D, H):
+    def _fusion(self, x, q, B, N, H):
         """Conv3DCrossAttentionBlockXformerMHA, has_mlp False: x += proj(axis_attn([wq ; w_kv] norm1(x)))."""
         ws, P = self._ws, self._packed
-        M = B * 3 * N
+        M, D = x.shape
         h = ws.get('h', (M, D), torch.bfloat16)
         ops.norm_modulate(x, h, M, D, kind=0, eps=1e-6, weight=q['ca_n'][0], shift=q['ca_n'][1], scale=P['zeros'], mod_rows=M, mod_ld=0)
         qkv = ws.get('ca_qkv', (M, 3 * D), torch.float32)
@@ -236,6 +170,23 @@ class VAE_LDM_V4_vit3D_v3_conv3D_depth2_xformer_mha_PEinit_2d_sincos_uvit_RodinR
         o = ws.get('o', (M, D), torch.bfloat16)
         ops.triplane_axis_attention(qkv, o, B, int(round(N ** 0.5)), H, scale=(D // H) ** -0.5)
         self._res_gemm(o, q['ca_o_w'], q['ca_o_b'], x)
+
+    def _conv_sr(self, up, res, planes_cl, B, r, R, Cm, Co):
+        """Both roll-out convolutions as one launch of the fused implicit-GEMM kernel per object; names the stage 'x0' [B, 3, R, R, 32]."""
+        ws, P = self._ws, self._packed
+        N = B * 3
+        rowm = ws.get('rowm0', (B, 3, R, Cm), torch.float32)
+        colm = ws.get('colm0', (B, 3, R, Cm), torch.float32)
+        ops.rollout_means(up, rowm, colm, N, R, R, Cm)
+        x0 = ws.get('x0', (B, 3, R, R, Co), torch.float32)
+        for b in range(B):
+            ops.conv3x3_rollout(up[b], rowm[b], colm[b], P['c0'][0], P['c0'][1], res[b], x0[b], R, R, Cm, Co, 0.01)
+        rowm1 = ws.get('rowm1', (B, 3, R, Co), torch.float32)
+        colm1 = ws.get('colm1', (B, 3, R, Co), torch.float32)
+        ops.rollout_means(x0, rowm1, colm1, N, R, R, Co)
+        for b in range(B):
+            ops.conv3x3_rollout(x0[b], rowm1[b], colm1[b], P['c1'][0], P['c1'][1], x0[b], planes_cl[b], R, R, Co, Co, 0.01)
+        return {'x0': x0}
 
     # ------------------------------------------------------------------ reference-named stages
     @torch.no_grad()
@@ -269,92 +220,6 @@ class VAE_LDM_V4_vit3D_v3_conv3D_depth2_xformer_mha_PEinit_2d_sincos_uvit_RodinR
         tok = self._ws.get('up_out', (B * L, D), torch.float32)
         ops.gemm(xb, P['up_wp'], P['up_b'], ops.EPI_F32, tok)
         return self.forward_vit_decoder(tok.view(B, L, D), img_size)
-
-    @torch.no_grad()
-    def forward_vit_decoder(self, x, img_size=None):
-        """x [B, 3*256, D] (ldm_upsample output) -> + pos_embed -> 6 fusion blocks with UViT skips -> norm; returns f32 [B, 3*256, D].
-        `stage_hook(name, tensor)`, when set on the instance, sees the token state after each fusion block (tests)."""
-        if not x.is_cuda:
-            raise RuntimeError("ln3diff_amd decoder runs on the HIP device only (no CPU fallback)")
-        self._ensure_packed(x.device)
-        P, ws = self._packed, self._ws
-        B, L, D = x.shape
-        H, N, M = P['H'], L // 3, B * L
-        h = ws.get('x', (M, D), torch.float32)
-        ops.add_table_rows(x.contiguous().float(), P['pos'], h, 1, B, L * D)
-        blocks = P['blocks']
-        hook = self.__dict__.get('stage_hook')
-        skips = []
-
-        def push():
-            s = ws.get(f'skip{len(skips)}', (M, D), torch.bfloat16)
-            ops.cast_bf16(h, s)
-            skips.append(s)
-        push()
-        for j, q in enumerate(blocks):
-            if j >= len(blocks) // 2:
-                xb = ws.get('skip_x', (M, D), torch.bfloat16)
-                ops.cast_bf16(h, xb)
-                self._res_gemm(xb, q['skip_wx'], q['skip_b'], h)
-                self._res_gemm(skips.pop(), q['skip_ws'], None, h)
-            for qb in q['vit']:
-                self._plane_block(h, qb, B, N, D, H)
-            self._fusion(h, q, B, N, D, H)
-            if j < len(blocks) // 2 - 1:
-                push()
-            if hook is not None:
-                hook(f'blk{j}', h.view(B, L, D))
-        out = torch.empty(B, L, D, device=x.device, dtype=torch.float32)
-        ops.layernorm_f32(h, P['norm'][0], P['norm'][1], out, M, D, 1e-6)
-        return out
-
-    @torch.no_grad()
-    def vit_decode_postprocess(self, latent_from_vit, ret_dict: dict, want_nchw=True, return_stages=False):
-        """decoder_pred -> unpatchify_triplane (p = 4) -> conv_sr.  Adds 'planes_channel_last' [B, 3, R, R, 32] (the renderer's layout),
-        'latent_after_vit' [B, 96, R, R] (want_nchw), 'sr_w_code' and 'cls_token' (None) to ret_dict; return_stages also adds
-        'decoder_pred' [B, 768, 2048], the low-resolution planes 'planes_lowres' [B, 3, 64, 64, 128] and 'x0' [B, 3, R, R, 32]
-        (channel-last)."""
-        P, ws = self._packed, self._ws
-        B, L, D = latent_from_vit.shape
-        dev = latent_from_vit.device
-        cs = self.superresolution['conv_sr']
-        S, p, Cm = self.token_size, 4, P['dp_w'].shape[0] // 16
-        r, R, Co = S * p, cs.input_resolution, cs.out_chans // 3
-        N = B * 3
-        xb = ws.get('tok_bf', (B * L, D), torch.bfloat16)
-        ops.cast_bf16(latent_from_vit.contiguous(), xb)
-        pred = ws.get('pred', (B * L, 16 * Cm), torch.float32)
-        ops.gemm(xb, P['dp_w'], P['dp_b'], ops.EPI_F32, pred)
-        lo = ws.get('lo', (N, r, r, Cm), torch.float32)
-        mixed = ws.get('mixed', (N * r * r, Cm), torch.bfloat16)
-        ops.sr_unpatchify(pred, lo, mixed, B, S, p, Cm)
-        res = ws.get('res', (B, 3, r, r, Co), torch.float32)
-        ops.gemm(mixed, P['sc_w'], P['sc_b'], ops.EPI_F32, res)
-        up = ws.get('up', (B, 3, R, R, Cm), torch.bfloat16)
-        ops.resize_bilinear_cl(lo, up, N, r, r, R, R, Cm, transpose=True)
-        rowm = ws.get('rowm0', (B, 3, R, Cm), torch.float32)
-        colm = ws.get('colm0', (B, 3, R, Cm), torch.float32)
-        ops.rollout_means(up, rowm, colm, N, R, R, Cm)
-        x0 = ws.get('x0', (B, 3, R, R, Co), torch.float32)
-        for b in range(B):
-            ops.conv3x3_rollout(up[b], rowm[b], colm[b], P['c0'][0], P['c0'][1], res[b], x0[b], R, R, Cm, Co, 0.01)
-        rowm1 = ws.get('rowm1', (B, 3, R, Co), torch.float32)
-        colm1 = ws.get('colm1', (B, 3, R, Co), torch.float32)
-        ops.rollout_means(x0, rowm1, colm1, N, R, R, Co)
-        planes_cl = torch.empty(B, 3, R, R, Co, device=dev, dtype=torch.float32)
-        for b in range(B):
-            ops.conv3x3_rollout(x0[b], rowm1[b], colm1[b], P['c1'][0], P['c1'][1], x0[b], planes_cl[b], R, R, Co, Co, 0.01)
-        ret_dict.update(dict(cls_token=None, planes_channel_last=planes_cl,
-                             sr_w_code=self.w_avg.reshape(1, 1, -1).expand(B, 1, self.w_avg.numel())))
-        if want_nchw:
-            nchw = torch.empty(B, 3 * Co, R, R, device=dev, dtype=torch.float32)
-            ops.planes_to_nchw(planes_cl, nchw, B, Co, R, R)
-            ret_dict['latent_after_vit'] = nchw
-        if return_stages:
-            ret_dict['decoder_pred'] = pred.view(B, L, -1).clone()
-            ret_dict['planes_lowres'] = lo.view(B, 3, r, r, Cm).clone()
-            ret_dict['x0'] = x0.clone()
-        return ret_dict
 
     # ------------------------------------------------------------------ the encoder side is not part of this package
     def vae_reparameterization(self, latent, sample_posterior=True, **kwargs):

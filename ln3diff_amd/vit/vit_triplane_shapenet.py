@@ -19,6 +19,11 @@ Network (launchers: --arch_decoder vitb, DINOv2 ViT-B/14 from torch.hub, --out_c
                    x   = x0 + lrelu(rollout_groupconv3x3(x0))     (plane i reads [x_i | row means of i+1 | column means of i+2])
 Everything runs channel-last; the convolutions are im2col gathers + the MFMA GEMM, one object plane at a time.
 
+This module also holds what this class shares with the FFHQ decoder class (vit_triplane_ffhq.py): the DINOv2 parameter containers and
+`_DinoTriplaneDecoderBase` (constructor, packing, forward_vit_decoder, head and tail of vit_decode_postprocess).  The per-plane DINOv2
+block is dit_models_xformers.vit_block_hip, the MLP half of the cross-plane block its vit_mlp_hip; the renderer and posterior seams
+are the mixins of vit_triplane.py.
+
 Not built: the encoder side (`ldm_downsample` is applied by vae_reparameterization, the ShapeNet VAE encoder itself is not part of
 this package), Triplane.superresolution (every launcher passes --sr_training False; `sr_w_code = w_avg` is carried in the dict and
 nothing reads it).  Batches decode each object independently; the reference's batched cross-plane attention re-orders query rows
@@ -28,10 +33,9 @@ import torch
 import torch.nn as nn
 
 from .. import ops, _cache
-from ..dit.dit_models_xformers import Workspace, bf16, f32
+from ..dit.dit_models_xformers import Workspace, bf16, f32, gate_res_gemm, vit_block_hip, vit_mlp_hip
 from ..nsr.triplane import Triplane
-from .vit_triplane import PatchEmbedTriplane, DiagonalGaussianDistribution, \
-    RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout_withSD_D_ditDecoder as _Objv
+from .vit_triplane import PatchEmbedTriplane, DiagonalGaussianDistribution, _RendererSeams, _PosteriorSeams
 
 # nsr/script_util.py rendering_options_defaults with the defaults of encoder_and_nsr_defaults() + loss_defaults() (c_scale 1,
 # density_reg 0, density_reg_p_dist 0.004, reg_type 'l1'), and the --cfg presets of the ShapeNet launchers (:679-700).  The
@@ -165,13 +169,35 @@ class RodinConv3D4X_lite_mlp_as_residual_lite(nn.Module):
         self.short_cut = nn.Linear(in_chans // 3, out_chans // 3)
 
 
-# ----------------------------------------------------------------------------- the decoder class
-class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(nn.Module):
-    def __init__(self, vit_decoder: DinoVisionTransformer, triplane_decoder: Triplane, cls_token=False, use_fusion_blk=True,
-                 fusion_blk_depth=2, fusion_blk=TriplaneFusionBlockv4_nested_init_from_dino, channel_multiplier=4, ldm_z_channels=4,
-                 ldm_embed_dim=4, vae_p=2, **kwargs):
+# ----------------------------------------------------------------------------- what the two DINO-based decoder classes share
+def _ln(m, dev):
+    return f32(m.weight, dev), f32(m.bias, dev)
+
+
+def _pack_mlp(b, dev, res_w=bf16):
+    """MLP half of a DINOv2 block as vit_mlp_hip's operands; res_w packs the weight of the GEMM that writes the residual stream."""
+    return {'n2': _ln(b.norm2, dev), 'fc1_w': bf16(b.mlp.fc1.weight, dev), 'fc1_b': f32(b.mlp.fc1.bias, dev),
+            'fc2_w': res_w(b.mlp.fc2.weight, dev), 'fc2_b': f32(b.mlp.fc2.bias, dev), 'ls2': f32(b.ls2.gamma, dev)}
+
+
+def _pack_dino(b, dev, res_w=bf16):
+    """A whole DINOv2 block as vit_block_hip's operands."""
+    return {'n1': _ln(b.norm1, dev), 'qkv_w': bf16(b.attn.qkv.weight, dev), 'qkv_b': f32(b.attn.qkv.bias, dev),
+            'o_w': res_w(b.attn.proj.weight, dev), 'o_b': f32(b.attn.proj.bias, dev), 'ls1': f32(b.ls1.gamma, dev), **_pack_mlp(b, dev, res_w)}
+
+
+class _DinoTriplaneDecoderBase(_RendererSeams, nn.Module):
+    """Latent tokens -> DINOv2 blocks in fusion groups with UViT long skips -> decoder_pred -> unpatchify -> conv_sr -> tri-planes.
+    A subclass gives its `superresolution` entries (_sr_modules), packs its token embedding, fusion groups and conv_sr convolutions
+    (_pack, _pack_group), runs one fusion group (_group) and the two convolutions of conv_sr (_conv_sr); `_res_w` / `_res_gemm` are how
+    it carries and applies the weights of the projections that write the residual stream."""
+    _res_w = staticmethod(bf16)
+    _res_gemm = staticmethod(gate_res_gemm)
+
+    def __init__(self, vit_decoder, triplane_decoder, cls_token, use_fusion_blk, fusion_blk_depth, fusion_blk, channel_multiplier,
+                 ldm_z_channels, ldm_embed_dim, vae_p):
         super().__init__()
-        assert not cls_token and vae_p == 2 and fusion_blk_depth == 2
+        assert not cls_token and fusion_blk_depth == 2
         self.cls_token, self.vae_p, self.token_size, self.plane_n = cls_token, vae_p, 16, 3
         self.ldm_z_channels, self.ldm_embed_dim, self.channel_multiplier = ldm_z_channels, ldm_embed_dim, channel_multiplier
         self.superresolution = nn.ModuleDict({})
@@ -189,11 +215,7 @@ class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(nn.Module):
                                                  for i in range(0, len(blks), fusion_blk_depth)])
         self.register_buffer('w_avg', torch.zeros([512]))
         self.rendering_kwargs = triplane_decoder.rendering_kwargs
-        self.superresolution.update(dict(
-            ldm_downsample=nn.Linear(384, vae_p * vae_p * 3 * ldm_z_channels * 2),
-            ldm_upsample=PatchEmbedTriplane(vae_p * self.token_size, vae_p, 3 * ldm_embed_dim, D),
-            quant_conv=nn.Conv2d(2 * 3 * ldm_z_channels, 2 * ldm_embed_dim * 3, kernel_size=1, groups=3),
-            conv_sr=RodinConv3D4X_lite_mlp_as_residual_lite(int(out_chans * channel_multiplier), int(out_chans))))
+        self.superresolution.update(self._sr_modules(D, out_chans))
         self.reparameterization_soft_clamp = True
         for blk in self.vit_decoder.blocks[len(self.vit_decoder.blocks) // 2:]:       # create_uvit_arch
             blk.skip_linear = nn.Linear(2 * D, D)
@@ -207,127 +229,37 @@ class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(nn.Module):
         _cache.bump()
         return super()._apply(fn, *a, **k)
 
-    # the posterior (encoder side) and the renderer seams are the Objaverse class's: same quant_conv / soft clamp / tri-plane gather
-    _quant_packed = _Objv._quant_packed
-    _posterior = _Objv._posterior
-    vae_encode = _Objv.vae_encode
-    triplane_renderer = _Objv.triplane_renderer
-    forward_points = _Objv.forward_points
-
     # ------------------------------------------------------------------ packing
     def _ensure_packed(self, dev):
         if _cache.fresh(self._packed, dev):
             return
-        vd, sr = self.vit_decoder, self.superresolution
+        vd, cs = self.vit_decoder, self.superresolution['conv_sr']
         D = vd.embed_dim
-        P = {'device': dev, 'D': D, 'H': vd.blocks[0].vit_blks[0].attn.num_heads}
-        P['pe_w'], P['pe_b'] = f32(sr['ldm_upsample'].proj.weight, dev), f32(sr['ldm_upsample'].proj.bias, dev)
-        P['pos'] = f32(vd.pos_embed.reshape(-1), dev)
-        ln = lambda m: (f32(m.weight, dev), f32(m.bias, dev))
-
-        def mlp_part(b):
-            return {'n2': ln(b.norm2), 'fc1_w': bf16(b.mlp.fc1.weight, dev), 'fc1_b': f32(b.mlp.fc1.bias, dev),
-                    'fc2_w': bf16(b.mlp.fc2.weight, dev), 'fc2_b': f32(b.mlp.fc2.bias, dev), 'ls2': f32(b.ls2.gamma, dev)}
-        P['pairs'] = []
+        P = {'device': dev, 'D': D, 'H': vd.blocks[0].vit_blks[0].attn.num_heads, 'pos': f32(vd.pos_embed.reshape(-1), dev), 'groups': []}
         for fb in vd.blocks:
-            b0, b1 = fb.vit_blks[0], fb.vit_blks[1]
-            q0 = {'n1': ln(b0.norm1), 'qkv_w': bf16(b0.attn.qkv.weight, dev), 'qkv_b': f32(b0.attn.qkv.bias, dev),
-                  'o_w': bf16(b0.attn.proj.weight, dev), 'o_b': f32(b0.attn.proj.bias, dev), 'ls1': f32(b0.ls1.gamma, dev), **mlp_part(b0)}
-            ca = b1.attn
-            g1 = b1.ls1.gamma.detach().float()
-            q1 = {'n1': ln(b1.norm1), 'n1g': (f32(b1.norm1.weight.detach().float() * g1, dev), f32(b1.norm1.bias.detach().float() * g1, dev)),
-                  'ca_n': ln(ca.norm1), 'qkv_w': bf16(torch.cat([ca.attn.wq.weight, ca.attn.w_kv.weight], 0), dev),
-                  'qkv_b': f32(torch.cat([ca.attn.wq.bias, ca.attn.w_kv.bias], 0), dev),
-                  'o_w': bf16(ca.attn.proj.weight, dev), 'o_b': f32(ca.attn.proj.bias, dev), 'ls1': f32(g1, dev), **mlp_part(b1)}
-            q = {'b0': q0, 'b1': q1}
+            q = self._pack_group(fb, dev)
             if hasattr(fb, 'skip_linear'):
                 w = fb.skip_linear.weight
-                q['skip_wx'], q['skip_ws'] = bf16(w[:, :D], dev), bf16(w[:, D:], dev)
+                q['skip_wx'], q['skip_ws'] = self._res_w(w[:, :D], dev), self._res_w(w[:, D:], dev)
                 q['skip_b'] = f32(fb.skip_linear.bias, dev)
-            P['pairs'].append(q)
-        P['norm'] = ln(vd.norm)
+            P['groups'].append(q)
+        P['norm'] = _ln(vd.norm, dev)
         P['dp_w'], P['dp_b'] = bf16(self.decoder_pred.weight, dev), f32(self.decoder_pred.bias, dev)
-        cs = sr['conv_sr']
         P['sc_w'], P['sc_b'] = bf16(cs.short_cut.weight, dev), f32(cs.short_cut.bias, dev)
-
-        def group_conv(conv):                    # [Cout, Cin/3, 3, 3] groups = 3 -> per group [Cout/3, Kpad] in (ky, kx, c) order
-            w = conv.weight.detach().float()
-            g = w.shape[0] // 3
-            k = 9 * w.shape[1]
-            kpad = (k + 63) // 64 * 64
-            out = []
-            for d in range(3):
-                m = torch.zeros(g, kpad)
-                m[:, :k] = w[d * g:(d + 1) * g].permute(0, 2, 3, 1).reshape(g, k).cpu()
-                out.append((bf16(m, dev), f32(conv.bias[d * g:(d + 1) * g], dev)))
-            return out, kpad
-        P['c0'], P['c0_kpad'] = group_conv(cs.conv3D_0.roll_out_inplane_conv)
-        P['c1'], P['c1_kpad'] = group_conv(cs.conv3D_1.roll_out_convs)
         P['zeros'] = torch.zeros(D, device=dev)
+        self._pack(P, dev)
         self._packed = _cache.stamp(P, self)
         self._ws = Workspace(dev)
 
     # ------------------------------------------------------------------ ViT pieces
-    def _mlp(self, x, q, M, D):
-        ws, P = self._ws, self._packed
-        h = ws.get('h', (M, D), torch.bfloat16)
-        ops.norm_modulate(x, h, M, D, kind=0, eps=1e-6, weight=q['n2'][0], shift=q['n2'][1], scale=P['zeros'], mod_rows=M, mod_ld=0)
-        f1 = ws.get('f1', (M, q['fc1_w'].shape[0]), torch.bfloat16)
-        ops.gemm(h, q['fc1_w'], q['fc1_b'], ops.EPI_GELU_ERF, f1)
-        ops.gemm(f1, q['fc2_w'], q['fc2_b'], ops.EPI_GATE_RES, x, gate=q['ls2'], gate_rows=M, gate_ld=0)
-
-    def _plane_block(self, x, q, B, N, D, H):
+    def _plane_block(self, x, q, B, N, H):
         """DINOv2 block over each plane's N tokens (objects x planes = B*3 attention batches)."""
-        ws, P = self._ws, self._packed
-        M, Dh = B * 3 * N, D // H
-        npad = (N + 63) // 64 * 64
-        h = ws.get('h', (M, D), torch.bfloat16)
-        ops.norm_modulate(x, h, M, D, kind=0, eps=1e-6, weight=q['n1'][0], shift=q['n1'][1], scale=P['zeros'], mod_rows=M, mod_ld=0)
-        qq = ws.get('q', (B * 3, H, npad, Dh), torch.bfloat16, zero=True)
-        kk = ws.get('k', (B * 3, H, npad, Dh), torch.bfloat16, zero=True)
-        vt = ws.get('vt', (B * 3, H, Dh, npad), torch.bfloat16, zero=True)
-        o = ws.get('o', (M, D), torch.bfloat16)
-        ops.gemm(h, q['qkv_w'], q['qkv_b'], ops.EPI_HEADS, qq, kk, vt, M=M, tokens=N, tok_pad=npad, heads=H, head_dim=Dh, transpose_mask=0b100)
-        ops.attention(qq, kk, vt, o, B * 3, H, N, npad, N, npad, Dh, scale=Dh ** -0.5)
-        ops.gemm(o, q['o_w'], q['o_b'], ops.EPI_GATE_RES, x, gate=q['ls1'], gate_rows=M, gate_ld=0)
-        self._mlp(x, q, M, D)
-
-    def _cross_block(self, x, q, B, N, D, H):
-        """DINOv2 block whose attention is the nested cross-plane block: x += ls1 * (n + proj(axis_attn(norm1'(n)))), n = norm1(x)."""
-        ws, P = self._ws, self._packed
-        M = B * 3 * N
-        n = ws.get('n', (M, D), torch.float32)
-        r = ws.get('r', (M, D), torch.float32)
-        ops.layernorm_f32(x, q['n1'][0], q['n1'][1], n, M, D, 1e-6)
-        ops.layernorm_f32(x, q['n1g'][0], q['n1g'][1], r, M, D, 1e-6)           # ls1 * n: the inner block's residual, gated
-        h = ws.get('h', (M, D), torch.bfloat16)
-        ops.norm_modulate(n, h, M, D, kind=0, eps=1e-6, weight=q['ca_n'][0], shift=q['ca_n'][1], scale=P['zeros'], mod_rows=M, mod_ld=0)
-        qkv = ws.get('ca_qkv', (M, 3 * D), torch.float32)
-        ops.gemm(h, q['qkv_w'], q['qkv_b'], ops.EPI_F32, qkv)
-        o = ws.get('o', (M, D), torch.bfloat16)
-        ops.triplane_axis_attention(qkv, o, B, int(round(N ** 0.5)), H, scale=(D // H) ** -0.5)
-        ops.gemm(o, q['o_w'], q['o_b'], ops.EPI_GATE_RES, x, gate=q['ls1'], gate_rows=1, gate_ld=0, res_bias=r, res_bias_ld=D)
-        self._mlp(x, q, M, D)
-
-    # ------------------------------------------------------------------ reference-named stages
-    @torch.no_grad()
-    def vit_decode_backbone(self, latent, img_size=None):
-        if isinstance(latent, dict):
-            latent = latent['latent_normalized_2Ddiffusion']
-        if not latent.is_cuda:
-            raise RuntimeError("ln3diff_amd decoder runs on the HIP device only (no CPU fallback)")
-        self._ensure_packed(latent.device)
-        B = latent.shape[0]
-        D, S = self._packed['D'], self.vae_p * self.token_size
-        L = 3 * self.token_size ** 2
-        raw = self._ws.get('pe_raw', (B * L, D), torch.float32)
-        ops.patch_embed_triplane(latent.contiguous().float(), self._packed['pe_w'], self._packed['pe_b'],
-                                 self._ws.get('pe_silu', (B * L, D), torch.bfloat16), raw, B, self.ldm_embed_dim, S, self.vae_p, D)
-        return self.forward_vit_decoder(raw.view(B, L, D), img_size)
+        vit_block_hip(self._ws, x, q, B * 3, N, H, self._packed['zeros'], 1e-6, ops.EPI_GELU_ERF, res_gemm=self._res_gemm)
 
     @torch.no_grad()
     def forward_vit_decoder(self, x, img_size=None):
-        """x [B, 3*256, D] (ldm_upsample output) -> + pos_embed -> 6 block pairs with UViT skips -> norm; returns f32 [B, 3*256, D]."""
+        """x [B, 3*256, D] (ldm_upsample output) -> + pos_embed -> 6 fusion groups with UViT skips -> norm; returns f32 [B, 3*256, D].
+        `stage_hook(name, tensor)`, when set on the instance, sees the token state after each fusion group (tests)."""
         if not x.is_cuda:
             raise RuntimeError("ln3diff_amd decoder runs on the HIP device only (no CPU fallback)")
         self._ensure_packed(x.device)
@@ -336,7 +268,8 @@ class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(nn.Module):
         H, N, M = P['H'], L // 3, B * L
         h = ws.get('x', (M, D), torch.float32)
         ops.add_table_rows(x.contiguous().float(), P['pos'], h, 1, B, L * D)
-        pairs = P['pairs']
+        groups = P['groups']
+        hook = self.__dict__.get('stage_hook')
         skips = []
 
         def push():
@@ -344,16 +277,17 @@ class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(nn.Module):
             ops.cast_bf16(h, s)
             skips.append(s)
         push()
-        for j, q in enumerate(pairs):
-            if j >= len(pairs) // 2:
+        for j, q in enumerate(groups):
+            if j >= len(groups) // 2:
                 xb = ws.get('skip_x', (M, D), torch.bfloat16)
                 ops.cast_bf16(h, xb)
-                ops.gemm(xb, q['skip_wx'], q['skip_b'], ops.EPI_GATE_RES, h)
-                ops.gemm(skips.pop(), q['skip_ws'], None, ops.EPI_GATE_RES, h)
-            self._plane_block(h, q['b0'], B, N, D, H)
-            self._cross_block(h, q['b1'], B, N, D, H)
-            if j < len(pairs) // 2 - 1:
+                self._res_gemm(xb, q['skip_wx'], q['skip_b'], h)
+                self._res_gemm(skips.pop(), q['skip_ws'], None, h)
+            self._group(h, q, B, N, H)
+            if j < len(groups) // 2 - 1:
                 push()
+            if hook is not None:
+                hook(f'blk{j}', h.view(B, L, D))
         out = torch.empty(B, L, D, device=x.device, dtype=torch.float32)
         ops.layernorm_f32(h, P['norm'][0], P['norm'][1], out, M, D, 1e-6)
         return out
@@ -362,7 +296,8 @@ class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(nn.Module):
     def vit_decode_postprocess(self, latent_from_vit, ret_dict: dict, want_nchw=True, return_stages=False):
         """decoder_pred -> unpatchify_triplane (p = 4) -> conv_sr.  Adds 'planes_channel_last' [B, 3, R, R, 32] (the renderer's layout),
         'latent_after_vit' [B, 96, R, R] (want_nchw), 'sr_w_code' and 'cls_token' (None) to ret_dict; return_stages also adds
-        'decoder_pred' [B, 768, 2048] and the low-resolution planes 'planes_lowres' [B, 3, 64, 64, 128] (channel-last)."""
+        'decoder_pred' [B, 768, 2048], the low-resolution planes 'planes_lowres' [B, 3, 64, 64, 128] (channel-last) and whatever stages
+        the class's _conv_sr names."""
         P, ws = self._packed, self._ws
         B, L, D = latent_from_vit.shape
         dev = latent_from_vit.device
@@ -377,10 +312,99 @@ class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(nn.Module):
         lo = ws.get('lo', (N, r, r, Cm), torch.float32)
         mixed = ws.get('mixed', (N * r * r, Cm), torch.bfloat16)
         ops.sr_unpatchify(pred, lo, mixed, B, S, p, Cm)
-        res = ws.get('res', (N, r, r, Co), torch.float32)
+        res = ws.get('res', (B, 3, r, r, Co), torch.float32)
         ops.gemm(mixed, P['sc_w'], P['sc_b'], ops.EPI_F32, res)
-        up = ws.get('up', (N, R, R, Cm), torch.bfloat16)
+        up = ws.get('up', (B, 3, R, R, Cm), torch.bfloat16)
         ops.resize_bilinear_cl(lo, up, N, r, r, R, R, Cm, transpose=True)
+        planes_cl = torch.empty(B, 3, R, R, Co, device=dev, dtype=torch.float32)
+        stages = self._conv_sr(up, res, planes_cl, B, r, R, Cm, Co)
+        ret_dict.update(dict(cls_token=None, planes_channel_last=planes_cl,
+                             sr_w_code=self.w_avg.reshape(1, 1, -1).expand(B, 1, self.w_avg.numel())))
+        if want_nchw:
+            nchw = torch.empty(B, 3 * Co, R, R, device=dev, dtype=torch.float32)
+            ops.planes_to_nchw(planes_cl, nchw, B, Co, R, R)
+            ret_dict['latent_after_vit'] = nchw
+        if return_stages:
+            ret_dict['decoder_pred'] = pred.view(B, L, -1).clone()
+            ret_dict['planes_lowres'] = lo.view(B, 3, r, r, Cm).clone()
+            ret_dict.update({k: v.clone() for k, v in stages.items()})
+        return ret_dict
+
+
+# ----------------------------------------------------------------------------- the decoder class
+class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(_PosteriorSeams, _DinoTriplaneDecoderBase):
+    def __init__(self, vit_decoder: DinoVisionTransformer, triplane_decoder: Triplane, cls_token=False, use_fusion_blk=True,
+                 fusion_blk_depth=2, fusion_blk=TriplaneFusionBlockv4_nested_init_from_dino, channel_multiplier=4, ldm_z_channels=4,
+                 ldm_embed_dim=4, vae_p=2, **kwargs):
+        assert vae_p == 2
+        super().__init__(vit_decoder, triplane_decoder, cls_token, use_fusion_blk, fusion_blk_depth, fusion_blk, channel_multiplier,
+                         ldm_z_channels, ldm_embed_dim, vae_p)
+
+    def _sr_modules(self, D, out_chans):
+        vae_p, z, cm = self.vae_p, self.ldm_z_channels, self.channel_multiplier
+        return dict(
+            ldm_downsample=nn.Linear(384, vae_p * vae_p * 3 * z * 2),
+            ldm_upsample=PatchEmbedTriplane(vae_p * self.token_size, vae_p, 3 * self.ldm_embed_dim, D),
+            quant_conv=nn.Conv2d(2 * 3 * z, 2 * self.ldm_embed_dim * 3, kernel_size=1, groups=3),
+            conv_sr=RodinConv3D4X_lite_mlp_as_residual_lite(int(out_chans * cm), int(out_chans)))
+
+    # ------------------------------------------------------------------ packing
+    def _pack_group(self, fb, dev):
+        b0, b1 = fb.vit_blks[0], fb.vit_blks[1]
+        ca = b1.attn
+        g1 = b1.ls1.gamma.detach().float()
+        q1 = {'n1': _ln(b1.norm1, dev), 'n1g': (f32(b1.norm1.weight.detach().float() * g1, dev), f32(b1.norm1.bias.detach().float() * g1, dev)),
+              'ca_n': _ln(ca.norm1, dev), 'qkv_w': bf16(torch.cat([ca.attn.wq.weight, ca.attn.w_kv.weight], 0), dev),
+              'qkv_b': f32(torch.cat([ca.attn.wq.bias, ca.attn.w_kv.bias], 0), dev),
+              'o_w': bf16(ca.attn.proj.weight, dev), 'o_b': f32(ca.attn.proj.bias, dev), 'ls1': f32(g1, dev), **_pack_mlp(b1, dev)}
+        return {'b0': _pack_dino(b0, dev), 'b1': q1}
+
+    def _pack(self, P, dev):
+        sr = self.superresolution
+        P['pe_w'], P['pe_b'] = f32(sr['ldm_upsample'].proj.weight, dev), f32(sr['ldm_upsample'].proj.bias, dev)
+        cs = sr['conv_sr']
+
+        def group_conv(conv):                    # [Cout, Cin/3, 3, 3] groups = 3 -> per group [Cout/3, Kpad] in (ky, kx, c) order
+            w = conv.weight.detach().float()
+            g = w.shape[0] // 3
+            k = 9 * w.shape[1]
+            kpad = (k + 63) // 64 * 64
+            out = []
+            for d in range(3):
+                m = torch.zeros(g, kpad)
+                m[:, :k] = w[d * g:(d + 1) * g].permute(0, 2, 3, 1).reshape(g, k).cpu()
+                out.append((bf16(m, dev), f32(conv.bias[d * g:(d + 1) * g], dev)))
+            return out, kpad
+        P['c0'], P['c0_kpad'] = group_conv(cs.conv3D_0.roll_out_inplane_conv)
+        P['c1'], P['c1_kpad'] = group_conv(cs.conv3D_1.roll_out_convs)
+
+    # ------------------------------------------------------------------ ViT pieces
+    def _group(self, x, q, B, N, H):
+        self._plane_block(x, q['b0'], B, N, H)
+        self._cross_block(x, q['b1'], B, N, H)
+
+    def _cross_block(self, x, q, B, N, H):
+        """DINOv2 block whose attention is the nested cross-plane block: x += ls1 * (n + proj(axis_attn(norm1'(n)))), n = norm1(x)."""
+        ws, P = self._ws, self._packed
+        M, D = x.shape
+        n = ws.get('n', (M, D), torch.float32)
+        r = ws.get('r', (M, D), torch.float32)
+        ops.layernorm_f32(x, q['n1'][0], q['n1'][1], n, M, D, 1e-6)
+        ops.layernorm_f32(x, q['n1g'][0], q['n1g'][1], r, M, D, 1e-6)           # ls1 * n: the inner block's residual, gated
+        h = ws.get('h', (M, D), torch.bfloat16)
+        ops.norm_modulate(n, h, M, D, kind=0, eps=1e-6, weight=q['ca_n'][0], shift=q['ca_n'][1], scale=P['zeros'], mod_rows=M, mod_ld=0)
+        qkv = ws.get('ca_qkv', (M, 3 * D), torch.float32)
+        ops.gemm(h, q['qkv_w'], q['qkv_b'], ops.EPI_F32, qkv)
+        o = ws.get('o', (M, D), torch.bfloat16)
+        ops.triplane_axis_attention(qkv, o, B, int(round(N ** 0.5)), H, scale=(D // H) ** -0.5)
+        ops.gemm(o, q['o_w'], q['o_b'], ops.EPI_GATE_RES, x, gate=q['ls1'], gate_rows=1, gate_ld=0, res_bias=r, res_bias_ld=D)
+        vit_mlp_hip(ws, x, q, P['zeros'], 1e-6, ops.EPI_GELU_ERF)
+
+    def _conv_sr(self, up, res, planes_cl, B, r, R, Cm, Co):
+        """Both 3x3 group convolutions as im2col gathers + the MFMA GEMM, one object plane at a time."""
+        P, ws = self._packed, self._ws
+        N = B * 3
+        up = up.view(N, R, R, Cm)
         t = ws.get('t', (N, R * R, Co), torch.float32)
         col = ws.get('col0', (R * R, P['c0_kpad']), torch.bfloat16)
         for n in range(N):
@@ -398,18 +422,24 @@ class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(nn.Module):
                 w, bias = P['c1'][i]
                 ops.im2col3x3_rollout(x0[b], rowm[b], colm[b], col, i, R, R, Co, P['c1_kpad'])
                 ops.gemm(col, w, bias, ops.EPI_F32, t[b * 3 + i])
-        planes_cl = torch.empty(B, 3, R, R, Co, device=dev, dtype=torch.float32)
         ops.resize_add_lrelu(x0, t, planes_cl, N, R, R, R, R, Co, 0.01)
-        ret_dict.update(dict(cls_token=None, planes_channel_last=planes_cl,
-                             sr_w_code=self.w_avg.reshape(1, 1, -1).expand(B, 1, self.w_avg.numel())))
-        if want_nchw:
-            nchw = torch.empty(B, 3 * Co, R, R, device=dev, dtype=torch.float32)
-            ops.planes_to_nchw(planes_cl, nchw, B, Co, R, R)
-            ret_dict['latent_after_vit'] = nchw
-        if return_stages:
-            ret_dict['decoder_pred'] = pred.view(B, L, -1).clone()
-            ret_dict['planes_lowres'] = lo.view(B, 3, r, r, Cm).clone()
-        return ret_dict
+        return {}
+
+    # ------------------------------------------------------------------ reference-named stages
+    @torch.no_grad()
+    def vit_decode_backbone(self, latent, img_size=None):
+        if isinstance(latent, dict):
+            latent = latent['latent_normalized_2Ddiffusion']
+        if not latent.is_cuda:
+            raise RuntimeError("ln3diff_amd decoder runs on the HIP device only (no CPU fallback)")
+        self._ensure_packed(latent.device)
+        B = latent.shape[0]
+        D, S = self._packed['D'], self.vae_p * self.token_size
+        L = 3 * self.token_size ** 2
+        raw = self._ws.get('pe_raw', (B * L, D), torch.float32)
+        ops.patch_embed_triplane(latent.contiguous().float(), self._packed['pe_w'], self._packed['pe_b'],
+                                 self._ws.get('pe_silu', (B * L, D), torch.bfloat16), raw, B, self.ldm_embed_dim, S, self.vae_p, D)
+        return self.forward_vit_decoder(raw.view(B, L, D), img_size)
 
     @torch.no_grad()
     def vae_reparameterization(self, latent, sample_posterior, eps=None):
@@ -444,24 +474,3 @@ class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(nn.Module):
         ret_dict = self.vae_reparameterization(latent, sample_posterior, eps=eps)
         tok = self.vit_decode_backbone(ret_dict, img_size)
         return self.vit_decode_postprocess(tok, ret_dict)
-
-    @torch.no_grad()
-    def triplane_decode(self, vit_decode_out, c, return_raw_only=False, **kwargs):
-        """The reference passes ws = sr_w_code, which only Triplane.superresolution reads (not built: --sr_training False)."""
-        return _Objv.triplane_decode(self, vit_decode_out, c, return_raw_only=return_raw_only, **kwargs)
-
-    @torch.no_grad()
-    def triplane_decode_grid(self, vit_decode_out, grid_size, aabb=None, **kwargs):
-        """vit_triplane.py:290-337: the grid spans sampler_bbox_min / max when the preset has them, else +- box_warp / 2 (ShapeNet)."""
-        pcl = vit_decode_out.get('planes_channel_last')
-        if pcl is None:
-            pcl = self.triplane_decoder.to_channel_last(vit_decode_out['latent_after_vit'])
-        N = pcl.shape[0]
-        rk = self.rendering_kwargs
-        if aabb is not None:
-            raise NotImplementedError("triplane_decode_grid: a per-object aabb is not supported; the preset's box is used")
-        lo, hi = (rk['sampler_bbox_min'], rk['sampler_bbox_max']) if 'sampler_bbox_min' in rk else (-rk['box_warp'] / 2, rk['box_warp'] / 2)
-        ax = torch.linspace(lo, hi, grid_size, device=pcl.device)
-        pts = torch.stack(torch.meshgrid(ax, ax, ax, indexing='ij'), dim=-1).reshape(1, -1, 3).expand(N, -1, -1)
-        f = self.forward_points(pcl, pts)
-        return {k: v.reshape(N, grid_size, grid_size, grid_size, -1) for k, v in f.items()}
