@@ -1,5 +1,5 @@
-"""ctypes binding of libln3d_hip.so (the C ABI of include/ln3d.h, include/ln3d_encoder.h, include/ln3d_shapenet.h, include/ln3d_mx.h, include/ln3d_ffhq.h
-and include/ln3d_planes16.h).
+"""ctypes binding of libln3d_hip.so (the C ABI of include/ln3d.h, include/ln3d_encoder.h, include/ln3d_shapenet.h, include/ln3d_mx.h, include/ln3d_ffhq.h,
+include/ln3d_planes16.h and include/ln3d_normals.h).
 
 There is NO fallback: if the library is missing or a kernel launch fails the product raises.
 """
@@ -30,6 +30,8 @@ SYMBOLS = [
     "ln3d_conv3x3_rollout_bf16", "ln3d_rollout_means_bf16",
     # include/ln3d_planes16.h (the opt-in fp16 tri-plane texels of the ray-marcher and the point query)
     "ln3d_planes_to_channel_last_f16", "ln3d_planes_f32_to_f16", "ln3d_render_triplane_f16", "ln3d_query_points_f16",
+    # include/ln3d_normals.h (sigma gradient at points, surface normals per ray)
+    "ln3d_query_points_grad", "ln3d_query_points_grad_f16", "ln3d_surface_normals", "ln3d_surface_normals_f16",
 ]
 
 EPI_F32, EPI_BF16, EPI_GELU_ERF, EPI_GELU_TANH, EPI_SILU, EPI_GATE_RES, EPI_HEADS, EPI_F32_SILU, EPI_QUICK_GELU, EPI_CROSS_ATTN = range(10)
@@ -81,6 +83,12 @@ class RenderArgs(C.Structure):
                 ("rays_per_view", i32), ("visibility", vp), ("depth_resolution", i32), ("depth_resolution_importance", i32),
                 ("ray_mode", i32), ("ray_start", f32), ("ray_end", f32), ("no_bbox_filter", i32),
                 ("weights", vp), ("all_coords", vp), ("feature_volume", vp)]
+
+
+class NormalsArgs(C.Structure):         # ln3d_normals_args (include/ln3d_normals.h)
+    _fields_ = [("planes", vp), ("H", i32), ("W", i32), ("plane_index", vp), ("cams", vp), ("V", i32), ("res", i32),
+                ("ray_o", vp), ("ray_d", vp), ("rays_per_view", i32), ("dec_w0", vp), ("dec_b0", vp), ("dec_w1", vp), ("dec_b1", vp),
+                ("box_warp", f32), ("depth", vp), ("wsum", vp), ("mask_threshold", f32), ("space", i32), ("normal", vp), ("points", vp)]
 
 
 _lib = None

@@ -26,6 +26,7 @@
 #include "common.h"
 #include "../../include/ln3d.h"
 #include "../../include/ln3d_planes16.h"
+#include "../../include/ln3d_normals.h"
 
 #define NS 64            // samples per pass (coarse == fine == 64, Objaverse preset)
 #define WAVE_LDS_BYTES 8192           // per wave: 64 points x (64 B hi + 64 B lo) feature rows; reused for cdf / merge arrays
@@ -1234,3 +1235,248 @@ extern "C" int ln3d_planes_f32_to_f16(const float* src, void* dst, int64_t n, vo
   hipLaunchKernelGGL(planes_f32_to_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, reinterpret_cast<uint16_t*>(dst), n);
   return ln3d_check_launch();
 }
+
+// ------------------------------------------------------------------ sigma and its gradient, surface normals (include/ln3d_normals.h)
+// One lane per point, everything fp32.  The decoder (layer 1 with its gain, the hidden bias, row 0 of layer 2 with its gain) sits in the
+// workgroup's LDS, 8.5 KB, and every lane of a wave reads the same word of it (a broadcast).  Per point:
+//   pass 1  the 12 taps -> the 32 features f (the marcher's order: ((nw + ne) + sw) + se per plane, plane sum, * 1/3)
+//   decoder h_j = W0_j . f + b0_j;  sigma += w1_j softplus(h_j);  q += w1_j sigmoid(h_j) W0_j   (q = d sigma / d f, 32 values)
+//   pass 2  the 12 taps again (L1 / L2 hits) -> t_k = q . texel_k; per plane d sigma / d ix = (t_ne - t_nw)(1 - wy) + (t_se - t_sw) wy and
+//           d sigma / d iy alike, times d ix / d p = coord_scale * W / 2 (H for iy) and the 1/3 of the plane mean
+// so f and q (64 registers) are all that lives across the decoder, instead of the 32 x 3 Jacobian of the features.
+#define NG_W0 0
+#define NG_B0 2048
+#define NG_W1 2112
+#define NG_B1 2176
+#define NG_FLOATS 2180
+
+__device__ __forceinline__ void stage_grad_decoder(float* dl, const float* w0, const float* b0, const float* w1, const float* b1) {
+  const float g0 = 1.0f / sqrtf(32.0f), g1 = 1.0f / sqrtf(64.0f);        // FullyConnectedLayer weight_gain
+  for (int i = threadIdx.x; i < 2048; i += blockDim.x) dl[NG_W0 + i] = w0[i] * g0;
+  for (int i = threadIdx.x; i < 64; i += blockDim.x) { dl[NG_B0 + i] = b0[i]; dl[NG_W1 + i] = w1[i] * g1; }
+  if (threadIdx.x == 0) dl[NG_B1] = b1[0];
+  __syncthreads();
+}
+
+struct GradTaps {
+  int off[4];            // element offset of channel 0 of the (clamped, always valid) texels nw, ne, sw, se inside the tri-plane
+  bool in[4];            // the tap lies inside the plane (zero padding otherwise)
+  float wx0, wx1, wy0, wy1;
+};
+__device__ __forceinline__ GradTaps grad_taps(float gx, float gy, int H, int W, int pl) {
+  GradTaps t;
+  const float ix = ((gx + 1.f) * W - 1.f) * 0.5f, iy = ((gy + 1.f) * H - 1.f) * 0.5f;
+  const float fx0 = floorf(ix), fy0 = floorf(iy);
+  // everything at or beyond column -2 / W is padding alike: the clamp keeps the conversion and x0 + 1 inside int for huge, infinite
+  // and NaN coordinates (fmaxf drops a NaN), which then have no tap inside
+  const int x0 = (int)fminf(fmaxf(fx0, -2.f), (float)W), y0 = (int)fminf(fmaxf(fy0, -2.f), (float)H);
+  t.wx0 = fx0 + 1.f - ix; t.wx1 = ix - fx0; t.wy0 = fy0 + 1.f - iy; t.wy1 = iy - fy0;
+  const bool xin0 = x0 >= 0 && x0 < W, xin1 = x0 + 1 >= 0 && x0 + 1 < W;
+  const bool yin0 = y0 >= 0 && y0 < H, yin1 = y0 + 1 >= 0 && y0 + 1 < H;
+  const int xc0 = min(max(x0, 0), W - 1), xc1 = min(max(x0 + 1, 0), W - 1);
+  const int yc0 = min(max(y0, 0), H - 1), yc1 = min(max(y0 + 1, 0), H - 1);
+  t.in[0] = xin0 && yin0; t.in[1] = xin1 && yin0; t.in[2] = xin0 && yin1; t.in[3] = xin1 && yin1;
+  const int pb = pl * H * W;
+  t.off[0] = (pb + yc0 * W + xc0) * 32; t.off[1] = (pb + yc0 * W + xc1) * 32;
+  t.off[2] = (pb + yc1 * W + xc0) * 32; t.off[3] = (pb + yc1 * W + xc1) * 32;
+  return t;
+}
+
+// the 32 channels of one texel in registers, in the storage type: binary16 values are widened where they enter a multiply-add
+template <typename TX> struct Texel32;
+template <> struct Texel32<float> {
+  float4 q[8];
+  __device__ __forceinline__ void load(const float* p) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) q[i] = reinterpret_cast<const float4*>(p)[i];
+  }
+  __device__ __forceinline__ float at(int c) const { const float4 v = q[c >> 2]; return (c & 3) == 0 ? v.x : (c & 3) == 1 ? v.y : (c & 3) == 2 ? v.z : v.w; }
+};
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+template <> struct Texel32<_Float16> {
+  f16x8 q[4];
+  __device__ __forceinline__ void load(const _Float16* p) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) q[i] = reinterpret_cast<const f16x8*>(p)[i];
+  }
+  __device__ __forceinline__ float at(int c) const { return (float)q[c >> 3][c & 7]; }
+};
+
+// planes: ONE tri-plane [3, H, W, 32]; (px, py, pz) in world units.  grad = d sigma / d (px, py, pz).
+template <typename TX>
+__device__ __forceinline__ void sigma_grad_point(const TX* __restrict__ planes, int H, int W, float coord_scale, const float* dl,
+                                                 float px, float py, float pz, float& sigma, float grad[3]) {
+  const float s3[3] = {px * coord_scale, py * coord_scale, pz * coord_scale};
+  const float third = 0.333333343267440796f;
+  float f[32];
+#pragma unroll
+  for (int pl = 0; pl < 3; ++pl) {                          // (x,y) (y,z) (z,x)
+    const GradTaps t = grad_taps(s3[pl], s3[(pl + 1) % 3], H, W, pl);
+    const float w[4] = {t.in[0] ? t.wx0 * t.wy0 : 0.f, t.in[1] ? t.wx1 * t.wy0 : 0.f, t.in[2] ? t.wx0 * t.wy1 : 0.f, t.in[3] ? t.wx1 * t.wy1 : 0.f};
+    float s[32];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      Texel32<TX> tx;
+      tx.load(planes + t.off[k]);
+#pragma unroll
+      for (int c = 0; c < 32; ++c) s[c] = k == 0 ? tx.at(c) * w[0] : __builtin_fmaf(tx.at(c), w[k], s[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < 32; ++c) f[c] = pl == 0 ? s[c] : f[c] + s[c];
+  }
+#pragma unroll
+  for (int c = 0; c < 32; ++c) f[c] *= third;
+
+  float sg = dl[NG_B1];
+  float q[32];
+#pragma unroll
+  for (int c = 0; c < 32; ++c) q[c] = 0.f;
+#pragma unroll 1
+  for (int j = 0; j < 64; ++j) {
+    float w[32];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float4 v = reinterpret_cast<const float4*>(dl + NG_W0 + j * 32)[i];
+      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+    float h4[4] = {dl[NG_B0 + j], 0.f, 0.f, 0.f};           // four chains of 8: the FMAs of a chain wait for each other
+#pragma unroll
+    for (int c = 0; c < 32; ++c) h4[c & 3] = __builtin_fmaf(w[c], f[c], h4[c & 3]);
+    const float h = (h4[0] + h4[1]) + (h4[2] + h4[3]);
+    const float w1 = dl[NG_W1 + j];
+    sg = __builtin_fmaf(w1, softplus20_hw(h), sg);
+    // d softplus / d h = sigmoid(h), and 1 on torch's linear branch (h > 20); e = exp(-|h|) <= 1 never overflows
+    const float e = __builtin_amdgcn_exp2f(fabsf(h) * -1.4426950408889634f);
+    const float r = 1.0f / (1.0f + e);
+    const float slope = h > 20.0f ? 1.0f : (h >= 0.f ? r : e * r);
+    const float tq = slope * w1;
+#pragma unroll
+    for (int c = 0; c < 32; ++c) q[c] = __builtin_fmaf(tq, w[c], q[c]);
+  }
+  sigma = sg;
+
+  grad[0] = 0.f; grad[1] = 0.f; grad[2] = 0.f;
+#pragma unroll
+  for (int pl = 0; pl < 3; ++pl) {
+    const GradTaps t = grad_taps(s3[pl], s3[(pl + 1) % 3], H, W, pl);
+    if (!(t.in[0] || t.in[1] || t.in[2] || t.in[3])) continue;          // all padding: the plane contributes exactly 0
+    float d[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      Texel32<TX> tx;
+      tx.load(planes + t.off[k]);
+      float a4[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < 32; ++c) a4[c & 3] = __builtin_fmaf(tx.at(c), q[c], a4[c & 3]);
+      d[k] = t.in[k] ? (a4[0] + a4[1]) + (a4[2] + a4[3]) : 0.f;
+    }
+    const float dsx = (d[1] - d[0]) * t.wy0 + (d[3] - d[2]) * t.wy1;
+    const float dsy = (d[2] - d[0]) * t.wx0 + (d[3] - d[1]) * t.wx1;
+    grad[pl] += dsx * (coord_scale * (float)W * 0.5f * third);
+    grad[(pl + 1) % 3] += dsy * (coord_scale * (float)H * 0.5f * third);
+  }
+}
+
+template <typename TX>
+__global__ __launch_bounds__(256) void query_points_grad_kernel(const TX* planes, int H, int W, float coord_scale, const float* pts, int64_t P,
+                                                                const float* w0, const float* b0, const float* w1, const float* b1,
+                                                                float* sigma, float* grad) {
+  __shared__ __attribute__((aligned(16))) float dl[NG_FLOATS];
+  stage_grad_decoder(dl, w0, b0, w1, b1);
+  const int64_t nt = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += nt) {
+    float sg, g[3];
+    sigma_grad_point<TX>(planes, H, W, coord_scale, dl, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], sg, g);
+    sigma[i] = sg; grad[3 * i] = g[0]; grad[3 * i + 1] = g[1]; grad[3 * i + 2] = g[2];
+  }
+}
+
+template <typename TX>
+static int query_points_grad_t(const void* planes, int H, int W, const float* points, int64_t P, const float* dec_w0, const float* dec_b0,
+                               const float* dec_w1, const float* dec_b1, float box_warp, float* sigma, float* grad, void* stream) {
+  if (!planes || !points || !sigma || !grad || P <= 0) return LN3D_ERR_BAD_ARG;
+  if (!dec_w0 || !dec_b0 || !dec_w1 || !dec_b1 || !planes_ok(H, W, box_warp, (int)sizeof(TX))) return LN3D_ERR_BAD_ARG;
+  int64_t blocks = (P + 255) / 256;
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  hipLaunchKernelGGL(query_points_grad_kernel<TX>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const TX*>(planes),
+                     H, W, (float)(2.0 / (double)box_warp), points, P, dec_w0, dec_b0, dec_w1, dec_b1, sigma, grad);
+  return ln3d_check_launch();
+}
+extern "C" int ln3d_query_points_grad(const float* planes, int H, int W, const float* points, int64_t P, const float* dec_w0,
+                                      const float* dec_b0, const float* dec_w1, const float* dec_b1, float box_warp, float* sigma,
+                                      float* grad, void* stream) {
+  return query_points_grad_t<float>(planes, H, W, points, P, dec_w0, dec_b0, dec_w1, dec_b1, box_warp, sigma, grad, stream);
+}
+extern "C" int ln3d_query_points_grad_f16(const void* planes, int H, int W, const float* points, int64_t P, const float* dec_w0,
+                                          const float* dec_b0, const float* dec_w1, const float* dec_b1, float box_warp, float* sigma,
+                                          float* grad, void* stream) {
+  return query_points_grad_t<_Float16>(planes, H, W, points, P, dec_w0, dec_b0, dec_w1, dec_b1, box_warp, sigma, grad, stream);
+}
+
+// One lane per ray: p = o + (depth / wsum) d on the marcher's own ray, n = -grad sigma / |grad sigma| there.
+template <typename TX>
+__global__ __launch_bounds__(256) void surface_normals_kernel(ln3d_normals_args a, int M, float coord_scale) {
+  __shared__ __attribute__((aligned(16))) float dl[NG_FLOATS];
+  stage_grad_decoder(dl, a.dec_w0, a.dec_b0, a.dec_w1, a.dec_b1);
+  const int64_t nr = (int64_t)a.V * M, nt = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t ray = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; ray < nr; ray += nt) {
+    const int v = (int)(ray / M), pix = (int)(ray % M);
+    float n[3] = {0.f, 0.f, 0.f}, p[3] = {0.f, 0.f, 0.f};
+    const float ws = a.wsum[ray];
+    if (ws >= a.mask_threshold) {                           // false for a NaN
+      float o[3], d[3];
+      if (a.ray_o) {
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) { o[ax] = a.ray_o[3 * ray + ax]; d[ax] = a.ray_d[3 * ray + ax]; }
+      } else {
+        make_ray(a.cams + 25 * v, a.res, pix, o, d);
+      }
+      RAY_FENCE(o, d);
+      const float t = a.depth[ray] / ws;
+#pragma unroll
+      for (int ax = 0; ax < 3; ++ax) p[ax] = o[ax] + t * d[ax];
+      const TX* planes = reinterpret_cast<const TX*>(a.planes) + (int64_t)a.plane_index[v] * 3 * a.H * a.W * 32;
+      float sg, g[3];
+      sigma_grad_point<TX>(planes, a.H, a.W, coord_scale, dl, p[0], p[1], p[2], sg, g);
+      // scaled by the largest component first: the squares can then neither overflow nor all vanish
+      const float m = fmaxf(fmaxf(fabsf(g[0]), fabsf(g[1])), fabsf(g[2]));
+      if (m > 0.f && m <= 3.0e38f && g[0] == g[0] && g[1] == g[1] && g[2] == g[2]) {
+        const float u[3] = {g[0] / m, g[1] / m, g[2] / m};
+        const float inv = -1.0f / sqrtf(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+        n[0] = u[0] * inv; n[1] = u[1] * inv; n[2] = u[2] * inv;
+        if (a.space == 1) {                                 // R^T n, R = the rotation of the view's cam2world
+          const float* c = a.cams + 25 * v;
+          const float w0 = n[0], w1 = n[1], w2 = n[2];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) n[k] = c[k] * w0 + c[4 + k] * w1 + c[8 + k] * w2;
+        }
+      }
+    }
+    float* out = a.normal + (int64_t)v * 3 * M + pix;
+    out[0] = n[0]; out[M] = n[1]; out[2 * (int64_t)M] = n[2];
+    if (a.points) { a.points[3 * ray] = p[0]; a.points[3 * ray + 1] = p[1]; a.points[3 * ray + 2] = p[2]; }
+  }
+}
+
+template <typename TX>
+static int surface_normals_t(const ln3d_normals_args* a, void* stream) {
+  if (!a || !a->planes || !a->plane_index || !a->depth || !a->wsum || !a->normal || !a->dec_w0 || !a->dec_b0 || !a->dec_w1 || !a->dec_b1)
+    return LN3D_ERR_BAD_ARG;
+  if (a->V <= 0 || a->rays_per_view < 0 || (a->res <= 0 && a->rays_per_view <= 0)) return LN3D_ERR_BAD_ARG;
+  if ((a->ray_o != nullptr) != (a->ray_d != nullptr)) return LN3D_ERR_BAD_ARG;
+  if (!a->cams && !a->ray_o) return LN3D_ERR_BAD_ARG;                     // cameras, or explicit rays
+  if ((!a->ray_o || a->rays_per_view == 0) && (a->res <= 0 || a->res > 32768)) return LN3D_ERR_BAD_ARG;   // wherever M = res * res (an int)
+  if (a->rays_per_view > 0 && !a->ray_o && a->rays_per_view != a->res * a->res) return LN3D_ERR_BAD_ARG;
+  if (a->space != 0 && a->space != 1) return LN3D_ERR_BAD_ARG;
+  if (a->space == 1 && !a->cams) return LN3D_ERR_BAD_ARG;                 // the camera frame comes from cams
+  if (!(a->mask_threshold > 0.f && a->mask_threshold <= 1.f)) return LN3D_ERR_BAD_ARG;
+  if (!planes_ok(a->H, a->W, a->box_warp, (int)sizeof(TX))) return LN3D_ERR_BAD_ARG;
+  const int M = a->rays_per_view > 0 ? a->rays_per_view : a->res * a->res;
+  const int64_t nr = (int64_t)a->V * M;
+  int64_t blocks = (nr + 255) / 256;
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  hipLaunchKernelGGL(surface_normals_kernel<TX>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *a, M, (float)(2.0 / (double)a->box_warp));
+  return ln3d_check_launch();
+}
+extern "C" int ln3d_surface_normals(const ln3d_normals_args* a, void* stream) { return surface_normals_t<float>(a, stream); }
+extern "C" int ln3d_surface_normals_f16(const ln3d_normals_args* a, void* stream) { return surface_normals_t<_Float16>(a, stream); }

@@ -99,7 +99,9 @@ def create_argparser(objaverse=True):
         dropout=0.0, mixing_logit_init=-6.0,
         ray_start=0.6, ray_end=1.8,          # nsr/script_util.py triplane_decoder_defaults; read by the ShapeNet decoder class only
         dit_precision='bf16',                # matmul precision of the T23D DiT (no reference counterpart): bf16 or the opt-in mxfp8
-        plane_precision='fp32')              # texel storage of the renderer's tri-planes (no reference counterpart): fp32 or the opt-in fp16
+        plane_precision='fp32',              # texel storage of the renderer's tri-planes (no reference counterpart): fp32 or the opt-in fp16
+        export_mesh_normals=False,           # `vn` records (the density field's outward normals) in the exported meshes; needs --export_mesh
+        save_normal_maps=False)              # normal_sample{i}.npy [V,3,R,R]: world-space surface normal maps next to the frames
     d.update(_IGNORED_DEFAULTS)
     d.update({k: v[0] for k, v in _CHECKED.items()})
     ap = argparse.ArgumentParser(allow_abbrev=False)
@@ -149,6 +151,13 @@ def validate(args):
     plane_prec = getattr(args, 'plane_precision', 'fp32')
     if plane_prec not in PLANE_PRECISIONS:
         raise SystemExit(f"--plane_precision {plane_prec}: expected one of {list(PLANE_PRECISIONS)}")
+    if getattr(args, 'export_mesh_normals', False) and not args.export_mesh:
+        raise SystemExit("--export_mesh_normals true: there is no mesh to put normals into without --export_mesh true")
+    if getattr(args, 'save_normal_maps', False):
+        world = int(os.environ.get('WORLD_SIZE', '1'))
+        if world > 1 and args.num_samples % world != 0:
+            raise SystemExit(f"--save_normal_maps true writes one [V,3,R,R] file per sample, so every rank must render whole samples: "
+                             f"--num_samples {args.num_samples} is not a multiple of the {world} ranks")
     if pixart_t23d and kind != 'flow':
         raise SystemExit("--dit_model_arch DiT-PixelArt-* (DiT_TriLatent_PixelArt) is the flow-matching T23D denoiser: use "
                          "--trainer_name flow_matching")
@@ -445,6 +454,9 @@ def run(args, objaverse=None):
     cond_all, cond_src = res[0], res[1]
     if rank == 0:
         meta = dict(vars(args), conditioning=cond_src, weights={k: (v or 'synthetic') for k, v in weights_from.items()})
+        for k in ('export_mesh_normals', 'save_normal_maps'):        # recorded when set: a run without them writes the args.json it always wrote
+            if not meta[k]:
+                del meta[k]
         with open(os.path.join(args.logdir, 'args.json'), 'w') as f:
             json.dump(meta, f, indent=2)
     P = next(iter(cond_all.values())).shape[0]                                             # the noClip multi-view denoisers take 'concat' only
@@ -495,7 +507,8 @@ def run(args, objaverse=None):
                           unconditional_guidance_scale=args.unconditional_guidance_scale)
 
     def render_fn(latent_all, pairs):                             # this rank's (sample, view) pairs: views are shared out when Bt < world
-        return render_pairs(latent_all, ae, cams, pairs, args.triplane_scaling_divider, resolution=args.image_size, noise_seed=args.seed)
+        return render_pairs(latent_all, ae, cams, pairs, args.triplane_scaling_divider, resolution=args.image_size, noise_seed=args.seed,
+                            return_normals=args.save_normal_maps)
 
     lat_all, frames, pairs = parallel.sharded_step(sample_fn, render_fn, Bt, V, rank, world)
     lo, hi = parallel.shard_range(Bt, rank, world)
@@ -511,7 +524,8 @@ def run(args, objaverse=None):
         grid = ae(latent=d, grid_size=args.mesh_grid, behaviour='triplane_decode_grid')
         for i in range(hi - lo):
             path = os.path.join(args.logdir, f'mesh_sample{lo + i}.obj')
-            mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path)
+            mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path,
+                           normals=args.export_mesh_normals)
             if not os.path.exists(path):
                 mesh_err = f"mesh export of sample {lo + i} produced no file at {path}"
                 break
@@ -522,6 +536,10 @@ def run(args, objaverse=None):
     np.save(os.path.join(args.logdir, f'depth_rank{rank}.npy'), frames['image_depth'].cpu().numpy())
     np.save(os.path.join(args.logdir, f'pairs_rank{rank}.npy'), frames['pair_index'].cpu().numpy())      # [P, 2] = (sample, view) of every frame
     np.save(os.path.join(args.logdir, f'latent_rank{rank}.npy'), lat_all[lo:hi].cpu().numpy())
+    if args.save_normal_maps:                                 # validate(): this rank's pairs are whole samples, views in order
+        nm = frames['image_normal'].cpu().numpy()
+        for j in range(0, nm.shape[0], V):
+            np.save(os.path.join(args.logdir, f"normal_sample{int(frames['pair_index'][j, 0])}.npy"), nm[j:j + V])
     fr = frames['image_raw'].cpu().numpy()
     for j, (smp, view) in enumerate(frames['pair_index'].tolist()):
         if view == 0:

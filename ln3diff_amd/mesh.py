@@ -42,20 +42,32 @@ def rotation_matrix_x(deg):
     return np.array([[1, 0, 0], [0, math.cos(a), -math.sin(a)], [0, math.sin(a), math.cos(a)]], dtype=np.float32)
 
 
-def write_obj(path, v, f, c):
-    """Wavefront .obj with per-vertex colours (what trimesh.Trimesh(vertex_colors=...).export(path, 'obj') writes)."""
+def write_obj(path, v, f, c, n=None):
+    """Wavefront .obj with per-vertex colours (what trimesh.Trimesh(vertex_colors=...).export(path, 'obj') writes).
+    n [Nv,3]: per-vertex normals, written as `vn` records behind the vertices, every face corner then names its own vertex's normal
+    (`f a//a b//b c//c`).  They are the outward normals -grad sigma / |grad sigma| of the density field (0 0 0 where it has none) and do
+    NOT depend on the winding of the faces."""
     with open(path, 'w') as fh:
         for i in range(v.shape[0]):
             fh.write('v %.6f %.6f %.6f %.4f %.4f %.4f\n' % (v[i, 0], v[i, 1], v[i, 2], c[i, 0], c[i, 1], c[i, 2]))
+        if n is None:
+            for t in f:
+                fh.write('f %d %d %d\n' % (t[0] + 1, t[1] + 1, t[2] + 1))
+            return
+        for i in range(n.shape[0]):
+            fh.write('vn %.6f %.6f %.6f\n' % (n[i, 0], n[i, 1], n[i, 2]))
         for t in f:
-            fh.write('f %d %d %d\n' % (t[0] + 1, t[1] + 1, t[2] + 1))
+            fh.write('f %d//%d %d//%d %d//%d\n' % (t[0] + 1, t[0] + 1, t[1] + 1, t[1] + 1, t[2] + 1, t[2] + 1))
 
 
 @torch.no_grad()
-def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes'):
+def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes', normals=False):
     """nsr/train_util_diffusion.py:221-244: iso-surface of the sigma grid at `thr`, vertices mapped to the +-0.45 box, coloured
     by re-querying the tri-plane at the vertices (forward_points), rotated -90 degrees about x.
-    Returns (verts [Nv,3] float32 numpy, faces [Nf,3] int64 numpy, colors [Nv,3] uint8 numpy); writes `path` when given."""
+    Returns (verts [Nv,3] float32 numpy, faces [Nf,3] int64 numpy, colors [Nv,3] uint8 numpy); writes `path` when given.
+    normals (opt-in; no reference counterpart): the query that colours the vertices also returns the field's unit outward normal there
+    (forward_points(with_grad=True), evaluated in box coordinates and rotated with the mesh); the return value is then the 4-tuple
+    (verts, faces, colors, vn [Nv,3] float32 numpy) and the .obj carries `vn` records."""
     sigma = sigma.reshape(grid_size, grid_size, grid_size)
     verts, faces = extract_isosurface(sigma, thr, method)
     vtx = (verts / (grid_size - 1) * 2 - 1) * 0.45                       # g-objaverse scale
@@ -63,19 +75,20 @@ def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0,
     if pcl is None:
         pcl = decoder.triplane_decoder.to_channel_last(dec_out['latent_after_vit'])        # f32, or f16 under set_plane_precision('fp16')
     pcl = pcl[sample_index:sample_index + 1]
-    col = decoder.forward_points(pcl, vtx[None])['rgb'][0] if vtx.shape[0] else vtx
-    colors = (col.clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
+    q = decoder.forward_points(pcl, vtx[None], with_grad=normals) if vtx.shape[0] else {'rgb': vtx[None], 'normal': vtx[None]}
+    colors = (q['rgb'][0].clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
     v = (rotation_matrix_x(-90) @ vtx.cpu().numpy().T).T.astype(np.float32)
     f = faces.cpu().numpy()
+    vn = (rotation_matrix_x(-90) @ q['normal'][0].cpu().numpy().T).T.astype(np.float32) if normals else None
     if path:
-        write_obj(path, v, f, colors.astype(np.float32) / 255.0)
-    return v, f, colors
+        write_obj(path, v, f, colors.astype(np.float32) / 255.0, vn)
+    return (v, f, colors, vn) if normals else (v, f, colors)
 
 
 @torch.no_grad()
-def export_mesh(decoder, dec_out, path, grid_size=192, thr=10.0, sample_index=0):
-    """decoder: the VAE decoder module; dec_out: its vit_decode_postprocess dict.  Writes `path` (.obj)."""
+def export_mesh(decoder, dec_out, path, grid_size=192, thr=10.0, sample_index=0, normals=False):
+    """decoder: the VAE decoder module; dec_out: its vit_decode_postprocess dict.  Writes `path` (.obj), with `vn` records when normals."""
     pcl = dec_out['planes_channel_last'][sample_index:sample_index + 1]
     grid = decoder.triplane_decode_grid({'planes_channel_last': pcl}, grid_size)
-    v, f, _ = mesh_from_grid(decoder, {'planes_channel_last': pcl}, grid['sigma'][0], grid_size, thr, 0, path)
+    v, f = mesh_from_grid(decoder, {'planes_channel_last': pcl}, grid['sigma'][0], grid_size, thr, 0, path, normals=normals)[:2]
     return v.shape[0], f.shape[0]

@@ -130,12 +130,18 @@ class Triplane(nn.Module):
 
     @torch.no_grad()
     def forward(self, planes=None, c=None, neural_rendering_resolution=None, jitter=None, u_fine=None,
-                planes_channel_last=None, plane_index=None, return_debug=False, views_per_call=0, **_):
+                planes_channel_last=None, plane_index=None, return_debug=False, views_per_call=0, return_normals=False,
+                normal_space='world', normal_mask_threshold=0.5, **_):
         """planes [V,96,H,W] (one tri-plane per camera row, as the reference) or
         planes_channel_last [NP,3,H,W,32] f32 or f16 + plane_index [V] (many views of few tri-planes).
         views_per_call: the reference reduces the ray-limit fix-up and the depth clamp range over everything ONE forward() call
         renders; 0 = this call is one such call (reference semantics of Triplane.forward), k = every k consecutive views are
-        (the drivers, which call the reference once per camera, pass 1)."""
+        (the drivers, which call the reference once per camera, pass 1).
+        return_normals (opt-in; no reference counterpart): adds 'image_normal' [V,3,res,res], the unit outward normal -grad sigma /
+        |grad sigma| at each ray's expected-depth surface point o + (depth / wsum) d (depth = 'image_depth', the renderer's clamped
+        output), in normal_space 'world' or 'camera'; 0 where
+        wsum < normal_mask_threshold or the gradient vanishes.  A second launch behind the render on the planes the render read;
+        every other key keeps its bits."""
         res = neural_rendering_resolution or self.neural_rendering_resolution
         self.neural_rendering_resolution = res
         if not c.is_cuda:
@@ -181,6 +187,11 @@ class Triplane(nn.Module):
         ret = {'feature_image': rgb, 'image_raw': rgb, 'image_depth': depth, 'weights_samples': wsum,
                'image_mask': wsum * (1 + 2 * 0.001) - 0.001,
                'shape_synthesized': {'image_depth': depth, 'depth': depth.reshape(V, M, 1)}}
+        if return_normals:
+            nrm = torch.empty(V, 3, res, res, device=dev)
+            ops.surface_normals(planes_channel_last, H, W, pidx, self._decoder_dev(dev), rk['box_warp'], depth, wsum, nrm, cams=cam, res=res,
+                                mask_threshold=normal_mask_threshold, space=normal_space)
+            ret['image_normal'] = nrm
         if return_debug:
             ret['shape_synthesized'].update(coarse_densities=cs.unsqueeze(-1), fine_depths=fd.unsqueeze(-1))
         if details:
@@ -189,15 +200,32 @@ class Triplane(nn.Module):
         return ret
 
     @torch.no_grad()
-    def query_points(self, planes_channel_last_one, points):
+    def query_points(self, planes_channel_last_one, points, with_grad=False):
         """points [P,3] against ONE tri-plane [3,H,W,32] (f32 or f16) -> {'sigma':[P,1],'rgb':[P,3]} (no bbox filter:
-        renderer._run_model as used by forward_points, vit/vit_triplane.py:2026-2041)."""
+        renderer._run_model as used by forward_points, vit/vit_triplane.py:2026-2041).  with_grad (opt-in; no reference counterpart)
+        adds 'sigma_grad' [P,3] = d sigma / d p in world units and 'normal' [P,3] = -sigma_grad / |sigma_grad| (unit, outward; 0 where
+        the gradient is 0 or not finite) from ln3d_query_points_grad; 'sigma' and 'rgb' stay those of ln3d_query_points."""
         dev = points.device
         P = points.shape[0]
         H, W = planes_channel_last_one.shape[-3], planes_channel_last_one.shape[-2]
         sigma = torch.empty(P, 1, device=dev)
         rgb = torch.empty(P, 3, device=dev)
         scal = torch.empty(RENDER_SCRATCH_FLOATS, device=dev)
-        ops.query_points(self.cast_planes(planes_channel_last_one).contiguous(), H, W, points.contiguous().float(), self._decoder_dev(dev),
-                         self.rendering_kwargs['box_warp'], sigma, rgb, scal)
-        return {'sigma': sigma, 'rgb': rgb}
+        pcl, pts, bw = self.cast_planes(planes_channel_last_one).contiguous(), points.contiguous().float(), self.rendering_kwargs['box_warp']
+        ops.query_points(pcl, H, W, pts, self._decoder_dev(dev), bw, sigma, rgb, scal)
+        ret = {'sigma': sigma, 'rgb': rgb}
+        if with_grad:
+            grad = torch.empty(P, 3, device=dev)
+            ops.query_points_grad(pcl, H, W, pts, self._decoder_dev(dev), bw, torch.empty(P, device=dev), grad)
+            ret['sigma_grad'] = grad
+            ret['normal'] = unit_outward(grad)
+        return ret
+
+
+def unit_outward(grad):
+    """-g / |g| per row of [..., 3] (density falls towards the outside); 0 where g is 0 or not finite.  Scaled by the largest component
+    first, like the kernel, so that the squares neither overflow nor vanish."""
+    m = grad.abs().amax(-1, keepdim=True)
+    ok = (m > 0) & torch.isfinite(grad).all(-1, keepdim=True)
+    u = grad / torch.where(ok, m, torch.ones_like(m))
+    return torch.where(ok, -u / u.norm(dim=-1, keepdim=True).clamp(min=0.5), torch.zeros_like(grad))

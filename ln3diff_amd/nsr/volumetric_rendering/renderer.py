@@ -76,13 +76,16 @@ class ImportanceRenderer(nn.Module):
 
     @torch.no_grad()
     def forward(self, planes, decoder, ray_origins, ray_directions, rendering_options, return_meta=False,
-                jitter=None, u_fine=None, planes_channel_last=None, plane_index=None, decoder_weights_dev=None):
+                jitter=None, u_fine=None, planes_channel_last=None, plane_index=None, decoder_weights_dev=None, return_normals=False,
+                normal_mask_threshold=0.5):
         """planes [N, 3, C, H, W] (or [N, 3*C, H, W]); ray_origins / ray_directions [N, M, 3], any M.
         Alternatively planes_channel_last [NP, 3, H, W, 32] + plane_index [N] (many ray bundles over few tri-planes).
         Returns the reference's dict (renderer.py:276-300): feature_samples [N, M, 3], depth_samples [N, M, 1], weights_samples [N, M, 1],
         visibility [N, M, 1], shape_synthesized; with return_meta also weights [N, M, S + NI - 1, 1], all_coords [N, M, S + NI, 3],
         feature_volume [N, M, S + NI, 3] (return_meta needs rendering_options['return_sampling_details_flag'] in the reference - it
-        reads shape_synthesized['coarse_coords'] - and does not here)."""
+        reads shape_synthesized['coarse_coords'] - and does not here).
+        return_normals (opt-in; no reference counterpart): adds normal_samples [N, M, 3], the unit outward world-space normal at each
+        ray's expected-depth surface point (ln3d_surface_normals), 0 where weights_samples < normal_mask_threshold."""
         rk = rendering_options
         check_rendering_options(rk)
         if not ray_origins.is_cuda:
@@ -124,6 +127,12 @@ class ImportanceRenderer(nn.Module):
                             weights=wall, all_coords=call, feature_volume=fvol, **render_call_kwargs(rk))
         ret = {'feature_samples': rgb.permute(0, 2, 1), 'depth_samples': depth, 'weights_samples': wsum,
                'shape_synthesized': {'depth': depth}, 'visibility': vis}
+        if return_normals:
+            nrm = torch.empty(N, 3, M, device=dev)
+            ops.surface_normals(planes_channel_last, H, W, plane_index.to(dev, torch.int32).contiguous(), dec, rk['box_warp'], depth, wsum, nrm,
+                                ray_o=ray_origins.to(torch.float32).contiguous(), ray_d=ray_directions.to(torch.float32).contiguous(),
+                                n_views=N, rays_per_view=M, mask_threshold=normal_mask_threshold)
+            ret['normal_samples'] = nrm.permute(0, 2, 1)
         if return_meta:
             ret.update(all_coords=call, feature_volume=fvol, weights=wall)
         if details:

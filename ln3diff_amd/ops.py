@@ -261,6 +261,34 @@ def query_points(planes_cl, H, W, points, dec, box_warp, sigma, rgb, scalars):
                                       C.c_float(box_warp), _p(sigma), _p(rgb), _p(scalars), _stream()), "query_points")
 
 
+def query_points_grad(planes_cl, H, W, points, dec, box_warp, sigma, grad):
+    """sigma [P] and d sigma / d p [P, 3] of ONE tri-plane [3, H, W, 32] (torch.float32 or torch.float16 texels) at points [P, 3]
+    (include/ln3d_normals.h)."""
+    L.check(_plane_entry(planes_cl, "query_points_grad")(_p(planes_cl), H, W, _p(points), C.c_int64(points.shape[0]), *(_p(t) for t in dec),
+                                                         C.c_float(box_warp), _p(sigma), _p(grad), _stream()), "query_points_grad")
+
+
+NORMAL_SPACES = {'world': 0, 'camera': 1}
+
+
+def surface_normals(planes_cl, H, W, plane_index, dec, box_warp, depth, wsum, normal, cams=None, res=0, ray_o=None, ray_d=None, n_views=None,
+                    rays_per_view=0, mask_threshold=0.5, space='world', points=None):
+    """normal [V, 3, M] at the expected-depth surface point of every ray of a finished render (its depth / wsum [V, M]); the rays are
+    cams [V, 25] + res (generated as the marcher generates them) or explicit ray_o / ray_d [V, M, 3].  space: 'world' or 'camera'
+    (needs cams).  points: optional [V, M, 3] output, the surface points (include/ln3d_normals.h)."""
+    if space not in NORMAL_SPACES:
+        raise ValueError(f"normal space {space!r}: expected one of {sorted(NORMAL_SPACES)}")
+    entry = _plane_entry(planes_cl, "surface_normals")
+    a = L.NormalsArgs()
+    a.planes, a.H, a.W, a.plane_index, a.cams = _p(planes_cl), H, W, _p(plane_index), _p(cams)
+    a.V, a.res = (n_views if n_views is not None else cams.shape[0]), int(res)
+    a.ray_o, a.ray_d, a.rays_per_view = _p(ray_o), _p(ray_d), int(rays_per_view)
+    a.dec_w0, a.dec_b0, a.dec_w1, a.dec_b1 = (_p(t) for t in dec)
+    a.box_warp, a.depth, a.wsum, a.mask_threshold = box_warp, _p(depth), _p(wsum), float(mask_threshold)
+    a.space, a.normal, a.points = NORMAL_SPACES[space], _p(normal), _p(points)
+    L.check(entry(C.byref(a), _stream()), "surface_normals")
+
+
 def groupnorm_swish(x, w, b, y, stats, N, HW, Cc, groups=32, eps=1e-6, swish=True):
     L.check(L.lib().ln3d_groupnorm_swish(_p(x), _p(w), _p(b), _p(y), _p(stats), N, HW, Cc, groups, C.c_float(eps), int(swish),
                                          _stream()), "groupnorm_swish")

@@ -152,8 +152,9 @@ class _RendererSeams:
         return self.forward_points(pcl, coordinates)
 
     @torch.no_grad()
-    def forward_points(self, planes_channel_last, points, chunk_size=2 ** 16):
-        outs = [self.triplane_decoder.query_points(planes_channel_last[n], points[n]) for n in range(points.shape[0])]
+    def forward_points(self, planes_channel_last, points, chunk_size=2 ** 16, with_grad=False):
+        """with_grad: also 'sigma_grad' and 'normal' [B,P,3] (Triplane.query_points)."""
+        outs = [self.triplane_decoder.query_points(planes_channel_last[n], points[n], with_grad=with_grad) for n in range(points.shape[0])]
         return {k: torch.stack([o[k] for o in outs], 0) for k in outs[0]}
 
     @torch.no_grad()
