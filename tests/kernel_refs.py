@@ -10,6 +10,12 @@ Bounds (tests/test_kernel_refs_cpu.py shows that they can fail):
   assert_bf16_close: |y - ref| <= max(1 bf16 ulp of ref, floor_ulps fp32 ulps of scale) for every element, and the fraction of
                      elements with y != bf16_rne(ref) at most max_mismatch (a correct fp32 kernel flips only near rounding ties);
   assert_f32_close:  |y - ref| <= ulps * 2^-23 * scale for every element.
+
+The bf16 GEMM and the fused attention (last section) are held per element too.  fp32 GEMM outputs: c = GEMM_F32_ULPS = 5.74 fp32 ulps of
+scale = sum_k |x w| + |b|, 4 x the worst (1.434) that a sequential and a 16-grouped fp32 restatement of the sum reach on the tests' own
+inputs, never above K; bf16 outputs: assert_bf16_close with floor_ulps = c, at most 1 % of elements off bf16_rne(ref), the erf-GELU
+polynomial's documented 1.5e-4 added; nothing is added for the __expf / tanhf epilogues (their fp32 formulas stay within 2^-10 of a bf16
+ulp of the float64 value, tests/test_gemm_attn_refs_cpu.py).  Attention outputs: 2^-8 * sum_j p_j |v_j| + 1 bf16 ulp (attention_bound).
 """
 import math
 
@@ -497,3 +503,346 @@ def rmsnorm_heads(x, w, eps, true_dim=0):
     td = true_dim or v.shape[-1]
     t = v * ((v * v).sum(-1, keepdim=True) / td + _f32(eps)).rsqrt() * _d(w)
     return t, t.abs()
+
+
+# ================================================================ bf16 GEMM (include/ln3d.h ln3d_gemm_bf16) and fused attention
+# Epilogue numbers of include/ln3d.h (the GPU test asserts that they equal ops.EPI_*).
+EPI_F32, EPI_BF16, EPI_GELU_ERF, EPI_GELU_TANH, EPI_SILU, EPI_GATE_RES, EPI_HEADS, EPI_F32_SILU, EPI_QUICK_GELU, EPI_CROSS_ATTN = range(10)
+
+# fp32 GEMM outputs are held to |y - ref| <= gemm_ulps(K) * 2^-23 * scale, scale = sum_k |x w| + |b| (propagated through the epilogue).
+# GEMM_F32_ULPS = 4 x the worst |y32 - ref| / (2^-23 scale) that two fp32 restatements of the sum reach on the tests' own random inputs
+# (gemm_inputs at every shape of gemm_shapes for the six tile sizes, K in {64, 320, 1024}, and (512, 512, 512)): gemm_f32_sequential adds
+# the exact bf16 x bf16 products one by one in k, gemm_f32_grouped16 adds 16-term partial sums (the grouping of the MFMA 32x32x16) one by
+# one.  Measured worst: 1.434 (sequential, at (512, 512, 512)) and 0.742 (grouped), so c = 4 x 1.434 = 5.74;
+# tests/test_gemm_attn_refs_cpu.py re-measures both at every shape.
+# The factor 4 covers an accumulation order and adder rounding mode that cannot be read off the ISA.  Never above the a-priori cap K: K
+# additions, each off by at most 2^-23 of a partial sum that is at most scale, hold for any order and for truncating adders.
+GEMM_F32_WORST_SEQ = 1.434
+GEMM_F32_WORST_G16 = 0.742
+GEMM_F32_ULPS = 5.74             # c = 4 x 1.434, rounded up
+GELU_ERF_ABS = 1.5e-4            # documented absolute error of the erf polynomial of csrc/common.h (test_gemm_gelu_erf_epilogue_tail)
+ATTN_P_REL = 2.0 ** -8           # attention bound: |o - ref| <= 2^-8 * sum_j p_j |v_j| + 1 bf16 ulp of ref (see attention_bound)
+
+
+def gemm_ulps(K):
+    return min(GEMM_F32_ULPS, float(K))
+
+
+def vt_key_order(n_pad):
+    """ops.vt_key_order on the CPU: position p of every 16-key group of a V^T row holds key p with bits 2 and 3 swapped."""
+    from ln3diff_amd.ops import vt_key_order as order
+    return order(n_pad)
+
+
+def gemm_inputs(M, N, K, seed=0, device=None):
+    """The random-data convention of tests/test_kernels_gpu.py: asymmetric operands (x rows and w columns scaled by index) so that
+    transposes show.  -> x bf16 [M, K], w bf16 [N, K], bias f32 [N] (on the CPU unless device is given)."""
+    g = torch.Generator().manual_seed(1000003 * seed + 4099 * M + 17 * N + K)
+    x = (torch.randn(M, K, generator=g) * (1 + torch.arange(M)[:, None] / M)).to(torch.bfloat16)
+    w = (torch.randn(N, K, generator=g) * 0.05 * (1 + torch.arange(K)[None, :] / K)).to(torch.bfloat16)
+    b = torch.randn(N, generator=g)
+    return tuple(t if device is None else t.to(device) for t in (x, w, b))
+
+
+def gemm_shapes(F, T):
+    """(M, N) at a tile of F features x T tokens: one row, one short of a tile, one past it (a 2 x 2 grid of ragged tiles), and two
+    token tiles less a row."""
+    return [(1, 4), (T - 1, F - 4), (T + 1, F + 4), (2 * T - 1, F)]
+
+
+TILE_SHAPE = {"auto": (128, 128), "s": (128, 128), "x7": (256, 256), "x8": (128, 384), "x9": (256, 192), "x12": (384, 192),
+              "x13": (256, 256), "x14": (128, 192), "x16": (256, 256)}     # LN3D_GEMM_TILE -> features x tokens of the tile it forces
+
+
+def act64(t, epilogue):
+    """The activation of an epilogue in double, and the upper bound of |f'| the scale is multiplied with."""
+    if epilogue == EPI_GELU_ERF:
+        return 0.5 * t * (1 + torch.erf(t / math.sqrt(2.0))), 1.13
+    if epilogue == EPI_GELU_TANH:
+        return 0.5 * t * (1 + torch.tanh(0.7978845608028654 * (t + 0.044715 * t ** 3))), 1.13
+    if epilogue in (EPI_SILU, EPI_F32_SILU):
+        return silu64(t), 1.1
+    if epilogue == EPI_QUICK_GELU:
+        return t * torch.sigmoid(1.702 * t), 1.1
+    return t, 1.0
+
+
+def gemm_lin(x, w, bias):
+    """(sum_k x w + b, sum_k |x w| + |b|) in double"""
+    x, w = _d(x), _d(w)
+    ref, scale = x @ w.t(), x.abs() @ w.abs().t()
+    if bias is not None:
+        ref, scale = ref + _d(bias), scale + _d(bias).abs()
+    return ref, scale
+
+
+def gemm_ref(x, w, bias, epilogue, gate=None, gate_rows=1, res=None, res_bias=None, lin=None):
+    """x bf16 [M, K], w bf16 [N, K], bias f32 [N] or None -> (ref, scale) [M, N] in double of the epilogue's (bf16 or activated)
+    output; for EPI_F32_SILU that is out1 (out0 is the EPI_F32 result).  EPI_GATE_RES: res + gate[m / gate_rows] * (.) +
+    res_bias[m / gate_rows] (gate / res_bias [samples, N] or None).  scale is propagated to first order: times the bound of |f'| for an
+    activation, times |gate| plus |res| and |res_bias| for GATE_RES.  lin: a gemm_lin result to reuse."""
+    ref, scale = lin if lin is not None else gemm_lin(x, w, bias)
+    if epilogue == EPI_GATE_RES:
+        M = ref.shape[0]
+        if gate is not None:
+            g = _d(gate).repeat_interleave(gate_rows, 0)[:M]
+            ref, scale = g * ref, g.abs() * scale
+        ref, scale = ref + _d(res), scale + _d(res).abs()
+        if res_bias is not None:
+            rb = _d(res_bias).repeat_interleave(gate_rows, 0)[:M]
+            ref, scale = ref + rb, scale + rb.abs()
+        return ref, scale
+    out, slope = act64(ref, epilogue)
+    return out, scale * slope
+
+
+def gemm_f32_sequential(x, w, bias):
+    """fp32 restatement: the exact products added one by one in k, then the bias."""
+    xf, wf = x.float(), w.float()
+    acc = torch.zeros(x.shape[0], w.shape[0])
+    for k in range(x.shape[1]):
+        acc += xf[:, k, None] * wf[None, :, k]
+    return acc + bias if bias is not None else acc
+
+
+def gemm_f32_grouped16(x, w, bias):
+    """fp32 restatement: 16-term partial sums (added in order), then added one by one, then the bias."""
+    xf, wf = x.float(), w.float()
+    acc = torch.zeros(x.shape[0], w.shape[0])
+    for k0 in range(0, x.shape[1], 16):
+        part = torch.zeros_like(acc)
+        for k in range(k0, min(k0 + 16, x.shape[1])):
+            part += xf[:, k, None] * wf[None, :, k]
+        acc += part
+    return acc + bias if bias is not None else acc
+
+
+def assert_bf16_close_abs(y, ref, scale, floor_ulps, extra_abs, what="", max_mismatch=0.01):
+    """assert_bf16_close with a documented absolute error of the formula added to every element's bound: |y - ref| <=
+    max(1 bf16 ulp, floor) + extra_abs.  The mismatch fraction is taken over the elements whose bf16 spacing is at least 100 extra_abs
+    (the formula's error moves at most about 1 % of those across a rounding boundary, which the fraction's own 1 % does not notice
+    because it is spent on near-ties)."""
+    yd = y.detach().double().cpu().reshape(-1)
+    rd = ref.detach().double().cpu().reshape(-1)
+    ulp = bf16_ulp(rd)
+    s = torch.as_tensor(scale, dtype=torch.float64).cpu().reshape(-1).expand_as(rd)
+    tol = torch.maximum(ulp, floor_ulps * F32_EPS * s) + extra_abs
+    err = (yd - rd).abs()
+    worst = float((err / tol).max())
+    wide = ulp >= 100 * extra_abs
+    mism = float((yd != bf16_rne(rd))[wide].double().mean()) if bool(wide.any()) else 0.0
+    print(f"[kref] {what}: bf16 worst {worst:.3g} of the bound (+{extra_abs:g} absolute), mismatch {mism:.3g} over {int(wide.sum())} wide elements")
+    bad = ~(err <= tol)
+    if bad.any():
+        i = _where(bad)
+        raise AssertionError(f"{what}: {int(bad.sum())} / {yd.numel()} elements beyond the bound; first at flat index {i}: y {float(yd[i])!r} "
+                             f"ref {float(rd[i])!r} bound {float(tol[i]):.3g}; worst {worst:.3g} of the bound")
+    assert mism <= max_mismatch, f"{what}: mismatch fraction {mism:.4g} > {max_mismatch}"
+    return worst, mism
+
+
+def ulp_dominated(ref, scale, floor_ulps):
+    """True where 1 bf16 ulp of ref is at least the fp32 term floor_ulps * 2^-23 * scale of the bound: there a correct fp32 kernel
+    differs from bf16_rne(ref) only near rounding ties."""
+    return bf16_ulp(ref) >= floor_ulps * F32_EPS * torch.as_tensor(scale, dtype=torch.float64)
+
+
+def heads_split_ref(M, N, tokens, tok_pad, heads, head_dim, head_dim_pad=0, transpose_mask=0):
+    """The layout map of LN3D_EPI_HEADS (include/ln3d.h): column n -> output n / (heads * head_dim), head, dim; row m -> sample
+    m / tokens, token m % tokens.  -> (shapes, which [N], index [M, N], untouched): shapes[w] the shape of out{w} ([B, heads, tok_pad,
+    head_dim_pad], or [B, heads, head_dim_pad, tok_pad] with the tokens of every 16-group in vt_key_order when bit w of transpose_mask
+    is set), index[m, n] the flat position of element (m, n) in out{which[n]}, untouched[w] a boolean tensor over out{w}.reshape(-1)
+    that is True where the GEMM writes nothing (padding rows and columns)."""
+    Dp = head_dim_pad or head_dim
+    B = (M + tokens - 1) // tokens
+    n_out = N // (heads * head_dim)
+    m, n = torch.arange(M)[:, None], torch.arange(N)[None, :]
+    b, t = m // tokens, m % tokens
+    which, h, d = n // (heads * head_dim), (n // head_dim) % heads, n % head_dim
+    order = vt_key_order(tok_pad)
+    nat = ((b * heads + h) * tok_pad + t) * Dp + d
+    tr = ((b * heads + h) * Dp + d) * tok_pad + order[t]
+    transposed = ((transpose_mask >> which) & 1).bool()
+    index = torch.where(transposed, tr, nat)
+    shapes, untouched = [], []
+    for wi in range(n_out):
+        shapes.append((B, heads, Dp, tok_pad) if (transpose_mask >> wi) & 1 else (B, heads, tok_pad, Dp))
+        u = torch.ones(B * heads * tok_pad * Dp, dtype=torch.bool)
+        u[index[:, wi * heads * head_dim:(wi + 1) * heads * head_dim].reshape(-1)] = False
+        untouched.append(u)
+    return shapes, which.reshape(-1), index, untouched
+
+
+def heads_norm_ref(lin, scale, weight, eps, head_dim=64):
+    """RMSNorm over each head of 64 of the fp32 accumulators (+ bias), in double: y_i = x_i * r * w_i, r = rsqrt(mean(x^2) + eps).
+    First order, with s the scale of the linear part: dy_i = w_i (r dx_i + x_i dr), dr = -r^3 sum_j x_j dx_j / 64, and
+    |sum_j x_j dx_j| <= ||x||_2 ||s||_2 <= (8 / r) ||s||_2, so the scale is (s_i + |x_i| r ||s||_2 / 8) * r * |w_i|, plus |y_i| for the
+    roundings of the normalisation itself (as kernel_refs.groupnorm: own term plus the shared statistic's)."""
+    M, W = lin.shape
+    v, s = lin.reshape(M, W // head_dim, head_dim), scale.reshape(M, W // head_dim, head_dim)
+    rstd = ((v * v).mean(-1, keepdim=True) + _f32(eps)).rsqrt()
+    w64 = _d(weight)
+    ref = v * rstd * w64
+    sc = (s + v.abs() * rstd * s.norm(dim=-1, keepdim=True) / 8.0) * rstd * w64.abs() + ref.abs()
+    return ref.reshape(M, W), sc.reshape(M, W)
+
+
+def attention_ref(q, k, v, scale, Nk=None, causal=False, base2=False):
+    """q [B, H, Nq(+), Dh], k / v [B, H, Nk(+), Dh] bf16 in natural key order -> (ref, S) [B, H, Nq, Dh] in double:
+    ref = softmax(scale * q k^T) v over the first Nk keys (query i sees keys <= i when causal), S = softmax(.) |v|.
+    base2: the scores q k^T are already scaled and in the exp2 domain (requantised_query): softmax(ln 2 * q k^T)."""
+    q, k, v = _d(q), _d(k), _d(v)
+    Nk = k.shape[2] if Nk is None else Nk
+    k, v = k[:, :, :Nk], v[:, :, :Nk]
+    s = torch.einsum("bhqd,bhkd->bhqk", q, k) * (math.log(2.0) if base2 else _f32(scale))
+    if causal:
+        keep = torch.arange(Nk)[None, :] <= torch.arange(q.shape[2])[:, None]
+        s = s.masked_fill(~keep, -math.inf)
+    p = torch.softmax(s, -1)
+    return p @ v, p @ v.abs()
+
+
+def attention_bound(ref, S):
+    """|o - ref| <= 2^-8 S + 1 bf16 ulp of ref.  Derived, not measured: every attention kernel rounds the probabilities to bf16 before
+    the P V MFMA (relative error <= 2^-9 each: 2^-9 S) and rounds the output once (half an ulp); both are doubled to cover exp2, the
+    fp32 scale and the re-basing of the online softmax."""
+    return ATTN_P_REL * S + bf16_ulp(ref)
+
+
+def assert_attention_close(o, ref, S, what="", factor=1.0, extra=None):
+    """o bf16 (any shape of ref's size) within factor * attention_bound (+ extra, a per-element term argued from the kernel's arithmetic) of
+    ref.  Returns the worst ratio."""
+    od = o.detach().double().cpu().reshape(-1)
+    rd, tol = ref.reshape(-1), factor * attention_bound(ref, S).reshape(-1)
+    if extra is not None:
+        tol = tol + extra.reshape(-1)
+    assert od.numel() == rd.numel(), (what, od.numel(), rd.numel())
+    err = (od - rd).abs()
+    worst = float((err / tol).max())
+    print(f"[kref] {what}: attention worst {worst:.3g} of the bound")
+    bad = ~(err <= tol)
+    if bad.any():
+        i = _where(bad)
+        raise AssertionError(f"{what}: {int(bad.sum())} / {od.numel()} elements beyond the bound; first at flat index {i}: o {float(od[i])!r} "
+                             f"ref {float(rd[i])!r} bound {float(tol[i]):.3g}; worst {worst:.3g} of the bound")
+    return worst
+
+
+def attention_q_rounding_term(q, k, v, scale, ref, Nk=None):
+    """The term the streaming and the K-resident kernel (attn_stream_kernel, attn_kres_kernel; Dh 64, Nk a multiple of 256) add to
+    attention_bound, from their arithmetic: they fold scale * log2(e) into the query fragment and round it to bf16 a SECOND time
+    (csrc/attention.hip read_q), a relative 2^-9 on every q_d.  Score j is then off by at most
+    d_j = 2^-9 |scale| sum_d |q_d k_jd|, the probabilities become p_j e^(delta_j) / Z with Z = sum_i p_i e^(delta_i) in
+    [e^-D, Zmax], Zmax = sum_i p_i e^(d_i) (Jensen: D = sum p_i d_i <= ln Zmax), so |p'_j / p_j - 1| <= e^(d_j) Zmax - 1 and, because
+    the changes of p sum to zero, |o' - o| <= sum_j p_j (e^(d_j) Zmax - 1) |v_j - o|.  Same shapes as attention_ref's result."""
+    q, k, v = _d(q), _d(k), _d(v)
+    Nk = k.shape[2] if Nk is None else Nk
+    k, v = k[:, :, :Nk], v[:, :, :Nk]
+    sc = _f32(scale)
+    p = torch.softmax(torch.einsum("bhqd,bhkd->bhqk", q, k) * sc, -1)
+    d = torch.einsum("bhqd,bhkd->bhqk", q.abs(), k.abs()) * abs(sc) * 2.0 ** -9
+    zmax = (p * d.exp()).sum(-1, keepdim=True)
+    wgt = p * (d.exp() * zmax - 1)                                                   # [B, H, Nq, Nk]
+    return torch.einsum("bhqk,bhqkd->bhqd", wgt, (v[:, :, None] - ref[:, :, :, None]).abs())
+
+
+def attention_inputs(B, H, Nq, Nk, Dh, seed=0, dh_pad=None, pad_value=0.0):
+    """Random attention operands by the convention of tests/test_kernels_gpu.py: q, k ~ 1.5 N(0, 1), v ~ N(0, 1) + d / Dh (asymmetric in
+    d), and, where Nk > 128, a late key that scores far above the rest for query 3 (the online softmax must re-base).  -> q
+    [B, H, Nq_pad, dh_pad], k, v [B, H, Nk_pad, dh_pad] bf16 (rows padded to multiples of 64; key rows >= Nk hold pad_value in the
+    first Dh dims, dims >= Dh hold zero)."""
+    Dp = dh_pad or Dh
+    g = torch.Generator().manual_seed(1000003 * seed + 7919 * Nq + 31 * Nk + Dh + B)
+    nqp, nkp = (Nq + 63) // 64 * 64, (Nk + 63) // 64 * 64
+    q, k, v = torch.zeros(B, H, nqp, Dp), torch.zeros(B, H, nkp, Dp), torch.zeros(B, H, nkp, Dp)
+    k[..., :Dh], v[..., :Dh] = pad_value, pad_value
+    q[:, :, :Nq, :Dh] = torch.randn(B, H, Nq, Dh, generator=g) * 1.5
+    k[:, :, :Nk, :Dh] = torch.randn(B, H, Nk, Dh, generator=g) * 1.5
+    v[:, :, :Nk, :Dh] = torch.randn(B, H, Nk, Dh, generator=g) + torch.arange(Dh) / Dh
+    if Nk > 128:
+        k[:, :, Nk - 5, :Dh] = q[:, :, min(3, Nq - 1), :Dh] * 4.0
+    return q.to(torch.bfloat16), k.to(torch.bfloat16), v.to(torch.bfloat16)
+
+
+def to_vt(v):
+    """v [..., Nk_pad, Dh] in natural order -> the key-permuted V^T layout [..., Dh, Nk_pad] ln3d_attention_bf16 reads."""
+    return v.transpose(-1, -2)[..., vt_key_order(v.shape[-2]).to(v.device)].contiguous()
+
+
+def selector_code(n, Dh, width=None):
+    """code(n)[d] = +32 where bit d mod 11 of n is set, else -32 (dims >= Dh of a wider row are zero)."""
+    n = torch.as_tensor(n)
+    d = torch.arange(Dh)
+    c = torch.where(((n[..., None] >> (d % 11)) & 1).bool(), 32.0, -32.0)
+    if width and width > Dh:
+        c = F.pad(c, (0, width - Dh))
+    return c
+
+
+def selector_perm(Nq, Nk, causal=False):
+    """the key each query selects: (7 i + 3) mod Nk, or i - (i mod 3) (>= 0) when causal"""
+    i = torch.arange(Nq)
+    return (i - i % 3).clamp(min=0) if causal else (7 * i + 3) % Nk
+
+
+def selector_values(B, H, Nk, Dh):
+    """V of the selector test, bf16 [B, H, Nk, Dh]: element (b, h, key, d) is a 64-bit mix (two multiply / xor-shift rounds) of its flat
+    index, reduced modulo the prime 16381 onto bf16 values of either sign and magnitude 2^-31 .. 2^33.  bf16 has too few values for
+    every element to differ, but no two (b, h, key) ROWS coincide and there is no period in key, head or batch
+    (tests/test_gemm_attn_refs_cpu.py asserts the rows pairwise distinct at every GPU shape), so a row read from the wrong batch, head,
+    key block or ring lap cannot pass."""
+    z = torch.arange(B * H * Nk * Dh, dtype=torch.int64) + 1
+    z = z * -7046029254386353131                       # 0x9E3779B97F4A7C15; int64 products wrap
+    z = z ^ (z >> 31)
+    z = z * -4658895280553007687                       # 0xBF58476D1CE4E5B9
+    z = z ^ (z >> 29)
+    hsh = z % 16381
+    bits = (0x3000 + (hsh >> 1) + ((hsh & 1) << 15)).to(torch.int32).to(torch.int16)
+    return bits.view(torch.bfloat16).reshape(B, H, Nk, Dh)
+
+
+def selector_inputs(B, H, Nq, Nk, Dh, Dp, nkp=None, causal=False):
+    """-> q [B, H, Nq_pad, Dp], k, v [B, H, Nk_pad, Dp] bf16 (natural key order) and pi: q_i = code(pi(i)), k_j = code(j), v =
+    selector_values; key rows >= Nk hold 1e4 in the first Dh dims, dims >= Dh hold zero."""
+    nqp, nkp = (Nq + 63) // 64 * 64, nkp or (Nk + 63) // 64 * 64
+    pi = selector_perm(Nq, Nk, causal)
+    q = torch.zeros(B, H, nqp, Dp)
+    q[:, :, :Nq] = selector_code(pi, Dh, Dp)
+    k = torch.full((B, H, nkp, Dp), 1e4)
+    k[:, :, :Nk] = selector_code(torch.arange(Nk), Dh, Dp)
+    v = torch.full((B, H, nkp, Dp), 1e4, dtype=torch.bfloat16)
+    v[:, :, :Nk, :Dh] = selector_values(B, H, Nk, Dh)
+    v[:, :, :, Dh:] = 0
+    k[:, :, :, Dh:] = 0
+    return q.to(torch.bfloat16), k.to(torch.bfloat16), v, pi
+
+
+def attention_cases():
+    """(path, Dh stored, Dh_true or 0, Nq, Nk, Nk_pad or None, causal): one set per kernel ln3d_attention_bf16 can reach (attn_kres, which
+    needs a head for every CU, is apart: KRES_SHAPES)."""
+    out = []
+    for Nk in (1, 63, 64, 65, 128):
+        for Nq in (1, 63, 65):
+            out.append(("attn64x2", 64, 0, Nq, Nk, None, False))
+    for Nk, nkp in ((129, None), (191, None), (257, None), (256, 320)):
+        out.append(("attn64x4", 64, 0, 65, Nk, nkp, False))
+    for Nq, Nk in ((1, 256), (65, 256), (200, 512), (256, 1280)):
+        out.append(("stream", 64, 0, Nq, Nk, None, False))
+    for Dh, dt in ((80, 0), (80, 72), (128, 0), (128, 72)):
+        for Nq, Nk in ((33, 77), (65, 129)):
+            out.append((f"attn{Dh}" + (f"_{dt}" if dt else ""), Dh, dt, Nq, Nk, None, False))
+    for n in (1, 31, 32, 33, 64, 77, 128):
+        out.append(("short_causal", 64, 0, n, n, None, True))
+    return out
+
+
+ATTENTION_BH = [(1, 1), (2, 3)]
+KRES_SHAPES = [(256, 512), (256, 768)]
+
+
+def requantised_query(q, scale):
+    """attn_stream_kernel / attn_kres_kernel fold scale * log2(e) into the query fragment and round it to bf16 a second time
+    (csrc/attention.hip read_q: pack2bf(q * scale_log2), scale_log2 the fp32 product of the fp32 scale and 1.4426950408889634f).  -> that
+    query, bf16; the scores it forms are in the exp2 domain (attention_ref(..., base2=True))."""
+    sl2 = torch.tensor(scale, dtype=torch.float32) * torch.tensor(1.4426950408889634, dtype=torch.float32)
+    return (q.float() * sl2).to(torch.bfloat16)
