@@ -315,10 +315,26 @@ int ln3d_query_points(const float* planes, int H, int W, const float* points, in
  * Replaces mcubes.marching_cubes(sigma[G,G,G], thr) at nsr/train_util_diffusion.py:221 (PyMCubes, third-party, absent:
  * parity unpinned) with marching tetrahedra (ln3d_mesh_*) or classic marching cubes (ln3d_mcubes_*, the default of the drivers).  Pass 1: triangles per cell -> counts[(G-1)^3] (cell = (x*(G-1)+y)*(G-1)+z);
  * caller takes the inclusive prefix sum; pass 2 writes for triangle k its 3 vertices (grid coordinates) to
- * tri_pos[k*9..] and the ids of the grid edges they lie on to tri_key[k*3..] (for welding).                          */
+ * tri_pos[k*9..] and the ids of the grid edges they lie on to tri_key[k*3..] (for welding).
+ * Order: cells in cell-index order, exactly counts[cell] triangles from offsets[cell-1] on (0 for cell 0), nothing else is written.
+ * Corner c of a cell sits at (c & 1, (c >> 1) & 1, c >> 2); inside = value > thr.
+ * Vertex on the edge between corners a and b, taken so that node id gid[a] < gid[b] (gid = (x G + y) G + z):
+ *   t = (thr - v[a]) / (v[b] - v[a]),  pos = a + t (b - a),  key = gid[a] * G^3 + gid[b]
+ * in fp32, so every copy of a vertex carries the same bits whichever cell wrote it.  G^6 must stay below 2^63:
+ * 2 <= G <= LN3D_MESH_MAX_GRID, anything else is LN3D_ERR_BAD_ARG.
+ * Non-finite values: a NaN corner is outside (`>`), -inf is outside, +inf inside.  A crossing between two finite values is finite and on
+ * its edge even where v[b] - v[a] overflows (the quotient is then taken of the halved values).  A crossing with one +-inf or NaN end sits
+ * ON THE OTHER, finite end (t = 0 or 1, whichever of the two has the smaller gid); with two such ends, at the edge's midpoint.  Finite
+ * inputs are not touched by these rules.
+ * Marching tetrahedra: the 6 Kuhn tetrahedra around the 0-7 diagonal in the order (0,1,3,7) (0,2,3,7) (0,2,6,7) (0,4,6,7) (0,4,5,7)
+ * (0,1,5,7); ins / outs = a tetrahedron's inside / outside corners in that order.  1 inside: (ins0-outs0, ins0-outs1, ins0-outs2);
+ * 3 inside: (outs0-ins0, outs0-ins1, outs0-ins2); 2 inside: q0 = ins0-outs0, q1 = ins0-outs1, q2 = ins1-outs1, q3 = ins1-outs0 as
+ * (q0, q1, q2), (q0, q2, q3).  A triangle's last two corners are swapped when (p1 - p0) x (p2 - p0) points against the vector from the
+ * inside corners' centroid to the outside corners' centroid (dot product < 0): normals point out of the dense side.        */
+#define LN3D_MESH_MAX_GRID 1448
 int ln3d_mesh_count(const float* sigma, int G, float thr, int32_t* counts, void* stream);
 /* Same two passes for CLASSIC marching cubes (Lorensen & Cline - the algorithm of mcubes.marching_cubes; 256-case table
- * csrc/mc_table.h, <= 5 triangles per cell, corner value > thr = inside).  Pinned against scikit-image's classic implementation
+ * csrc/mc_table.h, <= 5 triangles per cell in the table row's order and corner order, corner value > thr = inside).  Pinned against scikit-image's classic implementation
  * (tests/golden/mcubes_classic.npz); PyMCubes itself is absent. */
 int ln3d_mcubes_count(const float* sigma, int G, float thr, int32_t* counts, void* stream);
 int ln3d_mcubes_emit(const float* sigma, int G, float thr, const int64_t* offsets_inclusive, float* tri_pos, int64_t* tri_key,

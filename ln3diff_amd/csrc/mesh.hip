@@ -7,6 +7,7 @@
 // (6 tetrahedra around the 0-7 diagonal; face-consistent across cells, no 256-case table): every tetrahedron emits 0, 1
 // or 2 triangles; vertices are identified by the grid edge they lie on (key = min_vertex_id * G^3 + max_vertex_id), so the
 // host welds them with one unique() and no floating-point comparison.  Two passes (count, emit) around a prefix sum.
+// The key needs G^6 < 2^63: LN3D_MESH_MAX_GRID.
 #include "common.h"
 #include "../../include/ln3d.h"
 #include "mc_table.h"
@@ -45,7 +46,13 @@ __global__ void mesh_count_kernel(MeshP p, int64_t ncell, int32_t* counts) {
 __device__ __forceinline__ void edge_point(const MeshP& p, const float v[8], const int64_t gid[8], int cx, int cy, int cz, int a, int b,
                                            float out[3], int64_t& key) {
   if (gid[a] > gid[b]) { const int t = a; a = b; b = t; }            // canonical orientation: identical bits from every cell
-  const float t = (p.thr - v[a]) / (v[b] - v[a]);
+  // finite inputs take the first form, bit for bit; the selects only replace what would be NaN or off the edge (include/ln3d.h):
+  // v[b] - v[a] overflows between two finite values of opposite sign -> the same quotient of the halved values; a +-inf or NaN end
+  // -> the vertex sits on the other, finite end; two such ends -> the midpoint
+  float t = (p.thr - v[a]) / (v[b] - v[a]);
+  if (isinf(v[b] - v[a])) t = (0.5f * p.thr - 0.5f * v[a]) / (0.5f * v[b] - 0.5f * v[a]);
+  const bool fa = isfinite(v[a]), fb = isfinite(v[b]);
+  t = fa ? (fb ? t : 0.f) : (fb ? 1.f : 0.5f);
   const float ax = cx + (a & 1), ay = cy + ((a >> 1) & 1), az = cz + (a >> 2);
   const float bx = cx + (b & 1), by = cy + ((b >> 1) & 1), bz = cz + (b >> 2);
   out[0] = ax + t * (bx - ax); out[1] = ay + t * (by - ay); out[2] = az + t * (bz - az);
@@ -135,14 +142,14 @@ __global__ void mcubes_emit_kernel(MeshP p, int64_t ncell, const int64_t* offset
 }
 
 extern "C" int ln3d_mcubes_count(const float* sigma, int G, float thr, int32_t* counts, void* stream) {
-  if (!sigma || !counts || G < 2) return LN3D_ERR_BAD_ARG;
+  if (!sigma || !counts || G < 2 || G > LN3D_MESH_MAX_GRID) return LN3D_ERR_BAD_ARG;
   MeshP p{sigma, G, thr};
   const int64_t ncell = (int64_t)(G - 1) * (G - 1) * (G - 1);
   hipLaunchKernelGGL(mcubes_count_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, ncell, counts);
   return ln3d_check_launch();
 }
 extern "C" int ln3d_mcubes_emit(const float* sigma, int G, float thr, const int64_t* offsets, float* tri_pos, int64_t* tri_key, void* stream) {
-  if (!sigma || !offsets || !tri_pos || !tri_key || G < 2) return LN3D_ERR_BAD_ARG;
+  if (!sigma || !offsets || !tri_pos || !tri_key || G < 2 || G > LN3D_MESH_MAX_GRID) return LN3D_ERR_BAD_ARG;
   MeshP p{sigma, G, thr};
   const int64_t ncell = (int64_t)(G - 1) * (G - 1) * (G - 1);
   hipLaunchKernelGGL(mcubes_emit_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, ncell, offsets, tri_pos, tri_key);
@@ -150,14 +157,14 @@ extern "C" int ln3d_mcubes_emit(const float* sigma, int G, float thr, const int6
 }
 
 extern "C" int ln3d_mesh_count(const float* sigma, int G, float thr, int32_t* counts, void* stream) {
-  if (!sigma || !counts || G < 2) return LN3D_ERR_BAD_ARG;
+  if (!sigma || !counts || G < 2 || G > LN3D_MESH_MAX_GRID) return LN3D_ERR_BAD_ARG;
   MeshP p{sigma, G, thr};
   const int64_t ncell = (int64_t)(G - 1) * (G - 1) * (G - 1);
   hipLaunchKernelGGL(mesh_count_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, ncell, counts);
   return ln3d_check_launch();
 }
 extern "C" int ln3d_mesh_emit(const float* sigma, int G, float thr, const int64_t* offsets, float* tri_pos, int64_t* tri_key, void* stream) {
-  if (!sigma || !offsets || !tri_pos || !tri_key || G < 2) return LN3D_ERR_BAD_ARG;
+  if (!sigma || !offsets || !tri_pos || !tri_key || G < 2 || G > LN3D_MESH_MAX_GRID) return LN3D_ERR_BAD_ARG;
   MeshP p{sigma, G, thr};
   const int64_t ncell = (int64_t)(G - 1) * (G - 1) * (G - 1);
   hipLaunchKernelGGL(mesh_emit_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, ncell, offsets, tri_pos, tri_key);

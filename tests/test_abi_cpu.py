@@ -107,6 +107,10 @@ ZERO_CALLS = [
     ('ln3d_patch_embed_triplane', (P, P, P, P, P, 0, 4, 32, 2, 128, N)),
     ('ln3d_patch_embed_triplane', (P, P, P, P, P, 1, 4, 32, 0, 128, N)),
 ]
+# the iso-surface passes: 2 <= G <= LN3D_MESH_MAX_GRID = 1448 (a vertex key is gid[a] * G^3 + gid[b] < G^6, and 1449^6 > 2^63)
+for _name, _args in [('ln3d_mesh_count', (P, 8, F(1), P, N)), ('ln3d_mcubes_count', (P, 8, F(1), P, N)),
+                     ('ln3d_mcubes_emit', (P, 8, F(1), P, P, P, N)), ('ln3d_mesh_emit', (P, 8, F(1), P, P, P, N))]:
+    ZERO_CALLS += [(_name, _args[:1] + (g,) + _args[2:]) for g in (1449, 2048, 1 << 30, 1, 0, -1)]
 
 
 def _sizes_zeroed(name, args, positions):
