@@ -4,15 +4,14 @@ Same constructor / forward surface and state-dict keys as the reference's guided
 (`forward(x, timesteps, context=None, y=None, get_attr='', **kw)` -> float32 [B, C, H, W]; `mixing_logit` when mixed_prediction),
 with its building blocks as parameter containers under the reference's names - `ResBlock` (:164-278), `Downsample` / `Upsample`
 (:102-161), `AttentionBlock` (:281-336), and `SpatialTransformer` / `BasicTransformerBlock` / `CrossAttention` / `FeedForward` of
-ldm/modules/attention_compat.py:161-277.  The arithmetic is a fixed sequence of HIP launches on channel-last activations
-[N, H*W, C] (fp32 stream, bf16 GEMM operands, fp32 accumulation / norms / softmax):
+ldm/modules/attention_compat.py:161-277.  The arithmetic is a fixed sequence of HIP launches on channel-last activations; the
+blocks (3x3 conv as im2col + GEMM, ResBlock, self-attention, the transformer) and their launch sequences are those of
+ln3diff_amd/convstack.py, with GroupNorm by ln3d_groupnorm_any.  What is the U-Net's own:
 
-  conv 3x3        ln3d_im2col3x3 (nearest-2x upsample fused) / ln3d_im2col3x3_strided (stride 2) -> ln3d_gemm_bf16 (+ bias / + residual)
-  ResBlock        ln3d_groupnorm_any (+SiLU) -> conv -> emb Linear (GEMM) -> ln3d_groupnorm_any with `h + emb` or the scale / shift
-                  modulation folded in -> conv with the residual epilogue onto skip(x) (1x1 GEMM when the width changes)
-  transformer     GroupNorm -> 1x1 GEMM -> per block: LayerNorm (ln3d_norm_modulate) -> fused q|k|v GEMM -> ln3d_attention_small ->
-                  to_out GEMM (residual epilogue); the same against the text context; LayerNorm -> GEGLU (GEMM + ln3d_geglu) -> GEMM
-  AttentionBlock  GroupNorm -> qkv GEMM (rows re-ordered at packing so heads are contiguous per q / k / v) -> ln3d_attention_small -> proj
+  ResBlock        the emb Linear, with `h + emb` or the scale / shift modulation folded into the second GroupNorm; never in place (the
+                  input may be a saved skip activation)
+  transformer     attn2 against the text context: q GEMM, k|v GEMM of the context, ln3d_attention_small
+  AttentionBlock  GroupNorm -> self-attention (qkv rows re-ordered at packing so heads are contiguous per q / k / v) -> proj
 Not built (no released configuration uses them): class conditioning (num_classes), resblock_updown, dims != 2, use_fp16,
 predict_codebook_ids; they raise.
 """
@@ -22,14 +21,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops, _cache
-from ..dit.dit_models_xformers import Workspace, bf16, f32, pad_head_columns, self_attention_hip
-
-_MFMA_MIN_TOKENS = 256          # self-attention over at least this many tokens goes to the MFMA attention kernels (r6)
-
-
-def _mfma_head(dh):
-    """Head sizes the MFMA route takes: a multiple of 8 (the head-split GEMM epilogue) up to the attention kernels' 128."""
-    return dh % 8 == 0 and dh <= 128
+from ..convstack import ConvStack, empty_alloc, pack_conv3, pack_gn, pack_lin, pack_out_proj, pack_resblock, pack_transformer
+from ..dit.dit_models_xformers import f32
 
 
 def conv_nd(dims, *a, **k):
@@ -144,24 +137,6 @@ class SpatialTransformer(nn.Module):             # attention_compat.py:228-277
         self.proj_out = zero_module(nn.Conv2d(inner, in_channels, kernel_size=1))
 
 
-# ----------------------------------------------------------------------------- packing helpers
-def _pack_conv3(conv, dev, cin_pad=None):
-    w = conv.weight.detach().float().cpu()                    # [Cout, Cin, 3, 3] -> [Cout, (ky, kx, c)] with c padded to cin_pad
-    co, ci = w.shape[0], w.shape[1]
-    cp = cin_pad or ci
-    kpad = (9 * cp + 63) // 64 * 64
-    m = torch.zeros(co, 9, cp)
-    m[:, :, :ci] = w.permute(0, 2, 3, 1).reshape(co, 9, ci)
-    full = torch.zeros(co, kpad)
-    full[:, :9 * cp] = m.reshape(co, 9 * cp)
-    return {'w': bf16(full, dev), 'b': f32(conv.bias, dev), 'kpad': kpad, 'cin': cp, 'cout': co}
-
-
-def _pack_lin(w, b, dev):
-    w2 = w.detach().reshape(w.shape[0], -1)
-    return {'w': bf16(w2, dev), 'b': None if b is None else f32(b, dev), 'cout': w2.shape[0], 'cin': w2.shape[1]}
-
-
 class UNetModel(nn.Module):
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks, attention_resolutions, dropout=0,
                  channel_mult=(1, 2, 4, 8), conv_resample=True, dims=2, num_classes=None, use_checkpoint=False, use_fp16=False,
@@ -249,7 +224,7 @@ class UNetModel(nn.Module):
                     ds //= 2
                 self.output_blocks.append(TimestepEmbedSequential(*layers))
         self.out = nn.Sequential(normalization(ch), nn.SiLU(), zero_module(conv_nd(dims, model_channels, out_channels, 3, padding=1)))
-        self._packed, self._ws = None, None
+        self._packed, self._cs = None, None
         _cache.watch(self)
 
     # any parameter change invalidates the packed device copies
@@ -263,38 +238,20 @@ class UNetModel(nn.Module):
 
     # ------------------------------------------------------------------ packing
     def _pack_layer(self, m, dev):
-        gn = lambda g: (f32(g.weight, dev), f32(g.bias, dev), float(g.eps))
         if isinstance(m, nn.Conv2d):
             cin = m.weight.shape[1]
-            return ('conv', {'c': _pack_conv3(m, dev, cin_pad=(cin + 7) // 8 * 8), 'cin_raw': cin})
+            return ('conv', {'c': pack_conv3(m, dev, cin_pad=(cin + 7) // 8 * 8), 'cin_raw': cin})
         if isinstance(m, ResBlock):
-            q = {'n1': gn(m.in_layers[0]), 'c1': _pack_conv3(m.in_layers[2], dev), 'emb': _pack_lin(m.emb_layers[1].weight, m.emb_layers[1].bias, dev),
-                 'n2': gn(m.out_layers[0]), 'c2': _pack_conv3(m.out_layers[3], dev), 'ss': m.use_scale_shift_norm}
-            if not isinstance(m.skip_connection, nn.Identity):
-                q['skip'] = _pack_lin(m.skip_connection.weight, m.skip_connection.bias, dev)
+            q = pack_resblock(m.in_layers[0], m.in_layers[2], m.out_layers[0], m.out_layers[3], dev,
+                              shortcut=None if isinstance(m.skip_connection, nn.Identity) else m.skip_connection)
+            q['emb'], q['ss'] = pack_lin(m.emb_layers[1].weight, m.emb_layers[1].bias, dev), m.use_scale_shift_norm
             return ('res', q)
         if isinstance(m, Downsample):
-            return ('down', {'c': _pack_conv3(m.op, dev)})
+            return ('down', {'c': pack_conv3(m.op, dev)})
         if isinstance(m, Upsample):
-            return ('up', {'c': _pack_conv3(m.conv, dev)})
+            return ('up', {'c': pack_conv3(m.conv, dev)})
         if isinstance(m, SpatialTransformer):
-            blocks = []
-            for b in m.transformer_blocks:
-                ln = lambda n: (f32(n.weight - 1.0, dev), f32(n.bias, dev), float(n.eps))           # y = LN(x) (1 + (w - 1)) + b
-                blocks.append({
-                    'n1': ln(b.norm1), 'n2': ln(b.norm2), 'n3': ln(b.norm3),
-                    'qkv1': _pack_lin(torch.cat([b.attn1.to_q.weight, b.attn1.to_k.weight, b.attn1.to_v.weight], 0), None, dev),
-                    'o1': _pack_lin(b.attn1.to_out[0].weight, b.attn1.to_out[0].bias, dev),
-                    'o1p': _pack_lin(pad_head_columns(b.attn1.to_out[0].weight.detach(), m.n_heads, m.d_head), b.attn1.to_out[0].bias, dev)
-                    if _mfma_head(m.d_head) else None,
-                    'q2': _pack_lin(b.attn2.to_q.weight, None, dev),
-                    'kv2': _pack_lin(torch.cat([b.attn2.to_k.weight, b.attn2.to_v.weight], 0), None, dev),
-                    'o2': _pack_lin(b.attn2.to_out[0].weight, b.attn2.to_out[0].bias, dev),
-                    'ff1': _pack_lin(b.ff.net[0].proj.weight, b.ff.net[0].proj.bias, dev),
-                    'ff2': _pack_lin(b.ff.net[2].weight, b.ff.net[2].bias, dev)})
-            return ('transformer', {'n': gn(m.norm), 'pin': _pack_lin(m.proj_in.weight, m.proj_in.bias, dev),
-                                    'pout': _pack_lin(m.proj_out.weight, m.proj_out.bias, dev), 'blocks': blocks, 'heads': m.n_heads,
-                                    'dh': m.d_head})
+            return ('transformer', pack_transformer(m, True, dev))
         if isinstance(m, AttentionBlock):
             C, nh = m.channels, m.num_heads
             ch = C // nh
@@ -302,155 +259,76 @@ class UNetModel(nn.Module):
             # head is a contiguous column range of q, k and v
             idx = torch.arange(3 * C).reshape(nh, 3, ch).permute(1, 0, 2).reshape(-1)
             w = m.qkv.weight.detach().reshape(3 * C, C)[idx]
-            return ('attention', {'n': gn(m.norm), 'qkv': _pack_lin(w, m.qkv.bias.detach()[idx], dev),
-                                  'proj': _pack_lin(m.proj_out.weight, m.proj_out.bias, dev), 'heads': nh, 'dh': ch,
-                                  'projp': _pack_lin(pad_head_columns(m.proj_out.weight.detach().reshape(C, C), nh, ch), m.proj_out.bias, dev)
-                                  if _mfma_head(ch) else None})
+            q = {'n': pack_gn(m.norm, dev), 'qkv': pack_lin(w, m.qkv.bias.detach()[idx], dev), 'heads': nh, 'dh': ch}
+            q['proj'], q['projp'] = pack_out_proj(m.proj_out.weight, m.proj_out.bias, nh, ch, dev)
+            return ('attention', q)
         raise TypeError(type(m))
 
     def _ensure_packed(self, dev):
         if _cache.fresh(self._packed, dev):
             return
         P = {'device': dev}
-        P['t0'] = _pack_lin(self.time_embed[0].weight, self.time_embed[0].bias, dev)
-        P['t2'] = _pack_lin(self.time_embed[2].weight, self.time_embed[2].bias, dev)
+        P['t0'] = pack_lin(self.time_embed[0].weight, self.time_embed[0].bias, dev)
+        P['t2'] = pack_lin(self.time_embed[2].weight, self.time_embed[2].bias, dev)
         P['inp'] = [[self._pack_layer(m, dev) for m in blk] for blk in self.input_blocks]
         P['mid'] = [self._pack_layer(m, dev) for m in self.middle_block]
         P['out'] = [[self._pack_layer(m, dev) for m in blk] for blk in self.output_blocks]
-        P['norm_out'] = (f32(self.out[0].weight, dev), f32(self.out[0].bias, dev), float(self.out[0].eps))
-        P['conv_out'] = _pack_conv3(self.out[2], dev)
+        P['norm_out'] = pack_gn(self.out[0], dev)
+        P['conv_out'] = pack_conv3(self.out[2], dev)
         if self.mixed_prediction:
             P['mix'] = f32(self.mixing_logit.reshape(-1), dev)
         self._packed = _cache.stamp(P, self)
-        self._ws = Workspace(dev)
+        self._cs = ConvStack(dev, empty_alloc(dev), gn_any=True, who='UNetModel')
 
     # ------------------------------------------------------------------ pieces (h: f32 [N*H*W, C] channel-last)
     def _new(self, rows, cols, dtype=torch.float32):
         return torch.empty(rows, cols, device=self._packed['device'], dtype=dtype)
 
-    def _gn(self, h, nw, N, HW, C, swish, add_row=None, mod=None):
-        y = self._new(N * HW, C, torch.bfloat16)
-        ops.groupnorm_any(h, nw[0], nw[1], y, N, HW, C, 32, nw[2], swish, add_row=add_row,
-                          mod_scale=None if mod is None else mod[0], mod_shift=None if mod is None else mod[1])
-        return y
-
-    def _conv3(self, a_bf, N, H, W, pc, out, up=1, stride=1, epi=ops.EPI_F32):
-        Ho, Wo = (H * up, W * up) if stride == 1 else ((H - 1) // stride + 1, (W - 1) // stride + 1)
-        col = self._new(N * Ho * Wo, pc['kpad'], torch.bfloat16)
-        if stride == 1:
-            ops.im2col3x3(a_bf, col, N, H, W, pc['cin'], up, pc['kpad'])
-        else:
-            ops.im2col3x3_strided(a_bf, col, N, H, W, pc['cin'], stride, pc['kpad'])
-        ops.gemm(col, pc['w'], pc['b'], epi, out)
-        return Ho, Wo
-
-    def _bf(self, h):
-        y = torch.empty_like(h, dtype=torch.bfloat16)
-        ops.cast_bf16(h, y)
-        return y
-
-    def _res(self, h, q, N, H, W, emb_silu):
-        cin, cout, HW = q['c1']['cin'], q['c1']['cout'], H * W
-        a = self._gn(h, q['n1'], N, HW, cin, True)
-        t = self._new(N * HW, cout)
-        self._conv3(a, N, H, W, q['c1'], t)
-        e = self._new(N, q['emb']['cout'])
-        ops.gemm(emb_silu, q['emb']['w'], q['emb']['b'], ops.EPI_F32, e)
-        if q['ss']:                                   # GN(h) * (1 + scale) + shift, then SiLU (unet.py:267-271)
-            a2 = self._gn(t, q['n2'], N, HW, cout, True, mod=(e[:, :cout].contiguous(), e[:, cout:].contiguous()))
-        else:                                         # SiLU(GN(h + emb)) (unet.py:272-273)
-            a2 = self._gn(t, q['n2'], N, HW, cout, True, add_row=e)
-        if 'skip' in q:
-            s = self._new(N * HW, cout)
-            ops.gemm(self._bf(h), q['skip']['w'], q['skip']['b'], ops.EPI_F32, s)
-        else:
-            s = h.clone()                             # the block's input may be a saved skip activation: never updated in place
-        self._conv3(a2, N, H, W, q['c2'], s, epi=ops.EPI_GATE_RES)
-        return s
-
-    def _self_attend_mfma(self, a_bf, qkv, B, N, heads, dh):
-        """r6: self-attention over >= 256 tokens on the MFMA attention kernels (csrc/attention.hip) - the fused q|k|v GEMM splits heads in its
-        epilogue (q / k [B, H, N, Dp], V^T [B, H, Dp, N], head size zero-padded to 64 / 128: exact, the pad contributes 0 to q.k and meets zero
-        columns of the padded output projection) instead of ln3d_attention_small's one-wavefront-per-query scalar loop (1.3 GFLOP per
-        attention at the ShapeNet U-Net's 32 x 32 level).  Reference: guided_diffusion/unet.py:281-389, ldm/modules/attention_compat.py:161-277."""
-        return self_attention_hip(self._ws, 'u%d_' % dh, a_bf, B, N, heads * dh, heads, qkv['w'], qkv['b'])
-
-    def _attend(self, qv, kv, vv, B, heads, Nq, Nk, dh, ldq, ldkv):
-        o = self._new(B * Nq, heads * dh, torch.bfloat16)
-        ops.attention_small(qv, kv, vv, o, B, heads, Nq, Nk, dh, ldq, ldkv, ldkv, dh ** -0.5)
-        return o
-
     def _transformer(self, h, q, N, H, W, ctx_bf, Lc):
-        HW, C = H * W, h.shape[1]
         heads, dh = q['heads'], q['dh']
-        inner = heads * dh
-        rows = N * HW
-        a = self._gn(h, q['n'], N, HW, C, False)
-        tok = self._new(rows, inner)
-        ops.gemm(a, q['pin']['w'], q['pin']['b'], ops.EPI_F32, tok)
-        for b in q['blocks']:
-            def ln(nw):
-                y = self._new(rows, inner, torch.bfloat16)
-                ops.norm_modulate(tok, y, rows, inner, kind=0, eps=nw[2], shift=nw[1], scale=nw[0], mod_rows=rows, mod_ld=0)
-                return y
-            if b['o1p'] is not None and HW >= _MFMA_MIN_TOKENS and HW % 32 == 0:
-                o = self._self_attend_mfma(ln(b['n1']), b['qkv1'], N, HW, heads, dh)
-                ops.gemm(o, b['o1p']['w'], b['o1p']['b'], ops.EPI_GATE_RES, tok)
-            else:
-                qkv = self._new(rows, 3 * inner, torch.bfloat16)
-                ops.gemm(ln(b['n1']), b['qkv1']['w'], None, ops.EPI_BF16, qkv)
-                o = self._attend(qkv, qkv[:, inner:], qkv[:, 2 * inner:], N, heads, HW, HW, dh, 3 * inner, 3 * inner)
-                ops.gemm(o, b['o1']['w'], b['o1']['b'], ops.EPI_GATE_RES, tok)
+        inner, rows = heads * dh, N * H * W
+
+        def attn2(a, b):                              # against the text context
             q2 = self._new(rows, inner, torch.bfloat16)
-            ops.gemm(ln(b['n2']), b['q2']['w'], None, ops.EPI_BF16, q2)
+            ops.gemm(a, b['q2']['w'], None, ops.EPI_BF16, q2)
             if ctx_bf is None:                        # no context: cross-attention defaults to self-attention (attention_compat.py:183)
                 raise NotImplementedError("SpatialTransformer without a context")
             kv = self._new(N * Lc, 2 * inner, torch.bfloat16)
             ops.gemm(ctx_bf, b['kv2']['w'], None, ops.EPI_BF16, kv)
-            o = self._attend(q2, kv, kv[:, inner:], N, heads, HW, Lc, dh, inner, 2 * inner)
-            ops.gemm(o, b['o2']['w'], b['o2']['b'], ops.EPI_GATE_RES, tok)
-            g = self._new(rows, b['ff1']['cout'])
-            ops.gemm(ln(b['n3']), b['ff1']['w'], b['ff1']['b'], ops.EPI_F32, g)
-            gg = self._new(rows, b['ff1']['cout'] // 2, torch.bfloat16)
-            ops.geglu(g, gg, rows, b['ff1']['cout'] // 2)
-            ops.gemm(gg, b['ff2']['w'], b['ff2']['b'], ops.EPI_GATE_RES, tok)
-        s = h.clone()
-        ops.gemm(self._bf(tok), q['pout']['w'], q['pout']['b'], ops.EPI_GATE_RES, s)
-        return s
+            o = self._new(rows, inner, torch.bfloat16)
+            ops.attention_small(q2, kv, kv[:, inner:], o, N, heads, H * W, Lc, dh, inner, 2 * inner, 2 * inner, dh ** -0.5)
+            return o, b['o2']
+        return self._cs.transformer(h, q, N, H, W, attn2, in_place=False)       # h may be a saved skip activation
 
     def _attention(self, h, q, N, H, W):
-        HW, C = H * W, h.shape[1]
-        a = self._gn(h, q['n'], N, HW, C, False)
+        HW, cs = H * W, self._cs
+        a = cs.gn(h, q['n'], N, HW, h.shape[1], False)
         s = h.clone()
-        if q['projp'] is not None and HW >= _MFMA_MIN_TOKENS and HW % 32 == 0:
-            o = self._self_attend_mfma(a, q['qkv'], N, HW, q['heads'], q['dh'])
-            ops.gemm(o, q['projp']['w'], q['projp']['b'], ops.EPI_GATE_RES, s)
-            return s
-        qkv = self._new(N * HW, 3 * C, torch.bfloat16)
-        ops.gemm(a, q['qkv']['w'], q['qkv']['b'], ops.EPI_BF16, qkv)
-        o = self._attend(qkv, qkv[:, C:], qkv[:, 2 * C:], N, q['heads'], HW, HW, q['dh'], 3 * C, 3 * C)
-        ops.gemm(o, q['proj']['w'], q['proj']['b'], ops.EPI_GATE_RES, s)
+        o, padded = cs.self_attend(a, q['qkv'], N, HW, q['heads'], q['dh'], 'u')
+        proj = q['projp' if padded else 'proj']
+        ops.gemm(o, proj['w'], proj['b'], ops.EPI_GATE_RES, s)
         return s
 
     def _run(self, layers, h, N, H, W, emb_silu, ctx_bf, Lc, x_cl=None):
+        cs = self._cs
         for kind, q in layers:
             if kind == 'conv':
                 out = self._new(N * H * W, q['c']['cout'])
-                self._conv3(x_cl, N, H, W, q['c'], out)
+                cs.conv3(x_cl, N, H, W, q['c'], out)
                 h = out
             elif kind == 'res':
-                h = self._res(h, q, N, H, W, emb_silu)
+                h = cs.res(h, q, N, H, W, emb_silu, in_place=False)      # h may be a saved skip activation: never updated in place
             elif kind == 'transformer':
                 h = self._transformer(h, q, N, H, W, ctx_bf, Lc)
             elif kind == 'attention':
                 h = self._attention(h, q, N, H, W)
             elif kind == 'down':
                 out = self._new(N * ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1), q['c']['cout'])
-                H, W = self._conv3(self._bf(h), N, H, W, q['c'], out, stride=2)
+                H, W = cs.conv3(cs.bf(h), N, H, W, q['c'], out, stride=2)
                 h = out
             elif kind == 'up':
                 out = self._new(N * 4 * H * W, q['c']['cout'])
-                H, W = self._conv3(self._bf(h), N, H, W, q['c'], out, up=2)
+                H, W = cs.conv3(cs.bf(h), N, H, W, q['c'], out, up=2)
                 h = out
         return h, H, W
 
@@ -489,7 +367,7 @@ class UNetModel(nn.Module):
         ctx_bf, Lc = None, 0
         if context is not None:
             Lc = context.shape[1]
-            ctx_bf = self._bf(context.to(dev).float().reshape(B * Lc, -1).contiguous())
+            ctx_bf = self._cs.bf(context.to(dev).float().reshape(B * Lc, -1).contiguous())
         cpad = P['inp'][0][0][1]['c']['cin']
         x_cl = self._new(B * H * W, cpad, torch.bfloat16)
         ops.nchw_to_cl_bf16(x, x_cl, B, Cin, H * W, cpad)
@@ -503,9 +381,9 @@ class UNetModel(nn.Module):
             hp, _, _ = hs.pop()
             h = torch.cat([h, hp], dim=1)              # channel-last: the skip concat is along the last axis
             h, H, W = self._run(layers, h, B, H, W, emb_silu, ctx_bf, Lc)
-        a = self._gn(h, P['norm_out'], B, H * W, h.shape[1], True)
+        a = self._cs.gn(h, P['norm_out'], B, H * W, h.shape[1], True)
         o_cl = self._new(B * H * W, self.out_channels)
-        self._conv3(a, B, H, W, P['conv_out'], o_cl)
+        self._cs.conv3(a, B, H, W, P['conv_out'], o_cl)
         out = torch.empty(B, self.out_channels, H, W, device=dev, dtype=torch.float32)
         ops.cl_to_nchw_f32(o_cl, out, B, self.out_channels, H * W)
         if self.roll_out:                              # 'b c h (n w) -> b (n c) h w'

@@ -6,16 +6,13 @@ Same constructor arguments and state-dict keys as the reference's ldm/modules/di
 the middle attention (`attn_type="mv-vanilla"`).  Input [B*F, in_channels, S, S]: F = num_frames consecutive views of one object
 (the released input has 10 channels: normalised RGB, Pluecker rays o x d | d, normalised depth; datasets/g_buffer_objaverse.py).
 
-Everything runs channel-last on the device ([N, H*W, C] f32 activations, bf16 GEMM operands, fp32 accumulation / norms / softmax):
+Everything runs channel-last on the device; the blocks (3x3 conv as im2col + GEMM, ResnetBlock, the transformer) and their launch
+sequences are those of ln3diff_amd/convstack.py.  What is the encoder's own:
 
-  conv 3x3        ln3d_im2col3x3 -> ln3d_gemm_bf16 (+ bias / + residual epilogue); the input is cast and zero-padded 10 -> 16 channels
-                  by ln3d_nchw_to_cl_bf16
-  Downsample      ln3d_im2col3x3_pad01 (pad (0,1,0,1), stride 2, padding 0) -> GEMM
-  ResnetBlock     ln3d_groupnorm_swish (GroupNorm(32, eps 1e-6) + swish) -> conv -> GN + swish -> conv with the residual epilogue onto
-                  x (nin_shortcut: a 1x1 GEMM first when the width changes)
-  mid.attn_1      GroupNorm -> proj_in GEMM -> LayerNorm (ln3d_norm_modulate) -> q|k|v GEMM splitting heads -> ln3d_attention_bf16 over
-                  ALL F*H*W tokens of an object (attn1: `(b f) l c -> b (f l) c` is the row order already) -> to_out (residual
-                  epilogue); the same per frame (attn2); LayerNorm -> GEGLU (GEMM + ln3d_geglu) -> GEMM; proj_out onto the input
+  conv_in         the input is cast and zero-padded 10 -> 16 channels by ln3d_nchw_to_cl_bf16
+  Downsample      the pad-(0,1,0,1) stride-2 gather (ln3d_im2col3x3_pad01)
+  mid.attn_1      attn1 over ALL F*H*W tokens of an object (`(b f) l c -> b (f l) c` is the row order already), attn2 over the same
+                  tokens per frame
   pooling         ln3d_frame_mean (forward) or inside ln3d_mv_posterior (AE 'encoder_vae' / 'enc_dec': the decoder's
                   vae_reparameterization reads the per-frame output directly)
 
@@ -26,11 +23,10 @@ import torch
 import torch.nn as nn
 
 from .. import ops, _cache
-from ..dit.dit_models_xformers import Workspace, f32, self_attention_hip
-from ..guided_diffusion.unet import CrossAttention, FeedForward, _pack_conv3, _pack_lin
+from ..convstack import ConvStack, empty_alloc, pack_conv3, pack_gn, pack_resblock, pack_transformer
+from ..guided_diffusion.unet import CrossAttention, FeedForward
 
 RELEASED_DINO_VERSION = 'mv-sd-dit-dynaInp-trilatent'
-_MFMA_MIN_TOKENS = 256          # self-attention over at least this many tokens runs on the MFMA attention kernels (as in the U-Net)
 
 
 def Normalize(in_channels):     # model.py:29-30
@@ -142,7 +138,7 @@ class Encoder(nn.Module):
         self.mid.block_2 = ResnetBlock(in_channels=block_in, out_channels=block_in, dropout=dropout)
         self.norm_out = Normalize(block_in)
         self.conv_out = nn.Conv2d(block_in, 2 * z_channels if double_z else z_channels, 3, 1, 1)
-        self._packed, self._ws = None, None
+        self._packed, self._cs = None, None
         _cache.watch(self)
 
     def _apply(self, fn, *a, **k):
@@ -153,113 +149,17 @@ class Encoder(nn.Module):
     def _ensure_packed(self, dev):
         if _cache.fresh(self._packed, dev):
             return
-        gn = lambda g: (f32(g.weight, dev), f32(g.bias, dev), float(g.eps))
-
-        def res(b):
-            q = {'n1': gn(b.norm1), 'c1': _pack_conv3(b.conv1, dev), 'n2': gn(b.norm2), 'c2': _pack_conv3(b.conv2, dev)}
-            if hasattr(b, 'nin_shortcut'):
-                q['nin'] = _pack_lin(b.nin_shortcut.weight, b.nin_shortcut.bias, dev)
-            return q
+        res = lambda b: pack_resblock(b.norm1, b.conv1, b.norm2, b.conv2, dev, shortcut=getattr(b, 'nin_shortcut', None))
         P = {'device': dev}
-        P['conv_in'] = _pack_conv3(self.conv_in, dev, cin_pad=(self.in_channels + 7) // 8 * 8)
-        P['down'] = [{'blocks': [res(b) for b in d.block], 'down': _pack_conv3(d.downsample.conv, dev) if hasattr(d, 'downsample') else None}
+        P['conv_in'] = pack_conv3(self.conv_in, dev, cin_pad=(self.in_channels + 7) // 8 * 8)
+        P['down'] = [{'blocks': [res(b) for b in d.block], 'down': pack_conv3(d.downsample.conv, dev) if hasattr(d, 'downsample') else None}
                      for d in self.down]
         P['mid1'], P['mid2'] = res(self.mid.block_1), res(self.mid.block_2)
-        a = self.mid.attn_1
-        ln = lambda n: (f32(n.weight - 1.0, dev), f32(n.bias, dev), float(n.eps))           # y = LN(x) (1 + (w - 1)) + b
-        qkv = lambda at: _pack_lin(torch.cat([at.to_q.weight, at.to_k.weight, at.to_v.weight], 0), None, dev)
-        blocks = [{'n1': ln(b.norm1), 'n2': ln(b.norm2), 'n3': ln(b.norm3),
-                   'qkv1': qkv(b.attn1), 'o1': _pack_lin(b.attn1.to_out[0].weight, b.attn1.to_out[0].bias, dev),
-                   'qkv2': qkv(b.attn2), 'o2': _pack_lin(b.attn2.to_out[0].weight, b.attn2.to_out[0].bias, dev),
-                   'ff1': _pack_lin(b.ff.net[0].proj.weight, b.ff.net[0].proj.bias, dev),
-                   'ff2': _pack_lin(b.ff.net[2].weight, b.ff.net[2].bias, dev)} for b in a.transformer_blocks]
-        P['attn'] = {'n': gn(a.norm), 'pin': _pack_lin(a.proj_in.weight, a.proj_in.bias, dev),
-                     'pout': _pack_lin(a.proj_out.weight, a.proj_out.bias, dev), 'blocks': blocks, 'heads': a.n_heads, 'dh': a.d_head}
-        P['norm_out'] = gn(self.norm_out)
-        P['conv_out'] = _pack_conv3(self.conv_out, dev)
+        P['attn'] = pack_transformer(self.mid.attn_1, False, dev)
+        P['norm_out'] = pack_gn(self.norm_out, dev)
+        P['conv_out'] = pack_conv3(self.conv_out, dev)
         self._packed = _cache.stamp(P, self)
-        self._ws = Workspace(dev)
-
-    # ------------------------------------------------------------------ pieces (h: f32 [N*H*W, C] channel-last)
-    def _new(self, rows, cols, dtype=torch.float32):
-        return torch.empty(rows, cols, device=self._packed['device'], dtype=dtype)
-
-    def _bf(self, h):
-        y = torch.empty_like(h, dtype=torch.bfloat16)
-        ops.cast_bf16(h, y)
-        return y
-
-    def _gn(self, h, nw, N, HW, C, swish):
-        y = self._new(N * HW, C, torch.bfloat16)
-        st = torch.empty(N * 64 * (1 + (HW + 255) // 256), device=h.device, dtype=torch.float32)    # sums + per-chunk partials (ln3d.h)
-        ops.groupnorm_swish(h, nw[0], nw[1], y, st, N, HW, C, 32, nw[2], swish)
-        return y
-
-    def _conv3(self, a_bf, N, H, W, pc, out, epi=ops.EPI_F32):
-        col = self._new(N * H * W, pc['kpad'], torch.bfloat16)
-        ops.im2col3x3(a_bf, col, N, H, W, pc['cin'], 1, pc['kpad'])
-        ops.gemm(col, pc['w'], pc['b'], epi, out)
-
-    def _res(self, x, q, N, H, W):
-        cin, cout, HW = q['c1']['cin'], q['c1']['cout'], H * W
-        a = self._gn(x, q['n1'], N, HW, cin, True)
-        t = self._new(N * HW, cout)
-        self._conv3(a, N, H, W, q['c1'], t)
-        a2 = self._gn(t, q['n2'], N, HW, cout, True)
-        if 'nin' in q:
-            s = self._new(N * HW, cout)
-            ops.gemm(self._bf(x), q['nin']['w'], q['nin']['b'], ops.EPI_F32, s)
-        else:
-            s = x                                   # the block's input is not needed again: the residual lands in place
-        self._conv3(a2, N, H, W, q['c2'], s, epi=ops.EPI_GATE_RES)
-        return s
-
-    def _down(self, h, pc, N, H, W):
-        Ho, Wo = (H - 2) // 2 + 1, (W - 2) // 2 + 1
-        col = self._new(N * Ho * Wo, pc['kpad'], torch.bfloat16)
-        ops.im2col3x3_pad01(self._bf(h), col, N, H, W, pc['cin'], pc['kpad'])
-        out = self._new(N * Ho * Wo, pc['cout'])
-        ops.gemm(col, pc['w'], pc['b'], ops.EPI_F32, out)
-        return out, Ho, Wo
-
-    def _self_attend(self, a_bf, qkv, Bo, L, heads, dh, tag):
-        """Self-attention of Bo sequences of L tokens (rows of a_bf in sequence order) -> bf16 [Bo*L, heads*dh]."""
-        inner = heads * dh
-        if dh % 8 == 0 and dh <= 128 and L >= _MFMA_MIN_TOKENS and L % 32 == 0:
-            return self_attention_hip(self._ws, tag, a_bf, Bo, L, inner, heads, qkv['w'], qkv['b'])
-        if L > 1024:
-            raise ValueError(f"SpatialTransformer3D: {L} tokens per sequence need the MFMA attention kernels (a multiple of 32, head size "
-                             f"a multiple of 8 up to 128); got head size {dh}")
-        y = self._new(Bo * L, 3 * inner, torch.bfloat16)
-        ops.gemm(a_bf, qkv['w'], None, ops.EPI_BF16, y)
-        o = self._new(Bo * L, inner, torch.bfloat16)
-        ops.attention_small(y, y[:, inner:], y[:, 2 * inner:], o, Bo, heads, L, L, dh, 3 * inner, 3 * inner, 3 * inner, dh ** -0.5)
-        return o
-
-    def _transformer(self, h, q, N, H, W, F):
-        HW, C = H * W, h.shape[1]
-        heads, dh = q['heads'], q['dh']
-        inner, rows = heads * dh, N * HW
-        a = self._gn(h, q['n'], N, HW, C, False)
-        tok = self._new(rows, inner)
-        ops.gemm(a, q['pin']['w'], q['pin']['b'], ops.EPI_F32, tok)
-        for b in q['blocks']:
-            def ln(nw):
-                y = self._new(rows, inner, torch.bfloat16)
-                ops.norm_modulate(tok, y, rows, inner, kind=0, eps=nw[2], shift=nw[1], scale=nw[0], mod_rows=rows, mod_ld=0)
-                return y
-            # attn1 over the F frames of each object jointly: rows are (object, frame, pixel), so `(b f) l c -> b (f l) c` is a view
-            o = self._self_attend(ln(b['n1']), b['qkv1'], N // F, F * HW, heads, dh, 'j%d_' % F)
-            ops.gemm(o, b['o1']['w'], b['o1']['b'], ops.EPI_GATE_RES, tok)
-            o = self._self_attend(ln(b['n2']), b['qkv2'], N, HW, heads, dh, 'f_')                 # attn2: within each frame
-            ops.gemm(o, b['o2']['w'], b['o2']['b'], ops.EPI_GATE_RES, tok)
-            g = self._new(rows, b['ff1']['cout'])
-            ops.gemm(ln(b['n3']), b['ff1']['w'], b['ff1']['b'], ops.EPI_F32, g)
-            gg = self._new(rows, b['ff1']['cout'] // 2, torch.bfloat16)
-            ops.geglu(g, gg, rows, b['ff1']['cout'] // 2)
-            ops.gemm(gg, b['ff2']['w'], b['ff2']['b'], ops.EPI_GATE_RES, tok)
-        ops.gemm(self._bf(tok), q['pout']['w'], q['pout']['b'], ops.EPI_GATE_RES, h)
-        return h
+        self._cs = ConvStack(dev, empty_alloc(dev), who='SpatialTransformer3D')
 
     # ------------------------------------------------------------------ forward
     def _check_input(self, x, F):
@@ -282,11 +182,12 @@ class Encoder(nn.Module):
         self._ensure_packed(dev)
         P = self._packed
         N, Cin, H, W = x.shape
-        pc = P['conv_in']
-        x_cl = self._new(N * H * W, pc['cin'], torch.bfloat16)
+        cs, pc = self._cs, P['conv_in']
+        new = lambda rows, cols, dtype=torch.float32: torch.empty(rows, cols, device=dev, dtype=dtype)
+        x_cl = new(N * H * W, pc['cin'], torch.bfloat16)
         ops.nchw_to_cl_bf16(x.contiguous().float(), x_cl, N, Cin, H * W, pc['cin'])
-        h = self._new(N * H * W, pc['cout'])
-        self._conv3(x_cl, N, H, W, pc, h)
+        h = new(N * H * W, pc['cout'])
+        cs.conv3(x_cl, N, H, W, pc, h)
 
         def keep(name, t, H, W):
             if stages is not None:
@@ -294,20 +195,27 @@ class Encoder(nn.Module):
         keep('conv_in', h, H, W)
         for lvl, d in enumerate(P['down']):
             for q in d['blocks']:
-                h = self._res(h, q, N, H, W)
+                h = cs.res(h, q, N, H, W)
             keep(f'down{lvl}', h, H, W)
-            if d['down'] is not None:
-                h, H, W = self._down(h, d['down'], N, H, W)
+            if d['down'] is not None:                   # Downsample: pad (0,1,0,1), stride 2, padding 0
+                a = cs.bf(h)
+                h = new(N * ((H - 2) // 2 + 1) * ((W - 2) // 2 + 1), d['down']['cout'])
+                H, W = cs.conv3(a, N, H, W, d['down'], h, pad01=True)
                 keep(f'down{lvl}_ds', h, H, W)
-        h = self._res(h, P['mid1'], N, H, W)
+        h = cs.res(h, P['mid1'], N, H, W)
         keep('mid_block_1', h, H, W)
-        h = self._transformer(h, P['attn'], N, H, W, F)
+        att = P['attn']
+
+        def attn2(a, b):                                # within each frame
+            o, padded = cs.self_attend(a, b['qkv2'], N, H * W, att['heads'], att['dh'], 'f_')
+            return o, b['o2p' if padded else 'o2']
+        h = cs.transformer(h, att, N, H, W, attn2, frames=F)
         keep('mid_attn_1', h, H, W)
-        h = self._res(h, P['mid2'], N, H, W)
+        h = cs.res(h, P['mid2'], N, H, W)
         keep('mid_block_2', h, H, W)
-        a = self._gn(h, P['norm_out'], N, H * W, h.shape[1], True)
-        out = self._new(N * H * W, P['conv_out']['cout'])
-        self._conv3(a, N, H, W, P['conv_out'], out)
+        a = cs.gn(h, P['norm_out'], N, H * W, h.shape[1], True)
+        out = new(N * H * W, P['conv_out']['cout'])
+        cs.conv3(a, N, H, W, P['conv_out'], out)
         return out.view(N, H, W, -1).permute(0, 3, 1, 2)
 
     @torch.no_grad()

@@ -6,17 +6,18 @@ vit_decode_backbone :996, vit_decode_postprocess :1913, triplane_decode :1013, f
 triplane_decode_grid :2052; state-dict keys `superresolution.ldm_upsample.*`, `superresolution.conv_sr.*`
 (ldm Decoder: ldm/modules/diffusionmodules/model.py:625-745), `vit_decoder.*`, `triplane_decoder.decoder.*`.
 
-Everything runs channel-last on the device: the DiT2 token stream [B*3, 16*16, D] IS the NHWC input of the conv
-decoder, 3x3 convs are im2col (nearest-2x upsample fused into the gather) + the MFMA GEMM with bias /
-residual epilogues, GroupNorm+swish is one stats + one apply pass, and the decoder's last GEMM writes the
-planes directly in the [B,3,H,W,32] layout the ray-marcher gathers from (the reference layout [B,96,H,W] is
-produced only when a caller asks for `latent_after_vit`)."""
+Everything runs channel-last on the device: the DiT2 token stream [B*3, 16*16, D] IS the NHWC input of the conv decoder, whose blocks
+(3x3 conv as im2col + GEMM with the nearest-2x upsample fused into the gather, GroupNorm+swish, ResnetBlock) and their launch
+sequences are those of ln3diff_amd/convstack.py, on scratch from this decoder's Workspace.  The decoder's last GEMM writes the planes
+directly in the [B,3,H,W,32] layout the ray-marcher gathers from (the reference layout [B,96,H,W] is produced only when a caller
+asks for `latent_after_vit`)."""
 import torch
 import torch.nn as nn
 
 from .. import ops, _cache
+from ..convstack import ConvStack, pack_conv3, pack_gn, pack_lin, pack_resblock
 from ..dit.dit_decoder import DiT2
-from ..dit.dit_models_xformers import Workspace, bf16, f32
+from ..dit.dit_models_xformers import Workspace, f32, self_attention_hip
 from ..nsr.triplane import Triplane
 
 
@@ -96,20 +97,6 @@ class PatchEmbedTriplane(nn.Module):
     def __init__(self, img_size=32, patch_size=2, in_chans=12, embed_dim=768):
         super().__init__()
         self.proj = nn.Conv2d(in_chans, embed_dim * 3, kernel_size=patch_size, stride=patch_size, groups=3)
-
-
-def _pack_conv3(conv, device):
-    w = conv.weight.detach()                                   # [Cout, Cin, 3, 3] -> [Cout, (ky,kx,c)]
-    co, ci = w.shape[0], w.shape[1]
-    k = 9 * ci
-    kpad = (k + 63) // 64 * 64
-    m = torch.zeros(co, kpad)
-    m[:, :k] = w.permute(0, 2, 3, 1).reshape(co, k).float().cpu()
-    return {'w': bf16(m, device), 'b': f32(conv.bias, device), 'kpad': kpad, 'cin': ci, 'cout': co}
-
-
-def _pack_conv1(conv, device):
-    return {'w': bf16(conv.weight.detach().reshape(conv.weight.shape[0], -1), device), 'b': f32(conv.bias, device)}
 
 
 class _RendererSeams:
@@ -222,7 +209,7 @@ class RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout
             conv_sr=Decoder(ch=32, out_ch=32, ch_mult=[1, 2, 2, 4], num_res_blocks=1, z_channels=D)))
         self.rendering_kwargs = triplane_decoder.rendering_kwargs
         self._packed = None
-        self._ws = None
+        self._ws = self._cs = None
         _cache.watch(self)
 
     def _apply(self, fn, *a, **k):
@@ -237,74 +224,32 @@ class RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout
         P = {'device': dev}
         P['pe_w'], P['pe_b'] = f32(sr['ldm_upsample'].proj.weight, dev), f32(sr['ldm_upsample'].proj.bias, dev)
         d = sr['conv_sr']
-
-        def res(b):
-            q = {'n1': (f32(b.norm1.weight, dev), f32(b.norm1.bias, dev)), 'c1': _pack_conv3(b.conv1, dev),
-                 'n2': (f32(b.norm2.weight, dev), f32(b.norm2.bias, dev)), 'c2': _pack_conv3(b.conv2, dev)}
-            if hasattr(b, 'nin_shortcut'):
-                q['nin'] = _pack_conv1(b.nin_shortcut, dev)
-            return q
-        P['conv_in'] = _pack_conv3(d.conv_in, dev)
+        gn = lambda g: pack_gn(g, dev, eps=1e-6)            # the _GN containers carry no eps
+        res = lambda b: pack_resblock(b.norm1, b.conv1, b.norm2, b.conv2, dev, shortcut=getattr(b, 'nin_shortcut', None), eps=1e-6)
+        P['conv_in'] = pack_conv3(d.conv_in, dev)
         P['mid1'], P['mid2'] = res(d.mid.block_1), res(d.mid.block_2)
         a = d.mid.attn_1
-        P['attn'] = {'n': (f32(a.norm.weight, dev), f32(a.norm.bias, dev)),
-                     'qkv_w': bf16(torch.cat([a.q.weight, a.k.weight, a.v.weight], 0).reshape(3 * a.q.weight.shape[0], -1), dev),
-                     'qkv_b': f32(torch.cat([a.q.bias, a.k.bias, a.v.bias], 0), dev),
-                     'proj': _pack_conv1(a.proj_out, dev)}
+        P['attn'] = {'n': gn(a.norm), 'qkv': pack_lin(torch.cat([a.q.weight, a.k.weight, a.v.weight], 0),
+                                                       torch.cat([a.q.bias, a.k.bias, a.v.bias], 0), dev),
+                     'proj': pack_lin(a.proj_out.weight, a.proj_out.bias, dev)}
         P['up'] = []
         for lvl in range(d.num_resolutions):
             u = d.up[lvl]
             q = {'blocks': [res(b) for b in u.block]}
             if hasattr(u, 'upsample'):
-                q['upsample'] = _pack_conv3(u.upsample.conv, dev)
+                q['upsample'] = pack_conv3(u.upsample.conv, dev)
             P['up'].append(q)
-        P['norm_out'] = (f32(d.norm_out.weight, dev), f32(d.norm_out.bias, dev))
-        P['conv_out'] = _pack_conv3(d.conv_out, dev)
+        P['norm_out'] = gn(d.norm_out)
+        P['conv_out'] = pack_conv3(d.conv_out, dev)
         self._packed = _cache.stamp(P, self)
         self._ws = Workspace(dev)
-
-    # ------------------------------------------------------------------ conv decoder pieces (channel-last)
-    def _conv3(self, x_bf, N, H, W, pc, up, out, epi=ops.EPI_F32):
-        ws = self._ws
-        rows = N * H * up * W * up
-        col = ws.get('col', (rows, pc['kpad']), torch.bfloat16)
-        ops.im2col3x3(x_bf, col, N, H, W, pc['cin'], up, pc['kpad'])
-        ops.gemm(col, pc['w'], pc['b'], epi, out)
-
-    def _gn(self, x, nw, N, HW, C, swish=True):
-        ws = self._ws
-        y = ws.get('gn', (N * HW, C), torch.bfloat16)
-        st = ws.get('gn_stats', (N * 64 * (1 + (HW + 255) // 256),), torch.float32)        # sums + per-chunk partials (ln3d.h)
-        ops.groupnorm_swish(x, nw[0], nw[1], y, st, N, HW, C, 32, 1e-6, swish)
-        return y
-
-    def _resblock(self, x, q, N, H, W):
-        ws = self._ws
-        cin, cout = q['c1']['cin'], q['c1']['cout']
-        HW = H * W
-        h = self._gn(x, q['n1'], N, HW, cin)
-        t = ws.get(f'res_t', (N * HW, cout), torch.float32)
-        self._conv3(h, N, H, W, q['c1'], 1, t)
-        h2 = self._gn(t, q['n2'], N, HW, cout)
-        if 'nin' in q:
-            xb = ws.get('res_xb', (N * HW, cin), torch.bfloat16)
-            ops.cast_bf16(x, xb)
-            x = ws.get(f'res_x{cout}_{HW}', (N * HW, cout), torch.float32)
-            ops.gemm(xb, q['nin']['w'], q['nin']['b'], ops.EPI_F32, x)
-        self._conv3(h2, N, H, W, q['c2'], 1, x, epi=ops.EPI_GATE_RES)
-        return x
+        self._cs = ConvStack(dev, self._ws.get, ws=self._ws)             # scratch by name from the workspace: nothing is allocated after the first decode
 
     def _attn(self, x, q, N, H, W):
-        ws = self._ws
-        C, HW = 128, H * W
-        h = self._gn(x, q['n'], N, HW, C, swish=False)
-        qq = ws.get('ca_q', (N, 1, HW, C), torch.bfloat16)
-        kk = ws.get('ca_k', (N, 1, HW, C), torch.bfloat16)
-        vt = ws.get('ca_vt', (N, 1, C, HW), torch.bfloat16)
-        ops.gemm(h, q['qkv_w'], q['qkv_b'], ops.EPI_HEADS, qq, kk, vt, M=N * HW, tokens=HW, tok_pad=HW, heads=1,
-                 head_dim=C, transpose_mask=0b100)
-        o = ws.get('ca_o', (N * HW, C), torch.bfloat16)
-        ops.attention(qq, kk, vt, o, N, 1, HW, HW, HW, HW, C)
+        """mid.attn_1: one head as wide as the block (128 in the released decoder), on the MFMA attention kernels at any token count."""
+        C, HW = q['proj']['cout'], H * W
+        h = self._cs.gn(x, q['n'], N, HW, C, False)
+        o = self_attention_hip(self._ws, 'ca_', h, N, HW, C, 1, q['qkv']['w'], q['qkv']['b'])
         ops.gemm(o, q['proj']['w'], q['proj']['b'], ops.EPI_GATE_RES, x)
         return x
 
@@ -328,30 +273,27 @@ class RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout
 
     @torch.no_grad()
     def vit_decode_postprocess(self, latent_from_vit, ret_dict: dict, want_nchw=True):
-        P, ws = self._packed, self._ws
+        P, ws, cs = self._packed, self._ws, self._cs
         B, L, D = latent_from_vit.shape
         N, H, W = B * 3, 16, 16
-        xb = ws.get('tok_bf', (N * H * W, D), torch.bfloat16)
-        ops.cast_bf16(latent_from_vit.reshape(-1, D), xb)
+        xb = cs.bf(latent_from_vit.reshape(-1, D), 'tok_bf')
         x = ws.get('dec_x128_256', (N * H * W, 128), torch.float32)
-        self._conv3(xb, N, H, W, P['conv_in'], 1, x)
-        x = self._resblock(x, P['mid1'], N, H, W)
+        cs.conv3(xb, N, H, W, P['conv_in'], x)
+        x = cs.res(x, P['mid1'], N, H, W)
         x = self._attn(x, P['attn'], N, H, W)
-        x = self._resblock(x, P['mid2'], N, H, W)
+        x = cs.res(x, P['mid2'], N, H, W)
         for lvl in reversed(range(len(P['up']))):
             u = P['up'][lvl]
             for q in u['blocks']:
-                x = self._resblock(x, q, N, H, W)
+                x = cs.res(x, q, N, H, W)
             if 'upsample' in u:
                 C = u['upsample']['cin']
-                xb2 = ws.get('up_xb', (N * H * W, C), torch.bfloat16)
-                ops.cast_bf16(x, xb2)
+                xb2 = cs.bf(x, 'up_xb')
                 x = ws.get(f'up_x{C}_{H * 2}', (N * H * W * 4, C), torch.float32)
-                self._conv3(xb2, N, H, W, u['upsample'], 2, x)
-                H, W = H * 2, W * 2
-        h = self._gn(x, P['norm_out'], N, H * W, 32)
+                H, W = cs.conv3(xb2, N, H, W, u['upsample'], x, up=2)
+        h = cs.gn(x, P['norm_out'], N, H * W, 32, True)
         planes_cl = torch.empty(B, 3, H, W, 32, device=x.device, dtype=torch.float32)
-        self._conv3(h, N, H, W, P['conv_out'], 1, planes_cl)
+        cs.conv3(h, N, H, W, P['conv_out'], planes_cl)
         ret_dict.update(dict(cls_token=None, planes_channel_last=planes_cl))
         if want_nchw:
             nchw = torch.empty(B, 96, H, W, device=x.device, dtype=torch.float32)

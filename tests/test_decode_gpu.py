@@ -76,7 +76,7 @@ def test_conv_decoder_stages_vs_bf16_operand_oracle(hip_lib):
     sd, _ = load_synth(dec, 0)
     dec = dec.cuda()
     dec._ensure_packed(torch.device('cuda'))
-    P, pre = dec._packed, 'superresolution.conv_sr.'
+    P, cs, pre = dec._packed, dec._cs, 'superresolution.conv_sr.'
     cl = lambda x: x.permute(0, 2, 3, 1).reshape(-1, x.shape[1]).contiguous()                   # NCHW -> [N*H*W, C]
     nchw = lambda y, N, H, W: y.reshape(N, H, W, -1).permute(0, 3, 1, 2)
     g = torch.Generator().manual_seed(11)
@@ -86,7 +86,7 @@ def test_conv_decoder_stages_vs_bf16_operand_oracle(hip_lib):
               ('up.2.block.0.', P['up'][2]['blocks'][0], 32), ('up.0.block.0.', P['up'][0]['blocks'][0], 32)]
     for name, q, H in stages:
         x = torch.randn(N, q['c1']['cin'], H, H, generator=g)
-        y = dec._resblock(cl(x).cuda(), q, N, H, H).clone()
+        y = cs.res(cl(x).cuda(), q, N, H, H).clone()
         with odit.operand_rounding(torch.bfloat16):
             y_or = odec.resnet_block(sd, pre + name, x)
         e = rel_l2(nchw(y.cpu(), N, H, H), y_or)
@@ -104,16 +104,16 @@ def test_conv_decoder_stages_vs_bf16_operand_oracle(hip_lib):
     xb = torch.empty(N * 256, u['cin'], dtype=torch.bfloat16, device='cuda')
     ops.cast_bf16(cl(x).cuda(), xb)
     y = torch.empty(N * 1024, u['cout'], device='cuda')
-    dec._conv3(xb, N, 16, 16, u, 2, y)
+    cs.conv3(xb, N, 16, 16, u, y, up=2)
     with odit.operand_rounding(torch.bfloat16):
         y_or = odec._conv(torch.nn.functional.interpolate(x, scale_factor=2.0, mode='nearest'), sd, pre + 'up.3.upsample.conv.', 1)
     e = rel_l2(nchw(y.cpu(), N, 32, 32), y_or)
     print('upsample + conv', e)
     worst = max(worst, e)
     x = torch.randn(N, 32, 32, 32, generator=g)
-    h = dec._gn(cl(x).cuda(), P['norm_out'], N, 1024, 32)
+    h = cs.gn(cl(x).cuda(), P['norm_out'], N, 1024, 32, True)
     y = torch.empty(N * 1024, 32, device='cuda')
-    dec._conv3(h, N, 32, 32, P['conv_out'], 1, y)
+    cs.conv3(h, N, 32, 32, P['conv_out'], y)
     with odit.operand_rounding(torch.bfloat16):
         y_or = odec._conv(odec._swish(odec._gn(x, sd, pre + 'norm_out.')), sd, pre + 'conv_out.', 1)
     e = rel_l2(nchw(y.cpu(), N, 32, 32), y_or)

@@ -214,6 +214,40 @@ def test_released_size_vs_reference_golden(hip_lib):
         assert e < 1e-2, e
 
 
+def _two_route_difference(d_head):
+    """An encoder with 8 heads of d_head on 2 objects x 5 frames at 64 x 64: 8 x 8 middle tokens per frame, so attn1 attends 320 joint
+    tokens (the MFMA attention kernels) and attn2 64 (ln3d_attention_small).  -> rel-L2 between that forward and the same forward with
+    the threshold raised so that attn1 runs on ln3d_attention_small too."""
+    from ln3diff_amd import convstack
+    from ln3diff_amd.vit.mv_encoder import MVEncoderGSDynamicInp
+    enc = MVEncoderGSDynamicInp(double_z=True, resolution=64, in_channels=10, ch=32, ch_mult=[1, 2, 4, 4], num_res_blocks=1, num_frames=5,
+                                dropout=0.0, attn_resolutions=[], out_ch=3, z_channels=12, attn_kwargs={'n_heads': 8, 'd_head': d_head})
+    load_synth(enc, 0)
+    enc = enc.cuda()
+    x = _input('mv_heads', (10, 10, 64, 64), 12)
+    y_mfma = enc.forward_frames(x).clone()
+    saved = convstack.MFMA_MIN_TOKENS
+    convstack.MFMA_MIN_TOKENS = 1 << 30
+    try:
+        y_small = enc.forward_frames(x).clone()
+    finally:
+        convstack.MFMA_MIN_TOKENS = saved
+    assert torch.isfinite(y_mfma).all() and not torch.equal(y_mfma, y_small)        # two routes did run
+    return rel_l2(y_mfma, y_small)
+
+
+def test_head_size_48_takes_the_padded_output_projection(hip_lib):
+    """d_head = 48 runs on the MFMA route in 64-wide zero-padded heads, so attn1's output has 8 x 64 columns and meets the zero-padded
+    copy of to_out; the unpadded 384-column weight would raise on the GEMM's K mismatch.  (ch = 32 also makes down.1's nin_shortcut a
+    1x1 with 32 input channels, below the GEMM's K step: it runs as the centre tap of a 3x3.)  The two routes must agree as closely as
+    they do at the released d_head = 64, which needs no padded copy: _two_route_difference(64) measured 2.770e-3 on an MI355X (2.725e-3
+    with weight seed 1; d_head = 48 itself: 2.636e-3).  The gate is twice the d_head = 64 figure, one factor of two for the different
+    weights the seeded filler gives another width."""
+    e = _two_route_difference(48)
+    print(f'd_head 48: MFMA route vs attention_small route rel-L2 {e:.3e}')
+    assert e < 2 * 2.770e-3, e                 # 2 x the measured d_head = 64 figure
+
+
 # ----------------------------------------------------------------------------- end to end
 def _ae():
     from ln3diff_amd.nsr.script_util import AE

@@ -6,7 +6,7 @@ import runpy
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from ln3diff_amd.guided_diffusion import unet  # noqa: E402
-unet._MFMA_MIN_TOKENS = 1 << 30
+from ln3diff_amd import convstack  # noqa: E402
+convstack.MFMA_MIN_TOKENS = 1 << 30
 sys.argv = [os.path.join(ROOT, 'bench.py')] + sys.argv[1:]
 runpy.run_path(os.path.join(ROOT, 'bench.py'), run_name='__main__')
