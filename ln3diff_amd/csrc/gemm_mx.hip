@@ -24,6 +24,9 @@ __device__ __forceinline__ int mx_exp(float amax) {
   const int be = (int)((__float_as_uint(amax) >> 23) & 0xffu);
   return be == 0 ? -127 : max(be - 135, -127);                       // be <= 254: e <= 119, the upper clamp never binds
 }
+// non-finite rule (ln3d_mx.h): NaN and +-Inf take no part in a block's amax and are stored as the E4M3 NaN code with their sign
+__device__ __forceinline__ bool mx_nonfinite(float x) { return __builtin_amdgcn_class(x, 0x207); }      // sNaN | qNaN | -Inf | +Inf
+__device__ __forceinline__ float mx_fin_abs(float x) { return mx_nonfinite(x) ? 0.f : fabsf(x); }
 // v (already divided by the block scale) -> OCP e4m3fn bits: saturate to 448, round to nearest even, subnormals below 2^-6
 __device__ __forceinline__ uint32_t e4m3_rne(float v) {
   const uint32_t sign = (__float_as_uint(v) >> 24) & 0x80u;
@@ -33,7 +36,16 @@ __device__ __forceinline__ uint32_t e4m3_rne(float v) {
   u += 0x7ffffu + ((u >> 20) & 1u);                                          // RNE to 3 mantissa bits (448 is representable)
   return sign | (((u >> 23) - 120u) << 3) | ((u >> 20) & 7u);
 }
+// x / 2^e -> e4m3 bits; the class and the sign of a non-finite x are taken from x itself, not from the scaled value
+__device__ __forceinline__ uint32_t e4m3_of(float x, int e) {
+  const uint32_t c = e4m3_rne(__builtin_amdgcn_ldexpf(x, -e));
+  return mx_nonfinite(x) ? (((__float_as_uint(x) >> 24) & 0x80u) | 0x7fu) : c;
+}
 __device__ __forceinline__ uint32_t e4m3x4(float a, float b, float c, float d, int e) {
+  return e4m3_of(a, e) | (e4m3_of(b, e) << 8) | (e4m3_of(c, e) << 16) | (e4m3_of(d, e) << 24);
+}
+// the same for finite input only (the GELU epilogue: the class test and the two selects per element cost fc1 2.5 %, profiles/mx_elements.md)
+__device__ __forceinline__ uint32_t e4m3x4_finite(float a, float b, float c, float d, int e) {
   return e4m3_rne(__builtin_amdgcn_ldexpf(a, -e)) | (e4m3_rne(__builtin_amdgcn_ldexpf(b, -e)) << 8) |
          (e4m3_rne(__builtin_amdgcn_ldexpf(c, -e)) << 16) | (e4m3_rne(__builtin_amdgcn_ldexpf(d, -e)) << 24);
 }
@@ -58,7 +70,7 @@ __global__ __launch_bounds__(256) void quantize_mx_kernel(const void* x, int64_t
   }
   float amax = 0.f;
 #pragma unroll
-  for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
+  for (int i = 0; i < 32; ++i) amax = fmaxf(amax, mx_fin_abs(v[i]));
   const int e = mx_exp(amax);
   uint32_t w[8];
 #pragma unroll
@@ -121,7 +133,7 @@ __global__ __launch_bounds__(256) void norm_modulate_mx_kernel(NormMxP p) {
   for (int i = 0; i < MV8; ++i)
 #pragma unroll
     for (int k = 0; k < 2; ++k) s += (v[i][k].x + v[i][k].y) + (v[i][k].z + v[i][k].w);
-  float mean = 0.f, rstd;
+  float mean = 0.f, var;
   if (p.kind == 0) {
     mean = wave_sum_dpp(s) / p.D;
     float q = 0.f;
@@ -134,7 +146,7 @@ __global__ __launch_bounds__(256) void norm_modulate_mx_kernel(NormMxP p) {
           q += (a * a + b * b) + (c * c + d * d);
         }
       }
-    rstd = rsqrtf(wave_sum_dpp(q) / p.D + p.eps);
+    var = wave_sum_dpp(q) / p.D;
   } else {
     float q = 0.f;
 #pragma unroll
@@ -142,8 +154,11 @@ __global__ __launch_bounds__(256) void norm_modulate_mx_kernel(NormMxP p) {
 #pragma unroll
       for (int k = 0; k < 2; ++k)
         q += (v[i][k].x * v[i][k].x + v[i][k].y * v[i][k].y) + (v[i][k].z * v[i][k].z + v[i][k].w * v[i][k].w);
-    rstd = rsqrtf(wave_sum_dpp(q) / p.D + p.eps);
+    var = wave_sum_dpp(q) / p.D;
   }
+  // a row whose statistics are not finite (a NaN or Inf element, or squares that overflow f32) is NaN throughout: rsqrtf(Inf) = 0 would
+  // turn the finite elements of an RMSNorm row that holds an Inf into zeros
+  const float rstd = mx_nonfinite(var) ? __builtin_nanf("") : rsqrtf(var + p.eps);
 #pragma unroll
   for (int i = 0; i < MV8; ++i) {
     if (FULL && !ok[i]) continue;                                       // wave-uniform
@@ -161,7 +176,7 @@ __global__ __launch_bounds__(256) void norm_modulate_mx_kernel(NormMxP p) {
         o[k].x = o[k].x * (1.f + sc[i][k].x) + sh[i][k].x; o[k].y = o[k].y * (1.f + sc[i][k].y) + sh[i][k].y;
         o[k].z = o[k].z * (1.f + sc[i][k].z) + sh[i][k].z; o[k].w = o[k].w * (1.f + sc[i][k].w) + sh[i][k].w;
       }
-      amax = fmaxf(amax, fmaxf(fmaxf(fabsf(o[k].x), fabsf(o[k].y)), fmaxf(fabsf(o[k].z), fabsf(o[k].w))));
+      amax = fmaxf(amax, fmaxf(fmaxf(mx_fin_abs(o[k].x), mx_fin_abs(o[k].y)), fmaxf(mx_fin_abs(o[k].z), mx_fin_abs(o[k].w))));
     }
     amax = fmaxf(amax, __shfl_xor(amax, 1, 64));                        // a quad = one 32-feature block (D % 128 == 0: whole quads
     amax = fmaxf(amax, __shfl_xor(amax, 2, 64));                        // are in or out together)
@@ -213,6 +228,7 @@ __device__ __forceinline__ void lds_dma4_v(const void* vaddr, uint32_t lds) {
 
 // erf-GELU with an MXFP8 output, straight from the accumulators: acc[i][j] is one 32-feature block (= one MX block) of 32 tokens, a
 // lane holds 16 of its features and lane l ^ 32 the other 16
+// Finite input assumed (ln3d_mx.h): a NaN accumulator is stored as +-448 and skipped by the amax, an Inf zeroes its block's neighbours.
 template <int NJ>
 __device__ __forceinline__ void gelu_mx_epilogue(const MxP& p, f32x16 (&acc)[2][NJ], int fw0, int tw0, int lane) {
   const int l31 = lane & 31, hi = lane >> 5;
@@ -244,7 +260,7 @@ __device__ __forceinline__ void gelu_mx_epilogue(const MxP& p, f32x16 (&acc)[2][
         uint8_t* orow = (uint8_t*)g.out0 + (int64_t)tok * g.ldo + fblk;
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-          *reinterpret_cast<uint32_t*>(orow + 8 * q + 4 * hi) = e4m3x4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3], e);
+          *reinterpret_cast<uint32_t*>(orow + 8 * q + 4 * hi) = e4m3x4_finite(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3], e);
         if (hi == 0) p.os[(int64_t)tok * p.ldos + fblk / 32] = (uint8_t)(e + 127);
       }
     }
@@ -443,6 +459,8 @@ extern "C" int ln3d_gemm_mxfp8(const ln3d_gemm_mx_args* a, void* stream) {
       if (!a->out1 || !a->out2 || a->tokens <= 0 || a->heads <= 0 || a->head_dim <= 0 || (a->head_dim % 8) != 0 || a->tok_pad < a->tokens ||
           g.head_dim_pad < a->head_dim || ((a->heads * a->head_dim) % 64) != 0 || a->N != 3 * a->heads * a->head_dim || (a->M % a->tokens) != 0)
         return LN3D_ERR_BAD_ARG;
+      // a transposed output stores token t of a 16-group at t with bits 2 and 3 swapped: a row that ends inside a group would be overrun
+      if ((a->transpose_mask & 7) != 0 && (a->tok_pad % 16) != 0) return LN3D_ERR_BAD_ARG;
       return run_mx<LN3D_EPI_HEADS>(p, s);
     default: return LN3D_ERR_UNSUPPORTED;
   }

@@ -20,19 +20,24 @@ I64 = C.c_int64
 # ------------------------------------------------------------------------------------------------------------ reference quantizer
 def quantize_mx_ref(x):
     """x [R, K] (any float dtype, K % 32 == 0) -> (q uint8 [R, K] e4m3fn bits, s uint8 [R, K / 32] E8M0 bits).
-    e = floor(log2(amax)) - 8 clamped to [-127, 127] (all-zero block: -127); element = RNE(x / 2^e) saturated to +-448."""
+    e = floor(log2(amax)) - 8 clamped to [-127, 127] (all-zero block: -127); element = RNE(x / 2^e) saturated to +-448.
+    Non-finite values: amax is taken over the finite elements of a block (none, or only zeros: e = -127), a NaN or +-Inf element is
+    the E4M3 NaN code with its sign (0x7F / 0xFF), the finite elements of the block are quantized as if it were not there."""
     x = x.float()
     R, K = x.shape
     xb = x.reshape(R, K // 32, 32)
-    amax = xb.abs().amax(-1)
+    fin = torch.isfinite(xb)
+    xf = torch.where(fin, xb, torch.zeros_like(xb))
+    amax = xf.abs().amax(-1)
     _, ex = torch.frexp(amax)                                      # amax = m 2^ex, m in [0.5, 1): floor(log2 amax) = ex - 1 (exact)
     e = torch.where(amax > 0, ex - 1 - 8, torch.full_like(ex, -127)).clamp(-127, 127)
     scale = torch.ldexp(torch.ones_like(amax), e.float())          # 2^e (2^-127 is an f32 subnormal: exact)
     s = (e + 127).to(torch.uint8)
     assert torch.equal(s.view(torch.float8_e8m0fnu).float(), scale)   # the byte IS the E8M0 encoding of the scale
-    v = torch.ldexp(xb, -e.float()[..., None]).clamp(-448.0, 448.0)
-    q = v.to(torch.float8_e4m3fn).view(torch.uint8).reshape(R, K)
-    return q, s
+    v = torch.ldexp(xf, -e.float()[..., None]).clamp(-448.0, 448.0)
+    q = v.to(torch.float8_e4m3fn).view(torch.uint8)
+    nan_code = torch.where(torch.signbit(xb), torch.full_like(q, 0xFF), torch.full_like(q, 0x7F))
+    return torch.where(fin, q, nan_code).reshape(R, K), s
 
 
 def dequantize_mx(q, s):
@@ -85,6 +90,30 @@ def test_reference_quantizer_known_cases():
     x[0, 0], x[0, 1], x[0, 2] = 256.0, 1.0625 * 2 ** -8 * 256, 1.1875 * 2 ** -8 * 256
     q, s = quantize_mx_ref(x)
     assert q[0, 1] == 0x38 and q[0, 2] == 0x3A
+    # non-finite values (the rule of include/ln3d_mx.h).  A lone NaN / -Inf: its NaN code with the sign, no finite element -> byte 0
+    x = torch.zeros(2, 32)
+    x[0, 3], x[1, 31] = float('nan'), float('-inf')
+    q, s = quantize_mx_ref(x)
+    assert s.reshape(-1).tolist() == [0, 0] and q[0, 3] == 0x7F and q[1, 31] == 0xFF
+    assert int(q[0].sum()) == 0x7F and int(q[1].sum()) == 0xFF             # the zeros around them stay zero
+    x[0, 3] = -x[0, 3]                                                     # the sign of a NaN is kept
+    assert quantize_mx_ref(x)[0][0, 3] == 0xFF
+    # a block of NaN only next to an ordinary one: every element 0x7F, byte 0; the neighbour block is what it was
+    x = torch.full((1, 64), float('nan'))
+    x[0, 32:] = 1.0
+    q, s = quantize_mx_ref(x)
+    assert s[0].tolist() == [0, 119] and bool((q[0, :32] == 0x7F).all()) and bool((q[0, 32:] == 0x78).all())
+    # Inf next to finite values: their codes and the scale are those of the block without the Inf
+    x = torch.zeros(1, 32)
+    x[0, :6] = torch.tensor([4.0, 2.0, 1.0, 0.5, -0.25, 0.0])
+    q0, s0 = quantize_mx_ref(x)
+    x[0, 5], x[0, 9], x[0, 10] = float('inf'), float('-inf'), float('nan')
+    q, s = quantize_mx_ref(x)
+    assert torch.equal(s, s0) and q[0, :5].tolist() == q0[0, :5].tolist() == [0x78, 0x70, 0x68, 0x60, 0xD8]
+    assert q[0, 5] == 0x7F and q[0, 9] == 0xFF and q[0, 10] == 0x7F and int(q[0, 11:].max()) == 0 and int(q[0, 6:9].max()) == 0
+    xb = x.bfloat16()                                                      # bf16 input: the same classes (the NaN written as bits:
+    xb.view(torch.int16)[0, 10] = 0x7FC0                                   # torch's f32 -> bf16 cast of a NaN does not keep its sign)
+    assert torch.equal(quantize_mx_ref(xb)[0], q)
 
 
 # ------------------------------------------------------------------------------------------------------------ C ABI
@@ -125,6 +154,9 @@ def test_mx_shape_rules_are_validated(hip_lib):
     assert hip_lib.ln3d_gemm_mxfp8(C.byref(a), N) == -1                         # K = 96
     a.K, a.ldx, a.ldw, a.epilogue = 128, 128, 128, 2
     assert hip_lib.ln3d_gemm_mxfp8(C.byref(a), N) == -1                         # GELU_ERF without out_scale
+    a.out1 = a.out2 = fake
+    a.M, a.N, a.epilogue, a.tokens, a.tok_pad, a.heads, a.head_dim, a.transpose_mask = 16, 192, 6, 8, 8, 8, 8, 0b100
+    assert hip_lib.ln3d_gemm_mxfp8(C.byref(a), N) == -1                         # HEADS: a transposed output whose rows end inside a 16-token group
 
 
 # ------------------------------------------------------------------------------------------------------------ --dit_precision

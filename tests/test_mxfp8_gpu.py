@@ -6,7 +6,8 @@ import pytest
 import torch
 
 from conftest import golden, load_synth, rel_l2
-from test_mxfp8_cpu import dequantize_mx, e4m3_step, quantize_mx_ref
+from mx_refs import check_mx_output as _check_mx_output, gelu64 as _gelu64
+from test_mxfp8_cpu import dequantize_mx, quantize_mx_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -150,33 +151,6 @@ def test_gemm_mx_head_split_matches_the_bf16_layout(hip_lib, arch, M):
         # bf16 outputs of two fp32 results that differ by the MX MFMA's ~1.5e-5: a fraction of the elements round to the neighbouring
         # bf16 value.  Measured 2.2e-4 (B/2, L/2, XL/2); a misplaced head, dim or token is O(1)
         assert rel_l2(a, b) <= 5e-4, rel_l2(a, b)
-
-
-def _gelu64(x):
-    return 0.5 * x * (1.0 + torch.erf(x / 2 ** 0.5))
-
-
-def _check_mx_output(q, s, v64, what, near_rel):
-    """an MXFP8 output against the reference quantizer applied to the fp64 values it approximates: scales equal except blocks whose
-    amax lies within `near_rel` (relative) of a power of two, where the kernel's own value may fall on the other side; elements of the
-    other blocks within one e4m3 step of the reference quantizer's (+ the documented 1.3e-4 absolute error of the erf-GELU polynomial,
-    common.h gelu_erf2, for the GELU epilogue).  Saturation at 448 is part of the format: both sides saturate alike."""
-    q, s = q.cpu(), s.cpu()
-    q_ref, s_ref = quantize_mx_ref(v64.float())
-    R, K = v64.shape
-    amax = v64.abs().reshape(R, K // 32, 32).amax(-1)
-    m, _ = torch.frexp(amax)
-    near = ((m - 0.5).abs() / 0.5 < near_rel) | ((1.0 - m).abs() < near_rel)
-    diff = s != s_ref
-    print(what, 'blocks', diff.numel(), 'scale differs', int(diff.sum()), 'of which near a power of two', int((diff & near).sum()))
-    assert int((diff & ~near).sum()) == 0, (what, int((diff & ~near).sum()))
-    got, ref = dequantize_mx(q, s).double(), dequantize_mx(q_ref, s_ref).double()
-    same = (~diff).repeat_interleave(32, 1)
-    sc = torch.ldexp(torch.ones(R, K // 32, dtype=torch.float64), s.double() - 127).repeat_interleave(32, 1)
-    tol = e4m3_step((torch.maximum(got.abs(), ref.abs()) / sc).float()).double() * sc + (1.5e-4 if what == 'gelu' else 0.0)
-    err = torch.where(same, (got - ref).abs(), torch.zeros_like(got))
-    print(what, 'elements off the reference quantizer by > 0 / > 1 step:', int(((err > 0) & same).sum()), int((err > tol).sum()))
-    assert bool((err <= tol).all()), (what, float((err - tol).max()))
 
 
 @pytest.mark.parametrize("arch,M", [('DiT-B/2', 768 * 2), ('DiT-L/2', 768 * 2), ('DiT-XL/2', 768 * 2), ('DiT-L/2', 1000)])
