@@ -1,5 +1,5 @@
 """ctypes binding of libln3d_hip.so (the C ABI of include/ln3d.h, include/ln3d_encoder.h, include/ln3d_shapenet.h, include/ln3d_mx.h, include/ln3d_ffhq.h,
-include/ln3d_planes16.h and include/ln3d_normals.h).
+include/ln3d_planes16.h, include/ln3d_normals.h and include/ln3d_meshclean.h).
 
 There is NO fallback: if the library is missing or a kernel launch fails the product raises.
 """
@@ -32,6 +32,8 @@ SYMBOLS = [
     "ln3d_planes_to_channel_last_f16", "ln3d_planes_f32_to_f16", "ln3d_render_triplane_f16", "ln3d_query_points_f16",
     # include/ln3d_normals.h (sigma gradient at points, surface normals per ray)
     "ln3d_query_points_grad", "ln3d_query_points_grad_f16", "ln3d_surface_normals", "ln3d_surface_normals_f16",
+    # include/ln3d_meshclean.h (connected components of the extracted mesh, floater removal)
+    "ln3d_mesh_components", "ln3d_mesh_component_counts", "ln3d_mesh_mark", "ln3d_mesh_gather",
 ]
 
 EPI_F32, EPI_BF16, EPI_GELU_ERF, EPI_GELU_TANH, EPI_SILU, EPI_GATE_RES, EPI_HEADS, EPI_F32_SILU, EPI_QUICK_GELU, EPI_CROSS_ATTN = range(10)

@@ -10,6 +10,7 @@
 // The key needs G^6 < 2^63: LN3D_MESH_MAX_GRID.
 #include "common.h"
 #include "../../include/ln3d.h"
+#include "../../include/ln3d_meshclean.h"
 #include "mc_table.h"
 
 __constant__ int kTet[6][4] = {{0, 1, 3, 7}, {0, 2, 3, 7}, {0, 2, 6, 7}, {0, 4, 6, 7}, {0, 4, 5, 7}, {0, 1, 5, 7}};
@@ -168,5 +169,160 @@ extern "C" int ln3d_mesh_emit(const float* sigma, int G, float thr, const int64_
   MeshP p{sigma, G, thr};
   const int64_t ncell = (int64_t)(G - 1) * (G - 1) * (G - 1);
   hipLaunchKernelGGL(mesh_emit_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, ncell, offsets, tri_pos, tri_key);
+  return ln3d_check_launch();
+}
+
+// ------------------------------------------------------------------ mesh clean-up (include/ln3d_meshclean.h)
+// Connected components of the welded triangle soup by a lock-free union-find, then exact per-component counts, a keep mask and a
+// compaction.  label[] is the parent array: label[x] <= x always, a root has label[x] == x, and the only writes while hooking are
+// atomicMin, so every entry only ever decreases.  Every link points to a smaller index, so the root of a finished tree is the smallest
+// vertex index of its component: the labels are unique by definition, whatever the schedule.
+#define MC_RLX_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+
+__global__ void meshclean_init_kernel(int32_t* label, int64_t nv) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < nv) label[v] = (int32_t)v;
+}
+
+// Unite the sets of u and v.  Labels are read with relaxed agent-scope atomic loads (a plain load may be served from a line of this CU's
+// L1 that another CU has since lowered).  A stale value is an earlier parent of the same vertex: whoever replaced it took over the duty
+// of uniting it with its replacement (below), so it is still a member of the final component and following it costs steps only.
+__device__ __forceinline__ void meshclean_unite(int32_t* label, int32_t u, int32_t v) {
+  // terminates: every pass either returns or replaces the pair (hi, lo) by (old, lo) with old < hi and lo < hi, and the two walks only
+  // lower their end, so max(u, v) strictly decreases from pass to pass and is bounded below by 0
+  for (;;) {
+    int32_t p;
+    while ((p = MC_RLX_LOAD(&label[u])) < u) u = p;      // terminates: u strictly decreases (label[x] <= x)
+    while ((p = MC_RLX_LOAD(&label[v])) < v) v = p;      // terminates: v strictly decreases
+    if (u == v) return;
+    const int32_t hi = u > v ? u : v, lo = u > v ? v : u;
+    const int32_t old = atomicMin(&label[hi], lo);
+    if (old == hi || old == lo) return;                  // hi was a root and now hangs under lo / somebody else made the same link
+    // hi had been hooked under `old` between our load and the atomic: either lo < old and label[hi] = lo has just overwritten the
+    // link hi -> old, or old < lo and hi keeps its parent; both ways the set of `old` still has to be united with lo
+    u = old; v = lo;
+  }
+}
+
+__global__ void meshclean_hook_kernel(const int64_t* faces, int64_t nf, int32_t* label) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= nf) return;
+  const int32_t a = (int32_t)faces[3 * f], b = (int32_t)faces[3 * f + 1], c = (int32_t)faces[3 * f + 2];
+  meshclean_unite(label, a, b);                          // a - b and b - c connect all three; a - c adds nothing
+  meshclean_unite(label, b, c);
+}
+
+// After the hooking launch every tree is final; the walk may meet entries that other lanes of this launch have already replaced by their
+// root, which is the same root.
+__global__ void meshclean_flatten_kernel(int32_t* label, int64_t nv) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= nv) return;
+  int32_t r = (int32_t)v, p;
+  while ((p = MC_RLX_LOAD(&label[r])) < r) r = p;        // terminates: r strictly decreases
+  __hip_atomic_store(&label[v], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ void meshclean_zero_kernel(int32_t* nvert, int32_t* nface, unsigned long long* best, int64_t nv) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < nv) { nvert[v] = 0; nface[v] = 0; }
+  if (v == 0) *best = 0ull;
+}
+
+// One add per distinct destination of the wave: the lanes that share the first pending lane's destination are counted with a ballot and
+// added once by that lane, then the next pending destination, and so on.  On a real mesh nearly every lane names the same component (one
+// component owns almost every face), so a wave issues one or two atomics instead of 64 on one address.  Every lane of the wave must call
+// this; r < 0 = nothing to add.
+__device__ __forceinline__ void meshclean_wave_add(int32_t* cnt, int32_t r) {
+  unsigned long long todo = __ballot(r >= 0);
+  while (todo) {                                         // terminates: every pass clears at least the leading bit of todo
+    const int lead = __ffsll((long long)todo) - 1;
+    const int32_t r0 = __shfl(r, lead);
+    const unsigned long long same = __ballot(r == r0);
+    if ((int)(threadIdx.x & 63) == lead) atomicAdd(&cnt[r0], (int32_t)__popcll(same));
+    todo &= ~same;
+  }
+}
+
+__global__ void meshclean_count_kernel(const int64_t* faces, int64_t nf, const int32_t* label, int64_t nv, int32_t* nvert, int32_t* nface) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  meshclean_wave_add(nvert, i < nv ? label[i] : -1);
+  meshclean_wave_add(nface, i < nf ? label[faces[3 * i]] : -1);
+}
+
+// best = max over the components that own a face of (nface << 32) | (0x7fffffff - root): most faces first, then the smallest root.
+// One 64-bit atomic max per wave that holds a candidate.
+__global__ void meshclean_best_kernel(const int32_t* label, const int32_t* nface, int64_t nv, unsigned long long* best) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned long long k = 0ull;
+  if (v < nv && label[v] == (int32_t)v && nface[v] > 0) k = ((unsigned long long)(uint32_t)nface[v] << 32) | (unsigned long long)(0x7fffffff - (int32_t)v);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long t = __shfl_xor(k, o);
+    k = t > k ? t : k;
+  }
+  if ((threadIdx.x & 63) == 0 && k) atomicMax(best, k);
+}
+
+__device__ __forceinline__ int32_t meshclean_keep(const int32_t* nface, int32_t r, int64_t min_faces, int largest_only, int32_t best_root) {
+  return ((int64_t)nface[r] >= min_faces && (!largest_only || r == best_root)) ? 1 : 0;
+}
+
+__global__ void meshclean_mark_kernel(const int64_t* faces, int64_t nf, const int32_t* label, const int32_t* nface, int64_t nv, int64_t min_faces,
+                                      int largest_only, const unsigned long long* best, int32_t* keep_v, int32_t* keep_f) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int32_t best_root = 0x7fffffff - (int32_t)(*best & 0xffffffffull);
+  if (i < nv) keep_v[i] = meshclean_keep(nface, label[i], min_faces, largest_only, best_root);
+  if (i < nf) keep_f[i] = meshclean_keep(nface, label[faces[3 * i]], min_faces, largest_only, best_root);   // = keep_v[faces[i][0]]
+}
+
+__global__ void meshclean_gather_kernel(const uint32_t* verts, const int64_t* faces, const int32_t* keep_v, const int64_t* vprefix, const int32_t* keep_f,
+                                        const int64_t* fprefix, int64_t nv, int64_t nf, uint32_t* verts_out, int64_t* faces_out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nv && keep_v[i]) {
+    const int64_t o = vprefix[i] - 1;
+    verts_out[3 * o] = verts[3 * i]; verts_out[3 * o + 1] = verts[3 * i + 1]; verts_out[3 * o + 2] = verts[3 * i + 2];
+  }
+  if (i < nf && keep_f[i]) {
+    const int64_t o = fprefix[i] - 1;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) faces_out[3 * o + j] = vprefix[faces[3 * i + j]] - 1;
+  }
+}
+
+static inline bool meshclean_sizes_ok(int64_t nf, int64_t nv) { return nv >= 1 && nv <= 0x7fffffffll && nf >= 1 && nf <= 0x7fffffffll; }
+static inline dim3 meshclean_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
+extern "C" int ln3d_mesh_components(const int64_t* faces, int64_t nf, int64_t nv, int32_t* label, void* stream) {
+  if (!faces || !label || !meshclean_sizes_ok(nf, nv)) return LN3D_ERR_BAD_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(meshclean_init_kernel, meshclean_grid(nv), dim3(256), 0, s, label, nv);
+  hipLaunchKernelGGL(meshclean_hook_kernel, meshclean_grid(nf), dim3(256), 0, s, faces, nf, label);
+  hipLaunchKernelGGL(meshclean_flatten_kernel, meshclean_grid(nv), dim3(256), 0, s, label, nv);
+  return ln3d_check_launch();
+}
+
+extern "C" int ln3d_mesh_component_counts(const int64_t* faces, int64_t nf, const int32_t* label, int64_t nv, int32_t* nvert, int32_t* nface,
+                                          uint64_t* best, void* stream) {
+  if (!faces || !label || !nvert || !nface || !best || !meshclean_sizes_ok(nf, nv)) return LN3D_ERR_BAD_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(meshclean_zero_kernel, meshclean_grid(nv), dim3(256), 0, s, nvert, nface, (unsigned long long*)best, nv);
+  hipLaunchKernelGGL(meshclean_count_kernel, meshclean_grid(nv > nf ? nv : nf), dim3(256), 0, s, faces, nf, label, nv, nvert, nface);
+  hipLaunchKernelGGL(meshclean_best_kernel, meshclean_grid(nv), dim3(256), 0, s, label, nface, nv, (unsigned long long*)best);
+  return ln3d_check_launch();
+}
+
+extern "C" int ln3d_mesh_mark(const int64_t* faces, int64_t nf, const int32_t* label, const int32_t* nface, int64_t nv, int64_t min_faces,
+                              int largest_only, const uint64_t* best, int32_t* keep_v, int32_t* keep_f, void* stream) {
+  if (!faces || !label || !nface || !best || !keep_v || !keep_f || !meshclean_sizes_ok(nf, nv) || min_faces < 0) return LN3D_ERR_BAD_ARG;
+  hipLaunchKernelGGL(meshclean_mark_kernel, meshclean_grid(nv > nf ? nv : nf), dim3(256), 0, (hipStream_t)stream, faces, nf, label, nface, nv,
+                     min_faces, largest_only, (const unsigned long long*)best, keep_v, keep_f);
+  return ln3d_check_launch();
+}
+
+extern "C" int ln3d_mesh_gather(const float* verts, const int64_t* faces, const int32_t* keep_v, const int64_t* vprefix, const int32_t* keep_f,
+                                const int64_t* fprefix, int64_t nv, int64_t nf, float* verts_out, int64_t* faces_out, void* stream) {
+  if (!verts || !faces || !keep_v || !vprefix || !keep_f || !fprefix || !verts_out || !faces_out || !meshclean_sizes_ok(nf, nv)) return LN3D_ERR_BAD_ARG;
+  hipLaunchKernelGGL(meshclean_gather_kernel, meshclean_grid(nv > nf ? nv : nf), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)verts, faces,
+                     keep_v, vprefix, keep_f, fprefix, nv, nf, (uint32_t*)verts_out, faces_out);
   return ln3d_check_launch();
 }

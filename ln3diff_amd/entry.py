@@ -101,7 +101,9 @@ def create_argparser(objaverse=True):
         dit_precision='bf16',                # matmul precision of the T23D DiT (no reference counterpart): bf16 or the opt-in mxfp8
         plane_precision='fp32',              # texel storage of the renderer's tri-planes (no reference counterpart): fp32 or the opt-in fp16
         export_mesh_normals=False,           # `vn` records (the density field's outward normals) in the exported meshes; needs --export_mesh
-        save_normal_maps=False)              # normal_sample{i}.npy [V,3,R,R]: world-space surface normal maps next to the frames
+        save_normal_maps=False,              # normal_sample{i}.npy [V,3,R,R]: world-space surface normal maps next to the frames
+        mesh_keep='all',                     # all | largest: which connected components of an exported mesh are written; needs --export_mesh
+        mesh_min_faces=0)                    # components of an exported mesh with fewer faces are dropped (floaters); needs --export_mesh
     d.update(_IGNORED_DEFAULTS)
     d.update({k: v[0] for k, v in _CHECKED.items()})
     ap = argparse.ArgumentParser(allow_abbrev=False)
@@ -153,6 +155,13 @@ def validate(args):
         raise SystemExit(f"--plane_precision {plane_prec}: expected one of {list(PLANE_PRECISIONS)}")
     if getattr(args, 'export_mesh_normals', False) and not args.export_mesh:
         raise SystemExit("--export_mesh_normals true: there is no mesh to put normals into without --export_mesh true")
+    mesh_keep, mesh_min_faces = getattr(args, 'mesh_keep', 'all'), getattr(args, 'mesh_min_faces', 0)
+    if mesh_keep not in ('all', 'largest'):
+        raise SystemExit(f"--mesh_keep {mesh_keep}: expected all or largest")
+    if mesh_min_faces < 0:
+        raise SystemExit(f"--mesh_min_faces {mesh_min_faces}: expected a non-negative face count")
+    if (mesh_keep != 'all' or mesh_min_faces != 0) and not args.export_mesh:
+        raise SystemExit("--mesh_keep / --mesh_min_faces: there is no mesh to clean without --export_mesh true")
     if getattr(args, 'save_normal_maps', False):
         world = int(os.environ.get('WORLD_SIZE', '1'))
         if world > 1 and args.num_samples % world != 0:
@@ -457,6 +466,9 @@ def run(args, objaverse=None):
         for k in ('export_mesh_normals', 'save_normal_maps'):        # recorded when set: a run without them writes the args.json it always wrote
             if not meta[k]:
                 del meta[k]
+        for k, default in (('mesh_keep', 'all'), ('mesh_min_faces', 0)):
+            if meta[k] == default:
+                del meta[k]
         with open(os.path.join(args.logdir, 'args.json'), 'w') as f:
             json.dump(meta, f, indent=2)
     P = next(iter(cond_all.values())).shape[0]                                             # the noClip multi-view denoisers take 'concat' only
@@ -525,7 +537,7 @@ def run(args, objaverse=None):
         for i in range(hi - lo):
             path = os.path.join(args.logdir, f'mesh_sample{lo + i}.obj')
             mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path,
-                           normals=args.export_mesh_normals)
+                           normals=args.export_mesh_normals, keep=args.mesh_keep, min_faces=args.mesh_min_faces)
             if not os.path.exists(path):
                 mesh_err = f"mesh export of sample {lo + i} produced no file at {path}"
                 break

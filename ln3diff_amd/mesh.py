@@ -2,7 +2,9 @@
 nsr/train_util_diffusion.py:208-248): iso-surface at sigma = 10 on the G^3 grid, vertices mapped to the +-0.45 box,
 coloured by re-querying the tri-plane, rotated -90 degrees about x, written as .obj with per-vertex colours.
 The surface is classic marching cubes (what the reference's `mcubes.marching_cubes` is; method='cubes', the default) or marching
-tetrahedra (method='tetra'); both run on the GPU in two passes around a prefix sum and weld vertices by grid-edge id."""
+tetrahedra (method='tetra'); both run on the GPU in two passes around a prefix sum and weld vertices by grid-edge id.
+Opt-in clean-up (no reference counterpart; include/ln3d_meshclean.h): connected components of the welded mesh on the device, then only the
+components with at least `min_faces` faces, or only the largest one, are kept - before the colour query, so discarded vertices cost nothing."""
 import math
 
 import numpy as np
@@ -11,10 +13,83 @@ import torch
 from . import ops
 
 
+KEEP_MODES = ('all', 'largest')
+
+
+def _clean_args(keep, min_faces):
+    if keep not in KEEP_MODES:
+        raise ValueError(f"keep {keep!r}: expected one of {list(KEEP_MODES)}")
+    if int(min_faces) != min_faces or min_faces < 0:
+        raise ValueError(f"min_faces {min_faces!r}: expected a non-negative integer")
+    return keep, int(min_faces)
+
+
+def _label_and_count(faces, nv):
+    """faces already through ops.check_faces -> (label, nvert, nface [nv] int32, best int64[1])"""
+    dev = faces.device
+    label, nvert, nface = (torch.empty(nv, dtype=torch.int32, device=dev) for _ in range(3))
+    best = torch.empty(1, dtype=torch.int64, device=dev)
+    ops.mesh_components(faces, nv, label, check=False)
+    ops.mesh_component_counts(faces, label, nvert, nface, best, check=False)
+    return label, nvert, nface, best
+
+
 @torch.no_grad()
-def extract_isosurface(sigma, thr=10.0, method='cubes'):
+def mesh_components(faces, num_verts):
+    """The diagnostic view of the connected components of a mesh: faces [Nf,3] int64 device, num_verts ->
+    (label [Nv] int32: the smallest vertex index of every vertex's component, roots [R] int64 ascending: the labels that occur,
+    nvert [R], nface [R] int32: vertices and faces of every root's component).  Two vertices are connected when a face names both; a vertex
+    that no face names is a component of its own with no face.  Raises ValueError on a face index outside [0, num_verts)."""
+    faces = faces.contiguous()
+    ops.check_faces(faces, num_verts)
+    dev = faces.device
+    if num_verts == 0 or faces.shape[0] == 0:
+        label = torch.arange(num_verts, dtype=torch.int32, device=dev)
+        return label, label.long(), torch.ones_like(label), torch.zeros_like(label)
+    label, nvert, nface, _ = _label_and_count(faces, num_verts)
+    roots = torch.nonzero(label == torch.arange(num_verts, dtype=torch.int32, device=dev)).reshape(-1)
+    return label, roots, nvert[roots], nface[roots]
+
+
+@torch.no_grad()
+def clean_mesh(verts, faces, keep='all', min_faces=0):
+    """verts [Nv,3] f32, faces [Nf,3] int64 (device) -> (verts', faces') with only the surviving connected components: a component survives
+    when it has at least `min_faces` faces and, for keep='largest', is the one with the most faces (ties: the one that holds the smallest
+    vertex index).  Survivors keep their order, vertex coordinates their bits; faces are renumbered.  keep='all', min_faces=0 returns its
+    arguments and launches nothing; an empty input, or one of which nothing survives, gives empty tensors.  Labelling, counting, marking
+    and gathering are kernels (include/ln3d_meshclean.h); the two prefix sums and the one size read-back are torch's, as in
+    extract_isosurface."""
+    keep, min_faces = _clean_args(keep, min_faces)
+    if keep == 'all' and min_faces == 0:
+        return verts, faces
+    if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"verts: expected a float32 [Nv, 3] tensor, got {verts.dtype} {tuple(verts.shape)}")
+    dev = verts.device
+    empty = lambda: (torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.long, device=dev))
+    nv, nf = verts.shape[0], faces.shape[0]
+    if nv == 0 or nf == 0:
+        return empty()
+    verts, faces = verts.contiguous(), faces.contiguous()
+    ops.check_faces(faces, nv)
+    label, _, nface, best = _label_and_count(faces, nv)
+    keep_v = torch.empty(nv, dtype=torch.int32, device=dev)
+    keep_f = torch.empty(nf, dtype=torch.int32, device=dev)
+    ops.mesh_mark(faces, label, nface, min_faces, keep == 'largest', best, keep_v, keep_f, check=False)
+    vpre, fpre = torch.cumsum(keep_v.long(), 0), torch.cumsum(keep_f.long(), 0)
+    nv_out, nf_out = torch.stack([vpre[-1], fpre[-1]]).tolist()
+    if nf_out == 0:
+        return empty()
+    verts_out = torch.empty(nv_out, 3, device=dev)
+    faces_out = torch.empty(nf_out, 3, dtype=torch.int64, device=dev)
+    ops.mesh_gather(verts, faces, keep_v, vpre, keep_f, fpre, verts_out, faces_out, check=False)
+    return verts_out, faces_out
+
+
+@torch.no_grad()
+def extract_isosurface(sigma, thr=10.0, method='cubes', keep='all', min_faces=0):
     """sigma [G,G,G] f32 device -> (verts [Nv,3] in grid coordinates, faces [Nf,3] int64).  Faces keep the emission order
-    (cells in x-major order, the case table's triangle order inside a cell)."""
+    (cells in x-major order, the case table's triangle order inside a cell).  keep / min_faces (opt-in): clean_mesh on the welded result."""
+    keep, min_faces = _clean_args(keep, min_faces)
     count, emit = {'cubes': (ops.mcubes_count, ops.mcubes_emit), 'tetra': (ops.mesh_count, ops.mesh_emit)}[method]
     G = sigma.shape[0]
     dev = sigma.device
@@ -34,7 +109,7 @@ def extract_isosurface(sigma, thr=10.0, method='cubes'):
     verts[inv] = pos                                                   # identical bits for every copy of a vertex
     faces = inv.view(ntri, 3)
     ok = (faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])
-    return verts, faces[ok]
+    return clean_mesh(verts, faces[ok], keep, min_faces)
 
 
 def rotation_matrix_x(deg):
@@ -61,15 +136,18 @@ def write_obj(path, v, f, c, n=None):
 
 
 @torch.no_grad()
-def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes', normals=False):
+def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes', normals=False,
+                   keep='all', min_faces=0):
     """nsr/train_util_diffusion.py:221-244: iso-surface of the sigma grid at `thr`, vertices mapped to the +-0.45 box, coloured
     by re-querying the tri-plane at the vertices (forward_points), rotated -90 degrees about x.
     Returns (verts [Nv,3] float32 numpy, faces [Nf,3] int64 numpy, colors [Nv,3] uint8 numpy); writes `path` when given.
     normals (opt-in; no reference counterpart): the query that colours the vertices also returns the field's unit outward normal there
     (forward_points(with_grad=True), evaluated in box coordinates and rotated with the mesh); the return value is then the 4-tuple
-    (verts, faces, colors, vn [Nv,3] float32 numpy) and the .obj carries `vn` records."""
+    (verts, faces, colors, vn [Nv,3] float32 numpy) and the .obj carries `vn` records.
+    keep / min_faces (opt-in; no reference counterpart): clean_mesh right after the weld, so only the surviving components are coloured (and
+    given normals) and written; what survives has the bits it has in the uncleaned mesh.  Nothing surviving writes an .obj with no records."""
     sigma = sigma.reshape(grid_size, grid_size, grid_size)
-    verts, faces = extract_isosurface(sigma, thr, method)
+    verts, faces = extract_isosurface(sigma, thr, method, keep, min_faces)
     vtx = (verts / (grid_size - 1) * 2 - 1) * 0.45                       # g-objaverse scale
     pcl = dec_out.get('planes_channel_last')
     if pcl is None:
@@ -86,9 +164,11 @@ def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0,
 
 
 @torch.no_grad()
-def export_mesh(decoder, dec_out, path, grid_size=192, thr=10.0, sample_index=0, normals=False):
-    """decoder: the VAE decoder module; dec_out: its vit_decode_postprocess dict.  Writes `path` (.obj), with `vn` records when normals."""
+def export_mesh(decoder, dec_out, path, grid_size=192, thr=10.0, sample_index=0, normals=False, keep='all', min_faces=0):
+    """decoder: the VAE decoder module; dec_out: its vit_decode_postprocess dict.  Writes `path` (.obj), with `vn` records when normals;
+    keep / min_faces: mesh_from_grid's."""
     pcl = dec_out['planes_channel_last'][sample_index:sample_index + 1]
     grid = decoder.triplane_decode_grid({'planes_channel_last': pcl}, grid_size)
-    v, f = mesh_from_grid(decoder, {'planes_channel_last': pcl}, grid['sigma'][0], grid_size, thr, 0, path, normals=normals)[:2]
+    v, f = mesh_from_grid(decoder, {'planes_channel_last': pcl}, grid['sigma'][0], grid_size, thr, 0, path, normals=normals, keep=keep,
+                          min_faces=min_faces)[:2]
     return v.shape[0], f.shape[0]

@@ -345,6 +345,52 @@ def mcubes_emit(sigma, G, thr, offsets, tri_pos, tri_key):
     L.check(L.lib().ln3d_mcubes_emit(_p(sigma), G, C.c_float(thr), _p(offsets), _p(tri_pos), _p(tri_key), _stream()), "mcubes_emit")
 
 
+def check_faces(faces, nv):
+    """include/ln3d_meshclean.h takes face indices in [0, nv) as a precondition: an index outside that range must never reach a kernel, so
+    it is refused here (one read-back of the smallest and largest index)."""
+    if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous():
+        raise ValueError(f"faces: expected a contiguous int64 [Nf, 3] tensor, got {faces.dtype} {tuple(faces.shape)}")
+    if faces.shape[0]:
+        lo, hi = (int(x) for x in torch.aminmax(faces))
+        if lo < 0 or hi >= nv:
+            raise ValueError(f"faces: indices span [{lo}, {hi}], outside the {nv} vertices")
+    _chk_dev(faces)
+
+
+def mesh_components(faces, nv, label, check=True):
+    """label [nv] int32 <- the smallest vertex index of every vertex's connected component (include/ln3d_meshclean.h).  check=False: the
+    caller has already put these faces through check_faces."""
+    if check:
+        check_faces(faces, nv)
+    L.check(L.lib().ln3d_mesh_components(_p(faces), C.c_int64(faces.shape[0]), C.c_int64(nv), _p(label), _stream()), "mesh_components")
+
+
+def mesh_component_counts(faces, label, nvert, nface, best, check=True):
+    """nvert, nface [nv] int32 per label, best int64[1] (the uint64 word (nface << 32) | (0x7fffffff - root) of the largest component)"""
+    nv = label.shape[0]
+    if check:
+        check_faces(faces, nv)
+    L.check(L.lib().ln3d_mesh_component_counts(_p(faces), C.c_int64(faces.shape[0]), _p(label), C.c_int64(nv), _p(nvert), _p(nface), _p(best),
+                                               _stream()), "mesh_component_counts")
+
+
+def mesh_mark(faces, label, nface, min_faces, largest_only, best, keep_v, keep_f, check=True):
+    nv = label.shape[0]
+    if check:
+        check_faces(faces, nv)
+    L.check(L.lib().ln3d_mesh_mark(_p(faces), C.c_int64(faces.shape[0]), _p(label), _p(nface), C.c_int64(nv), C.c_int64(min_faces),
+                                   int(bool(largest_only)), _p(best), _p(keep_v), _p(keep_f), _stream()), "mesh_mark")
+
+
+def mesh_gather(verts, faces, keep_v, vprefix, keep_f, fprefix, verts_out, faces_out, check=True):
+    """vprefix / fprefix: int64 inclusive prefix sums of the int32 masks; verts_out / faces_out: at least vprefix[-1] / fprefix[-1] rows"""
+    nv = verts.shape[0]
+    if check:
+        check_faces(faces, nv)
+    L.check(L.lib().ln3d_mesh_gather(_p(verts), _p(faces), _p(keep_v), _p(vprefix), _p(keep_f), _p(fprefix), C.c_int64(nv),
+                                     C.c_int64(faces.shape[0]), _p(verts_out), _p(faces_out), _stream()), "mesh_gather")
+
+
 def lincomb(y, ks, cs, out):
     n = len(ks)
     arr_k = (C.c_void_p * n)(*[k.data_ptr() for k in ks])
