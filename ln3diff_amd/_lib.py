@@ -1,6 +1,16 @@
 """ctypes binding of libln3d_hip.so (the C ABI of include/ln3d.h, include/ln3d_encoder.h, include/ln3d_shapenet.h, include/ln3d_mx.h, include/ln3d_ffhq.h,
 include/ln3d_planes16.h, include/ln3d_normals.h and include/ln3d_meshclean.h).
 
+Every export is declared once, in PROTOTYPES: name -> (restype, argtypes), which lib() applies, so a call site passes plain Python values
+and a value of the wrong kind is a ctypes.ArgumentError.  One rule maps a C parameter to its argtype:
+    const ln3d_*_args*  (one of the six argument structs)  -> POINTER(<its Structure below>)   (takes the Structure itself: ctypes passes
+                                                              its address, and that is cheaper per call than byref(...) at the call site)
+    any other pointer, device or host                      -> c_void_p   (takes an int address, None, a ctypes array, byref(...))
+    int64_t -> c_int64        int -> c_int        float -> c_float        (void) -> no arguments
+Results are c_int (0 or a negative LN3D_ERR_*), except ln3d_strerror (c_char_p) and ln3d_reload_env (void: None).
+The headers are not read here: tests/test_abi_types_cpu.py parses them and compares the table, the six Structure layouts (against a
+compiled offsetof probe) and the constants below with what they declare.
+
 There is NO fallback: if the library is missing or a kernel launch fails the product raises.
 """
 import ctypes as C
@@ -9,33 +19,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libln3d_hip.so")
 
-SYMBOLS = [
-    "ln3d_strerror", "ln3d_abi_version", "ln3d_reload_env", "ln3d_gemm_bf16", "ln3d_gemm_heads_norm_fusable", "ln3d_attention_bf16",
-    "ln3d_rmsnorm_heads_bf16", "ln3d_norm_modulate", "ln3d_timestep_embedding",
-    "ln3d_add_act_cast", "ln3d_cast_f32_bf16", "ln3d_patch_embed", "ln3d_final_layer",
-    "ln3d_edm_euler_step", "ln3d_ddpm_step", "ln3d_flow_euler_step", "ln3d_axpby",
-    "ln3d_planes_to_channel_last", "ln3d_planes_to_nchw", "ln3d_render_triplane",
-    "ln3d_query_points", "ln3d_groupnorm_swish", "ln3d_im2col3x3", "ln3d_patch_embed_triplane", "ln3d_tile_rows", "ln3d_add_table_rows", "ln3d_cfg_combine_dup", "ln3d_ddim_step", "ln3d_mesh_count", "ln3d_mesh_emit", "ln3d_mcubes_count", "ln3d_mcubes_emit", "ln3d_lincomb", "ln3d_err_ratio_sq", "ln3d_embed_tokens", "ln3d_layernorm_f32", "ln3d_vit_patchify", "ln3d_vit_assemble", "ln3d_image_preprocess", "ln3d_plucker_rays",
-    "ln3d_device_cus", "ln3d_probe_mfma_bf16",
-    "ln3d_groupnorm_any", "ln3d_im2col3x3_strided", "ln3d_geglu", "ln3d_attention_small", "ln3d_nchw_to_cl_bf16", "ln3d_cl_to_nchw_f32",
-    "ln3d_mix_prediction",
-    # include/ln3d_encoder.h (the multi-view VAE encoder)
-    "ln3d_im2col3x3_pad01", "ln3d_frame_mean", "ln3d_mv_posterior",
-    # include/ln3d_shapenet.h (the ShapeNet VAE decoder class)
-    "ln3d_triplane_axis_attention", "ln3d_sr_unpatchify", "ln3d_resize_bilinear_cl", "ln3d_resize_add_lrelu", "ln3d_rollout_means",
-    "ln3d_im2col3x3_rollout",
-    # include/ln3d_mx.h (the opt-in MX-FP8 GEMMs of the T23D DiT)
-    "ln3d_quantize_mx", "ln3d_gemm_mxfp8", "ln3d_norm_modulate_mx",
-    # include/ln3d_ffhq.h (the FFHQ VAE decoder class)
-    "ln3d_conv3x3_rollout_bf16", "ln3d_rollout_means_bf16",
-    # include/ln3d_planes16.h (the opt-in fp16 tri-plane texels of the ray-marcher and the point query)
-    "ln3d_planes_to_channel_last_f16", "ln3d_planes_f32_to_f16", "ln3d_render_triplane_f16", "ln3d_query_points_f16",
-    # include/ln3d_normals.h (sigma gradient at points, surface normals per ray)
-    "ln3d_query_points_grad", "ln3d_query_points_grad_f16", "ln3d_surface_normals", "ln3d_surface_normals_f16",
-    # include/ln3d_meshclean.h (connected components of the extracted mesh, floater removal)
-    "ln3d_mesh_components", "ln3d_mesh_component_counts", "ln3d_mesh_mark", "ln3d_mesh_gather",
-]
-
+ABI_VERSION = 10
 EPI_F32, EPI_BF16, EPI_GELU_ERF, EPI_GELU_TANH, EPI_SILU, EPI_GATE_RES, EPI_HEADS, EPI_F32_SILU, EPI_QUICK_GELU, EPI_CROSS_ATTN = range(10)
 RENDER_SCRATCH_FLOATS = 16384
 RENDER_MAX_CALLS = (RENDER_SCRATCH_FLOATS - 2644) // 8      # per-call range records after the decoder image (csrc/render.hip)
@@ -93,6 +77,100 @@ class NormalsArgs(C.Structure):         # ln3d_normals_args (include/ln3d_normal
                 ("box_warp", f32), ("depth", vp), ("wsum", vp), ("mask_threshold", f32), ("space", i32), ("normal", vp), ("points", vp)]
 
 
+def _int(*argtypes):
+    return (C.c_int, argtypes)
+
+
+_gemm, _gemm_mx, _attn, _norm = C.POINTER(GemmArgs), C.POINTER(MxGemmArgs), C.POINTER(AttnArgs), C.POINTER(NormArgs)
+_render, _normals = C.POINTER(RenderArgs), C.POINTER(NormalsArgs)
+
+PROTOTYPES = {
+    # include/ln3d.h
+    "ln3d_strerror": (C.c_char_p, (i32,)),
+    "ln3d_abi_version": _int(),
+    "ln3d_reload_env": (None, ()),
+    "ln3d_device_cus": _int(),
+    "ln3d_probe_mfma_bf16": _int(vp, i32, i32, vp),
+    "ln3d_gemm_bf16": _int(_gemm, vp),
+    "ln3d_gemm_heads_norm_fusable": _int(i32, i32, i32, i32, i32),
+    "ln3d_attention_bf16": _int(_attn, vp),
+    "ln3d_embed_tokens": _int(vp, vp, vp, vp, i32, i32, i32, i32, vp),
+    "ln3d_layernorm_f32": _int(vp, vp, vp, vp, i64, i32, f32, vp),
+    "ln3d_vit_patchify": _int(vp, vp, i32, i32, i32, i32, i32, vp),
+    "ln3d_plucker_rays": _int(vp, vp, i32, i32, vp),
+    "ln3d_vit_assemble": _int(vp, vp, vp, vp, vp, i32, i32, i32, i32, vp),
+    "ln3d_image_preprocess": _int(vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp),
+    "ln3d_rmsnorm_heads_bf16": _int(vp, vp, i64, i32, i32, f32, vp),
+    "ln3d_norm_modulate": _int(_norm, vp),
+    "ln3d_timestep_embedding": _int(vp, vp, i32, i32, vp),
+    "ln3d_add_act_cast": _int(vp, vp, vp, vp, i64, i32, vp),
+    "ln3d_cast_f32_bf16": _int(vp, vp, i64, vp),
+    "ln3d_patch_embed": _int(vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp),
+    "ln3d_patch_embed_triplane": _int(vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp),
+    "ln3d_tile_rows": _int(vp, vp, i64, i32, vp),
+    "ln3d_final_layer": _int(vp, vp, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp),
+    "ln3d_edm_euler_step": _int(vp, vp, f32, f32, f32, i64, vp),
+    "ln3d_ddpm_step": _int(vp, vp, vp, f32, f32, f32, f32, f32, i32, i64, vp),
+    "ln3d_ddim_step": _int(vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, i32, i64, vp),
+    "ln3d_flow_euler_step": _int(vp, vp, f32, f32, i64, vp),
+    "ln3d_add_table_rows": _int(vp, vp, vp, i32, i32, i64, vp),
+    "ln3d_cfg_combine_dup": _int(vp, f32, i64, vp),
+    "ln3d_lincomb": _int(vp, vp, vp, i32, vp, i64, vp),                    # ks, cs: host arrays
+    "ln3d_err_ratio_sq": _int(vp, vp, vp, f32, f32, vp, i64, vp),
+    "ln3d_axpby": _int(vp, vp, f32, f32, i64, vp),
+    "ln3d_planes_to_channel_last": _int(vp, vp, i32, i32, i32, i32, vp),
+    "ln3d_planes_to_nchw": _int(vp, vp, i32, i32, i32, i32, vp),
+    "ln3d_render_triplane": _int(_render, vp),
+    "ln3d_query_points": _int(vp, i32, i32, vp, i64, vp, vp, vp, vp, f32, vp, vp, vp, vp),
+    "ln3d_mesh_count": _int(vp, i32, f32, vp, vp),
+    "ln3d_mcubes_count": _int(vp, i32, f32, vp, vp),
+    "ln3d_mcubes_emit": _int(vp, i32, f32, vp, vp, vp, vp),
+    "ln3d_mesh_emit": _int(vp, i32, f32, vp, vp, vp, vp),
+    "ln3d_groupnorm_swish": _int(vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp),
+    "ln3d_im2col3x3": _int(vp, vp, i32, i32, i32, i32, i32, i32, vp),
+    "ln3d_groupnorm_any": _int(vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp),
+    "ln3d_im2col3x3_strided": _int(vp, vp, i32, i32, i32, i32, i32, i32, vp),
+    "ln3d_geglu": _int(vp, vp, i64, i32, vp),
+    "ln3d_attention_small": _int(vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, f32, vp),
+    "ln3d_nchw_to_cl_bf16": _int(vp, vp, i32, i32, i32, i32, vp),
+    "ln3d_cl_to_nchw_f32": _int(vp, vp, i32, i32, i32, vp),
+    "ln3d_mix_prediction": _int(vp, vp, vp, f32, i32, i32, i32, vp),
+    # include/ln3d_encoder.h (the multi-view VAE encoder)
+    "ln3d_im2col3x3_pad01": _int(vp, vp, i32, i32, i32, i32, i32, vp),
+    "ln3d_frame_mean": _int(vp, vp, i32, i32, i32, i32, vp),
+    "ln3d_mv_posterior": _int(vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp),
+    # include/ln3d_shapenet.h (the ShapeNet VAE decoder class)
+    "ln3d_triplane_axis_attention": _int(vp, i64, vp, i32, i32, i32, f32, vp),
+    "ln3d_sr_unpatchify": _int(vp, vp, vp, i32, i32, i32, i32, vp),
+    "ln3d_resize_bilinear_cl": _int(vp, vp, i32, i32, i32, i32, i32, i32, i32, vp),
+    "ln3d_resize_add_lrelu": _int(vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp),
+    "ln3d_rollout_means": _int(vp, vp, vp, i32, i32, i32, i32, vp),
+    "ln3d_im2col3x3_rollout": _int(vp, vp, vp, vp, i32, i32, i32, i32, i32, vp),
+    # include/ln3d_mx.h (the opt-in MX-FP8 GEMMs of the T23D DiT)
+    "ln3d_quantize_mx": _int(vp, i32, i64, i32, i32, vp, i64, vp, i64, vp),
+    "ln3d_gemm_mxfp8": _int(_gemm_mx, vp),
+    "ln3d_norm_modulate_mx": _int(_norm, vp, vp),
+    # include/ln3d_ffhq.h (the FFHQ VAE decoder class)
+    "ln3d_conv3x3_rollout_bf16": _int(vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, f32, vp),
+    "ln3d_rollout_means_bf16": _int(vp, vp, vp, i32, i32, i32, i32, vp),
+    # include/ln3d_planes16.h (the opt-in fp16 tri-plane texels of the ray-marcher and the point query)
+    "ln3d_planes_to_channel_last_f16": _int(vp, vp, i32, i32, i32, i32, vp),
+    "ln3d_planes_f32_to_f16": _int(vp, vp, i64, vp),
+    "ln3d_render_triplane_f16": _int(_render, vp),
+    "ln3d_query_points_f16": _int(vp, i32, i32, vp, i64, vp, vp, vp, vp, f32, vp, vp, vp, vp),
+    # include/ln3d_normals.h (sigma gradient at points, surface normals per ray)
+    "ln3d_query_points_grad": _int(vp, i32, i32, vp, i64, vp, vp, vp, vp, f32, vp, vp, vp),
+    "ln3d_query_points_grad_f16": _int(vp, i32, i32, vp, i64, vp, vp, vp, vp, f32, vp, vp, vp),
+    "ln3d_surface_normals": _int(_normals, vp),
+    "ln3d_surface_normals_f16": _int(_normals, vp),
+    # include/ln3d_meshclean.h (connected components of the extracted mesh, floater removal)
+    "ln3d_mesh_components": _int(vp, i64, i64, vp, vp),
+    "ln3d_mesh_component_counts": _int(vp, i64, vp, i64, vp, vp, vp, vp),
+    "ln3d_mesh_mark": _int(vp, i64, vp, vp, i64, i64, i32, vp, vp, vp, vp),
+    "ln3d_mesh_gather": _int(vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp),
+}
+SYMBOLS = list(PROTOTYPES)
+
 _lib = None
 
 
@@ -110,10 +188,9 @@ def lib():
         # fail with "HIP kernel launch failed".
         import torch  # noqa: F401
         _lib = C.CDLL(LIB_PATH)
-        _lib.ln3d_strerror.restype = C.c_char_p
-        for s in SYMBOLS:
-            if s != "ln3d_strerror":
-                getattr(_lib, s).restype = C.c_int
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(_lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     return _lib
 
 
@@ -122,7 +199,7 @@ def check_symbols():
     missing = [s for s in SYMBOLS if not hasattr(L, s)]
     if missing:
         raise RuntimeError(f"libln3d_hip.so lacks symbols: {missing}")
-    assert L.ln3d_abi_version() == 10
+    assert L.ln3d_abi_version() == ABI_VERSION
     return True
 
 

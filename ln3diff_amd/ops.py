@@ -9,18 +9,21 @@ from ._lib import (EPI_F32, EPI_BF16, EPI_GELU_ERF, EPI_GELU_TANH, EPI_SILU, EPI
                    EPI_HEADS, EPI_F32_SILU, EPI_QUICK_GELU, EPI_CROSS_ATTN)
 
 
+_NEED_DEVICE = "ln3diff_amd ops need device tensors (no CPU fallback exists)"
+
+
 def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+    """the address of a device tensor (None stays NULL): the one place a tensor becomes a kernel argument, so the one place that refuses
+    a host tensor"""
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise RuntimeError(_NEED_DEVICE)
+    return t.data_ptr()
 
 
 def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _chk_dev(*ts):
-    for t in ts:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("ln3diff_amd ops need device tensors (no CPU fallback exists)")
+    return torch.cuda.current_stream().cuda_stream
 
 
 def reload_env():
@@ -32,7 +35,6 @@ def gemm(x, w, bias, epilogue, out0, out1=None, out2=None, *, M=None, ldo=None, 
          gate_ld=0, tokens=0, tok_pad=0, heads=0, head_dim=0, transpose_mask=0, head_dim_pad=0, ctx_keys=0, ctx_pad=0,
          ctx_scale=0.0, head_norm0=None, head_norm1=None, head_norm_eps=1e-5, res_bias=None, res_bias_ld=0):
     """out = epi(x[M,K] @ w[N,K]^T + bias).  x, w bf16 (row stride = shape[-1])."""
-    _chk_dev(x, w, out0)
     assert x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
     a = L.GemmArgs()
     K = w.shape[1]
@@ -51,7 +53,7 @@ def gemm(x, w, bias, epilogue, out0, out1=None, out2=None, *, M=None, ldo=None, 
     a.ctx_keys, a.ctx_pad, a.ctx_scale = ctx_keys, ctx_pad, float(ctx_scale)
     a.head_norm0, a.head_norm1, a.head_norm_eps = _p(head_norm0), _p(head_norm1), float(head_norm_eps)
     a.res_bias, a.res_bias_ld = _p(res_bias), int(res_bias_ld)
-    L.check(L.lib().ln3d_gemm_bf16(C.byref(a), _stream()), "gemm")
+    L.check(L.lib().ln3d_gemm_bf16(a, _stream()), "gemm")
 
 
 class MX:
@@ -73,12 +75,11 @@ class MX:
 
 def quantize_mx(x, out=None):
     """x [R, K] f32 or bf16 (row stride = x.stride(0)) -> MX (one E8M0 scale per 32 values, OCP e4m3 elements)."""
-    _chk_dev(x)
     assert x.dtype in (torch.float32, torch.bfloat16) and x.dim() == 2 and x.stride(1) == 1
     R, K = x.shape
     out = out if out is not None else MX.empty(R, K, x.device)
-    L.check(L.lib().ln3d_quantize_mx(_p(x), int(x.dtype == torch.bfloat16), C.c_int64(x.stride(0)), int(R), int(K), _p(out.q),
-                                     C.c_int64(out.q.stride(0)), _p(out.s), C.c_int64(out.s.stride(0)), _stream()), "quantize_mx")
+    L.check(L.lib().ln3d_quantize_mx(_p(x), x.dtype == torch.bfloat16, x.stride(0), R, K, _p(out.q), out.q.stride(0), _p(out.s),
+                                     out.s.stride(0), _stream()), "quantize_mx")
     return out
 
 
@@ -86,7 +87,6 @@ def gemm_mx(x, w, bias, epilogue, out0, out1=None, out2=None, *, M=None, ldo=Non
             tokens=0, tok_pad=0, heads=0, head_dim=0, transpose_mask=0, head_dim_pad=0):
     """out = epi(deq(x)[M,K] @ deq(w)[N,K]^T + bias) on the MX-FP8 MFMA.  x, w: MX.  epilogue: EPI_F32, EPI_HEADS, EPI_GATE_RES or
     EPI_GELU_ERF, whose output is MXFP8 (out0 uint8 e4m3 [M, ldo], out_scale uint8 [M, N / 32])."""
-    _chk_dev(x.q, w.q, out0)
     a = L.MxGemmArgs()
     K = w.q.shape[1]
     if x.q.shape[-1] != K:
@@ -103,7 +103,7 @@ def gemm_mx(x, w, bias, epilogue, out0, out1=None, out2=None, *, M=None, ldo=Non
     a.ldos = int(out_scale.stride(0)) if out_scale is not None else 0
     a.gate, a.gate_rows, a.gate_ld = _p(gate), gate_rows, gate_ld
     a.tokens, a.tok_pad, a.heads, a.head_dim, a.transpose_mask, a.head_dim_pad = tokens, tok_pad, heads, head_dim, transpose_mask, head_dim_pad
-    L.check(L.lib().ln3d_gemm_mxfp8(C.byref(a), _stream()), "gemm_mx")
+    L.check(L.lib().ln3d_gemm_mxfp8(a, _stream()), "gemm_mx")
 
 
 def heads_norm_fusable(M, N, tokens, head_dim, head_dim_pad=0):
@@ -114,39 +114,36 @@ def heads_norm_fusable(M, N, tokens, head_dim, head_dim_pad=0):
 
 def attention(q, k, vt, out, B, H, Nq, Nq_pad, Nk, Nk_pad, Dh, scale=None, causal=False, dh_true=0):
     """dh_true: true head size when q / k / vt rows are zero-padded to Dh; the output is then compact [B, Nq, H * dh_true]."""
-    _chk_dev(q, k, vt, out)
     a = L.AttnArgs()
     a.Q, a.K, a.Vt, a.O = _p(q), _p(k), _p(vt), _p(out)
     a.B, a.H, a.Nq, a.Nq_pad, a.Nk, a.Nk_pad, a.Dh = B, H, Nq, Nq_pad, Nk, Nk_pad, Dh
     a.Dh_true = int(dh_true)
     a.ldo = H * (dh_true if dh_true and dh_true != Dh else Dh)
     a.scale = float(scale if scale is not None else Dh ** -0.5)
-    a.causal = int(bool(causal))
-    L.check(L.lib().ln3d_attention_bf16(C.byref(a), _stream()), "attention")
+    a.causal = causal
+    L.check(L.lib().ln3d_attention_bf16(a, _stream()), "attention")
 
 
 def rmsnorm_heads(x, w, rows, Dh, eps=1e-5, true_dim=0):
     """x rows of Dh (64 / 128) bf16 in place; true_dim < Dh when heads are zero-padded (w padded with zeros to Dh)."""
-    L.check(L.lib().ln3d_rmsnorm_heads_bf16(_p(x), _p(w), C.c_int64(rows), Dh, int(true_dim), C.c_float(eps), _stream()), "rmsnorm_heads")
+    L.check(L.lib().ln3d_rmsnorm_heads_bf16(_p(x), _p(w), rows, Dh, int(true_dim), eps, _stream()), "rmsnorm_heads")
 
 
 def norm_modulate(x, y, rows, D, kind=0, eps=1e-6, weight=None, shift=None, scale=None, mod_rows=1, mod_ld=0,
                   shift_table=None, scale_table=None, rows_in=0, rows_out=0):
-    _chk_dev(x, y)
     a = L.NormArgs()
     a.x, a.y, a.rows, a.D, a.kind, a.eps, a.weight = _p(x), _p(y), rows, D, kind, eps, _p(weight)
     a.shift, a.scale, a.mod_rows, a.mod_ld = _p(shift), _p(scale), mod_rows, mod_ld
     a.shift_table, a.scale_table, a.rows_in, a.rows_out = _p(shift_table), _p(scale_table), rows_in, rows_out
-    L.check(L.lib().ln3d_norm_modulate(C.byref(a), _stream()), "norm_modulate")
+    L.check(L.lib().ln3d_norm_modulate(a, _stream()), "norm_modulate")
 
 
 def norm_modulate_mx(x, y, rows, D, kind=0, eps=1e-6, weight=None, shift=None, scale=None, mod_rows=1, mod_ld=0):
     """norm_modulate with an MXFP8 output: y MX [rows, D] (contiguous)."""
-    _chk_dev(x, y.q)
     a = L.NormArgs()
     a.x, a.y, a.rows, a.D, a.kind, a.eps, a.weight = _p(x), _p(y.q), rows, D, kind, eps, _p(weight)
     a.shift, a.scale, a.mod_rows, a.mod_ld = _p(shift), _p(scale), mod_rows, mod_ld
-    L.check(L.lib().ln3d_norm_modulate_mx(C.byref(a), _p(y.s), _stream()), "norm_modulate_mx")
+    L.check(L.lib().ln3d_norm_modulate_mx(a, _p(y.s), _stream()), "norm_modulate_mx")
 
 
 def timestep_embedding(t, out, B, dim=256):
@@ -154,11 +151,11 @@ def timestep_embedding(t, out, B, dim=256):
 
 
 def add_act_cast(a, b, y_bf16, sum_f32, n, act):
-    L.check(L.lib().ln3d_add_act_cast(_p(a), _p(b), _p(y_bf16), _p(sum_f32), C.c_int64(n), act, _stream()), "add_act_cast")
+    L.check(L.lib().ln3d_add_act_cast(_p(a), _p(b), _p(y_bf16), _p(sum_f32), n, act, _stream()), "add_act_cast")
 
 
 def cast_bf16(x, y):
-    L.check(L.lib().ln3d_cast_f32_bf16(_p(x), _p(y), C.c_int64(x.numel()), _stream()), "cast")
+    L.check(L.lib().ln3d_cast_f32_bf16(_p(x), _p(y), x.numel(), _stream()), "cast")
 
 
 def patch_embed(x, in_scale, w, bias, pos, tokens, Bx, Bn, Cc, S, p, D):
@@ -167,27 +164,24 @@ def patch_embed(x, in_scale, w, bias, pos, tokens, Bx, Bn, Cc, S, p, D):
 
 
 def final_layer(tokens, shift, scale, mod_ld, shift_table, scale_table, w, bias, out, Bn, Cc, S, p, D):
-    L.check(L.lib().ln3d_final_layer(_p(tokens), _p(shift), _p(scale), C.c_int64(mod_ld), _p(shift_table), _p(scale_table),
+    L.check(L.lib().ln3d_final_layer(_p(tokens), _p(shift), _p(scale), mod_ld, _p(shift_table), _p(scale_table),
                                      _p(w), _p(bias), _p(out), Bn, Cc, S, p, D, _stream()), "final_layer")
 
 
 def edm_euler_step(x, eps2, sigma, sigma_next, cfg_scale):
-    L.check(L.lib().ln3d_edm_euler_step(_p(x), _p(eps2), C.c_float(sigma), C.c_float(sigma_next), C.c_float(cfg_scale),
-                                        C.c_int64(x.numel()), _stream()), "edm_euler_step")
+    L.check(L.lib().ln3d_edm_euler_step(_p(x), _p(eps2), sigma, sigma_next, cfg_scale, x.numel(), _stream()), "edm_euler_step")
 
 
 def ddpm_step(x, eps, noise, a, b, c1, c2, sig, clip):
-    L.check(L.lib().ln3d_ddpm_step(_p(x), _p(eps), _p(noise), C.c_float(a), C.c_float(b), C.c_float(c1), C.c_float(c2),
-                                   C.c_float(sig), int(clip), C.c_int64(x.numel()), _stream()), "ddpm_step")
+    L.check(L.lib().ln3d_ddpm_step(_p(x), _p(eps), _p(noise), a, b, c1, c2, sig, clip, x.numel(), _stream()), "ddpm_step")
 
 
 def flow_euler_step(x2, v2, dt, cfg_scale):
-    L.check(L.lib().ln3d_flow_euler_step(_p(x2), _p(v2), C.c_float(dt), C.c_float(cfg_scale), C.c_int64(x2.numel() // 2),
-                                         _stream()), "flow_euler_step")
+    L.check(L.lib().ln3d_flow_euler_step(_p(x2), _p(v2), dt, cfg_scale, x2.numel() // 2, _stream()), "flow_euler_step")
 
 
 def axpby(x, y, a, b):
-    L.check(L.lib().ln3d_axpby(_p(x), _p(y), C.c_float(a), C.c_float(b), C.c_int64(x.numel()), _stream()), "axpby")
+    L.check(L.lib().ln3d_axpby(_p(x), _p(y), a, b, x.numel(), _stream()), "axpby")
 
 
 def planes_to_channel_last(src, dst, NP, Cc, H, W):
@@ -205,7 +199,7 @@ def planes_f32_to_f16(src, dst):
     """contiguous f32 planes (any layout) -> torch.float16, element for element, by the rule of planes_to_channel_last_f16."""
     if src.dtype != torch.float32 or dst.dtype != torch.float16:
         raise TypeError(f"planes_f32_to_f16: f32 source and f16 destination expected, got {src.dtype} -> {dst.dtype}")
-    L.check(L.lib().ln3d_planes_f32_to_f16(_p(src), _p(dst), C.c_int64(src.numel()), _stream()), "planes_f32_to_f16")
+    L.check(L.lib().ln3d_planes_f32_to_f16(_p(src), _p(dst), src.numel(), _stream()), "planes_f32_to_f16")
 
 
 def _plane_entry(planes, what):
@@ -251,21 +245,21 @@ def render_triplane(planes_cl, H, W, plane_index, cams, res, dec, jitter, u_fine
         a.ray_mode, a.ray_start, a.ray_end = 1, float(ray_start), float(ray_end)
     a.no_bbox_filter = 0 if filter_out_of_bbox else 1
     a.weights, a.all_coords, a.feature_volume = _p(weights), _p(all_coords), _p(feature_volume)
-    L.check(entry(C.byref(a), _stream()), "render_triplane")
+    L.check(entry(a, _stream()), "render_triplane")
 
 
 def query_points(planes_cl, H, W, points, dec, box_warp, sigma, rgb, scalars):
     """scalars: caller-owned f32 scratch of _lib.RENDER_SCRATCH_FLOATS (no allocation inside the library).  planes_cl: torch.float32 or
     torch.float16 texels (ln3d_query_points_f16)."""
-    L.check(_plane_entry(planes_cl, "query_points")(_p(planes_cl), H, W, _p(points), C.c_int64(points.shape[0]), *(_p(t) for t in dec),
-                                      C.c_float(box_warp), _p(sigma), _p(rgb), _p(scalars), _stream()), "query_points")
+    L.check(_plane_entry(planes_cl, "query_points")(_p(planes_cl), H, W, _p(points), points.shape[0], *(_p(t) for t in dec),
+                                      box_warp, _p(sigma), _p(rgb), _p(scalars), _stream()), "query_points")
 
 
 def query_points_grad(planes_cl, H, W, points, dec, box_warp, sigma, grad):
     """sigma [P] and d sigma / d p [P, 3] of ONE tri-plane [3, H, W, 32] (torch.float32 or torch.float16 texels) at points [P, 3]
     (include/ln3d_normals.h)."""
-    L.check(_plane_entry(planes_cl, "query_points_grad")(_p(planes_cl), H, W, _p(points), C.c_int64(points.shape[0]), *(_p(t) for t in dec),
-                                                         C.c_float(box_warp), _p(sigma), _p(grad), _stream()), "query_points_grad")
+    L.check(_plane_entry(planes_cl, "query_points_grad")(_p(planes_cl), H, W, _p(points), points.shape[0], *(_p(t) for t in dec),
+                                                         box_warp, _p(sigma), _p(grad), _stream()), "query_points_grad")
 
 
 NORMAL_SPACES = {'world': 0, 'camera': 1}
@@ -286,11 +280,11 @@ def surface_normals(planes_cl, H, W, plane_index, dec, box_warp, depth, wsum, no
     a.dec_w0, a.dec_b0, a.dec_w1, a.dec_b1 = (_p(t) for t in dec)
     a.box_warp, a.depth, a.wsum, a.mask_threshold = box_warp, _p(depth), _p(wsum), float(mask_threshold)
     a.space, a.normal, a.points = NORMAL_SPACES[space], _p(normal), _p(points)
-    L.check(entry(C.byref(a), _stream()), "surface_normals")
+    L.check(entry(a, _stream()), "surface_normals")
 
 
 def groupnorm_swish(x, w, b, y, stats, N, HW, Cc, groups=32, eps=1e-6, swish=True):
-    L.check(L.lib().ln3d_groupnorm_swish(_p(x), _p(w), _p(b), _p(y), _p(stats), N, HW, Cc, groups, C.c_float(eps), int(swish),
+    L.check(L.lib().ln3d_groupnorm_swish(_p(x), _p(w), _p(b), _p(y), _p(stats), N, HW, Cc, groups, eps, swish,
                                          _stream()), "groupnorm_swish")
 
 
@@ -304,15 +298,15 @@ def patch_embed_triplane(latent, w, bias, out_silu, out_raw, B, Cg, S, p, D):
 
 
 def tile_rows(x, y, per, reps):
-    L.check(L.lib().ln3d_tile_rows(_p(x), _p(y), C.c_int64(per), reps, _stream()), "tile_rows")
+    L.check(L.lib().ln3d_tile_rows(_p(x), _p(y), per, reps, _stream()), "tile_rows")
 
 
 def add_table_rows(t0, tables, out, layers, B, W):
-    L.check(L.lib().ln3d_add_table_rows(_p(t0), _p(tables), _p(out), layers, B, C.c_int64(W), _stream()), "add_table_rows")
+    L.check(L.lib().ln3d_add_table_rows(_p(t0), _p(tables), _p(out), layers, B, W, _stream()), "add_table_rows")
 
 
 def cfg_combine_dup(v2, cfg_scale):
-    L.check(L.lib().ln3d_cfg_combine_dup(_p(v2), C.c_float(cfg_scale), C.c_int64(v2.numel() // 2), _stream()), "cfg_combine_dup")
+    L.check(L.lib().ln3d_cfg_combine_dup(_p(v2), cfg_scale, v2.numel() // 2, _stream()), "cfg_combine_dup")
 
 
 def vt_key_order(n_pad, device=None):
@@ -324,25 +318,24 @@ def vt_key_order(n_pad, device=None):
 
 
 def ddim_step(x, eps_u, eps_c, noise, cfg_scale, a, b, sqrt_ab_prev, coef_eps, sigma, clip):
-    L.check(L.lib().ln3d_ddim_step(_p(x), _p(eps_u), _p(eps_c), _p(noise), C.c_float(cfg_scale), C.c_float(a), C.c_float(b),
-                                   C.c_float(sqrt_ab_prev), C.c_float(coef_eps), C.c_float(sigma), int(clip),
-                                   C.c_int64(x.numel()), _stream()), "ddim_step")
+    L.check(L.lib().ln3d_ddim_step(_p(x), _p(eps_u), _p(eps_c), _p(noise), cfg_scale, a, b, sqrt_ab_prev, coef_eps, sigma, clip, x.numel(),
+                                   _stream()), "ddim_step")
 
 
 def mesh_count(sigma, G, thr, counts):
-    L.check(L.lib().ln3d_mesh_count(_p(sigma), G, C.c_float(thr), _p(counts), _stream()), "mesh_count")
+    L.check(L.lib().ln3d_mesh_count(_p(sigma), G, thr, _p(counts), _stream()), "mesh_count")
 
 
 def mesh_emit(sigma, G, thr, offsets, tri_pos, tri_key):
-    L.check(L.lib().ln3d_mesh_emit(_p(sigma), G, C.c_float(thr), _p(offsets), _p(tri_pos), _p(tri_key), _stream()), "mesh_emit")
+    L.check(L.lib().ln3d_mesh_emit(_p(sigma), G, thr, _p(offsets), _p(tri_pos), _p(tri_key), _stream()), "mesh_emit")
 
 
 def mcubes_count(sigma, G, thr, counts):
-    L.check(L.lib().ln3d_mcubes_count(_p(sigma), G, C.c_float(thr), _p(counts), _stream()), "mcubes_count")
+    L.check(L.lib().ln3d_mcubes_count(_p(sigma), G, thr, _p(counts), _stream()), "mcubes_count")
 
 
 def mcubes_emit(sigma, G, thr, offsets, tri_pos, tri_key):
-    L.check(L.lib().ln3d_mcubes_emit(_p(sigma), G, C.c_float(thr), _p(offsets), _p(tri_pos), _p(tri_key), _stream()), "mcubes_emit")
+    L.check(L.lib().ln3d_mcubes_emit(_p(sigma), G, thr, _p(offsets), _p(tri_pos), _p(tri_key), _stream()), "mcubes_emit")
 
 
 def check_faces(faces, nv):
@@ -354,7 +347,8 @@ def check_faces(faces, nv):
         lo, hi = (int(x) for x in torch.aminmax(faces))
         if lo < 0 or hi >= nv:
             raise ValueError(f"faces: indices span [{lo}, {hi}], outside the {nv} vertices")
-    _chk_dev(faces)
+    if not faces.is_cuda:
+        raise RuntimeError(_NEED_DEVICE)
 
 
 def mesh_components(faces, nv, label, check=True):
@@ -362,7 +356,7 @@ def mesh_components(faces, nv, label, check=True):
     caller has already put these faces through check_faces."""
     if check:
         check_faces(faces, nv)
-    L.check(L.lib().ln3d_mesh_components(_p(faces), C.c_int64(faces.shape[0]), C.c_int64(nv), _p(label), _stream()), "mesh_components")
+    L.check(L.lib().ln3d_mesh_components(_p(faces), faces.shape[0], nv, _p(label), _stream()), "mesh_components")
 
 
 def mesh_component_counts(faces, label, nvert, nface, best, check=True):
@@ -370,7 +364,7 @@ def mesh_component_counts(faces, label, nvert, nface, best, check=True):
     nv = label.shape[0]
     if check:
         check_faces(faces, nv)
-    L.check(L.lib().ln3d_mesh_component_counts(_p(faces), C.c_int64(faces.shape[0]), _p(label), C.c_int64(nv), _p(nvert), _p(nface), _p(best),
+    L.check(L.lib().ln3d_mesh_component_counts(_p(faces), faces.shape[0], _p(label), nv, _p(nvert), _p(nface), _p(best),
                                                _stream()), "mesh_component_counts")
 
 
@@ -378,8 +372,8 @@ def mesh_mark(faces, label, nface, min_faces, largest_only, best, keep_v, keep_f
     nv = label.shape[0]
     if check:
         check_faces(faces, nv)
-    L.check(L.lib().ln3d_mesh_mark(_p(faces), C.c_int64(faces.shape[0]), _p(label), _p(nface), C.c_int64(nv), C.c_int64(min_faces),
-                                   int(bool(largest_only)), _p(best), _p(keep_v), _p(keep_f), _stream()), "mesh_mark")
+    L.check(L.lib().ln3d_mesh_mark(_p(faces), faces.shape[0], _p(label), _p(nface), nv, min_faces, largest_only, _p(best), _p(keep_v),
+                                   _p(keep_f), _stream()), "mesh_mark")
 
 
 def mesh_gather(verts, faces, keep_v, vprefix, keep_f, fprefix, verts_out, faces_out, check=True):
@@ -387,20 +381,19 @@ def mesh_gather(verts, faces, keep_v, vprefix, keep_f, fprefix, verts_out, faces
     nv = verts.shape[0]
     if check:
         check_faces(faces, nv)
-    L.check(L.lib().ln3d_mesh_gather(_p(verts), _p(faces), _p(keep_v), _p(vprefix), _p(keep_f), _p(fprefix), C.c_int64(nv),
-                                     C.c_int64(faces.shape[0]), _p(verts_out), _p(faces_out), _stream()), "mesh_gather")
+    L.check(L.lib().ln3d_mesh_gather(_p(verts), _p(faces), _p(keep_v), _p(vprefix), _p(keep_f), _p(fprefix), nv, faces.shape[0],
+                                     _p(verts_out), _p(faces_out), _stream()), "mesh_gather")
 
 
 def lincomb(y, ks, cs, out):
     n = len(ks)
-    arr_k = (C.c_void_p * n)(*[k.data_ptr() for k in ks])
+    arr_k = (C.c_void_p * n)(*[_p(k) for k in ks])
     arr_c = (C.c_float * n)(*[float(c) for c in cs])
-    L.check(L.lib().ln3d_lincomb(_p(y), arr_k, arr_c, n, _p(out), C.c_int64(out.numel()), _stream()), "lincomb")
+    L.check(L.lib().ln3d_lincomb(_p(y), arr_k, arr_c, n, _p(out), out.numel(), _stream()), "lincomb")
 
 
 def err_ratio_sq(err, y0, y1, atol, rtol, acc):
-    L.check(L.lib().ln3d_err_ratio_sq(_p(err), _p(y0), _p(y1), C.c_float(atol), C.c_float(rtol), _p(acc),
-                                      C.c_int64(err.numel()), _stream()), "err_ratio_sq")
+    L.check(L.lib().ln3d_err_ratio_sq(_p(err), _p(y0), _p(y1), atol, rtol, _p(acc), err.numel(), _stream()), "err_ratio_sq")
 
 
 def embed_tokens(ids, tok_emb, pos_emb, out, B, T, D):
@@ -409,19 +402,18 @@ def embed_tokens(ids, tok_emb, pos_emb, out, B, T, D):
 
 
 def layernorm_f32(x, w, b, y, rows, D, eps=1e-5):
-    L.check(L.lib().ln3d_layernorm_f32(_p(x), _p(w), _p(b), _p(y), C.c_int64(rows), D, C.c_float(eps), _stream()), "layernorm_f32")
+    L.check(L.lib().ln3d_layernorm_f32(_p(x), _p(w), _p(b), _p(y), rows, D, eps, _stream()), "layernorm_f32")
 
 
 def image_preprocess(x, S, antialias, mean, std):
     """[N, C, H, W] f32 in [-1, 1] -> resized (kornia bicubic, align_corners, optional antialias blur) and normalised [N, C, S, S]"""
-    _chk_dev(x)
     N, Cc, H, W = x.shape
     x = x.contiguous().float()
     out = torch.empty(N, Cc, S, S, device=x.device, dtype=torch.float32)
     tmp = torch.empty(2 * x.numel(), device=x.device, dtype=torch.float32) if (antialias and (H > S or W > S)) else None
     m = (C.c_float * Cc)(*[float(v) for v in mean])
     sd = (C.c_float * Cc)(*[float(v) for v in std])
-    L.check(L.lib().ln3d_image_preprocess(_p(x), _p(out), _p(tmp), N, Cc, H, W, S, int(bool(antialias)), m, sd, _stream()), "image_preprocess")
+    L.check(L.lib().ln3d_image_preprocess(_p(x), _p(out), _p(tmp), N, Cc, H, W, S, antialias, m, sd, _stream()), "image_preprocess")
     return out
 
 
@@ -431,7 +423,6 @@ def vit_patchify(img, out, B, S, p, Kpad, C=3):
 
 def plucker_rays(c, S):
     """c f32 [V, 25] (c2w 4x4 + intrinsics 3x3) -> Pluecker maps f32 [V, 6, S, S] (o x d, d)."""
-    _chk_dev(c)
     V = c.shape[0]
     out = torch.empty(V, 6, S, S, device=c.device, dtype=torch.float32)
     c32 = c.contiguous().float()                     # kept alive across the launch (a temporary's block could be handed out again)
@@ -456,9 +447,8 @@ def probe_mfma(out, wgs, iters):
 
 # ---------------------------------------------------------------- U-Net pieces (csrc/unet_ops.hip)
 def groupnorm_any(x, w, b, y, N, HW, Cc, groups=32, eps=1e-5, swish=True, add_row=None, mod_scale=None, mod_shift=None):
-    _chk_dev(x, y)
-    L.check(L.lib().ln3d_groupnorm_any(_p(x), _p(add_row), _p(w), _p(b), _p(mod_scale), _p(mod_shift), _p(y), N, HW, Cc, groups, C.c_float(eps),
-                                       int(swish), _stream()), "groupnorm_any")
+    L.check(L.lib().ln3d_groupnorm_any(_p(x), _p(add_row), _p(w), _p(b), _p(mod_scale), _p(mod_shift), _p(y), N, HW, Cc, groups, eps,
+                                       swish, _stream()), "groupnorm_any")
 
 
 def im2col3x3_strided(x, col, N, H, W, Cc, stride, Kpad):
@@ -466,14 +456,12 @@ def im2col3x3_strided(x, col, N, H, W, Cc, stride, Kpad):
 
 
 def geglu(x, y, rows, inner):
-    L.check(L.lib().ln3d_geglu(_p(x), _p(y), C.c_int64(rows), inner, _stream()), "geglu")
+    L.check(L.lib().ln3d_geglu(_p(x), _p(y), rows, inner, _stream()), "geglu")
 
 
 def attention_small(q, k, v, out, B, H, Nq, Nk, Dh, ldq, ldk, ldv, scale):
     """q / k / v: bf16 tensors (or views into wider projection outputs) whose data_ptr is column 0 of head 0; ld* = their row strides"""
-    _chk_dev(q, k, v, out)
-    L.check(L.lib().ln3d_attention_small(_p(q), _p(k), _p(v), _p(out), B, H, Nq, Nk, Dh, C.c_int64(ldq), C.c_int64(ldk), C.c_int64(ldv),
-                                         C.c_float(scale), _stream()), "attention_small")
+    L.check(L.lib().ln3d_attention_small(_p(q), _p(k), _p(v), _p(out), B, H, Nq, Nk, Dh, ldq, ldk, ldv, scale, _stream()), "attention_small")
 
 
 def nchw_to_cl_bf16(x, y, N, Cc, HW, Cpad):
@@ -485,13 +473,12 @@ def cl_to_nchw_f32(x, y, N, Cc, HW):
 
 
 def mix_prediction(eps, x, mixing_logit, sqrt_one_minus_ab, N, Cc, HW):
-    L.check(L.lib().ln3d_mix_prediction(_p(eps), _p(x), _p(mixing_logit), C.c_float(sqrt_one_minus_ab), N, Cc, HW, _stream()), "mix_prediction")
+    L.check(L.lib().ln3d_mix_prediction(_p(eps), _p(x), _p(mixing_logit), sqrt_one_minus_ab, N, Cc, HW, _stream()), "mix_prediction")
 
 
 # ---------------------------------------------------------------- multi-view VAE encoder (include/ln3d_encoder.h, csrc/conv_ops.hip)
 def im2col3x3_pad01(x, col, N, H, W, Cc, Kpad):
     """Downsample of the encoder: F.pad(x, (0, 1, 0, 1)) + 3x3 conv stride 2 padding 0, as an im2col gather ([N*Ho*Wo, Kpad] bf16)."""
-    _chk_dev(x, col)
     Ho, Wo = (H - 2) // 2 + 1, (W - 2) // 2 + 1
     if x.numel() < N * H * W * Cc or col.numel() < N * Ho * Wo * Kpad:
         raise ValueError("im2col3x3_pad01: buffers smaller than the problem")
@@ -506,7 +493,6 @@ def _channel_last_view(h):
 
 def frame_mean(h, out, B, F, HW, Cc):
     """h [B*F, C, H, W] (channel-last memory) -> out f32 [B, C, H, W] contiguous: mean over each object's F frames."""
-    _chk_dev(h, out)
     if h.dtype != torch.float32 or out.dtype != torch.float32 or not _channel_last_view(h) or not out.is_contiguous():
         raise ValueError("frame_mean: h must be an f32 channel-last [B*F, C, H, W] view, out a contiguous f32 tensor")
     if h.shape[0] != B * F or h.shape[1] != Cc or h.shape[2] * h.shape[3] != HW or out.numel() != B * Cc * HW:
@@ -518,7 +504,6 @@ def mv_posterior(h, qw, qb, eps, B, F, E=4):
     """Fused posterior (ln3d_mv_posterior): h [B*F, 6E, H, W] f32 of any strides with a uniform pixel stride (the per-frame channel-last
     encoder output, or the pooled NCHW one with F = 1); qw [6E, 2E] / qb [6E] f32 (quant_conv); eps f32 [B, E, 3, H*W] or None (mode).
     Returns dict of f32 tensors: mean, logvar, z, log_q, entropy [B, E, 3, H*W] and latent_tok [B, 3*H*W, E] (E = ldm_embed_dim)."""
-    _chk_dev(h, qw, qb, eps)
     N, Cm, H, W = h.shape
     HW = H * W
     if h.dtype != torch.float32 or N != B * F or Cm != 6 * E or h.stride(2) != W * h.stride(3):
@@ -529,7 +514,7 @@ def mv_posterior(h, qw, qb, eps, B, F, E=4):
         raise ValueError(f"mv_posterior: eps must be a contiguous f32 [{B}, {E}, 3, {HW}] tensor")
     out = {k: torch.empty(B, E, 3, HW, device=h.device, dtype=torch.float32) for k in ('mean', 'logvar', 'z', 'log_q', 'entropy')}
     out['latent_tok'] = torch.empty(B, 3 * HW, E, device=h.device, dtype=torch.float32)
-    L.check(L.lib().ln3d_mv_posterior(_p(h), C.c_int64(h.stride(0)), C.c_int64(h.stride(3)), C.c_int64(h.stride(1)), _p(qw), _p(qb), _p(eps),
+    L.check(L.lib().ln3d_mv_posterior(_p(h), h.stride(0), h.stride(3), h.stride(1), _p(qw), _p(qb), _p(eps),
                                       _p(out['mean']), _p(out['logvar']), _p(out['z']), _p(out['latent_tok']), _p(out['log_q']),
                                       _p(out['entropy']), B, F, HW, E, _stream()), "mv_posterior")
     return out
@@ -544,17 +529,15 @@ def _need(cond, msg):
 def triplane_axis_attention(qkv, out, B, p, H, scale=None):
     """qkv f32 [B*3*p*p, >= 3*H*64] ([q | k | v] columns) -> out bf16 [B*3*p*p, H*64]: plane i's query at (y, x) attends to row y of
     plane (i+1) % 3 and column x of plane (i+2) % 3 (Conv3DCrossAttentionBlockXformerMHANested)."""
-    _chk_dev(qkv, out)
     rows, D = B * 3 * p * p, H * 64
     _need(qkv.dtype == torch.float32 and qkv.stride(-1) == 1 and qkv.shape[0] == rows and qkv.shape[1] >= 3 * D,
           "triplane_axis_attention: qkv must be f32 [B*3*p*p, >= 3*H*64] with unit column stride")
     _need(out.dtype == torch.bfloat16 and out.is_contiguous() and out.numel() == rows * D, "triplane_axis_attention: out bf16 [rows, H*64]")
-    L.check(L.lib().ln3d_triplane_axis_attention(_p(qkv), C.c_int64(qkv.stride(0)), _p(out), B, p, H, C.c_float(scale or 64 ** -0.5),
+    L.check(L.lib().ln3d_triplane_axis_attention(_p(qkv), qkv.stride(0), _p(out), B, p, H, scale or 64 ** -0.5,
                                                  _stream()), "triplane_axis_attention")
 
 
 def sr_unpatchify(pred, planes, mixed, B, S, P, Cc):
-    _chk_dev(pred, planes, mixed)
     n = B * 3 * S * P * S * P * Cc
     _need(pred.dtype == torch.float32 and pred.is_contiguous() and pred.numel() == n, "sr_unpatchify: pred f32 [B, 3*S*S, P*P*C]")
     _need(planes.dtype == torch.float32 and planes.is_contiguous() and planes.numel() == n, "sr_unpatchify: planes f32 [B, 3, R, R, C]")
@@ -563,22 +546,19 @@ def sr_unpatchify(pred, planes, mixed, B, S, P, Cc):
 
 
 def resize_bilinear_cl(x, y, N, h, w, Ho, Wo, Cc, transpose=False):
-    _chk_dev(x, y)
     _need(x.dtype == torch.float32 and x.is_contiguous() and x.numel() == N * h * w * Cc, "resize_bilinear_cl: x f32 [N, h, w, C]")
     _need(y.dtype == torch.bfloat16 and y.is_contiguous() and y.numel() == N * Ho * Wo * Cc, "resize_bilinear_cl: y bf16 [N, Ho, Wo, C]")
-    L.check(L.lib().ln3d_resize_bilinear_cl(_p(x), _p(y), N, h, w, Ho, Wo, Cc, int(bool(transpose)), _stream()), "resize_bilinear_cl")
+    L.check(L.lib().ln3d_resize_bilinear_cl(_p(x), _p(y), N, h, w, Ho, Wo, Cc, transpose, _stream()), "resize_bilinear_cl")
 
 
 def resize_add_lrelu(base, t, out, N, h, w, Ho, Wo, Cc, slope=0.01):
-    _chk_dev(base, t, out)
     _need(base.dtype == torch.float32 and base.is_contiguous() and base.numel() == N * h * w * Cc, "resize_add_lrelu: base f32 [N, h, w, C]")
     for z in (t, out):
         _need(z.dtype == torch.float32 and z.is_contiguous() and z.numel() == N * Ho * Wo * Cc, "resize_add_lrelu: t / out f32 [N, Ho, Wo, C]")
-    L.check(L.lib().ln3d_resize_add_lrelu(_p(base), _p(t), _p(out), N, h, w, Ho, Wo, Cc, C.c_float(slope), _stream()), "resize_add_lrelu")
+    L.check(L.lib().ln3d_resize_add_lrelu(_p(base), _p(t), _p(out), N, h, w, Ho, Wo, Cc, slope, _stream()), "resize_add_lrelu")
 
 
 def rollout_means(x, rowmean, colmean, N, H, W, Cc):
-    _chk_dev(x, rowmean, colmean)
     _need(x.is_contiguous() and x.numel() == N * H * W * Cc and rowmean.numel() == N * H * Cc and colmean.numel() == N * W * Cc,
           "rollout_means: x [N, H, W, C], rowmean [N, H, C], colmean [N, W, C] (f32, contiguous)")
     if x.dtype == torch.bfloat16:                # include/ln3d_ffhq.h: the same means of bf16 planes
@@ -588,7 +568,6 @@ def rollout_means(x, rowmean, colmean, N, H, W, Cc):
 
 def im2col3x3_rollout(x, rowmean, colmean, col, plane, H, W, Cc, Kpad):
     """x f32 [3, H, W, C] (one object), rowmean [3, H, C], colmean [3, W, C] -> col bf16 [H*W, Kpad] of plane `plane`'s roll-out conv."""
-    _chk_dev(x, rowmean, colmean, col)
     _need(x.dtype == torch.float32 and x.is_contiguous() and x.numel() == 3 * H * W * Cc, "im2col3x3_rollout: x f32 [3, H, W, C]")
     _need(rowmean.is_contiguous() and rowmean.numel() == 3 * H * Cc and colmean.is_contiguous() and colmean.numel() == 3 * W * Cc,
           "im2col3x3_rollout: rowmean [3, H, C] / colmean [3, W, C]")
@@ -600,7 +579,6 @@ def conv3x3_rollout(x, rowmean, colmean, w, bias, base, out, H, W, Cc, Cout, slo
     """Fused roll-out 3x3 conv of one object (include/ln3d_ffhq.h): x f32 / bf16 [3, H, W, C], rowmean [3, H, C], colmean [3, W, C],
     w bf16 [3, Cout, 27C], bias f32 [3, Cout], base f32 [3, h, w, Cout] (resized when h, w differ from H, W) -> out f32 [3, H, W, Cout]
     = base + leaky_relu(conv + bias)."""
-    _chk_dev(x, rowmean, colmean, w, bias, base, out)
     _need(x.dtype in (torch.float32, torch.bfloat16) and x.is_contiguous() and x.numel() == 3 * H * W * Cc, "conv3x3_rollout: x f32 / bf16 [3, H, W, C]")
     for z, n, what in ((rowmean, 3 * H * Cc, "rowmean f32 [3, H, C]"), (colmean, 3 * W * Cc, "colmean f32 [3, W, C]"), (bias, 3 * Cout, "bias f32 [3, Cout]"),
                        (out, 3 * H * W * Cout, "out f32 [3, H, W, Cout]")):
@@ -609,5 +587,5 @@ def conv3x3_rollout(x, rowmean, colmean, w, bias, base, out, H, W, Cc, Cout, slo
     _need(base.dtype == torch.float32 and base.is_contiguous() and base.dim() == 4 and base.shape[0] == 3 and base.shape[3] == Cout,
           "conv3x3_rollout: base f32 [3, h, w, Cout]")
     _need(out.data_ptr() != x.data_ptr(), "conv3x3_rollout: out must not be x")
-    L.check(L.lib().ln3d_conv3x3_rollout_bf16(_p(x), int(x.dtype == torch.bfloat16), _p(rowmean), _p(colmean), _p(w), _p(bias), _p(base),
-                                              base.shape[1], base.shape[2], _p(out), H, W, Cc, Cout, C.c_float(slope), _stream()), "conv3x3_rollout")
+    L.check(L.lib().ln3d_conv3x3_rollout_bf16(_p(x), x.dtype == torch.bfloat16, _p(rowmean), _p(colmean), _p(w), _p(bias), _p(base),
+                                              base.shape[1], base.shape[2], _p(out), H, W, Cc, Cout, slope, _stream()), "conv3x3_rollout")

@@ -23,8 +23,6 @@ def test_encoder_entry_points_reject_missing_buffers(hip_lib):
     hdr = open(os.path.join(ROOT, 'include', 'ln3d_encoder.h')).read()
     declared = set(re.findall(r'^int (ln3d_[a-z0-9_]+)\(', hdr, re.M))
     assert declared == set(NULL_CALLS), declared ^ set(NULL_CALLS)
-    from ln3diff_amd import _lib
-    assert declared <= set(_lib.SYMBOLS)
     for name, args in NULL_CALLS.items():
         assert getattr(hip_lib, name)(*args) == -1, name                    # LN3D_ERR_BAD_ARG
     # one real-looking buffer is not enough either: every output of the posterior is required

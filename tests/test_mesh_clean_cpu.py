@@ -96,7 +96,6 @@ def test_header_declares_the_entry_points_and_the_library_has_them(hip_lib):
     for name in ENTRY_POINTS:
         assert hasattr(hip_lib, name), name
     from ln3diff_amd import _lib
-    assert all(name in _lib.SYMBOLS for name in ENTRY_POINTS)
     assert _lib.check_symbols() is True
     assert hip_lib.ln3d_abi_version() == 10
     assert 'ln3d_mesh_components' not in open(os.path.join(ROOT, 'include', 'ln3d.h')).read()

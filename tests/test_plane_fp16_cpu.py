@@ -28,7 +28,6 @@ def test_the_header_s_entry_points_exist_and_reject_missing_buffers(hip_lib):
     hdr = open(os.path.join(ROOT, 'include', 'ln3d_planes16.h')).read()
     declared = set(re.findall(r'^int (ln3d_[a-z0-9_]+)\(', hdr, re.M))
     assert declared == set(NULL_CALLS), declared ^ set(NULL_CALLS)
-    assert declared <= set(_lib.SYMBOLS)
     assert _lib.check_symbols()
     for name, args in NULL_CALLS.items():
         assert getattr(hip_lib, name)(*args) == BAD_ARG, name
