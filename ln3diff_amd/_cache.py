@@ -3,7 +3,14 @@
 Every module that keeps such a cache stamps it with the global weights EPOCH; anything that changes parameters bumps the
 epoch: `load_state_dict` anywhere in a tree that holds a cache (post-hook on the holder), `Module._apply` (.to / .cuda),
 and the in-place writers of this package (`parallel.broadcast_flat`, `synth.fill_module_random_`, `checkpoint.load_checkpoint`).
-Callers that write parameters in place themselves call `ln3diff_amd.invalidate_weight_caches()`.
+Callers that write parameters in place themselves call `ln3diff_amd.invalidate_weight_caches()`.  So do callers that REPLACE a submodule
+of a holder after its first forward (`dit.blocks[3] = other`): the load hooks sit on the submodules that existed when the cache was stamped
+(`watch_tree`), the new module has none, and assigning it is no parameter write - the holder keeps serving the old child's packed copies,
+and a state dict loaded into the new child later goes unseen, until the epoch moves.
+
+What a holder hands to its caller to pass back in (DiT `prepare_context` / `prepare_timesteps`) carries the epoch of the weights it was made
+from; forward refuses it under any other epoch.  The epoch is global: a load into an unrelated module invalidates too - the conservative
+rule, the same for the packed copies.
 """
 EPOCH = [0]
 
@@ -27,6 +34,7 @@ def fresh(cache, device=None, key='device'):
 
 
 def watch_tree(module):
+    """Load hook on every submodule `module` has NOW; one that replaces a child later is not covered (module docstring)."""
     for sub in module.modules():
         if not sub.__dict__.get('_ln3d_watched', False):
             sub.register_load_state_dict_post_hook(bump)

@@ -86,7 +86,7 @@ class DiT_I23D_PixelArt(DiT_TriLatent):
         ops.norm_modulate(ca[..., :C1].contiguous().float(), clip_n, Bn * Lc, C1, kind=1, eps=1e-5, weight=self._packed['ynorm_w'])
         dino = self._appended_tokens(ca[..., C1:])
         k_all, vt_all, lpad = self._cross_kv(clip_n, Bn, Lc)
-        return self._fold_uc({'k': k_all, 'vt': vt_all, 'Lc': Lc, 'lpad': lpad, 'Bn': Bn, 'cls': cls, 'dino': dino}, ca[..., :C1])
+        return self._finish_context({'k': k_all, 'vt': vt_all, 'Lc': Lc, 'lpad': lpad, 'Bn': Bn, 'cls': cls, 'dino': dino}, ca[..., :C1])
 
     @torch.no_grad()
     def forward(self, x, timesteps=None, context=None, y=None, get_attr='', context_cache=None, in_scale=None, **kwargs):
@@ -98,6 +98,7 @@ class DiT_I23D_PixelArt(DiT_TriLatent):
         self._ensure_packed(dev)
         P, ws = self._packed, self._ws
         cc = context_cache if context_cache is not None else self.prepare_context(context)
+        self._check_prepared(cc, 'prepare_context')
         D, H, depth = self.embed_dim, self.num_heads, self.depth
         Bn, Bx = timesteps.shape[0], x.shape[0]
         assert cc['Bn'] == Bn
@@ -144,7 +145,7 @@ class DiT_I23D_PixelArt(DiT_TriLatent):
                 # sequence never changes); their K / V^T rows land in front of the cached ones of this layer
                 sa_k, sa_vt, npad, Dp = akv
                 ops.norm_modulate(xt, hb, M, D, kind=nk, eps=neps, weight=q['n1'], shift=mi[:, 0:], scale=mi[:, D:], mod_rows=N, mod_ld=ld)
-                qs = ws.get('sa_q', (Bn, H, npad, Dp), torch.bfloat16, zero=True)
+                qs = ws.get('sa_q', (Bn, H, npad, Dp), torch.bfloat16, zero=True, extent=N)
                 Do = attn_out_dim(D // H)
                 ao = ws.get('sa_o', (M, H * Do), torch.bfloat16)
                 ops.gemm(hb, q['qkv_w'], q['qkv_b'], ops.EPI_HEADS, qs, sa_k[i], sa_vt[i], M=M, tokens=N, tok_pad=npad, heads=H,
@@ -180,9 +181,9 @@ class DiT_I23D_PixelArt(DiT_TriLatent):
         (+ fused qk-norm) the blocks use; forward() then projects the x tokens only (25 % fewer QKV GEMM rows per layer and step
         at 768 + 256 tokens).  Needs the fused qk-norm epilogue (an unfused norm pass would re-normalise the cached rows every
         step); LN3D_NO_APPEND_CACHE=1 or a cache above APPEND_CACHE_MAX_BYTES fall back to projecting the whole sequence."""
-        if 'akv' in cc:
+        if 'akv' in cc and cc.get('akv_N') == N:
             return cc['akv']
-        cc['akv'] = None
+        cc['akv'], cc['akv_N'] = None, N               # per token count: the point-cloud variant takes any number of points per call
         P, ws, D, H = self._packed, self._ws, self.embed_dim, self.num_heads
         Ld = cc['dino'].shape[1]
         Dh = D // H
@@ -207,7 +208,7 @@ class DiT_I23D_PixelArt(DiT_TriLatent):
             sa_vt = torch.zeros(self.depth, Bn, H, Dp, npad, dtype=torch.bfloat16, device=dev)
         except torch.cuda.OutOfMemoryError:
             return None
-        qs = ws.get('sa_q', (Bn, H, npad, Dp), torch.bfloat16, zero=True)
+        qs = ws.get('sa_q', (Bn, H, npad, Dp), torch.bfloat16, zero=True, extent=N)
         rows = cc['dino'].reshape(Bn * Ld, D)
         for i, q in enumerate(P['blocks']):
             # outputs 1 / 2 start at token N of every (sample, head): the epilogue addresses [b, h, t, :] / [b, h, :, t] with the
@@ -302,7 +303,7 @@ class DiT_I23D(DiT_I23D_PixelArt):
         cls = self._cls_token(vec)
         dino = self._appended_tokens(ca[..., C1:])
         k_all, vt_all, lpad = self._cross_kv(ca[..., :C1], Bn, Lc, block_norm=True)      # the BLOCK's attention_y_norm
-        return self._fold_uc({'k': k_all, 'vt': vt_all, 'Lc': Lc, 'lpad': lpad, 'Bn': Bn, 'cls': cls, 'dino': dino}, ca[..., :C1])
+        return self._finish_context({'k': k_all, 'vt': vt_all, 'Lc': Lc, 'lpad': lpad, 'Bn': Bn, 'cls': cls, 'dino': dino}, ca[..., :C1])
 
 
 class DiT_I23D_PixelArt_MVCond(DiT_I23D_PixelArt):
@@ -333,7 +334,7 @@ class DiT_I23D_PixelArt_MVCond(DiT_I23D_PixelArt):
         mvb = ws.get('mv_in', (Bn * Lk, mv.shape[3]), torch.bfloat16)
         ops.cast_bf16(mv.reshape(Bn * Lk, mv.shape[3]).contiguous().float(), mvb)
         k_all, vt_all, lpad = self._cross_kv(mvb, Bn, Lk)
-        return self._fold_uc({'k': k_all, 'vt': vt_all, 'Lc': Lk, 'lpad': lpad, 'Bn': Bn, 'cls': cls, 'dino': appended}, mv.reshape(Bn, Lk, -1))
+        return self._finish_context({'k': k_all, 'vt': vt_all, 'Lc': Lk, 'lpad': lpad, 'Bn': Bn, 'cls': cls, 'dino': appended}, mv.reshape(Bn, Lk, -1))
 
 
 class DiT_I23D_PixelArt_MVCond_noClip(DiT_I23D_PixelArt):
@@ -360,7 +361,7 @@ class DiT_I23D_PixelArt_MVCond_noClip(DiT_I23D_PixelArt):
         mvb = self._ws.get('mv_in', (Bn * Lk, mv.shape[3]), torch.bfloat16)
         ops.cast_bf16(mv.reshape(Bn * Lk, mv.shape[3]).contiguous().float(), mvb)
         k_all, vt_all, lpad = self._cross_kv(mvb, Bn, Lk)
-        return self._fold_uc({'k': k_all, 'vt': vt_all, 'Lc': Lk, 'lpad': lpad, 'Bn': Bn, 'cls': torch.zeros(Bn, D, device=dev),
+        return self._finish_context({'k': k_all, 'vt': vt_all, 'Lc': Lk, 'lpad': lpad, 'Bn': Bn, 'cls': torch.zeros(Bn, D, device=dev),
                               'dino': torch.zeros(Bn, 0, D, device=dev, dtype=torch.bfloat16)}, mv.reshape(Bn, Lk, -1))
 
 
@@ -400,7 +401,7 @@ class DiT_TriLatent_PixelArt(DiT_I23D_PixelArt):
         D = self.embed_dim
         cls = self._cls_token(vec)
         k_all, vt_all, lpad = self._cross_kv(ca, Bn, Lc, block_norm=True)               # the BLOCK's attention_y_norm
-        return self._fold_uc({'k': k_all, 'vt': vt_all, 'Lc': Lc, 'lpad': lpad, 'Bn': Bn, 'cls': cls,
+        return self._finish_context({'k': k_all, 'vt': vt_all, 'Lc': Lc, 'lpad': lpad, 'Bn': Bn, 'cls': cls,
                               'dino': torch.zeros(Bn, 0, D, device=dev, dtype=torch.bfloat16)}, ca)
 
 

@@ -216,13 +216,23 @@ class Workspace:
     def __init__(self, device):
         self.device = device
         self._t = {}
+        self._extent = {}          # key -> extent written by the last call through it
 
-    def get(self, name, shape, dtype, zero=False):
+    def get(self, name, shape, dtype, zero=False, extent=None):
+        """extent: for a zero=True buffer whose padding is "never written", the extent that IS written by this call (the true token
+        count behind a padded shape).  When it shrinks from one call to the next, the buffer is zeroed again: the attention kernels mask
+        padded keys' scores, but the masked probability 0 still multiplies the padded V^T columns, and 0 * NaN (what a diverged sample
+        left in rows that the smaller call no longer rewrites) is NaN.  One buffer per (name, shape, dtype) whatever the extents seen:
+        scratch stays bounded by the padded shapes; a steady extent (every sampling loop, every captured graph) never re-zeroes."""
         key = (name, tuple(shape), dtype)
         t = self._t.get(key)
         if t is None:
             t = (torch.zeros if zero else torch.empty)(tuple(shape), dtype=dtype, device=self.device)
             self._t[key] = t
+        if extent is not None:
+            if extent < self._extent.get(key, extent):
+                t.zero_()
+            self._extent[key] = extent
         return t
 
 
@@ -298,9 +308,9 @@ def self_attention_hip(ws, tag, h_bf16, B, N, D, H, qkv_w, qkv_b, qn=None, kn=No
     Dp = attn_head_pad(Dh)
     nq = N if nq is None else nq
     npad = (N + 63) // 64 * 64
-    q = ws.get(tag + 'q', (B, H, npad, Dp), torch.bfloat16, zero=True)
-    k = ws.get(tag + 'k', (B, H, npad, Dp), torch.bfloat16, zero=True)
-    vt = ws.get(tag + 'vt', (B, H, Dp, npad), torch.bfloat16, zero=True)
+    q = ws.get(tag + 'q', (B, H, npad, Dp), torch.bfloat16, zero=True, extent=N)
+    k = ws.get(tag + 'k', (B, H, npad, Dp), torch.bfloat16, zero=True, extent=N)
+    vt = ws.get(tag + 'vt', (B, H, Dp, npad), torch.bfloat16, zero=True, extent=N)
     Do = attn_out_dim(Dh)
     o = ws.get(tag + 'o', (B * nq, H * Do), torch.bfloat16)
     if isinstance(h_bf16, ops.MX):
@@ -352,9 +362,9 @@ def vit_block_hip(ws, x, q, B, T, H, zeros, eps, act, causal=False, res_gemm=gat
     tpad = (T + 63) // 64 * 64
     h = ws.get('h', (M, D), torch.bfloat16)
     ops.norm_modulate(x, h, M, D, kind=0, eps=eps, weight=q['n1'][0], shift=q['n1'][1], scale=zeros, mod_rows=M, mod_ld=0)
-    qq = ws.get('q', (B, H, tpad, Dh), torch.bfloat16, zero=True)
-    kk = ws.get('k', (B, H, tpad, Dh), torch.bfloat16, zero=True)
-    vt = ws.get('vt', (B, H, Dh, tpad), torch.bfloat16, zero=True)
+    qq = ws.get('q', (B, H, tpad, Dh), torch.bfloat16, zero=True, extent=T)
+    kk = ws.get('k', (B, H, tpad, Dh), torch.bfloat16, zero=True, extent=T)
+    vt = ws.get('vt', (B, H, Dh, tpad), torch.bfloat16, zero=True, extent=T)
     o = ws.get('o', (M, D), torch.bfloat16)
     ops.gemm(h, q['qkv_w'], q['qkv_b'], ops.EPI_HEADS, qq, kk, vt, M=M, tokens=T, tok_pad=tpad, heads=H, head_dim=Dh, transpose_mask=0b100)
     ops.attention(qq, kk, vt, o, B, H, T, tpad, T, tpad, Dh, scale=Dh ** -0.5, causal=causal)

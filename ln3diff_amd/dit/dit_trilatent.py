@@ -230,6 +230,12 @@ class DiT_TriLatent(DiT):
         cc['fold'], cc['const'] = fold, const
         return cc
 
+    def _finish_context(self, cc, rows):
+        """Last step of every prepare_context: the cache is stamped with the epoch of the weights its K / V^T were made from (forward()
+        refuses it under any other, _check_prepared), then the zero-context fold."""
+        cc['epoch'] = self._packed['epoch']
+        return self._fold_uc(cc, rows)
+
     def _fc1(self, probe, i, hb, q, f1):
         """Block i's MLP fc1 GEMM (erf-GELU epilogue; MX-FP8 in and out when hb is an ops.MX).  `probe`: bench.py's `_fc1_probe`
         measurement hook {'layer', 'events', 'max'}: HIP events on the launch stream around this one GEMM of that layer, inside the real step."""
@@ -262,7 +268,7 @@ class DiT_TriLatent(DiT):
         # K copy whose 64 head dims are stored in the 16-group order [0-3, 8-11, 4-7, 12-15]: the order in which the query
         # projection's accumulators hand q to the MFMA when cross-attention runs inside that GEMM (LN3D_EPI_CROSS_ATTN)
         kp_all = k_all[..., ops.vt_key_order(64, context.device)].contiguous()
-        return self._fold_uc({'k': k_all, 'kp': kp_all, 'vt': vt_all, 'Lc': Lc, 'lpad': lpad, 'Bn': Bn}, context)
+        return self._finish_context({'k': k_all, 'kp': kp_all, 'vt': vt_all, 'Lc': Lc, 'lpad': lpad, 'Bn': Bn}, context)
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
@@ -288,7 +294,9 @@ class DiT_TriLatent(DiT):
         re-streaming those weights every step.  Returns the cache for forward(..., mod_cache=(cache, step)): {'mod': [n * rows,
         nmod] f32, 'rows': rows}.  When every sample of a step has the same timestep (all samplers of this path) ONE row per step is
         kept (rows = 1: 150 MB at 250 steps instead of 2.4 GB at network batch 16) and the kernels read it with a sample stride of 0.
-        A schedule whose cache would exceed MODCACHE_MAX_BYTES returns None: the caller runs the modulation GEMMs per step."""
+        A schedule whose cache would exceed MODCACHE_MAX_BYTES returns None: the caller runs the modulation GEMMs per step.
+        The rows are storage of the returned cache's own (one allocation per sampling run): a second prepared schedule, of the same
+        length or not, leaves this one alone."""
         dev = next(self.parameters()).device
         self._ensure_packed(dev)
         n, Bn = t_table.shape
@@ -296,9 +304,17 @@ class DiT_TriLatent(DiT):
         rows = 1 if bool((t_table == t_table[:, :1]).all()) else Bn
         if n * rows * nmod * 4 > self.MODCACHE_MAX_BYTES:
             return None
-        mod_all = self._ws.get('mod_all', (n * rows, nmod), torch.float32)
+        mod_all = torch.empty(n * rows, nmod, dtype=torch.float32, device=dev)
         self._timestep_modulation(t_table[:, :rows].reshape(-1).to(dev), mod_all, 'ma')
-        return {'mod': mod_all, 'rows': rows}
+        return {'mod': mod_all, 'rows': rows, 'epoch': self._packed['epoch']}
+
+    def _check_prepared(self, cache, maker):
+        """A prepared context / timestep cache holds values computed from the weights of ONE epoch (ln3diff_amd/_cache.py); after any
+        weight change - the epoch is global, so a load into another module counts - it is refused instead of being mixed with the
+        re-packed blocks.  One host integer compare: no device read, nothing inside a captured graph."""
+        if cache.get('epoch') != self._packed['epoch']:
+            raise RuntimeError(f"{type(self).__name__}: this cache was made by {maker}() before the weights changed (weights epoch "
+                               f"{cache.get('epoch')}, now {self._packed['epoch']}); call {maker}() again")
 
     def forward(self, x, timesteps=None, context=None, y=None, get_attr='', context_cache=None, in_scale=None,
                 mod_cache=None, **kwargs):
@@ -318,6 +334,7 @@ class DiT_TriLatent(DiT):
         N = 3 * L
         M = Bn * N
         cc = context_cache if context_cache is not None else self.prepare_context(context)
+        self._check_prepared(cc, 'prepare_context')
         assert cc['Bn'] == Bn
 
         # -- timestep embedding and all adaLN modulations (or the rows prepared for the whole schedule)
@@ -325,6 +342,7 @@ class DiT_TriLatent(DiT):
         ld = nmod                                              # stride between the samples' modulation rows
         if mod_cache is not None:
             mc, step = mod_cache
+            self._check_prepared(mc, 'prepare_timesteps')
             rows = mc['rows']
             assert rows in (1, Bn) and mc['mod'].shape[1] == nmod
             mod = mc['mod'][step * rows:(step + 1) * rows]

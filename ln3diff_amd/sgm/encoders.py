@@ -88,6 +88,10 @@ class FrozenCLIPEmbedder(nn.Module):
         if freeze:
             self.freeze()
 
+    def _apply(self, fn, *a, **k):
+        _cache.bump()
+        return super()._apply(fn, *a, **k)
+
     def freeze(self):
         self.transformer = self.transformer.eval()
         for p in self.parameters():

@@ -390,7 +390,7 @@ class EulerEDMSampler:
         t_dev, s_dev, the step's modulation rows copied into mod_step)."""
         st['x'] = st['x'].contiguous()
         mrows = mod_all['rows']
-        mod_step = {'mod': torch.empty_like(mod_all['mod'][:mrows]), 'rows': mrows}
+        mod_step = {'mod': torch.empty_like(mod_all['mod'][:mrows]), 'rows': mrows, 'epoch': mod_all.get('epoch')}
         mod_step['mod'].copy_(mod_all['mod'][:mrows])
         st['t_dev'].fill_(float(st['quant'][0][1]))
         st['s_dev'].fill_(1.0)

@@ -441,6 +441,15 @@ class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(_PosteriorSeams, _Din
                                  self._ws.get('pe_silu', (B * L, D), torch.bfloat16), raw, B, self.ldm_embed_dim, S, self.vae_p, D)
         return self.forward_vit_decoder(raw.view(B, L, D), img_size)
 
+    def _down_packed(self, dev):
+        """ldm_downsample's GEMM operands, per weights epoch (as _quant_packed)"""
+        q = self.__dict__.get('_down')
+        if not _cache.fresh(q, dev):
+            ld = self.superresolution['ldm_downsample']
+            q = _cache.stamp({'device': dev, 'w': bf16(ld.weight, dev), 'b': f32(ld.bias, dev)}, self)
+            self.__dict__['_down'] = q
+        return q
+
     @torch.no_grad()
     def vae_reparameterization(self, latent, sample_posterior, eps=None):
         """latent: ViT encoder tokens [B, 256, 384] -> ldm_downsample -> unpatchify3D (p = 2) -> quant_conv posterior (mode, or
@@ -449,10 +458,7 @@ class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(_PosteriorSeams, _Din
             raise RuntimeError("ln3diff_amd decoder runs on the HIP device only (no CPU fallback)")
         dev = latent.device
         ld = self.superresolution['ldm_downsample']
-        q = self.__dict__.get('_down')
-        if not _cache.fresh(q, dev):
-            q = _cache.stamp({'device': dev, 'w': bf16(ld.weight, dev), 'b': f32(ld.bias, dev)}, self)
-            self.__dict__['_down'] = q
+        q = self._down_packed(dev)
         B, T, Ce = latent.shape
         xb = torch.empty(B * T, Ce, device=dev, dtype=torch.bfloat16)
         ops.cast_bf16(latent.contiguous().float(), xb)
