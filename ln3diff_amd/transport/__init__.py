@@ -8,6 +8,7 @@ Linear path + velocity prediction: dx/dt = model(x, t), t from 0 (noise) to 1 (d
 published algorithm of the absent third-party torchdiffeq 0.2.3: parity unpinned against the package - SURVEY.md §8c; pinned to
 oracle/samplers.py's restatement step for step, and validated by convergence to the fixed-step solution).
 """
+import numpy as np
 import torch
 
 from .. import ops
@@ -97,7 +98,8 @@ class Sampler:
             last_step_size = 0.0
         t1 = 1.0 if last_step_size == 0 else 1 - last_step_size
         ts = torch.linspace(0.0, t1, num_steps)
-        dt = float(ts[1] - ts[0])
+        dt32 = ts[1] - ts[0]
+        dt = float(dt32)
 
         def D(t):
             if diffusion_form == "constant":       # the reference hands a Python float to th.sqrt (integrators.py:37)
@@ -128,8 +130,11 @@ class Sampler:
                 return model_fn(xx, t_dev, **model_kwargs).contiguous()
 
             def drift_coefs(t):                     # sde_drift(x, t) = cv * v + cx * x
-                d = D(t)
-                return 1.0 + d * t / (1 - t), -d / (1 - t)
+                # at t = 1 (the second Heun stage of the last step when last_step=None) the reference's tensor arithmetic divides by
+                # zero without raising and returns non-finite states (integrators.py:40-49): IEEE division here too
+                d, om = np.float64(D(t)), np.float64(1 - t)
+                with np.errstate(divide='ignore', invalid='ignore'):
+                    return float(1.0 + d * t / om), float(-d / om)
 
             xs = []
             for ti in ts[:-1]:
@@ -148,8 +153,9 @@ class Sampler:
                     v1 = vel(xhat, t)
                     xp = torch.empty_like(x)
                     ops.lincomb(None, [xhat, v1], [1.0 + dt * cx1, dt * cv1], xp)
-                    cv2, cx2 = drift_coefs(t + dt)
-                    v2 = vel(xp, t + dt)
+                    t2 = float(ti + dt32)           # the reference's fp32 `t_cur + self.dt`: it is this sum that reaches 1 exactly
+                    cv2, cx2 = drift_coefs(t2)
+                    v2 = vel(xp, t2)
                     xn = torch.empty_like(x)
                     # xhat + 0.5 dt (K1 + K2), K1 = cv1 v1 + cx1 xhat, K2 = cv2 v2 + cx2 xp
                     ops.lincomb(None, [xhat, v1, v2, xp], [1.0 + 0.5 * dt * cx1, 0.5 * dt * cv1, 0.5 * dt * cv2, 0.5 * dt * cx2], xn)

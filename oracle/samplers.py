@@ -65,10 +65,14 @@ def denoiser_scaling(kind, sb, sigma_data=0.5):
 
 
 def edm_denoise_cfg(net, x, sigma, cond, uc, scale, table, scaling='eps', discrete=True, quantize_c_noise=True):
-    """VanillaCFG.prepare_inputs ([uc, c] order) -> Denoiser / DiscreteDenoiser.forward (denoiser.py:24-44, 69-78) -> CFG."""
-    xin = torch.cat([x, x])
-    s = torch.cat([sigma, sigma])
-    c_all = {k: torch.cat((uc[k], cond[k]), 0) for k in cond}
+    """VanillaCFG.prepare_inputs ([uc, c] order) -> Denoiser / DiscreteDenoiser.forward (denoiser.py:24-44, 69-78) -> CFG.
+    scale None: IdentityGuider (guiders.py:45-57) - the batch is not doubled, uc is not read, the denoised batch is returned as is."""
+    if scale is None:
+        xin, s, c_all = x, sigma, dict(cond)
+    else:
+        xin = torch.cat([x, x])
+        s = torch.cat([sigma, sigma])
+        c_all = {k: torch.cat((uc[k], cond[k]), 0) for k in cond}
     if discrete:
         s = table[sigma_to_idx(s, table)]             # possibly_quantize_sigma
     sb = s.view(-1, *([1] * (x.ndim - 1)))
@@ -77,16 +81,26 @@ def edm_denoise_cfg(net, x, sigma, cond, uc, scale, table, scaling='eps', discre
     if discrete and quantize_c_noise:
         c_noise = sigma_to_idx(c_noise, table)        # quantize_c_noise -> index 0..999
     out = net(xin * c_in, c_noise, c_all) * c_out + xin * c_skip
+    if scale is None:
+        return out
     x_u, x_c = out.chunk(2)
     return x_u + scale * (x_c - x_u)
 
 
+def _sigma_table(num_steps, sigmas):
+    """the descending fp32 table with its appended zero: the legacy DDPM one, or `sigmas` - a tensor of that form, or a discretization
+    callable n -> tensor (sgm's Discretization.__call__ with do_append_zero)"""
+    if sigmas is None:
+        return legacy_ddpm_sigmas(num_steps)
+    return sigmas(num_steps) if callable(sigmas) else sigmas
+
+
 def edm_euler_sample(net, z, cond, uc, num_steps=250, scale=6.5, trace=None, s_churn=0.0, s_tmin=0.0, s_tmax=float('inf'), s_noise=1.0,
-                     step_noise=None, **denoiser_kw):
+                     step_noise=None, sigmas=None, **denoiser_kw):
     """EulerEDMSampler.__call__ (sgm/modules/diffusionmodules/sampling.py:82-130,211-215).  s_churn = 0: gamma = 0, deterministic after z.
     s_churn > 0 (r6): gamma_i = min(s_churn / (num_sigmas - 1), sqrt 2 - 1) where s_tmin <= sigma_i <= s_tmax; sigma_hat = sigma (1 + gamma),
     x += randn * s_noise * sqrt(sigma_hat^2 - sigma^2) before the denoiser runs at sigma_hat; step_noise(i) supplies the draw of step i."""
-    sigmas = legacy_ddpm_sigmas(num_steps)
+    sigmas = _sigma_table(num_steps, sigmas)
     table = discrete_denoiser_table()
     x = z * torch.sqrt(1.0 + sigmas[0] ** 2.0)
     s_in = x.new_ones([x.shape[0]])
@@ -123,10 +137,10 @@ def ancestral_step_sizes(sigma_from, sigma_to, eta=1.0):
 
 
 def edm_heun_sample(net, z, cond, uc, num_steps=10, scale=6.5, trace=None, s_churn=0.0, s_tmin=0.0, s_tmax=float('inf'), s_noise=1.0,
-                    step_noise=None):
+                    step_noise=None, sigmas=None, **denoiser_kw):
     """HeunEDMSampler (sampling.py:82-130 + 218-236): the Euler step, then - unless every next sigma is 0 - a second denoiser call at
     (x_euler, next_sigma) and the trapezoidal update x + dt (d + d_new) / 2."""
-    sigmas = legacy_ddpm_sigmas(num_steps)
+    sigmas = _sigma_table(num_steps, sigmas)
     table = discrete_denoiser_table()
     x = z * torch.sqrt(1.0 + sigmas[0] ** 2.0)
     s_in = x.new_ones([x.shape[0]])
@@ -138,14 +152,14 @@ def edm_heun_sample(net, z, cond, uc, num_steps=10, scale=6.5, trace=None, s_chu
         if gamma > 0:
             eps = (step_noise(i) if step_noise is not None else torch.randn_like(x)) * s_noise
             x = x + eps * _bc(sigma_hat ** 2 - sigma ** 2, x) ** 0.5
-        den = edm_denoise_cfg(net, x, sigma_hat, cond, uc, scale, table)
+        den = edm_denoise_cfg(net, x, sigma_hat, cond, uc, scale, table, **denoiser_kw)
         d = (x - den) / _bc(sigma_hat, x)
         dt = _bc(nxt - sigma_hat, x)
         x_e = x + dt * d
         if torch.sum(nxt) < 1e-14:
             x = x_e
         else:
-            den2 = edm_denoise_cfg(net, x_e, nxt, cond, uc, scale, table)
+            den2 = edm_denoise_cfg(net, x_e, nxt, cond, uc, scale, table, **denoiser_kw)
             d_new = (x_e - den2) / _bc(nxt, x)
             x = torch.where(_bc(nxt, x) > 0.0, x + (d + d_new) / 2.0 * dt, x_e)
         if trace is not None:
@@ -153,17 +167,18 @@ def edm_heun_sample(net, z, cond, uc, num_steps=10, scale=6.5, trace=None, s_chu
     return x
 
 
-def euler_ancestral_sample(net, z, cond, uc, num_steps=10, scale=6.5, eta=1.0, s_noise=1.0, step_noise=None, trace=None):
+def euler_ancestral_sample(net, z, cond, uc, num_steps=10, scale=6.5, eta=1.0, s_noise=1.0, step_noise=None, trace=None, sigmas=None,
+                           **denoiser_kw):
     """EulerAncestralSampler (sampling.py:133-170, 239-246): Euler step to sigma_down, then sigma_up of fresh noise where next_sigma > 0.
     The reference draws randn_like(x) at EVERY step (torch.where evaluates both branches): step_noise(i) is called for every i."""
-    sigmas = legacy_ddpm_sigmas(num_steps)
+    sigmas = _sigma_table(num_steps, sigmas)
     table = discrete_denoiser_table()
     x = z * torch.sqrt(1.0 + sigmas[0] ** 2.0)
     s_in = x.new_ones([x.shape[0]])
     for i in range(len(sigmas) - 1):
         sigma, nxt = s_in * sigmas[i], s_in * sigmas[i + 1]
         sigma_down, sigma_up = ancestral_step_sizes(sigma, nxt, eta)
-        den = edm_denoise_cfg(net, x, sigma, cond, uc, scale, table)
+        den = edm_denoise_cfg(net, x, sigma, cond, uc, scale, table, **denoiser_kw)
         x = x + (x - den) / _bc(sigma, x) * _bc(sigma_down - sigma, x)
         noise = step_noise(i) if step_noise is not None else torch.randn_like(x)
         x = torch.where(_bc(nxt, x) > 0.0, x + noise * s_noise * _bc(sigma_up, x), x)
@@ -172,17 +187,18 @@ def euler_ancestral_sample(net, z, cond, uc, num_steps=10, scale=6.5, eta=1.0, s
     return x
 
 
-def dpmpp2s_ancestral_sample(net, z, cond, uc, num_steps=10, scale=6.5, eta=1.0, s_noise=1.0, step_noise=None, trace=None):
+def dpmpp2s_ancestral_sample(net, z, cond, uc, num_steps=10, scale=6.5, eta=1.0, s_noise=1.0, step_noise=None, trace=None, sigmas=None,
+                             **denoiser_kw):
     """DPMPP2SAncestralSampler (sampling.py:249-287): the exponential-integrator midpoint step in t = -log sigma towards sigma_down
     (a second denoiser call at sigma(t + h / 2)), Euler when sigma_down is 0, then the ancestral noise."""
-    sigmas = legacy_ddpm_sigmas(num_steps)
+    sigmas = _sigma_table(num_steps, sigmas)
     table = discrete_denoiser_table()
     x = z * torch.sqrt(1.0 + sigmas[0] ** 2.0)
     s_in = x.new_ones([x.shape[0]])
     for i in range(len(sigmas) - 1):
         sigma, nxt = s_in * sigmas[i], s_in * sigmas[i + 1]
         sigma_down, sigma_up = ancestral_step_sizes(sigma, nxt, eta)
-        den = edm_denoise_cfg(net, x, sigma, cond, uc, scale, table)
+        den = edm_denoise_cfg(net, x, sigma, cond, uc, scale, table, **denoiser_kw)
         x_euler = x + (x - den) / _bc(sigma, x) * _bc(sigma_down - sigma, x)
         if torch.sum(sigma_down) < 1e-14:
             x = x_euler
@@ -193,7 +209,7 @@ def dpmpp2s_ancestral_sample(net, z, cond, uc, num_steps=10, scale=6.5, eta=1.0,
             m1, m2 = sm.neg().exp() / t.neg().exp(), (-0.5 * h).expm1()
             m3, m4 = t_next.neg().exp() / t.neg().exp(), (-h).expm1()
             x2 = _bc(m1, x) * x - _bc(m2, x) * den
-            den2 = edm_denoise_cfg(net, x2, sm.neg().exp(), cond, uc, scale, table)
+            den2 = edm_denoise_cfg(net, x2, sm.neg().exp(), cond, uc, scale, table, **denoiser_kw)
             x = torch.where(_bc(sigma_down, x) > 0.0, _bc(m3, x) * x - _bc(m4, x) * den2, x_euler)
         noise = step_noise(i) if step_noise is not None else torch.randn_like(x)
         x = torch.where(_bc(nxt, x) > 0.0, x + noise * s_noise * _bc(sigma_up, x), x)
@@ -202,10 +218,10 @@ def dpmpp2s_ancestral_sample(net, z, cond, uc, num_steps=10, scale=6.5, eta=1.0,
     return x
 
 
-def dpmpp2m_sample(net, z, cond, uc, num_steps=10, scale=6.5, trace=None):
+def dpmpp2m_sample(net, z, cond, uc, num_steps=10, scale=6.5, trace=None, sigmas=None, **denoiser_kw):
     """DPMPP2MSampler (sampling.py:290-365): the second-order multistep form - the previous step's denoised output extrapolates the
     current one (ratio r of the two log-sigma steps); first step and the step onto sigma = 0 are first order."""
-    sigmas = legacy_ddpm_sigmas(num_steps)
+    sigmas = _sigma_table(num_steps, sigmas)
     table = discrete_denoiser_table()
     x = z * torch.sqrt(1.0 + sigmas[0] ** 2.0)
     s_in = x.new_ones([x.shape[0]])
@@ -213,7 +229,7 @@ def dpmpp2m_sample(net, z, cond, uc, num_steps=10, scale=6.5, trace=None):
     for i in range(len(sigmas) - 1):
         sigma, nxt = s_in * sigmas[i], s_in * sigmas[i + 1]
         prev = None if i == 0 else s_in * sigmas[i - 1]
-        den = edm_denoise_cfg(net, x, sigma, cond, uc, scale, table)
+        den = edm_denoise_cfg(net, x, sigma, cond, uc, scale, table, **denoiser_kw)
         t, t_next = sigma.log().neg(), nxt.log().neg()
         h = t_next - t
         m1, m2 = t_next.neg().exp() / t.neg().exp(), (-h).expm1()
@@ -245,9 +261,9 @@ def linear_multistep_coeff(order, t, i, j):
     return float(prim(float(t[i + 1])) - prim(float(t[i])))
 
 
-def linear_multistep_sample(net, z, cond, uc, num_steps=10, scale=6.5, order=4, trace=None):
+def linear_multistep_sample(net, z, cond, uc, num_steps=10, scale=6.5, order=4, trace=None, sigmas=None, **denoiser_kw):
     """LinearMultistepSampler (sampling.py:172-208): Adams-Bashforth in sigma over the last `order` derivatives d = (x - denoised) / sigma."""
-    sigmas = legacy_ddpm_sigmas(num_steps)
+    sigmas = _sigma_table(num_steps, sigmas)
     table = discrete_denoiser_table()
     x = z * torch.sqrt(1.0 + sigmas[0] ** 2.0)
     s_in = x.new_ones([x.shape[0]])
@@ -255,7 +271,7 @@ def linear_multistep_sample(net, z, cond, uc, num_steps=10, scale=6.5, order=4, 
     ds = []
     for i in range(len(sigmas) - 1):
         sigma = s_in * sigmas[i]
-        den = edm_denoise_cfg(net, x, sigma, cond, uc, scale, table)
+        den = edm_denoise_cfg(net, x, sigma, cond, uc, scale, table, **denoiser_kw)
         ds.append((x - den) / _bc(sigma, x))
         if len(ds) > order:
             ds.pop(0)
@@ -399,12 +415,15 @@ def ddim_sample_loop(net, x, cond, tables, eta=0.0, cfg_scale=1.0, ucond=None, n
 
 
 # ------------------------------------------------------- flow matching (transport)
-def flow_ode_sample(model_fn, x, num_steps=50, method="euler", **model_kwargs):
+def flow_ode_sample(model_fn, x, num_steps=50, method="euler", trace=None, **model_kwargs):
     """transport.Sampler.sample_ode for Linear path / velocity prediction: integrate
     dx/dt = model_fn(x, t) over t = linspace(0, 1, num_steps) (num_steps-1 fixed steps).
-    Returns the final state (the reference returns the whole trajectory; callers take [-1])."""
+    Returns the final state (the reference returns the whole trajectory; callers take [-1]); trace: a list that receives that
+    trajectory, the initial state first (num_steps entries)."""
     ts = torch.linspace(0.0, 1.0, num_steps)
     f = lambda t, y: model_fn(y, torch.ones(y.size(0)) * t, **model_kwargs)
+    if trace is not None:
+        trace.append(x.clone())
     for i in range(num_steps - 1):
         t0, t1 = ts[i], ts[i + 1]
         dt = t1 - t0
@@ -425,6 +444,8 @@ def flow_ode_sample(model_fn, x, num_steps=50, method="euler", **model_kwargs):
             x = x + dt * (k1 + 3 * (k2 + k3) + k4) / 8
         else:
             raise ValueError(method)
+        if trace is not None:
+            trace.append(x.clone())
     return x
 
 

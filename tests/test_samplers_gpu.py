@@ -1,7 +1,8 @@
 """GPU parity of the device-resident sampler loops against the reference goldens (final latents).
 The loops are chaotic amplifiers of rounding error, so the tolerance is on the FINAL latent relative to its norm:
 bf16 network inside an fp32 sampler state: rel-L2 <= 1e-2 after 10..250 steps (measured 1.6e-4 .. 3.2e-4: the samplers
-contract, the per-step network error ~1e-3 does not compound)."""
+contract, the per-step network error ~1e-3 does not compound).
+The loops' own coefficients are pinned per step, to 1e-5 against float64 with an exact network, in tests/test_sampler_loops_gpu.py."""
 import numpy as np
 import pytest
 import torch
