@@ -8,8 +8,7 @@ per-row gates (gate_rows = 1)."""
 import torch
 import torch.nn as nn
 
-from .. import ops
-from .. import _cache
+from .. import ops, _cache
 from .dit_models_xformers import DiTBlock, Workspace, bf16, f32, get_2d_sincos_pos_embed, pack_block, self_attention_hip
 
 
@@ -17,7 +16,7 @@ class DiTBlock2(DiTBlock):
     pass
 
 
-class DiT2(nn.Module):
+class DiT2(_cache.PackedWeights, nn.Module):
     def __init__(self, input_size=16, patch_size=2, in_channels=4, hidden_size=1152, depth=28, num_heads=16,
                  mlp_ratio=4, class_dropout_prob=0.1, num_classes=1000, learn_sigma=True, mixing_logit_init=-3,
                  mixed_prediction=True, context_dim=False, roll_out=False, plane_n=3, return_all_layers=False,
@@ -30,29 +29,19 @@ class DiT2(nn.Module):
         self.blocks = nn.ModuleList([DiTBlock2(hidden_size, num_heads, mlp_ratio=mlp_ratio) for _ in range(depth)])
         pe = get_2d_sincos_pos_embed(hidden_size, (3 * 16, 16)).reshape(3 * 256, hidden_size)   # vit_triplane.py:333-343
         self.pos_embed.data.copy_(torch.from_numpy(pe).float().unsqueeze(0))
-        self._packed = None
-        _cache.watch(self)
 
-    def _apply(self, fn, *a, **k):
-        _cache.bump()
-        return super()._apply(fn, *a, **k)
-
-    def pack(self, device):
-        if _cache.fresh(self._packed, device):
-            return self._packed
-        P = {'device': device, 'pos': f32(self.pos_embed[0], device), 'blocks': []}
+    def _pack(self, P, device):
+        P['pos'], P['blocks'] = f32(self.pos_embed[0], device), []
         for b in self.blocks:
             q = pack_block(b, self.num_heads, self.embed_dim // self.num_heads, device)
             q['ada_w'], q['ada_b'] = bf16(b.adaLN_modulation[1].weight, device), f32(b.adaLN_modulation[1].bias, device)
             P['blocks'].append(q)
-        self._packed = _cache.stamp(P, self)
-        return P
 
     @torch.no_grad()
     def forward_tokens(self, silu_c, B, ws):
         """silu_c bf16 [B*768, D] -> tokens f32 [B*768, D] (workspace tensor)."""
         dev = silu_c.device
-        P = self.pack(dev)
+        P = self._ensure_packed(dev)
         D, H, N = self.embed_dim, self.num_heads, self.plane_n * 256
         M = B * N
         x = ws.get('d2_x', (M, D), torch.float32)

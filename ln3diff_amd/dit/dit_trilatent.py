@@ -28,7 +28,7 @@ from .dit_models_xformers import (CaptionEmbedder, DiTBlock, FinalLayer, PatchEm
                                   get_2d_sincos_pos_embed, self_attention_hip, pack_block, pack_block_mx, pack_caption)
 
 
-class DiT(nn.Module):
+class DiT(_cache.PackedWeights, nn.Module):
     """Base container (reference dit/dit_models_xformers.py:681-835)."""
 
     def __init__(self, input_size=32, patch_size=2, in_channels=4, hidden_size=1152, depth=28, num_heads=16,
@@ -53,8 +53,6 @@ class DiT(nn.Module):
                                              context_dim=context_dim) for _ in range(depth)])
         self.final_layer = final_layer_blk(hidden_size, patch_size, self.out_channels)
         self.initialize_weights()
-        self._packed = None
-        _cache.watch(self)
         self._ws = None
 
     def initialize_weights(self):
@@ -78,15 +76,6 @@ class DiT(nn.Module):
             nn.init.constant_(self.final_layer.adaLN_modulation[-1].bias, 0)
         nn.init.constant_(self.final_layer.linear.weight, 0)
         nn.init.constant_(self.final_layer.linear.bias, 0)
-
-    # any parameter change invalidates the packed device copies
-    def load_state_dict(self, *a, **k):
-        _cache.bump()
-        return super().load_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        _cache.bump()
-        return super()._apply(fn, *a, **k)
 
 
 class DiT_TriLatent(DiT):
@@ -129,11 +118,8 @@ class DiT_TriLatent(DiT):
         return self._matmul_precision
 
     # ------------------------------------------------------------------ packing
-    def _ensure_packed(self, device):
-        if _cache.fresh(self._packed, device):
-            return
+    def _pack(self, P, device):
         H = self.num_heads
-        P = {'device': device}
         self._pack_embedder(P, device)
         P['t_w0'], P['t_b0'] = bf16(self.t_embedder.mlp[0].weight, device), f32(self.t_embedder.mlp[0].bias, device)
         P['t_w2'], P['t_b2'] = bf16(self.t_embedder.mlp[2].weight, device), f32(self.t_embedder.mlp[2].bias, device)
@@ -152,7 +138,6 @@ class DiT_TriLatent(DiT):
         if P['precision'] == 'mxfp8':
             P['blocks'] = [pack_block_mx(q, b, device) for q, b in zip(P['blocks'], self.blocks)]
         P['fin_w'], P['fin_b'] = f32(self.final_layer.linear.weight, device), f32(self.final_layer.linear.bias, device)
-        self._packed = _cache.stamp(P, self)
         self._ws = Workspace(device)
 
     def _pack_embedder(self, P, device):

@@ -137,7 +137,7 @@ class SpatialTransformer(nn.Module):             # attention_compat.py:228-277
         self.proj_out = zero_module(nn.Conv2d(inner, in_channels, kernel_size=1))
 
 
-class UNetModel(nn.Module):
+class UNetModel(_cache.PackedWeights, nn.Module):
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks, attention_resolutions, dropout=0,
                  channel_mult=(1, 2, 4, 8), conv_resample=True, dims=2, num_classes=None, use_checkpoint=False, use_fp16=False,
                  num_heads=-1, num_head_channels=-1, num_heads_upsample=-1, use_scale_shift_norm=False, resblock_updown=False,
@@ -224,17 +224,7 @@ class UNetModel(nn.Module):
                     ds //= 2
                 self.output_blocks.append(TimestepEmbedSequential(*layers))
         self.out = nn.Sequential(normalization(ch), nn.SiLU(), zero_module(conv_nd(dims, model_channels, out_channels, 3, padding=1)))
-        self._packed, self._cs = None, None
-        _cache.watch(self)
-
-    # any parameter change invalidates the packed device copies
-    def load_state_dict(self, *a, **k):
-        _cache.bump()
-        return super().load_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        _cache.bump()
-        return super()._apply(fn, *a, **k)
+        self._cs = None
 
     # ------------------------------------------------------------------ packing
     def _pack_layer(self, m, dev):
@@ -264,10 +254,7 @@ class UNetModel(nn.Module):
             return ('attention', q)
         raise TypeError(type(m))
 
-    def _ensure_packed(self, dev):
-        if _cache.fresh(self._packed, dev):
-            return
-        P = {'device': dev}
+    def _pack(self, P, dev):
         P['t0'] = pack_lin(self.time_embed[0].weight, self.time_embed[0].bias, dev)
         P['t2'] = pack_lin(self.time_embed[2].weight, self.time_embed[2].bias, dev)
         P['inp'] = [[self._pack_layer(m, dev) for m in blk] for blk in self.input_blocks]
@@ -277,7 +264,6 @@ class UNetModel(nn.Module):
         P['conv_out'] = pack_conv3(self.out[2], dev)
         if self.mixed_prediction:
             P['mix'] = f32(self.mixing_logit.reshape(-1), dev)
-        self._packed = _cache.stamp(P, self)
         self._cs = ConvStack(dev, empty_alloc(dev), gn_any=True, who='UNetModel')
 
     # ------------------------------------------------------------------ pieces (h: f32 [N*H*W, C] channel-last)
@@ -348,8 +334,7 @@ class UNetModel(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("ln3diff_amd.UNetModel runs on the HIP device only (no CPU fallback)")
         dev = x.device
-        self._ensure_packed(dev)
-        P = self._packed
+        P = self._ensure_packed(dev)
         B = x.shape[0]
         if self.roll_out:                              # 'b (n c) h w -> b c h (n w)', n = 3
             _, C3, Hh, Ww = x.shape

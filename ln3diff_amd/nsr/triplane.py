@@ -54,7 +54,7 @@ OBJAVERSE_RENDERING_KWARGS = dict(
     return_sampling_details_flag=False, image_resolution=256, z_near=1.05, z_far=2.45, radius_range=[1.5, 2])
 
 
-class Triplane(nn.Module):
+class Triplane(_cache.PackedWeights, nn.Module):
     def __init__(self, c_dim=25, img_resolution=128, img_channels=3, out_chans=96, triplane_size=224,
                  rendering_kwargs=None, decoder_in_chans=32, decoder_output_dim=3, sr_kwargs=None, bcg_synthesis_kwargs=None,
                  lrm_decoder=False, create_triplane=False, **_):
@@ -76,22 +76,13 @@ class Triplane(nn.Module):
         self.neural_rendering_resolution = img_resolution
         self.decoder_in_chans = decoder_in_chans
         self.decoder = OSGDecoder(decoder_in_chans, {'decoder_lr_mul': 1, 'decoder_output_dim': decoder_output_dim})
-        self._dec = None
-        self._dec_epoch = -1
-        _cache.watch(self)
 
-    def _apply(self, fn, *a, **k):
-        _cache.bump()
-        return super()._apply(fn, *a, **k)
+    def _pack(self, P, dev):
+        n = self.decoder.net                            # output rows 0 - 3 = sigma, r, g, b (a wider decoder's other rows feed SR only)
+        P['dec'] = tuple(t.detach().to(dev, torch.float32).contiguous() for t in (n[0].weight, n[0].bias, n[2].weight[:4], n[2].bias[:4]))
 
     def _decoder_dev(self, dev):
-        if self._dec is None or self._dec[0].device != dev or self._dec_epoch != _cache.EPOCH[0]:
-            self._dec_epoch = _cache.EPOCH[0]
-            _cache.watch_tree(self)
-            n = self.decoder.net                        # output rows 0 - 3 = sigma, r, g, b (a wider decoder's other rows feed SR only)
-            self._dec = tuple(t.detach().to(dev, torch.float32).contiguous()
-                              for t in (n[0].weight, n[0].bias, n[2].weight[:4], n[2].bias[:4]))
-        return self._dec
+        return self._ensure_packed(dev)['dec']
 
     # ------------------------------------------------------------------ plane (texel) precision
     PLANE_PRECISIONS = ('fp32', 'fp16')

@@ -69,7 +69,7 @@ class CLIPTextModel(nn.Module):
         self.text_model = _TextModel(vocab_size, max_position_embeddings, hidden_size, intermediate_size, num_hidden_layers)
 
 
-class FrozenCLIPEmbedder(nn.Module):
+class FrozenCLIPEmbedder(_cache.PackedWeights, nn.Module):
     LAYERS = ["last", "pooled", "hidden"]
 
     def __init__(self, version="openai/clip-vit-large-patch14", device="cuda", max_length=77, freeze=True, layer="last",
@@ -83,14 +83,8 @@ class FrozenCLIPEmbedder(nn.Module):
         self.transformer = CLIPTextModel(**model_kwargs)
         self._tok = None
         self.tokenizer_dir = tokenizer_dir          # directory with vocab.json + merges.txt -> ln3diff_amd.sgm.tokenizer (no hub cache needed)
-        self._packed = None
-        _cache.watch(self)
         if freeze:
             self.freeze()
-
-    def _apply(self, fn, *a, **k):
-        _cache.bump()
-        return super()._apply(fn, *a, **k)
 
     def freeze(self):
         self.transformer = self.transformer.eval()
@@ -119,12 +113,10 @@ class FrozenCLIPEmbedder(nn.Module):
         return enc["input_ids"]
 
     # ------------------------------------------------------------------ packing
-    def _ensure_packed(self, dev):
-        if _cache.fresh(self._packed, dev, 'dev'):
-            return
+    def _pack(self, P, dev):
         tm = self.transformer.text_model
-        P = {'dev': dev, 'tok': f32(tm.embeddings.token_embedding.weight, dev), 'pos': f32(tm.embeddings.position_embedding.weight, dev),
-             'fw': f32(tm.final_layer_norm.weight, dev), 'fb': f32(tm.final_layer_norm.bias, dev), 'layers': []}
+        P.update({'tok': f32(tm.embeddings.token_embedding.weight, dev), 'pos': f32(tm.embeddings.position_embedding.weight, dev),
+                  'fw': f32(tm.final_layer_norm.weight, dev), 'fb': f32(tm.final_layer_norm.bias, dev), 'layers': []})
         for l in tm.encoder.layers:
             a = l.self_attn
             P['layers'].append({
@@ -137,7 +129,7 @@ class FrozenCLIPEmbedder(nn.Module):
                 'fc2_w': bf16(l.mlp.fc2.weight, dev), 'fc2_b': f32(l.mlp.fc2.bias, dev)})
         D = P['tok'].shape[1]
         P['zeros'] = torch.zeros(D, device=dev)
-        self._packed, self._ws = _cache.stamp(P, self), Workspace(dev)
+        self._ws = Workspace(dev)
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
@@ -146,8 +138,7 @@ class FrozenCLIPEmbedder(nn.Module):
         dev = text.device if (torch.is_tensor(text) and text.is_cuda) else torch.device(self.device)
         if dev.type != 'cuda':
             raise RuntimeError("ln3diff_amd.FrozenCLIPEmbedder runs on the HIP device only (no CPU fallback)")
-        self._ensure_packed(dev)
-        P, ws, tm = self._packed, self._ws, self.transformer
+        P, ws, tm = self._ensure_packed(dev), self._ws, self.transformer
         B, T = ids.shape
         D = P['tok'].shape[1]
         H = tm.heads

@@ -157,21 +157,14 @@ class _ViTRunner:
         return y, R
 
 
-class _ImageEmbedderBase(nn.Module):
+class _ImageEmbedderBase(_cache.PackedWeights, nn.Module):
     MEAN, STD = (0.0, 0.0, 0.0), (1.0, 1.0, 1.0)
 
     def __init__(self, device="cuda", freeze=True):
         super().__init__()
         self.device = device
-        self._runner = None
-        self._epoch = -1
-        _cache.watch(self)
         self.register_buffer("mean", torch.tensor(self.MEAN), persistent=False)
         self.register_buffer("std", torch.tensor(self.STD), persistent=False)
-
-    def _apply(self, fn, *a, **k):
-        _cache.bump()
-        return super()._apply(fn, *a, **k)
 
     def freeze(self):
         self.model = self.model.eval()
@@ -188,15 +181,12 @@ class _ImageEmbedderBase(nn.Module):
         # UNPINNED against kornia itself.
         return ops.image_preprocess(x, S, getattr(self, 'antialias', True), self.MEAN, self.STD)
 
-    def _ensure_packed(self, dev):
-        """the tower's packed copies (the runner) and whatever else a subclass keeps of its weights (`_pack_extra`), per weights epoch"""
-        if self._runner is None or self._runner.dev != dev or self._epoch != _cache.EPOCH[0]:
-            self._runner = _ViTRunner(self._spec(), dev)
-            self._epoch = _cache.EPOCH[0]
-            self._pack_extra(dev)
-            _cache.watch_tree(self)
+    def _pack(self, P, dev):
+        """the tower's packed copies (the runner) and whatever else a subclass keeps of its weights (`_pack_extra`)"""
+        P['runner'] = _ViTRunner(self._spec(), dev)
+        self._pack_extra(P, dev)
 
-    def _pack_extra(self, dev):
+    def _pack_extra(self, P, dev):
         pass
 
     def _run(self, image, extra=None):
@@ -204,11 +194,11 @@ class _ImageEmbedderBase(nn.Module):
             raise RuntimeError("ln3diff_amd image embedders run on the HIP device only (no CPU fallback)")
         if image.dim() == 5:
             image = image.reshape(-1, *image.shape[2:])
-        self._ensure_packed(image.device)
+        P = self._ensure_packed(image.device)
         x = self.preprocess(image.float())
         if extra is not None:                             # channels that bypass the image normalisation (Pluecker ray maps)
             x = torch.cat([x, extra.to(x.dtype)], 1)
-        return self._runner(x)
+        return P['runner'](x)
 
 
 class FrozenOpenCLIPImageEmbedder(_ImageEmbedderBase):
@@ -231,8 +221,8 @@ class FrozenOpenCLIPImageEmbedder(_ImageEmbedderBase):
     def _spec_model(self):
         return self.model.visual
 
-    def _pack_extra(self, dev):
-        self._proj_bf = bf16(self.model.visual.proj.t(), dev)
+    def _pack_extra(self, P, dev):
+        P['proj_bf'] = bf16(self.model.visual.proj.t(), dev)
 
     def _spec(self):
         v = self.model.visual
@@ -253,7 +243,7 @@ class FrozenOpenCLIPImageEmbedder(_ImageEmbedderBase):
         v = self.model.visual
         B, D = y.shape[0], y.shape[2]
         cls_bf = y[:, 0].to(torch.bfloat16).contiguous()
-        pw = self._proj_bf                                               # [embed_dim, width], packed with the tower
+        pw = self._packed['proj_bf']                                     # [embed_dim, width], packed with the tower
         z = torch.empty(B, pw.shape[0], device=y.device, dtype=torch.float32)
         ops.gemm(cls_bf, pw, None, ops.EPI_F32, z)
         z = z.to(image.dtype)

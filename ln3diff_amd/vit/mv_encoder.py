@@ -86,7 +86,7 @@ class SpatialTransformer3D(nn.Module):          # attention.py:405-463 (use_line
         self.use_linear = False
 
 
-class Encoder(nn.Module):
+class Encoder(_cache.PackedWeights, nn.Module):
     """ldm Encoder (model.py:459-561) with the multi-view middle attention: forward(x) -> conv_out output [N, 2*z_channels, H/8, W/8]
     (per frame, not pooled).  `forward_frames` returns the same values as a channel-last tensor seen through an NCHW view."""
 
@@ -138,19 +138,11 @@ class Encoder(nn.Module):
         self.mid.block_2 = ResnetBlock(in_channels=block_in, out_channels=block_in, dropout=dropout)
         self.norm_out = Normalize(block_in)
         self.conv_out = nn.Conv2d(block_in, 2 * z_channels if double_z else z_channels, 3, 1, 1)
-        self._packed, self._cs = None, None
-        _cache.watch(self)
-
-    def _apply(self, fn, *a, **k):
-        _cache.bump()
-        return super()._apply(fn, *a, **k)
+        self._cs = None
 
     # ------------------------------------------------------------------ packing
-    def _ensure_packed(self, dev):
-        if _cache.fresh(self._packed, dev):
-            return
+    def _pack(self, P, dev):
         res = lambda b: pack_resblock(b.norm1, b.conv1, b.norm2, b.conv2, dev, shortcut=getattr(b, 'nin_shortcut', None))
-        P = {'device': dev}
         P['conv_in'] = pack_conv3(self.conv_in, dev, cin_pad=(self.in_channels + 7) // 8 * 8)
         P['down'] = [{'blocks': [res(b) for b in d.block], 'down': pack_conv3(d.downsample.conv, dev) if hasattr(d, 'downsample') else None}
                      for d in self.down]
@@ -158,7 +150,6 @@ class Encoder(nn.Module):
         P['attn'] = pack_transformer(self.mid.attn_1, False, dev)
         P['norm_out'] = pack_gn(self.norm_out, dev)
         P['conv_out'] = pack_conv3(self.conv_out, dev)
-        self._packed = _cache.stamp(P, self)
         self._cs = ConvStack(dev, empty_alloc(dev), who='SpatialTransformer3D')
 
     # ------------------------------------------------------------------ forward
@@ -179,8 +170,7 @@ class Encoder(nn.Module):
         F = self.num_frames
         self._check_input(x, F)
         dev = x.device
-        self._ensure_packed(dev)
-        P = self._packed
+        P = self._ensure_packed(dev)
         N, Cin, H, W = x.shape
         cs, pc = self._cs, P['conv_in']
         new = lambda rows, cols, dtype=torch.float32: torch.empty(rows, cols, device=dev, dtype=dtype)

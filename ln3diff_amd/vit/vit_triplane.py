@@ -163,15 +163,11 @@ class _RendererSeams:
 
 class _PosteriorSeams:
     """The quant_conv posterior of the encoder side (vit_triplane.py:912-933, :1152-1199).  The class that inherits it provides
-    `superresolution['quant_conv']` (grouped 1 x 1 conv) and `ldm_embed_dim`."""
+    `superresolution['quant_conv']` (grouped 1 x 1 conv), `ldm_embed_dim` and, as a _cache.PackedWeights, `_side_pack`."""
 
     def _quant_packed(self, dev):
-        q = self.__dict__.get('_quant')
-        if not _cache.fresh(q, dev):
-            qc = self.superresolution['quant_conv']
-            q = _cache.stamp({'device': dev, 'w': f32(qc.weight.reshape(qc.weight.shape[0], -1), dev), 'b': f32(qc.bias, dev)}, self)
-            self.__dict__['_quant'] = q
-        return q
+        qc = self.superresolution['quant_conv']
+        return self._side_pack('quant', dev, lambda dev: {'w': f32(qc.weight.reshape(qc.weight.shape[0], -1), dev), 'b': f32(qc.bias, dev)})
 
     def _posterior(self, h, eps, num_frames):
         if not h.is_cuda:
@@ -192,7 +188,7 @@ class _PosteriorSeams:
         return DiagonalGaussianDistribution(r['mean'], r['logvar'])
 
 
-class RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout_withSD_D_ditDecoder(_RendererSeams, _PosteriorSeams, nn.Module):
+class RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout_withSD_D_ditDecoder(_RendererSeams, _PosteriorSeams, _cache.PackedWeights, nn.Module):
     grid_ignores_aabb = True
 
     def __init__(self, vit_decoder: DiT2, triplane_decoder: Triplane, cls_token=False, normalize_feat=True,
@@ -208,20 +204,11 @@ class RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout
             quant_conv=nn.Conv2d(2 * 3 * ldm_z_channels, 2 * ldm_embed_dim * 3, kernel_size=1, groups=3),  # encoder side
             conv_sr=Decoder(ch=32, out_ch=32, ch_mult=[1, 2, 2, 4], num_res_blocks=1, z_channels=D)))
         self.rendering_kwargs = triplane_decoder.rendering_kwargs
-        self._packed = None
         self._ws = self._cs = None
-        _cache.watch(self)
-
-    def _apply(self, fn, *a, **k):
-        _cache.bump()
-        return super()._apply(fn, *a, **k)
 
     # ------------------------------------------------------------------ packing
-    def _ensure_packed(self, dev):
-        if _cache.fresh(self._packed, dev):
-            return
+    def _pack(self, P, dev):
         sr = self.superresolution
-        P = {'device': dev}
         P['pe_w'], P['pe_b'] = f32(sr['ldm_upsample'].proj.weight, dev), f32(sr['ldm_upsample'].proj.bias, dev)
         d = sr['conv_sr']
         gn = lambda g: pack_gn(g, dev, eps=1e-6)            # the _GN containers carry no eps
@@ -241,7 +228,6 @@ class RodinSR_256_fusionv6_ConvQuant_liteSR_dinoInit3DAttn_SD_B_3L_C_withrollout
             P['up'].append(q)
         P['norm_out'] = gn(d.norm_out)
         P['conv_out'] = pack_conv3(d.conv_out, dev)
-        self._packed = _cache.stamp(P, self)
         self._ws = Workspace(dev)
         self._cs = ConvStack(dev, self._ws.get, ws=self._ws)             # scratch by name from the workspace: nothing is allocated after the first decode
 

@@ -130,7 +130,7 @@ class VAE_LDM_V4_vit3D_v3_conv3D_depth2_xformer_mha_PEinit_2d_sincos_uvit_RodinR
                 'ca_qkv_b': f32(torch.cat([ca.attn.wq.bias, ca.attn.w_kv.bias], 0), dev),
                 'ca_o_w': self._res_w(ca.attn.proj.weight, dev), 'ca_o_b': f32(ca.attn.proj.bias, dev)}
 
-    def _pack(self, P, dev):
+    def _pack_sr(self, P, dev):
         sr = self.superresolution
         P['up_w32'], P['up_b'] = f32(sr['ldm_upsample'].weight, dev), f32(sr['ldm_upsample'].bias, dev)
         cs = sr['conv_sr']

@@ -186,10 +186,10 @@ def _pack_dino(b, dev, res_w=bf16):
             'o_w': res_w(b.attn.proj.weight, dev), 'o_b': f32(b.attn.proj.bias, dev), 'ls1': f32(b.ls1.gamma, dev), **_pack_mlp(b, dev, res_w)}
 
 
-class _DinoTriplaneDecoderBase(_RendererSeams, nn.Module):
+class _DinoTriplaneDecoderBase(_RendererSeams, _cache.PackedWeights, nn.Module):
     """Latent tokens -> DINOv2 blocks in fusion groups with UViT long skips -> decoder_pred -> unpatchify -> conv_sr -> tri-planes.
     A subclass gives its `superresolution` entries (_sr_modules), packs its token embedding, fusion groups and conv_sr convolutions
-    (_pack, _pack_group), runs one fusion group (_group) and the two convolutions of conv_sr (_conv_sr); `_res_w` / `_res_gemm` are how
+    (_pack_sr, _pack_group), runs one fusion group (_group) and the two convolutions of conv_sr (_conv_sr); `_res_w` / `_res_gemm` are how
     it carries and applies the weights of the projections that write the residual stream."""
     _res_w = staticmethod(bf16)
     _res_gemm = staticmethod(gate_res_gemm)
@@ -221,21 +221,13 @@ class _DinoTriplaneDecoderBase(_RendererSeams, nn.Module):
             blk.skip_linear = nn.Linear(2 * D, D)
             nn.init.constant_(blk.skip_linear.weight, 0)
             nn.init.constant_(blk.skip_linear.bias, 0)
-        self._packed = None
         self._ws = None
-        _cache.watch(self)
-
-    def _apply(self, fn, *a, **k):
-        _cache.bump()
-        return super()._apply(fn, *a, **k)
 
     # ------------------------------------------------------------------ packing
-    def _ensure_packed(self, dev):
-        if _cache.fresh(self._packed, dev):
-            return
+    def _pack(self, P, dev):
         vd, cs = self.vit_decoder, self.superresolution['conv_sr']
         D = vd.embed_dim
-        P = {'device': dev, 'D': D, 'H': vd.blocks[0].vit_blks[0].attn.num_heads, 'pos': f32(vd.pos_embed.reshape(-1), dev), 'groups': []}
+        P.update({'D': D, 'H': vd.blocks[0].vit_blks[0].attn.num_heads, 'pos': f32(vd.pos_embed.reshape(-1), dev), 'groups': []})
         for fb in vd.blocks:
             q = self._pack_group(fb, dev)
             if hasattr(fb, 'skip_linear'):
@@ -247,8 +239,7 @@ class _DinoTriplaneDecoderBase(_RendererSeams, nn.Module):
         P['dp_w'], P['dp_b'] = bf16(self.decoder_pred.weight, dev), f32(self.decoder_pred.bias, dev)
         P['sc_w'], P['sc_b'] = bf16(cs.short_cut.weight, dev), f32(cs.short_cut.bias, dev)
         P['zeros'] = torch.zeros(D, device=dev)
-        self._pack(P, dev)
-        self._packed = _cache.stamp(P, self)
+        self._pack_sr(P, dev)
         self._ws = Workspace(dev)
 
     # ------------------------------------------------------------------ ViT pieces
@@ -359,7 +350,7 @@ class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(_PosteriorSeams, _Din
               'o_w': bf16(ca.attn.proj.weight, dev), 'o_b': f32(ca.attn.proj.bias, dev), 'ls1': f32(g1, dev), **_pack_mlp(b1, dev)}
         return {'b0': _pack_dino(b0, dev), 'b1': q1}
 
-    def _pack(self, P, dev):
+    def _pack_sr(self, P, dev):
         sr = self.superresolution
         P['pe_w'], P['pe_b'] = f32(sr['ldm_upsample'].proj.weight, dev), f32(sr['ldm_upsample'].proj.bias, dev)
         cs = sr['conv_sr']
@@ -442,13 +433,9 @@ class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(_PosteriorSeams, _Din
         return self.forward_vit_decoder(raw.view(B, L, D), img_size)
 
     def _down_packed(self, dev):
-        """ldm_downsample's GEMM operands, per weights epoch (as _quant_packed)"""
-        q = self.__dict__.get('_down')
-        if not _cache.fresh(q, dev):
-            ld = self.superresolution['ldm_downsample']
-            q = _cache.stamp({'device': dev, 'w': bf16(ld.weight, dev), 'b': f32(ld.bias, dev)}, self)
-            self.__dict__['_down'] = q
-        return q
+        """ldm_downsample's GEMM operands (a side pack, as _quant_packed)"""
+        ld = self.superresolution['ldm_downsample']
+        return self._side_pack('down', dev, lambda dev: {'w': bf16(ld.weight, dev), 'b': f32(ld.bias, dev)})
 
     @torch.no_grad()
     def vae_reparameterization(self, latent, sample_posterior, eps=None):

@@ -4,7 +4,8 @@
 A holder is described by
   root()        the module that is built (on the CPU, weights seeded by `reseed(root, 0)`),
   pick(root)    the cache holder inside it (the root itself unless the holder only exists inside a parent: DiT2, Triplane),
-  pack(h, dev)  builds every cache the holder keeps for `dev` and returns them as one tree (dicts / lists / tuples / runner objects),
+  pack(h, dev)  builds every pack the holder keeps for `dev` (_cache.PackedWeights: `_ensure_packed`, plus the side packs chosen per
+                holder) and returns them as one tree (dicts / lists / tuples / runner objects),
   child         dotted path, below the holder, of a submodule with parameters (a block, a res-block),
   ckpt          the keyword of checkpoint.load_checkpoint that takes the ROOT.
 """
@@ -12,6 +13,7 @@ import copy
 import os
 import sys
 
+import pytest
 import torch
 import torch.nn as nn
 
@@ -86,15 +88,13 @@ def _dino():
 
 # ----------------------------------------------------------------------------- packing
 def _pack_ensure(h, dev):
-    h._ensure_packed(dev)
-    return {'packed': h._packed}
+    return {'packed': h._ensure_packed(dev)}
 
 
 def _pack_ae(h, dev, quant, down):
     """quant / down: whether this class keeps the posterior's quant_conv operands / the ldm_downsample operands (chosen per holder in
     HOLDERS, not probed: a renamed method must fail here, not drop out of the comparison)"""
-    h._ensure_packed(dev)
-    out = {'packed': h._packed, 'dec': h.triplane_decoder._decoder_dev(dev)}
+    out = {'packed': h._ensure_packed(dev), 'dec': h.triplane_decoder._ensure_packed(dev)}
     if quant:
         out['quant'] = h._quant_packed(dev)
     if down:
@@ -103,12 +103,7 @@ def _pack_ae(h, dev, quant, down):
 
 
 def _pack_ae_dit2(h, dev):
-    return dict(_pack_ae(h, dev, True, False), vit=h.vit_decoder.pack(dev))
-
-
-def _pack_embedder(h, dev):
-    h._ensure_packed(dev)
-    return {'runner': h._runner, 'proj_bf': getattr(h, '_proj_bf', None)}
+    return dict(_pack_ae(h, dev, True, False), vit=h.vit_decoder._ensure_packed(dev))
 
 
 class Holder:
@@ -125,17 +120,17 @@ HOLDERS = [
     Holder('DiT_TriLatent', _t23d, _pack_ensure, 'blocks.1', 'dit'),
     Holder('DiT_I23D_PixelArt', _i23d, _pack_ensure, 'blocks.1', 'dit'),
     Holder('DiT_pcd_I23D_PixelArt_MVCond', _pcd, _pack_ensure, 'blocks.0', 'dit'),
-    Holder('DiT2', _ae, lambda h, dev: {'packed': h.pack(dev)}, 'blocks.1', 'decoder', pick=lambda r: r.vit_decoder),
+    Holder('DiT2', _ae, _pack_ensure, 'blocks.1', 'decoder', pick=lambda r: r.vit_decoder),
     Holder('AE_decoder', _ae, _pack_ae_dit2, 'superresolution.conv_sr.mid.block_1', 'decoder'),
     Holder('ShapeNet_decoder', _shapenet, lambda h, dev: _pack_ae(h, dev, True, True), 'vit_decoder.blocks.0', 'decoder'),
     Holder('FFHQ_decoder', _ffhq, lambda h, dev: _pack_ae(h, dev, False, False),      # its encoder side is not built
             'vit_decoder.blocks.0', 'decoder'),
     Holder('mv_Encoder', _encoder, _pack_ensure, 'mid.block_1', 'encoder'),
     Holder('UNetModel', _unet, _pack_ensure, 'input_blocks.1', 'dit'),
-    Holder('Triplane', _ae, lambda h, dev: {'dec': h._decoder_dev(dev)}, 'decoder.net', 'decoder', pick=lambda r: r.triplane_decoder),
+    Holder('Triplane', _ae, _pack_ensure, 'decoder.net', 'decoder', pick=lambda r: r.triplane_decoder),
     Holder('FrozenCLIPEmbedder', _clip_text, _pack_ensure, 'transformer.text_model.encoder.layers.0', 'conditioner'),
-    Holder('FrozenOpenCLIPImageEmbedder', _openclip, _pack_embedder, 'model.visual.transformer.resblocks.0', 'conditioner'),
-    Holder('FrozenDinov2ImageEmbedder', _dino, _pack_embedder, 'model.blocks.0', 'conditioner'),
+    Holder('FrozenOpenCLIPImageEmbedder', _openclip, _pack_ensure, 'model.visual.transformer.resblocks.0', 'conditioner'),
+    Holder('FrozenDinov2ImageEmbedder', _dino, _pack_ensure, 'model.blocks.0', 'conditioner'),
 ]
 BY_NAME = {h.name: h for h in HOLDERS}
 
@@ -232,6 +227,14 @@ def ch_load_holder(root, h, spec, tmp):
     h.load_state_dict(new_values(h.state_dict(), 11), strict=True)
 
 
+def ch_load_strict_error(root, h, spec, tmp):
+    """a strict load that ends in RuntimeError (one key missing): the tensors that matched were copied before it raised"""
+    sd = new_values(h.state_dict(), 17)
+    sd.popitem()
+    with pytest.raises(RuntimeError, match='Missing key'):
+        h.load_state_dict(sd, strict=True)
+
+
 def ch_load_parent(root, h, spec, tmp):
     parent = nn.ModuleDict({'inner': root})
     parent.load_state_dict({'inner.' + k: v for k, v in new_values(root.state_dict(), 12).items()}, strict=True)
@@ -292,9 +295,9 @@ def ch_replace_child(root, h, spec, tmp):
     ln3diff_amd.invalidate_weight_caches()
 
 
-CHANNELS = {'load_state_dict': ch_load_holder, 'load_parent': ch_load_parent, 'load_child': ch_load_child, 'apply': ch_apply,
-            'fill_module_random_': ch_fill_random, 'load_checkpoint': ch_checkpoint, 'broadcast_flat': ch_broadcast,
-            'invalidate_weight_caches': ch_invalidate, 'replace_submodule': ch_replace_child}
+CHANNELS = {'load_state_dict': ch_load_holder, 'load_strict_error': ch_load_strict_error, 'load_parent': ch_load_parent,
+            'load_child': ch_load_child, 'apply': ch_apply, 'fill_module_random_': ch_fill_random, 'load_checkpoint': ch_checkpoint,
+            'broadcast_flat': ch_broadcast, 'invalidate_weight_caches': ch_invalidate, 'replace_submodule': ch_replace_child}
 
 
 def fresh_like(spec, root, dev=None):

@@ -63,3 +63,61 @@ def test_walker_sees_a_difference():
     b['n'] = 5
     del b['w']
     assert same(snapshot(a), snapshot(b)) == ['/l/0/b', '/n', '/w']
+
+
+# ----------------------------------------------------------------------------- the protocol has one owner: _cache.PackedWeights
+def _package_files():
+    import os
+    import ln3diff_amd
+    root = os.path.dirname(ln3diff_amd.__file__)
+    return root, sorted(os.path.join(d, f) for d, _, fs in os.walk(root) for f in fs if f.endswith('.py'))
+
+
+def _package_modules():
+    import importlib
+    import os
+    root, files = _package_files()
+    names = [os.path.relpath(f, os.path.dirname(root))[:-3].replace(os.sep, '.') for f in files]
+    return [importlib.import_module(n[:-9] if n.endswith('.__init__') else n) for n in names]
+
+
+def test_every_direct_holder_is_in_the_table():
+    """every class of the package that lists PackedWeights in its bases is state-tested: it is in the MRO of some HOLDERS entry"""
+    from ln3diff_amd._cache import PackedWeights
+    _package_modules()
+    direct = {c for c in PackedWeights.__subclasses__() if c.__module__.startswith('ln3diff_amd.')}
+    assert len(direct) >= 9, sorted(c.__name__ for c in direct)
+    tested = set()
+    for spec in HOLDERS:
+        tested.update(type(spec.pick(spec.root())).__mro__)
+    assert direct - tested == set(), sorted(c.__name__ for c in direct - tested)
+    from ln3diff_amd.vit.vit_triplane import _PosteriorSeams          # the seam calls _side_pack: its concrete classes must be holders
+    users = _PosteriorSeams.__subclasses__()
+    assert len(users) >= 2 and all(issubclass(c, PackedWeights) for c in users), users
+
+
+def test_cache_protocol_is_spelled_in_one_place():
+    """no file of the package but _cache.py uses the primitives of the protocol, and no class but PackedWeights overrides _apply"""
+    import ast
+    import os
+    from ln3diff_amd._cache import PackedWeights
+    _, files = _package_files()
+    assert len(files) > 20
+    bad, private = [], {'stamp', 'fresh', 'watch', 'watch_tree', 'EPOCH'}
+    for path in files:
+        src = open(path).read()
+        outside = os.path.basename(path) != '_cache.py'
+        if outside:
+            bad += [(path, w) for w in ('_cache.stamp', '_cache.fresh', '_cache.watch', '_cache.EPOCH') if w in src]
+        for node in ast.walk(ast.parse(src)):
+            if outside and isinstance(node, ast.Attribute) and node.attr in private:         # under any name of the module
+                bad.append((path, node.lineno, '.' + node.attr))
+            if outside and isinstance(node, ast.ImportFrom) and (node.module or '').split('.')[-1] == '_cache':
+                bad += [(path, node.lineno, 'import ' + n.name) for n in node.names if n.name in private or n.name == '*']
+            if isinstance(node, ast.ClassDef) and node.name != 'PackedWeights':
+                bad += [(path, node.name + '._apply') for f in node.body if isinstance(f, ast.FunctionDef) and f.name == '_apply']
+    assert bad == []
+    for mod in _package_modules():                 # and at run time: every _apply in the package is PackedWeights' or torch's
+        for c in vars(mod).values():
+            if isinstance(c, type) and c.__module__ == mod.__name__ and c is not PackedWeights:
+                assert '_apply' not in vars(c), c

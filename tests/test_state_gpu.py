@@ -16,6 +16,7 @@ this file).  Every test also asserts that what it changes does change the output
     a pair of extents that share one padded scratch shape (100 / 121 point tokens + 256 appended: both pad to 384 keys; 736 / 768 with the append cache: 1024).
     The text tower takes integer ids: it has no input that can hold a non-finite value.  One case per DiT family runs the poisoned and
     the finite call through ONE prepared context (the server loop after a diverged sample).
+(e) one pack per device: 'cuda' and 'cuda:<current>' get the same pack object and the same scratch.
 """
 import pytest
 import torch
@@ -456,3 +457,23 @@ def test_prepared_context_survives_a_diverged_latent(hip_lib, name, fin, bad):
         assert same(m(i_bad['x'], i_bad['t'], context_cache=cc).clone(), want_bad, f'{name} after {value}, the poisoned shape'), value
     if name != 'DiT_TriLatent':
         assert cc.get('akv') is not None                                 # the appended-token cache was engaged throughout
+
+
+# ----------------------------------------------------------------------------- (e) one pack per device, however the device is spelled
+@pytest.mark.parametrize('name', ['Triplane', 'AE_decoder'])
+def test_bare_cuda_and_indexed_cuda_name_one_pack(hip_lib, name):
+    """torch.device('cuda') and torch.device('cuda', current_device) compare unequal; _ensure_packed normalises, so the second spelling
+    gets the first one's pack (and the decoder keeps its Workspace and ConvStack) instead of a rebuild.  Packing only, no kernel."""
+    if name == 'Triplane':
+        from ln3diff_amd.nsr.triplane import Triplane
+        h = Triplane(img_resolution=16).to(DEV)
+    else:
+        h = built(name)[1]
+    bare, indexed = torch.device('cuda'), torch.device('cuda', torch.cuda.current_device())
+    assert bare != indexed
+    P = h._ensure_packed(bare)
+    scratch = (h._ws, h._cs) if name == 'AE_decoder' else ()
+    assert None not in scratch
+    assert h._ensure_packed(indexed) is P and h._ensure_packed(bare) is P and P['device'] == indexed
+    if name == 'AE_decoder':
+        assert h._ws is scratch[0] and h._cs is scratch[1]
