@@ -14,6 +14,7 @@
 #include <type_traits>
 #include "common.h"
 #include "../../include/ln3d.h"
+#include "kernel_plan.h"
 
 struct AttnP {
   const bf16_t* Q; const bf16_t* K; const bf16_t* Vt; bf16_t* O;
@@ -1161,8 +1162,9 @@ __global__ __launch_bounds__(256, 3) void attn_short_kernel(AttnP p) {
   }
 }
 
-// The attention kernels have no switches - one kernel per shape class (the r1 - r4 A/B switches LN3D_ATTN_V / _KRES / _SHORT /
-// _QT / _SPLIT and the instantiations they selected are gone; their measurements are in profiles/r2 - r4_attn*.md).
+// The attention kernels have no switches - one kernel per shape class, chosen by ln3d_plan_attention (csrc/kernel_plan.h).  The r1 - r4
+// A/B switches LN3D_ATTN_V / _KRES / _SHORT / _QT / _SPLIT and the instantiations they selected are gone; their measurements are in
+// profiles/r2 - r4_attn*.md.
 static int launch_attn_short(const AttnP& p, hipStream_t s) {
   // one query tile per wave (128 queries per workgroup): twice the workgroups, so load, compute and store phases of
   // different workgroups overlap on a CU (the kernel is a latency-bound stream of Q in / O out)
@@ -1192,7 +1194,7 @@ static int launch_attn_stream(AttnP p, hipStream_t s) {
   }
   // one workgroup per (batch, head) walks all its query blocks; with fewer heads than CUs the query blocks of a head are
   // shared out so that every CU has work
-  const int nqb = (p.Nq + 255) / 256, BH = p.B * p.H, cus = ln3d_stream_cus(s);
+  const int nqb = (p.Nq + 255) / 256, BH = p.B * p.H, cus = ln3d_device_cus();
   int nsplit = 1;
   if (BH < cus) { nsplit = (cus + BH - 1) / BH; if (nsplit > nqb) nsplit = nqb; }
   p.nsplit = nsplit;
@@ -1213,7 +1215,8 @@ static int launch_attn_kres(AttnP p, hipStream_t s) {
 
 extern "C" int ln3d_attention_bf16(const ln3d_attn_args* a, void* stream) {
   if (!a || !a->Q || !a->K || !a->Vt || !a->O) return LN3D_ERR_BAD_ARG;
-  if (a->Nk <= 0 || a->Nq <= 0 || a->Nk_pad % 64 != 0 || a->Nk_pad < a->Nk || a->Nq_pad < a->Nq) return LN3D_ERR_BAD_ARG;
+  const int plan = ln3d_plan_attention(a->Dh, a->Dh_true, a->Nq, a->Nq_pad, a->Nk, a->Nk_pad, a->B * a->H, a->causal != 0, ln3d_device_cus());
+  if (plan < 0) return plan;
   AttnP p;
   p.Q = (const bf16_t*)a->Q; p.K = (const bf16_t*)a->K; p.Vt = (const bf16_t*)a->Vt; p.O = (bf16_t*)a->O;
   p.B = a->B; p.H = a->H; p.Nq = a->Nq; p.Nq_pad = a->Nq_pad; p.Nk = a->Nk; p.Nk_pad = a->Nk_pad;
@@ -1222,34 +1225,18 @@ extern "C" int ln3d_attention_bf16(const ln3d_attn_args* a, void* stream) {
   p.causal = a->causal ? 1 : 0;
   p.nsplit = 1;
   hipStream_t s = (hipStream_t)stream;
-  // causal masking exists in the short-sequence kernel only (its one user is the 77-token CLIP text tower)
-  if (a->causal && !(a->Dh == 64 && a->Nk <= 128)) return LN3D_ERR_UNSUPPORTED;
-  if (a->Dh_true != 0 && a->Dh_true != a->Dh && a->Dh != 128 && a->Dh != 80) return LN3D_ERR_UNSUPPORTED;   // compact heads: the padded kernels only
-  if (a->Dh == 64) {
-    // The short-sequence kernel serves the causal text tower; for the non-causal 77-key cross-attention it measures 2 us
-    // faster in isolation but slower inside the sampling loop than the ring kernel (and the DiT runs that attention inside
-    // the query-projection GEMM anyway, LN3D_EPI_CROSS_ATTN), so the ring kernel serves it.
-    if (a->Nk <= 128 && a->causal) return launch_attn_short(p, s);
-    if ((a->Nk & 255) == 0 && a->Nk_pad == a->Nk) {
-      // K-resident kernel: K of a head fits beside the V^T ring (Nk <= 768) and there is a head for every CU, so that one
-      // workgroup per head walks all its query blocks (fewer heads: the query blocks of a head are shared out - attn_stream)
-      if (a->Nk >= 512 && a->Nk <= 768 && (a->Nq & 255) == 0 && a->Nq_pad == a->Nq && p.B * p.H >= ln3d_stream_cus(s))
-        return launch_attn_kres(p, s);
-      return launch_attn_stream(p, s);
-    }
-    return a->Nk > 128 ? launch_attn<64, 4>(p, s) : launch_attn<64, 2>(p, s);
+  switch (plan) {                                     // csrc/kernel_plan.h
+    case LN3D_ATTN_SHORT: return launch_attn_short(p, s);
+    case LN3D_ATTN_KRES: return launch_attn_kres(p, s);
+    case LN3D_ATTN_STREAM: return launch_attn_stream(p, s);
+    case LN3D_ATTN_RING64_OCC4: return launch_attn<64, 4>(p, s);
+    case LN3D_ATTN_RING64_OCC2: return launch_attn<64, 2>(p, s);
+    case LN3D_ATTN_RING80: return launch_attn<80, 2>(p, s);
+    case LN3D_ATTN_RING80_T72: return launch_attn<80, 2, 72>(p, s);
+    case LN3D_ATTN_RING128: return launch_attn<128, 2>(p, s);
+    case LN3D_ATTN_RING128_T72: return launch_attn<128, 2, 72>(p, s);
+    default: return LN3D_ERR_UNSUPPORTED;
   }
-  if (a->Dh == 80) {                                                        // r6: 65 - 80 wide heads stored 80 wide
-    if (a->Dh_true == 0 || a->Dh_true == 80) return launch_attn<80, 2>(p, s);   // the U-Net's 80-wide heads
-    if (a->Dh_true == 72) return launch_attn<80, 2, 72>(p, s);                // DiT-XL/2
-    return LN3D_ERR_UNSUPPORTED;
-  }
-  if (a->Dh == 128) {
-    if (a->Dh_true == 0 || a->Dh_true == 128) return launch_attn<128, 2>(p, s);
-    if (a->Dh_true == 72) return launch_attn<128, 2, 72>(p, s);           // DiT-XL/2
-    return LN3D_ERR_UNSUPPORTED;
-  }
-  return LN3D_ERR_UNSUPPORTED;
 }
 
 // ---------------------------------------------------------------------------------------------

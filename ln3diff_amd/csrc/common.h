@@ -132,9 +132,6 @@ struct AttrOnce {
   }
 };
 
-// compute units a launch on this stream can occupy (csrc/runtime.hip): the device's, or the CU mask's of a lane stream
-int ln3d_stream_cus(hipStream_t s);
-
 static inline int ln3d_check_launch() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? LN3D_OK : LN3D_ERR_LAUNCH;

@@ -21,6 +21,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "../../include/ln3d.h"
+#include "kernel_plan.h"
 
 #define BMF 128  // features per block
 #define BTK 128  // tokens per block
@@ -799,13 +800,9 @@ static int launch_p4(const GemmP& p, hipStream_t s) {
   static AttrOnce attr_once;
   if (attr_once.need())
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_p4_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSB);
-  const int ntiles = (p.N / 256) * (p.M / 256), cus = ln3d_stream_cus(s);
+  const int ntiles = (p.N / 256) * (p.M / 256), cus = ln3d_device_cus();
   hipLaunchKernelGGL((gemm_bf16_p4_kernel<EPI>), dim3(ntiles < cus ? ntiles : cus), dim3(256), LDSB, s, p);
   return ln3d_check_launch();
-}
-static bool p4_ok(const GemmP& p) {
-  return (p.M % 256) == 0 && (p.N % 256) == 0 && (p.K % 128) == 0 && p.K >= 512 && (p.ldo % 8) == 0 &&
-         ((uintptr_t)p.out0 & 15) == 0 && (!p.bias || ((uintptr_t)p.bias & 15) == 0);
 }
 
 template <int EPI, int NW, int WGT, int NI, int NJ>
@@ -835,39 +832,36 @@ static int launch(const GemmP& p, hipStream_t s) {
   return ln3d_check_launch();
 }
 
-// cfg 0 = 128x128 register-staged kernel; 16 = persistent 256f x 256t with 4 waves (r6); 7 = 256f x 256t, 8 = 128f x 384t, 9 = 256f x 192t (8 waves), 12 = 384f x 192t (12 waves,
-// 3 per SIMD), 14 = 128f x 192t (4 waves), 13 = 256f x 256t with 4 waves (r5: long-K GEMMs only, see pick_cfg).  r2's 384x192 / 8-wave variant (11) was
-// measured slower and is gone.
+// The launch of one row of ln3d_gemm_tiles (csrc/kernel_plan.h): kernel and template parameters come from the row.  ln3d_plan_gemm only
+// returns rows that are instantiated for the epilogue, so the refusal below is never reached; it keeps the other epilogues' kernels
+// from being instantiated.
+template <int EPI, int ROW>
+static int launch_tile(const GemmP& p, hipStream_t s) {
+  constexpr Ln3dGemmTile t = ln3d_gemm_tiles[ROW];
+  if constexpr (!(t.epis & ln3d_epi_bit(EPI))) return LN3D_ERR_UNSUPPORTED;
+  else if constexpr (t.kind == LN3D_TILE_STAGED) return launch<EPI>(p, s);
+  else if constexpr (t.kind == LN3D_TILE_PERSISTENT) return launch_p4<EPI>(p, s);
+  else return launch_ring64<EPI, t.nw, t.wgt, t.ni, t.nj>(p, s);
+}
 template <int EPI>
-static int run_cfg(const GemmP& p, hipStream_t s, int cfg) {
-  if constexpr (EPI == LN3D_EPI_CROSS_ATTN) return cfg == 14 ? launch_ring64<EPI, 4, 2, 2, 3>(p, s) : launch_ring64<EPI, 8, 2, 2, 3>(p, s);
-  else
-  switch (cfg) {
-    case 7: return launch_ring64<EPI, 8, 4, 4, 2>(p, s);
-    case 8: return launch_ring64<EPI, 8, 4, 2, 3>(p, s);
-    case 9: return launch_ring64<EPI, 8, 2, 2, 3>(p, s);
-    case 12: return launch_ring64<EPI, 12, 2, 2, 3>(p, s);
-    case 14: return launch_ring64<EPI, 4, 2, 2, 3>(p, s);      // 128f x 192t, 4 waves, 80 KB: two workgroups per CU (the half-batch GEMMs)
-    case 16:   // r6: the persistent form of 13 (plain bf16 / erf-GELU epilogues, interior tiles only)
-      if constexpr (EPI == LN3D_EPI_BF16 || EPI == LN3D_EPI_GELU_ERF) { if (p4_ok(p)) return launch_p4<EPI>(p, s); }
-      return launch_ring64<EPI, 8, 4, 4, 2>(p, s);
-    case 13:   // 256f x 256t with 4 waves: ONE wave per SIMD, 128 x 128 per wave, the 16 accumulator tiles in AGPRs (hipcc allocates them
-               // there by itself: only MFMAs touch them inside the K loop).  Instantiated for the epilogues that have long-K users.
-      if constexpr (EPI == LN3D_EPI_GATE_RES || EPI == LN3D_EPI_BF16 || EPI == LN3D_EPI_F32) return launch_ring64<EPI, 4, 2, 4, 4>(p, s);
-      else return launch_ring64<EPI, 8, 4, 4, 2>(p, s);
-    default: return launch<EPI>(p, s);
+static int run_tile(const GemmP& p, hipStream_t s, int row) {
+  static_assert(LN3D_GEMM_TILE_ROWS == 8, "one case per row");
+  switch (row) {
+    case LN3D_TILE_256x256: return launch_tile<EPI, LN3D_TILE_256x256>(p, s);
+    case LN3D_TILE_128x384: return launch_tile<EPI, LN3D_TILE_128x384>(p, s);
+    case LN3D_TILE_256x192: return launch_tile<EPI, LN3D_TILE_256x192>(p, s);
+    case LN3D_TILE_384x192: return launch_tile<EPI, LN3D_TILE_384x192>(p, s);
+    case LN3D_TILE_128x192: return launch_tile<EPI, LN3D_TILE_128x192>(p, s);
+    case LN3D_TILE_256x256_P4: return launch_tile<EPI, LN3D_TILE_256x256_P4>(p, s);
+    case LN3D_TILE_256x256_W4: return launch_tile<EPI, LN3D_TILE_256x256_W4>(p, s);
+    default: return launch_tile<EPI, LN3D_TILE_S128>(p, s);
   }
 }
 
-
-// Tile selection.  Small problems (per-sample adaLN / timestep GEMMs, the conv decoder's 32/64 channels) take the 128x128
-// kernel.  Otherwise the ring configuration with the least estimated time: rounds of one tile per CU x tile area / relative
-// throughput of the tile shape (measured at K = 1024 on MI355X: 256x256 1.00, 256x192 0.95, 128x384 0.945 - the L2 -> LDS
-// fill is the limiter, so throughput follows the tile's flop/byte).  DiT-L/2 at 12288 tokens: N = 4096 -> 256x256 (3 full
-// rounds), N = 3072 -> 384x192 with 12 waves (2 full rounds), N = 1024 -> 256x192 (1 full round).
-// LN3D_GEMM_TILE (measurement switch, read once per process): s = the 128x128 register-staged kernel, x<cfg> = that ring configuration
+// LN3D_GEMM_TILE (measurement switch, read once per process): s = the 128x128 register-staged kernel, x<id> = that row of the tile
+// table (an id the table does not have runs the 128x128 kernel), anything else = unforced
 static int g_gemm_forced = -2;           // environment switch, parsed once (ln3d_reload_env() re-reads it)
-static int forced_cfg() {
+static int forced_tile() {
   if (g_gemm_forced == -2) {
     const char* e = getenv("LN3D_GEMM_TILE");
     g_gemm_forced = !e ? -1 : (e[0] == 's' ? 0 : (e[0] == 'x' ? atoi(e + 1) : -1));
@@ -875,50 +869,12 @@ static int forced_cfg() {
   return g_gemm_forced;
 }
 extern "C" void ln3d_gemm_reload_env(void) { g_gemm_forced = -2; }
-static int pick_cfg(int M, int N, bool head_aligned = false, hipStream_t s = nullptr, int K = 0, int epi = -1) {
-  if (forced_cfg() >= 0) return forced_cfg();
-  if (!(M >= 1536 && N >= 128)) return 0;
-  static const struct { int cfg, bf, bt; float speed; } C[4] = {{7, 256, 256, 1.0f}, {12, 384, 192, 1.0f}, {9, 256, 192, 0.95f},
-                                                               {8, 128, 384, 0.945f}};
-  const int cus = ln3d_stream_cus(s);          // a lane stream owns part of the chip (csrc/runtime.hip)
-  int best = 8; float best_cost = 1e30f; int64_t best_tiles = 0;
-  for (int i = 0; i < 4; ++i) {
-    // head split with 64-wide heads: only the configurations whose wave row is ONE head (64 features, NI = 2) have the
-    // head-contiguous staged epilogue; at the I23D shapes (65536 x 3072) 256x256 costs 550 us against 500 (384x192)
-    if (head_aligned && C[i].cfg == 7) continue;
-    const int64_t tiles = (int64_t)((N + C[i].bf - 1) / C[i].bf) * ((M + C[i].bt - 1) / C[i].bt);
-    const float cost = (float)((tiles + cus - 1) / cus) * (float)(C[i].bf * C[i].bt) / C[i].speed;
-    if (cost < best_cost) { best_cost = cost; best = C[i].cfg; best_tiles = tiles; }
-  }
-  // Under-filled launch (the best 8-wave tiling leaves half the CUs idle - the conditional half of a CFG batch, M = 6144 x
-  // N = 1024: 128 tiles of 256x192): 128x192 tiles with 4 waves double the tile count.  r3: 22.5 us vs 27.0 (GATE_RES), 15.7 vs 21.1
-  // (plain); at full M the two tie (35.9 vs 36.2), so it is only taken here.
-  if (best_tiles * 2 <= cus) {
-    const int64_t t14 = (int64_t)((N + 127) / 128) * ((M + 191) / 192);
-    if (t14 > best_tiles) best = 14;
-  }
-  // r5: long K loops over several rounds of 256x256 tiles (the I23D family's fc2: 49152 x 1024 x 4096, 3 rounds) run faster with ONE
-  // wave per SIMD holding 128 x 128 (a third fewer LDS fragment bytes per flop): 372 - 379 us against 412, 500 against 538 at M = 65536,
-  // bit-identical output.  With 16 K stages (K = 1024) the exposed prologue / epilogue of a lone wave costs more than the loop gains
-  // (fc1 111 vs 98 us), and below two rounds the tile count decides (T23D fc2 takes 256x192) - profiles/r5_gemm_x13.log, r5_gemm_x15.log.
-  // In situ (same-box A/B of the configs[2] line, temporary switch removed): 11.60 -> 11.70 samples/s, golden check unchanged.
-  if (best == 7 && K >= 2048 && best_tiles >= 2 * (int64_t)cus && (epi == LN3D_EPI_GATE_RES || epi == LN3D_EPI_BF16 || epi == LN3D_EPI_F32))
-    best = 13;
-  // r6: the persistent one-wave-per-SIMD kernel (cfg 16) for the bf16 / erf-GELU epilogues when every CU gets >= 2 whole 256 x 256 tiles
-  // and the last round is >= 85 % full (DiT-L/2 fc1: 768 tiles = 3 rounds; I23D fc1: 12).  Sustained (3000-launch loops, profiles/r6_gemm.md):
-  // fc1 + GELU 102.8 -> 99.0 us, plain 94.0 -> 87.2, I23D fc1 + GELU 411.6 -> 398.0.  run_cfg falls back to cfg 7 when p4_ok() refuses.
-  if ((epi == LN3D_EPI_BF16 || epi == LN3D_EPI_GELU_ERF) && (M % 256) == 0 && (N % 256) == 0 && (K % 128) == 0 && K >= 512) {
-    const int64_t t = (int64_t)(N / 256) * (M / 256), rounds = (t + cus - 1) / cus;
-    if (t >= 2 * (int64_t)cus && t * 100 >= rounds * cus * 85) best = 16;
-  }
-  return best;
-}
 
 extern "C" int ln3d_gemm_heads_norm_fusable(int M, int N, int tokens, int head_dim, int head_dim_pad) {
   if (head_dim_pad <= 0) head_dim_pad = head_dim;
   if (!(head_dim == 64 && head_dim_pad == 64 && tokens > 0 && (tokens & 31) == 0 && (M % tokens) == 0 && (N % 64) == 0)) return 0;
-  const int cfg = pick_cfg(M, N, true);
-  return (cfg == 8 || cfg == 9 || cfg == 12 || cfg == 14) ? 1 : 0;
+  // neither K nor the output alignment enters the plan of a LN3D_EPI_HEADS launch
+  return ln3d_gemm_tiles[ln3d_plan_gemm(M, N, 0, LN3D_EPI_HEADS, true, true, ln3d_device_cus(), forced_tile())].head_row ? 1 : 0;
 }
 
 extern "C" int ln3d_gemm_bf16(const ln3d_gemm_args* a, void* stream) {
@@ -945,38 +901,38 @@ extern "C" int ln3d_gemm_bf16(const ln3d_gemm_args* a, void* stream) {
   p.hn0 = a->head_norm0; p.hn1 = a->head_norm1; p.hn_eps = a->head_norm_eps;
   p.rb = a->epilogue == LN3D_EPI_GATE_RES ? a->res_bias : nullptr; p.rb_ld = a->res_bias_ld;
   hipStream_t s = (hipStream_t)stream;
-  // head split: the tiles whose wave row is 64 features (NI = 2) have the staged, head-aware epilogue (any head size that is a
-  // multiple of 8 with heads * head_dim a multiple of 64)
+  // head split: the head_row tiles have the staged, head-aware epilogue (any head size that is a multiple of 8 with
+  // heads * head_dim a multiple of 64)
   const bool head_staged = a->epilogue == LN3D_EPI_HEADS && a->head_dim > 0 && (a->head_dim & 7) == 0 && a->heads > 0 &&
                            ((a->heads * a->head_dim) & 63) == 0 && a->tokens > 0 && (a->tokens & 31) == 0 && (a->M % a->tokens) == 0 &&
                            (a->N % 64) == 0;
-  const int cfg = pick_cfg(a->M, a->N, head_staged, s, a->K, a->epilogue);
+  const bool out_aligned = (a->ldo % 8) == 0 && ((uintptr_t)a->out0 & 15) == 0 && (!a->bias || ((uintptr_t)a->bias & 15) == 0);
+  const int row = ln3d_plan_gemm(a->M, a->N, a->K, a->epilogue, head_staged, out_aligned, ln3d_device_cus(), forced_tile());
   switch (a->epilogue) {
-    case LN3D_EPI_F32: return run_cfg<LN3D_EPI_F32>(p, s, cfg);
-    case LN3D_EPI_BF16: return run_cfg<LN3D_EPI_BF16>(p, s, cfg);
-    case LN3D_EPI_GELU_ERF: return run_cfg<LN3D_EPI_GELU_ERF>(p, s, cfg);
-    case LN3D_EPI_GELU_TANH: return run_cfg<LN3D_EPI_GELU_TANH>(p, s, cfg);
-    case LN3D_EPI_SILU: return run_cfg<LN3D_EPI_SILU>(p, s, cfg);
-    case LN3D_EPI_QUICK_GELU: return run_cfg<LN3D_EPI_QUICK_GELU>(p, s, cfg);
+    case LN3D_EPI_F32: return run_tile<LN3D_EPI_F32>(p, s, row);
+    case LN3D_EPI_BF16: return run_tile<LN3D_EPI_BF16>(p, s, row);
+    case LN3D_EPI_GELU_ERF: return run_tile<LN3D_EPI_GELU_ERF>(p, s, row);
+    case LN3D_EPI_GELU_TANH: return run_tile<LN3D_EPI_GELU_TANH>(p, s, row);
+    case LN3D_EPI_SILU: return run_tile<LN3D_EPI_SILU>(p, s, row);
+    case LN3D_EPI_QUICK_GELU: return run_tile<LN3D_EPI_QUICK_GELU>(p, s, row);
     case LN3D_EPI_CROSS_ATTN:
       if (!a->out1 || !a->out2 || a->bias || a->head_dim != 64 || a->heads <= 0 || a->N != a->heads * 64 || a->tokens <= 0 ||
           (a->tokens % 192) != 0 || (a->M % a->tokens) != 0 || a->ctx_keys <= 0 || a->ctx_keys > 96 || a->ctx_pad < a->ctx_keys ||
           (a->ctx_pad % 64) != 0 || (a->N % 256) != 0)
         return LN3D_ERR_BAD_ARG;
-      // 256x192 tiles (8 waves); when they would leave half the chip idle, 128x192 tiles with 4 waves (2 heads per tile)
-      return run_cfg<LN3D_EPI_CROSS_ATTN>(p, s, ((int64_t)(a->N / 256) * ((a->M + 191) / 192) * 2 <= ln3d_stream_cus(s) && forced_cfg() != 9) ? 14 : 9);
-    case LN3D_EPI_GATE_RES: return run_cfg<LN3D_EPI_GATE_RES>(p, s, cfg);
+      return run_tile<LN3D_EPI_CROSS_ATTN>(p, s, row);
+    case LN3D_EPI_GATE_RES: return run_tile<LN3D_EPI_GATE_RES>(p, s, row);
     case LN3D_EPI_F32_SILU:
       if (!a->out1) return LN3D_ERR_BAD_ARG;
-      return run_cfg<LN3D_EPI_F32_SILU>(p, s, cfg);
+      return run_tile<LN3D_EPI_F32_SILU>(p, s, row);
     case LN3D_EPI_HEADS:
       if (a->tokens <= 0 || a->heads <= 0 || a->head_dim <= 0 || (a->head_dim % 4) != 0 || a->tok_pad < a->tokens)
         return LN3D_ERR_BAD_ARG;
       if ((a->head_norm0 || a->head_norm1) &&
-          !((cfg == 8 || cfg == 9 || cfg == 12 || cfg == 14) && a->head_dim == 64 && p.head_dim_pad == 64 && (a->tokens & 31) == 0 &&
+          !(ln3d_gemm_tiles[row].head_row && a->head_dim == 64 && p.head_dim_pad == 64 && (a->tokens & 31) == 0 &&
             (a->M % a->tokens) == 0 && (a->N % 64) == 0))
         return LN3D_ERR_UNSUPPORTED;                  // only the head-aligned staged epilogue normalises
-      return run_cfg<LN3D_EPI_HEADS>(p, s, cfg);
+      return run_tile<LN3D_EPI_HEADS>(p, s, row);
     default: return LN3D_ERR_UNSUPPORTED;
   }
 }

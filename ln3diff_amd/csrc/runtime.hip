@@ -14,9 +14,7 @@ static int device_cus() {
   return n;
 }
 
-// compute units a launch on `s` can occupy (kept as a function of the stream: the launchers' tile selection calls it)
-int ln3d_stream_cus(hipStream_t) { return device_cus(); }
-
+// compute units of the device: every launcher sizes its tiling and its persistent grids by it (csrc/kernel_plan.h)
 extern "C" int ln3d_device_cus(void) { return device_cus(); }
 
 // ------------------------------------------------------------------ diagnostic: what the matrix pipes sustain on THIS box (bench.py's roofline)
