@@ -3,16 +3,25 @@
 Mirrors the reference's sgm surface for this path (same class names / call signatures):
   LegacyDDPMDiscretization, EDMDiscretization   sgm/modules/diffusionmodules/discretizer.py:27-69
   Denoiser / DiscreteDenoiser + EpsScaling / VScaling / VScalingWithEDMcNoise / EDMScaling   sgm/modules/diffusionmodules/denoiser.py:13-78, denoiser_scaling.py:14-59
-  VanillaCFG                 sgm/modules/diffusionmodules/guiders.py:24-42
-  EulerEDMSampler            sgm/modules/diffusionmodules/sampling.py:82-130,211-215
-  HeunEDMSampler, EulerAncestralSampler, DPMPP2SAncestralSampler, DPMPP2MSampler, LinearMultistepSampler (r6)   sampling.py:133-365
-The sigma tables are built on the host in fp64/fp32 exactly like the reference; the per-step work is one
-network call on [uc ; c] (2B) with the c_in scale folded into the patch-embed kernel, and ONE fused
-elementwise kernel for denoiser-combine + CFG + Euler update (ln3d_edm_euler_step).  Context K/V are
-computed once per call, not once per step.
+  VanillaCFG, IdentityGuider sgm/modules/diffusionmodules/guiders.py:24-57
+  EulerEDMSampler, HeunEDMSampler, EulerAncestralSampler, DPMPP2SAncestralSampler, DPMPP2MSampler, LinearMultistepSampler
+                             sgm/modules/diffusionmodules/sampling.py:82-365
+The sigma tables are built on the host in fp64/fp32 exactly like the reference.
+
+`_Sampler` owns what every sampler shares: the constructor, `_resolve` for the `denoiser` / `network=` arguments, the set-up and the loop
+`for i: self._step(run, i)` with its `trace`.  A sampler is its `_step` over the shared helpers plus what `_begin` adds to the run's
+state; `_EDMSampler` adds the noise injection Euler and Heun share.  Every update is ONE ln3d_lincomb launch with the guidance
+x_u + s (x_c - x_u) folded into its coefficients (the updates are linear in x and the denoised halves); sigma is one number per step
+(s_in * sigma in the reference), so the coefficients are host float64 scalars.
+EulerEDMSampler alone has a second, fused loop (`_fast`), taken when `denoiser` is recognisably this package's DiscreteDenoiser over one
+of its networks (`_find_pair`): context K/V once per call, the timestep sub-network once per schedule, per step one network call on
+[uc ; c] (2B) with c_in folded into the patch-embed kernel and ONE fused kernel for denoiser-combine + CFG + Euler update
+(ln3d_edm_euler_step).
 """
+import dis
 import math
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -205,6 +214,7 @@ class DiscreteDenoiser(Denoiser):
         """the fused network loop of EulerEDMSampler bakes EpsScaling + the index timestep in"""
         return type(self.scaling) is EpsScaling and self.quantize_c_noise
 
+
 class BoundDenoiser:
     def __init__(self, denoiser, network, **additional_model_inputs):
         self.denoiser, self.network, self.kw = denoiser, network, additional_model_inputs
@@ -213,33 +223,52 @@ class BoundDenoiser:
         return self.denoiser(self.network, input, sigma, c, **self.kw)
 
 
-_REF_LAMBDA_OPS = {'LOAD_DEREF', 'LOAD_ATTR', 'LOAD_METHOD', 'LOAD_FAST', 'BUILD_TUPLE', 'BUILD_MAP', 'DICT_MERGE', 'CALL_FUNCTION_EX',
-                   'CALL_FUNCTION', 'CALL_METHOD', 'CALL_FUNCTION_KW', 'RETURN_VALUE', 'RESUME', 'COPY_FREE_VARS', 'PUSH_NULL', 'PRECALL', 'CALL',
-                   'LOAD_CONST', 'KW_NAMES'}
-_CALL_OPS = {'CALL_FUNCTION_EX', 'CALL_FUNCTION', 'CALL_METHOD', 'CALL_FUNCTION_KW', 'CALL'}
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Which `denoiser` arguments the sampler may look into.  The engine's closure is recognised by EQUALITY of its code with the two
+# functions below, compiled by the interpreter that compiled the caller's: nothing here names an instruction.
+def _engine_closures():
+    """sgm_DiffusionEngine.py:401-403 as the engine writes it, and the same expression without the forwarded inputs"""
+    self, additional_model_inputs = None, {}
+    return (lambda input, sigma, c: self.denoiser(self.model, input, sigma, c, **additional_model_inputs),
+            lambda input, sigma, c: self.denoiser(self.model, input, sigma, c))
+
+
+def _code_shape(fn):
+    """What must be equal between `fn` and a template: the argument layout (no *args / **kwargs, no defaults) and every instruction
+    with its argument.  Free variables are renamed by order of first appearance and arguments replaced by their position, so the
+    caller's spelling of `self`, `additional_model_inputs`, `input`, `sigma`, `c` does not matter; attribute names, constants, the
+    number and order of calls, a store, a nested function: all of that does.  None for something that has no code."""
+    code = getattr(fn, '__code__', None)
+    if code is None:
+        return None
+    free = {}
+
+    def norm(op, v):
+        if op in dis.hasfree and isinstance(v, str):
+            return ('free', free.setdefault(v, len(free)))
+        if op in dis.haslocal and isinstance(v, str):
+            return ('local', code.co_varnames.index(v))
+        return v
+    return (code.co_argcount, code.co_kwonlyargcount, code.co_flags & 0x0C,
+            bool(getattr(fn, '__defaults__', None) or getattr(fn, '__kwdefaults__', None)),
+            [(i.opname, norm(i.opcode, i.argval)) for i in dis.get_instructions(code)])
+
+
+_ENGINE_SHAPES = [_code_shape(f) for f in _engine_closures()]
 
 
 def _is_reference_lambda(fn):
     """True when `fn`'s code is the engine's closure and nothing else (sgm_DiffusionEngine.py:401-403):
-    `lambda input, sigma, c: self.denoiser(self.model, input, sigma, c, **additional_model_inputs)` - three positional arguments, ONE call,
-    the attribute names `denoiser` and `model` only, every argument passed through untouched.  A closure that post-processes the
-    denoised output, wraps the network or adds inputs has other opcodes / names and is run as written (generic loop)."""
-    import dis
-    code = getattr(fn, '__code__', None)
-    if code is None or code.co_argcount != 3 or code.co_kwonlyargcount or (code.co_flags & 0x0C):      # no *args / **kwargs of its own
-        return False
-    if set(code.co_names) != {'denoiser', 'model'}:
-        return False
-    ins = list(dis.get_instructions(code))
-    if any(i.opname not in _REF_LAMBDA_OPS for i in ins) or sum(i.opname in _CALL_OPS for i in ins) != 1:
-        return False
-    fast = [i.argval for i in ins if i.opname == 'LOAD_FAST']
-    return fast == list(code.co_varnames[:3])                  # input, sigma, c: each once, in order
+    `lambda input, sigma, c: self.denoiser(self.model, input, sigma, c, **additional_model_inputs)`, with or without the `**` part,
+    under any names for its arguments and closure variables (_code_shape).  Anything else - an extra argument or keyword, another
+    callee, a post-processed result, a wrapped network - is another code and is run as written (generic loop)."""
+    shape = _code_shape(fn)
+    return shape is not None and shape in _ENGINE_SHAPES
 
 
 def _find_pair(denoiser):
     """(DiscreteDenoiser, ln3diff_amd network) behind the sampler's `denoiser` argument, or (None, None).
-    Recognised (ADVICE r5: nothing heuristic): `BoundDenoiser` without extra inputs; a callable that opts in with
+    Recognised (nothing heuristic): `BoundDenoiser` without extra inputs; a callable that opts in with
     `_ln3d_pair = (denoiser, network)`; a closure whose CODE is exactly the reference's lambda over an engine object with
     `.denoiser` / `.model` and an empty `additional_model_inputs` (_is_reference_lambda).  Anything else runs the generic loop."""
     if isinstance(denoiser, BoundDenoiser):
@@ -268,21 +297,86 @@ def _find_pair(denoiser):
     return (den, net) if den is not None else (None, None)
 
 
-class EulerEDMSampler:
-    """sampling.py:82-130,211-215: EDMSampler + the Euler step.  The released configuration is s_churn = 0 (gamma = 0: deterministic);
-    s_churn / s_tmin / s_tmax / s_noise > 0 (r6) add the reference's noise injection: where s_tmin <= sigma_i <= s_tmax,
-    gamma = min(s_churn / (num_sigmas - 1), sqrt 2 - 1), sigma_hat = sigma_i (1 + gamma), x += randn * s_noise * sqrt(sigma_hat^2 -
-    sigma_i^2), and the denoiser runs at sigma_hat (quantised to the 1000-entry table for c_out / c_in / the timestep, the Euler step
-    itself on sigma_hat).  The draw of step i comes from `step_noise(i)` (a [B, ...] tensor; parity runs feed the recorded stream) or
-    torch.randn on the device."""
+def _resolve(denoiser, network):
+    """(call, pair) for the sampler's `denoiser` / `network=` arguments: call is (input, sigma, c) -> denoised; pair the (denoiser, network)
+    it stands for - a Denoiser given with `network=`, or what _find_pair recognises - or None for any other callable, called as given."""
+    den, net = (denoiser, network) if network is not None and isinstance(denoiser, Denoiser) else _find_pair(denoiser)
+    if net is None:
+        return denoiser, None
+    return (lambda x, s, c: den(net, x, s, c)), (den, net)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+class _Sampler:
+    """What every sampler shares.  `run` is the state of one call: n, table (the fp32 sigma table with its appended zero), sigmas (the
+    same as floats), call and pair (_resolve), cond, uc, step_noise, B, x (the latent, updated in place) and what `_begin` / `_loop` add."""
+
+    def __init__(self, num_steps=250, guider=None, discretization=None, **_):
+        self.num_steps = num_steps
+        self.guider = guider or VanillaCFG(6.5)
+        self.discretization = discretization or LegacyDDPMDiscretization()
+
+    @torch.no_grad()
+    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, *, network=None, trace=None, step_noise=None):
+        """The reference's call (sampling.py:109): denoiser = the engine's closure (input, sigma, c) -> denoised, or a Denoiser with
+        `network=`; x [B, ...] f32 device noise; cond / uc dicts with 'crossattn'.  Returns the final latent; trace receives a copy of
+        it after every step; step_noise(i) ([B, ...] tensor) replaces the device draw of step i (parity runs feed the recorded stream)."""
+        call, pair = _resolve(denoiser, network)
+        n = self.num_steps if num_steps is None else num_steps
+        table = self.discretization(n, device="cpu")
+        x = (x * float(torch.sqrt(1.0 + table[0] ** 2.0))).contiguous()          # the reference's fp32 arithmetic
+        run = SimpleNamespace(n=n, table=table, sigmas=[float(v) for v in table], call=call, pair=pair, cond=cond,
+                              uc=cond if uc is None else uc, step_noise=step_noise, B=x.shape[0], x=x)
+        self._begin(run)
+        return self._loop(run, trace)
+
+    def _begin(self, run):
+        pass
+
+    def _loop(self, run, trace):
+        run.s_in = run.x.new_ones([run.B])
+        for i in range(run.n):
+            self._step(run, i)
+            if trace is not None:
+                trace.append(run.x.clone())
+        return run.x
+
+    def _den(self, run, x, sig, keep=False):
+        """the denoised batch at noise level sig as the guider laid it out ([uc ; c] for VanillaCFG); keep = it must survive the next call"""
+        out = run.call(*self.guider.prepare_inputs(x, run.s_in * sig, run.cond, run.uc)).contiguous().float()
+        return out.clone() if keep else out
+
+    @staticmethod
+    def _noise(run, i):
+        x = run.x
+        return run.step_noise(i).to(x.device).float().contiguous() if run.step_noise is not None else torch.randn(x.shape, device=x.device)
+
+    def _euler_to(self, run, den, sig, target, out):
+        """out = x + (target - sig) / sig * (x - guided(den)): guider + to_d + euler_step in one combination"""
+        r = (target - sig) / sig
+        k, c = _guided_terms(self.guider, den, run.B, -r)
+        ops.lincomb(run.x, [run.x] + k, [r] + c, out)
+
+    def _affine(self, run, a, terms, out):
+        """out = a x + sum coef * guided(den) over terms = [(coef, den), ...]"""
+        ks, cs = [run.x], [a]
+        for coef, den in terms:
+            k, c = _guided_terms(self.guider, den, run.B, coef)
+            ks, cs = ks + k, cs + c
+        ops.lincomb(None, ks, cs, out)
+
+
+class _EDMSampler(_Sampler):
+    """sampling.py:82-130, the reference's EDMSampler: the noise injection Euler and Heun share.  The released configuration is
+    s_churn = 0 (gamma = 0: deterministic); where s_tmin <= sigma_i <= s_tmax, gamma = min(s_churn / (num_sigmas - 1), sqrt 2 - 1),
+    sigma_hat = sigma_i (1 + gamma), x += randn * s_noise * sqrt(sigma_hat^2 - sigma_i^2), and the denoiser runs at sigma_hat.
+    use_graph is read by EulerEDMSampler's fused loop alone (None: follow LN3D_GRAPH)."""
 
     def __init__(self, num_steps=250, guider=None, discretization=None, s_churn=0.0, s_tmin=0.0, s_tmax=float('inf'), s_noise=1.0,
                  use_graph=None, **_):
-        self.num_steps = num_steps
-        self.use_graph = use_graph            # None: follow LN3D_GRAPH
+        super().__init__(num_steps, guider, discretization)
+        self.use_graph = use_graph
         self.s_churn, self.s_tmin, self.s_tmax, self.s_noise = float(s_churn), float(s_tmin), float(s_tmax), float(s_noise)
-        self.guider = guider or VanillaCFG(6.5)
-        self.discretization = discretization or LegacyDDPMDiscretization()
 
     def _gammas(self, sigmas):
         """gamma per step (sampling.py:114-118): num_sigmas = len(sigmas) counts the appended zero."""
@@ -290,65 +384,46 @@ class EulerEDMSampler:
         g = min(self.s_churn / (n - 1), 2 ** 0.5 - 1)
         return [g if (self.s_churn > 0 and self.s_tmin <= float(sigmas[i]) <= self.s_tmax) else 0.0 for i in range(n - 1)]
 
-    @torch.no_grad()
-    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, *, network=None, trace=None, step_noise=None):
-        """The reference's call (sampling.py:109): denoiser = the engine's closure (input, sigma, c) -> denoised; x [B,12,32,32]
-        f32 device noise (consumed in place: returns the final latent); cond / uc dicts with 'crossattn'.
-        Fast path (context K/V, the timestep sub-network of the whole schedule and the CFG + Euler update fused): taken when the
-        closure is recognisably this package's DiscreteDenoiser over one of its networks (`DiscreteDenoiser.bind(network)`, the
-        reference's own lambda over an engine, or `network=` with a DiscreteDenoiser).  Any other callable runs the generic loop
-        with the same arithmetic, one closure call per step."""
-        if network is not None and isinstance(denoiser, Denoiser):
-            den, net = denoiser, network
-        else:
-            den, net = _find_pair(denoiser)
-        if net is None or isinstance(self.guider, IdentityGuider) or not getattr(den, 'fused_ok', False):   # the fused loop: CFG-doubled, EpsScaling
-            gen = denoiser if net is None else (lambda x_, s_, c_: den(net, x_, s_, c_))
-            return self._generic(gen, x, cond, uc, num_steps, trace, step_noise)
-        uc = cond if uc is None else uc
-        return self._fast(den, net, x, cond, uc, num_steps, trace, step_noise)
+    def _begin(self, run):
+        run.gammas = self._gammas(run.sigmas)
 
-    # ------------------------------------------------------------------ generic: the reference loop, one closure call per step
-    def _churn(self, x, sig, gamma, i, step_noise):
-        """x += randn * s_noise * sqrt(sigma_hat^2 - sigma^2) in place; returns sigma_hat (sampling.py:96-99)."""
+    def _churn(self, run, i):
+        """sigma_hat of step i; where gamma > 0, x += randn * s_noise * sqrt(sigma_hat^2 - sigma^2) in place (sampling.py:96-99)"""
+        sig, gamma = run.sigmas[i], run.gammas[i]
+        if not gamma > 0:
+            return sig
         sig_hat = sig * (gamma + 1.0)
-        eps = step_noise(i).to(x.device).float().contiguous() if step_noise is not None else torch.randn(x.shape, device=x.device)
-        ops.lincomb(x, [eps], [self.s_noise * (sig_hat ** 2 - sig ** 2) ** 0.5], x)
+        ops.lincomb(run.x, [self._noise(run, i)], [self.s_noise * (sig_hat ** 2 - sig ** 2) ** 0.5], run.x)
         return sig_hat
 
-    def _generic(self, denoiser, x, cond, uc, num_steps, trace, step_noise=None):
-        n = self.num_steps if num_steps is None else num_steps
-        sigmas = self.discretization(n, device="cpu")
-        gammas = self._gammas(sigmas)
-        uc = cond if uc is None else uc
-        x = (x * float(torch.sqrt(1.0 + sigmas[0] ** 2.0))).contiguous()
-        B = x.shape[0]
-        s_in = x.new_ones([B])
-        for i in range(n):
-            sig, nxt = float(sigmas[i]), float(sigmas[i + 1])
-            if gammas[i] > 0:
-                sig = self._churn(x, sig, gammas[i], i, step_noise)
-            den = denoiser(*self.guider.prepare_inputs(x, s_in * sig, cond, uc)).contiguous().float()
-            # guider + to_d + euler_step in one combination: x + dt/sigma * (x - (x_u + s (x_c - x_u)))
-            r = (nxt - sig) / sig
-            dk, dcf = _guided_terms(self.guider, den, B, -r)
-            ops.lincomb(x, [x] + dk, [r] + dcf, x)
-            if trace is not None:
-                trace.append(x.clone())
-        return x
 
-    # ------------------------------------------------------------------ fast path pieces
-    def _prepare(self, den, network, x, cond, uc, n):
-        sigmas = self.discretization(n, device="cpu")
-        B, dev = x.shape[0], x.device
-        ctx = torch.cat((uc['crossattn'], cond['crossattn']), 0).to(dev)      # VanillaCFG: [uc, c]
-        gammas = self._gammas(sigmas)
-        st = {'cache': network.prepare_context(ctx), 'sigmas': sigmas, 'B': B, 'gammas': gammas,
-              't_dev': torch.empty(2 * B, device=dev, dtype=torch.float32), 's_dev': torch.empty(2 * B, device=dev, dtype=torch.float32),
-              # the denoiser sees sigma_hat = sigma (1 + gamma), quantised to its table (denoiser.py:66-78)
-              'quant': [den.quantize(float(sigmas[i]) * (gammas[i] + 1.0)) for i in range(n)]}
-        st['x'] = x * float(torch.sqrt(1.0 + sigmas[0] ** 2.0))
-        return st
+class EulerEDMSampler(_EDMSampler):
+    """sampling.py:82-130,211-215: EDMSampler + the Euler step.
+    Fused loop (context K/V, the timestep sub-network of the whole schedule and the CFG + Euler update fused): taken under VanillaCFG
+    when the `denoiser` argument is recognisably this package's DiscreteDenoiser (EpsScaling, index timesteps) over one of its networks -
+    `DiscreteDenoiser.bind(network)`, the reference's own lambda over an engine, or `network=` with a DiscreteDenoiser.  Any other
+    callable runs the generic loop with the same arithmetic, one closure call per step.  Under noise injection the denoiser sees
+    sigma_hat quantised to its table (c_out, c_in, the timestep); the Euler step itself is on sigma_hat."""
+
+    def _step(self, run, i):
+        sig = self._churn(run, i)
+        self._euler_to(run, self._den(run, run.x, sig), sig, run.sigmas[i + 1], run.x)
+
+    def _loop(self, run, trace):
+        if run.pair is None or isinstance(self.guider, IdentityGuider) or not getattr(run.pair[0], 'fused_ok', False):
+            return super()._loop(run, trace)
+        return self._fast(*run.pair, run, trace)
+
+    # ------------------------------------------------------------------ the fused loop: CFG-doubled, EpsScaling
+    def _prepare(self, run, den, network):
+        dev = run.x.device
+        ctx = torch.cat((run.uc['crossattn'], run.cond['crossattn']), 0).to(dev)      # VanillaCFG: [uc, c]
+        run.cache = network.prepare_context(ctx)
+        run.t_dev, run.s_dev = (torch.empty(2 * run.B, device=dev, dtype=torch.float32) for _ in range(2))
+        # the denoiser sees sigma_hat = sigma (1 + gamma), quantised to its table (denoiser.py:66-78); c_in is its scaling's, at that entry
+        run.quant = [den.quantize(run.sigmas[i] * (run.gammas[i] + 1.0)) for i in range(run.n)]
+        run.c_in = [den.scaling(sig_q)[2] for sig_q, _ in run.quant]
+        run.graph = None
 
     def _mod_all(self, network, quant, n, B):
         if not hasattr(network, 'prepare_timesteps'):
@@ -357,108 +432,93 @@ class EulerEDMSampler:
         t_table = torch.tensor([float(q[1]) for q in quant], dtype=torch.float32)[:, None].expand(n, 2 * B)
         return network.prepare_timesteps(t_table)
 
-    def _step(self, network, st, i, mod_all, step_noise=None):
-        sig, idx = st['quant'][i]
-        gamma = st['gammas'][i]
-        if gamma > 0:
-            sig_hat = self._churn(st['x'], float(st['sigmas'][i]), gamma, i, step_noise)
-        c_in = float(1.0 / (torch.tensor(sig, dtype=torch.float32) ** 2 + 1.0) ** 0.5)
-        st['t_dev'].fill_(float(idx))
-        st['s_dev'].fill_(c_in)
-        g = st.get('graph')
+    def _fused_step(self, network, run, i, mod_all):
+        sig, idx = run.quant[i]
+        sig_hat = self._churn(run, i)
+        run.t_dev.fill_(float(idx))
+        run.s_dev.fill_(run.c_in[i])
+        g = run.graph
         if g is not None:
             g['mod_step']['mod'].copy_(mod_all['mod'][i * g['mrows']:(i + 1) * g['mrows']])
             g['graph'].replay()
             eps2 = g['eps']
         elif mod_all is not None:      # cfg_twins: [uc ; c] are the same latents, timestep and c_in twice (VanillaCFG.prepare_inputs)
-            eps2 = network(st['x'], st['t_dev'], context_cache=st['cache'], in_scale=st['s_dev'], mod_cache=(mod_all, i), cfg_twins=True)
+            eps2 = network(run.x, run.t_dev, context_cache=run.cache, in_scale=run.s_dev, mod_cache=(mod_all, i), cfg_twins=True)
         else:
-            eps2 = network(st['x'], st['t_dev'], context_cache=st['cache'], in_scale=st['s_dev'], cfg_twins=True)
-        if gamma > 0:
+            eps2 = network(run.x, run.t_dev, context_cache=run.cache, in_scale=run.s_dev, cfg_twins=True)
+        if run.gammas[i] > 0:
             # denoised = x - sig_q (eps_u + s (eps_c - eps_u)); d = (x - denoised) / sigma_hat; x += d (sigma_next - sigma_hat): sig_q (the table
             # entry c_out uses) and sigma_hat differ here, which the fused kernel's single sigma cannot express - one linear combination instead
-            B, sc = st['B'], float(self.guider.scale)
-            r = (float(st['sigmas'][i + 1]) - sig_hat) / sig_hat * sig
+            sc = float(self.guider.scale)
+            r = (run.sigmas[i + 1] - sig_hat) / sig_hat * sig
             e2 = eps2.reshape(2, -1)
-            ops.lincomb(st['x'], [e2[0].reshape(st['x'].shape), e2[1].reshape(st['x'].shape)], [r * (1.0 - sc), r * sc], st['x'])
+            ops.lincomb(run.x, [e2[0].reshape(run.x.shape), e2[1].reshape(run.x.shape)], [r * (1.0 - sc), r * sc], run.x)
         else:
-            ops.edm_euler_step(st['x'], eps2, sig, float(st['sigmas'][i + 1]), float(self.guider.scale))
+            ops.edm_euler_step(run.x, eps2, sig, run.sigmas[i + 1], float(self.guider.scale))
 
-    def _capture(self, network, st, mod_all, dev):
+    _capture_streams = {}                             # ONE stream per device for warm-up and capture
+
+    @classmethod
+    def _capture_stream(cls, dev):
+        key = dev.index if dev.index is not None else torch.cuda.current_device()
+        if key not in cls._capture_streams:
+            cls._capture_streams[key] = torch.cuda.Stream(device=dev)
+        return cls._capture_streams[key]
+
+    def _capture(self, network, run, mod_all):
         """Optional HIP-graph replay of the network evaluation (LN3D_GRAPH=1 or use_graph=True): the ~220 launches of a forward
         are captured once and replayed per step; what changes between steps goes through fixed device buffers (x in place,
         t_dev, s_dev, the step's modulation rows copied into mod_step)."""
-        st['x'] = st['x'].contiguous()
+        dev = run.x.device
         mrows = mod_all['rows']
         mod_step = {'mod': torch.empty_like(mod_all['mod'][:mrows]), 'rows': mrows, 'epoch': mod_all.get('epoch')}
         mod_step['mod'].copy_(mod_all['mod'][:mrows])
-        st['t_dev'].fill_(float(st['quant'][0][1]))
-        st['s_dev'].fill_(1.0)
-        side = _capture_stream(dev)                      # ONE stream per device for warm-up and capture (ADVICE r5)
+        run.t_dev.fill_(float(run.quant[0][1]))
+        run.s_dev.fill_(1.0)
+        side = self._capture_stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):                     # warm-up outside the capture: workspaces (allocated and zeroed here, once), kernel attributes
-            network(st['x'], st['t_dev'], context_cache=st['cache'], in_scale=st['s_dev'], mod_cache=(mod_step, 0), cfg_twins=True)
+            network(run.x, run.t_dev, context_cache=run.cache, in_scale=run.s_dev, mod_cache=(mod_step, 0), cfg_twins=True)
         torch.cuda.current_stream(dev).wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=side):
-            eps_g = network(st['x'], st['t_dev'], context_cache=st['cache'], in_scale=st['s_dev'], mod_cache=(mod_step, 0), cfg_twins=True)
-        st['graph'] = {'graph': graph, 'eps': eps_g, 'mod_step': mod_step, 'mrows': mrows}
+            eps_g = network(run.x, run.t_dev, context_cache=run.cache, in_scale=run.s_dev, mod_cache=(mod_step, 0), cfg_twins=True)
+        run.graph = {'graph': graph, 'eps': eps_g, 'mod_step': mod_step, 'mrows': mrows}
 
-    def _fast(self, den, network, x, cond, uc, num_steps, trace, step_noise=None):
-        n = self.num_steps if num_steps is None else num_steps
-        st = self._prepare(den, network, x, cond, uc, n)
-        mod_all = self._mod_all(network, st['quant'], n, st['B'])
+    def _fast(self, den, network, run, trace):
+        self._prepare(run, den, network)
+        mod_all = self._mod_all(network, run.quant, run.n, run.B)
         want_graph = self.use_graph if self.use_graph is not None else bool(os.environ.get('LN3D_GRAPH'))
-        if want_graph and mod_all is not None and n > 2:
-            self._capture(network, st, mod_all, x.device)
-        for i in range(n):
-            self._step(network, st, i, mod_all, step_noise)
+        if want_graph and mod_all is not None and run.n > 2:
+            self._capture(network, run, mod_all)
+        for i in range(run.n):
+            self._fused_step(network, run, i, mod_all)
             if trace is not None:
-                trace.append(st['x'].clone())
-        return st['x']
+                trace.append(run.x.clone())
+        return run.x
 
 
-_CAPTURE_STREAMS = {}
+class HeunEDMSampler(_EDMSampler):
+    """sampling.py:218-236: EDMSampler's step (noise injection included) + the trapezoidal correction, a second network evaluation per step
+    except onto sigma = 0."""
 
+    def _begin(self, run):
+        super()._begin(run)
+        run.xe = torch.empty_like(run.x)
 
-# ---------------------------------------------------------------------------------------------------------------------------------
-# r6: the other samplers of sgm/modules/diffusionmodules/sampling.py (HeunEDMSampler 218-236, EulerAncestralSampler 133-170 / 239-246,
-# DPMPP2SAncestralSampler 249-287, DPMPP2MSampler 290-365).  None of the released launchers selects them; they are here so that a sampler
-# config of the reference's family resolves.  Host loops over the same device pieces as EulerEDMSampler's generic path: one closure call per
-# network evaluation (the CFG-doubled batch), every update ONE ln3d_lincomb launch with the guidance x_u + s (x_c - x_u) folded into its
-# coefficients (all of these updates are linear in x and the denoised halves).  sigma is one number per step (s_in * sigma in the reference),
-# so the step sizes are host scalars.  LinearMultistepSampler's weights are the closed-form integrals of the Lagrange basis (the reference integrates the same polynomials numerically).
-def _closure(denoiser, network):
-    """(input, sigma, c) -> denoised [2B, ...]: the reference's lambda / BoundDenoiser as given, or DiscreteDenoiser + network= bound here."""
-    if network is not None and isinstance(denoiser, Denoiser):
-        return lambda x, s, c: denoiser(network, x, s, c)
-    return denoiser
-
-
-class _LoopSampler:
-    def __init__(self, num_steps=250, guider=None, discretization=None, **_):
-        self.num_steps = num_steps
-        self.guider = guider or VanillaCFG(6.5)
-        self.discretization = discretization or LegacyDDPMDiscretization()
-
-    def _setup(self, denoiser, x, cond, uc, num_steps, network):
-        n = self.num_steps if num_steps is None else num_steps
-        sigmas = [float(v) for v in self.discretization(n, device="cpu")]
-        x = (x * float((1.0 + sigmas[0] ** 2.0) ** 0.5)).contiguous()
-        return n, sigmas, _closure(denoiser, network), (cond if uc is None else uc), x
-
-    def _den(self, call, x, sig, cond, uc, keep=False):
-        """the denoised batch at noise level sig as the guider laid it out ([uc ; c] for VanillaCFG); keep = it must survive the next call"""
-        B = x.shape[0]
-        out = call(*self.guider.prepare_inputs(x, x.new_ones([B]) * sig, cond, uc)).contiguous().float()
-        return out.clone() if keep else out
-
-    def _g(self, den, x, coef):
-        return _guided_terms(self.guider, den, x.shape[0], coef)
-
-    @staticmethod
-    def _noise(x, i, step_noise):
-        return step_noise(i).to(x.device).float().contiguous() if step_noise is not None else torch.randn(x.shape, device=x.device)
+    def _step(self, run, i):
+        x, xe, nxt = run.x, run.xe, run.sigmas[i + 1]
+        sig = self._churn(run, i)
+        d1 = self._den(run, x, sig, keep=True)
+        self._euler_to(run, d1, sig, nxt, xe)                                                    # the Euler step
+        if nxt < 1e-14:
+            x.copy_(xe)
+        else:                                                                                    # x + dt ((x - D) / sig + (x_e - D2) / nxt) / 2
+            d2 = self._den(run, xe, nxt)
+            a, b = (nxt - sig) / (2.0 * sig), (nxt - sig) / (2.0 * nxt)
+            k1, c1 = _guided_terms(self.guider, d1, run.B, -a)
+            k2, c2 = _guided_terms(self.guider, d2, run.B, -b)
+            ops.lincomb(x, [x] + k1 + [xe] + k2, [a] + c1 + [b] + c2, x)
 
 
 def _ancestral(sig, nxt, eta):
@@ -469,134 +529,80 @@ def _ancestral(sig, nxt, eta):
     return (nxt ** 2 - up ** 2) ** 0.5, up
 
 
-class HeunEDMSampler(EulerEDMSampler):
-    """sampling.py:218-236: EDMSampler's step (noise injection included) + the trapezoidal correction, a second network evaluation per step
-    except onto sigma = 0.  Always the generic loop (the fused network loop of EulerEDMSampler is a one-evaluation-per-step schedule)."""
-
-    @torch.no_grad()
-    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, *, network=None, trace=None, step_noise=None):
-        n = self.num_steps if num_steps is None else num_steps
-        sig_t = self.discretization(n, device="cpu")
-        gammas = self._gammas(sig_t)
-        sigmas = [float(v) for v in sig_t]
-        call = _closure(denoiser, network)
-        uc = cond if uc is None else uc
-        x = (x * float((1.0 + sigmas[0] ** 2.0) ** 0.5)).contiguous()
-        B = x.shape[0]
-        xe = torch.empty_like(x)
-        den = _LoopSampler._den
-        for i in range(n):
-            sig, nxt = sigmas[i], sigmas[i + 1]
-            if gammas[i] > 0:
-                sig = self._churn(x, sig, gammas[i], i, step_noise)
-            d1 = den(self, call, x, sig, cond, uc, keep=True)
-            r = (nxt - sig) / sig
-            k1, c1 = _guided_terms(self.guider, d1, B, -r)
-            ops.lincomb(x, [x] + k1, [r] + c1, xe)                                               # the Euler step
-            if nxt < 1e-14:
-                x.copy_(xe)
-            else:                                                                                # x + dt ((x - D) / sig + (x_e - D2) / nxt) / 2
-                d2 = den(self, call, xe, nxt, cond, uc)
-                a, b = (nxt - sig) / (2.0 * sig), (nxt - sig) / (2.0 * nxt)
-                k1, c1 = _guided_terms(self.guider, d1, B, -a)
-                k2, c2 = _guided_terms(self.guider, d2, B, -b)
-                ops.lincomb(x, [x] + k1 + [xe] + k2, [a] + c1 + [b] + c2, x)
-            if trace is not None:
-                trace.append(x.clone())
-        return x
-
-
-class EulerAncestralSampler(_LoopSampler):
-    """sampling.py:133-170, 239-246: Euler step to sigma_down, then s_noise * sigma_up of fresh noise where the next sigma is not 0.
-    step_noise(i) ([B, ...] tensor) replaces the device draw of step i (parity runs; the reference draws at every step)."""
+class EulerAncestralSampler(_Sampler):
+    """sampling.py:133-170, 239-246: Euler step to sigma_down, then s_noise * sigma_up of fresh noise where the next sigma is not 0
+    (the reference draws at every step)."""
 
     def __init__(self, eta=1.0, s_noise=1.0, **kw):
         super().__init__(**kw)
         self.eta, self.s_noise = float(eta), float(s_noise)
 
-    def _ancestral_noise(self, x, i, nxt, up, step_noise):
+    def _ancestral_noise(self, run, i, nxt, up):
         if nxt > 0.0:
-            ops.lincomb(x, [self._noise(x, i, step_noise)], [self.s_noise * up], x)
+            ops.lincomb(run.x, [self._noise(run, i)], [self.s_noise * up], run.x)
 
-    @torch.no_grad()
-    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, *, network=None, trace=None, step_noise=None):
-        n, sigmas, call, uc, x = self._setup(denoiser, x, cond, uc, num_steps, network)
-        for i in range(n):
-            sig, nxt = sigmas[i], sigmas[i + 1]
-            down, up = _ancestral(sig, nxt, self.eta)
-            d1 = self._den(call, x, sig, cond, uc)
-            r = (down - sig) / sig
-            k1, c1 = self._g(d1, x, -r)
-            ops.lincomb(x, [x] + k1, [r] + c1, x)
-            self._ancestral_noise(x, i, nxt, up, step_noise)
-            if trace is not None:
-                trace.append(x.clone())
-        return x
+    def _step(self, run, i):
+        sig, nxt = run.sigmas[i], run.sigmas[i + 1]
+        down, up = _ancestral(sig, nxt, self.eta)
+        self._euler_to(run, self._den(run, run.x, sig), sig, down, run.x)
+        self._ancestral_noise(run, i, nxt, up)
 
 
 class DPMPP2SAncestralSampler(EulerAncestralSampler):
     """sampling.py:249-287: exponential-integrator midpoint step in t = -log sigma towards sigma_down (second evaluation at sigma(t + h / 2)),
     the Euler step when sigma_down is 0, then the ancestral noise."""
 
-    @torch.no_grad()
-    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, *, network=None, trace=None, step_noise=None):
-        n, sigmas, call, uc, x = self._setup(denoiser, x, cond, uc, num_steps, network)
-        x2 = torch.empty_like(x)
-        for i in range(n):
-            sig, nxt = sigmas[i], sigmas[i + 1]
-            down, up = _ancestral(sig, nxt, self.eta)
-            d1 = self._den(call, x, sig, cond, uc)
-            if down < 1e-14:
-                r = (down - sig) / sig
-                k1, c1 = self._g(d1, x, -r)
-                ops.lincomb(x, [x] + k1, [r] + c1, x)
-            else:
-                t, t_next = -math.log(sig), -math.log(down)
-                h = t_next - t
-                sm = t + 0.5 * h
-                m1, m2 = math.exp(-sm) / math.exp(-t), math.expm1(-0.5 * h)
-                m3, m4 = math.exp(-t_next) / math.exp(-t), math.expm1(-h)
-                k1, c1 = self._g(d1, x, -m2)
-                ops.lincomb(None, [x] + k1, [m1] + c1, x2)                                         # x2 = m1 x - m2 D
-                d2 = self._den(call, x2, math.exp(-sm), cond, uc)
-                k2, c2 = self._g(d2, x, -m4)
-                ops.lincomb(None, [x] + k2, [m3] + c2, x)                                          # x = m3 x - m4 D2
-            self._ancestral_noise(x, i, nxt, up, step_noise)
-            if trace is not None:
-                trace.append(x.clone())
-        return x
+    def _begin(self, run):
+        run.x2 = torch.empty_like(run.x)
+
+    def _step(self, run, i):
+        sig, nxt = run.sigmas[i], run.sigmas[i + 1]
+        down, up = _ancestral(sig, nxt, self.eta)
+        d1 = self._den(run, run.x, sig)
+        if down < 1e-14:
+            self._euler_to(run, d1, sig, down, run.x)
+        else:
+            t, t_next = -math.log(sig), -math.log(down)
+            h = t_next - t
+            sm = t + 0.5 * h
+            m1, m2 = math.exp(-sm) / math.exp(-t), math.expm1(-0.5 * h)
+            m3, m4 = math.exp(-t_next) / math.exp(-t), math.expm1(-h)
+            self._affine(run, m1, [(-m2, d1)], run.x2)                                            # x2 = m1 x - m2 D
+            d2 = self._den(run, run.x2, math.exp(-sm))
+            self._affine(run, m3, [(-m4, d2)], run.x)                                             # x = m3 x - m4 D2
+        self._ancestral_noise(run, i, nxt, up)
 
 
-class DPMPP2MSampler(_LoopSampler):
+class _NoDrawSampler(_Sampler):
+    """the samplers that draw nothing: `step_noise` and any other keyword are accepted and ignored, like the reference's **kwargs"""
+
+    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, *, network=None, trace=None, **_):
+        return super().__call__(denoiser, x, cond, uc, num_steps, network=network, trace=trace)
+
+
+class DPMPP2MSampler(_NoDrawSampler):
     """sampling.py:290-365: second-order multistep - the previous step's denoised output extrapolates the current one by the ratio of the two
     log-sigma steps; the first step and the step onto sigma = 0 are first order (that last step returns the denoised sample itself)."""
 
-    @torch.no_grad()
-    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, *, network=None, trace=None, **_):
-        n, sigmas, call, uc, x = self._setup(denoiser, x, cond, uc, num_steps, network)
-        old = None
-        for i in range(n):
-            sig, nxt = sigmas[i], sigmas[i + 1]
-            d1 = self._den(call, x, sig, cond, uc, keep=True)
-            t = -math.log(sig)
-            if nxt < 1e-14:                                   # t_next = +inf: mult1 = 0, mult2 = expm1(-inf) = -1
-                m1, m2, h = 0.0, -1.0, float('inf')
-            else:
-                h = -math.log(nxt) - t
-                m1, m2 = nxt / sig, math.expm1(-h)
-            if old is None or nxt < 1e-14:
-                k1, c1 = self._g(d1, x, -m2)
-                ops.lincomb(None, [x] + k1, [m1] + c1, x)
-            else:
-                r = (t + math.log(sigmas[i - 1])) / h
-                m3, m4 = 1.0 + 1.0 / (2.0 * r), 1.0 / (2.0 * r)
-                k1, c1 = self._g(d1, x, -m2 * m3)
-                k0, c0 = self._g(old, x, m2 * m4)
-                ops.lincomb(None, [x] + k1 + k0, [m1] + c1 + c0, x)
-            old = d1
-            if trace is not None:
-                trace.append(x.clone())
-        return x
+    def _begin(self, run):
+        run.old = None
+
+    def _step(self, run, i):
+        sig, nxt = run.sigmas[i], run.sigmas[i + 1]
+        d1 = self._den(run, run.x, sig, keep=True)
+        t = -math.log(sig)
+        if nxt < 1e-14:                                   # t_next = +inf: mult1 = 0, mult2 = expm1(-inf) = -1
+            m1, m2, h = 0.0, -1.0, float('inf')
+        else:
+            h = -math.log(nxt) - t
+            m1, m2 = nxt / sig, math.expm1(-h)
+        if run.old is None or nxt < 1e-14:
+            self._affine(run, m1, [(-m2, d1)], run.x)
+        else:
+            r = (t + math.log(run.sigmas[i - 1])) / h
+            m3, m4 = 1.0 + 1.0 / (2.0 * r), 1.0 / (2.0 * r)
+            self._affine(run, m1, [(-m2 * m3, d1), (m2 * m4, run.old)], run.x)
+        run.old = d1
 
 
 def linear_multistep_coeff(order, t, i, j):
@@ -614,36 +620,26 @@ def linear_multistep_coeff(order, t, i, j):
     return float(prim(float(t[i + 1])) - prim(float(t[i])))
 
 
-class LinearMultistepSampler(_LoopSampler):
+class LinearMultistepSampler(_NoDrawSampler):
     """sampling.py:172-208: Adams-Bashforth in sigma over the last `order` derivatives d = (x - denoised) / sigma; one evaluation per step.
-    Each d is one ln3d_lincomb (guidance folded in), the update another."""
+    Each d is one ln3d_lincomb (guidance folded in), the update another.  The weights are the closed-form integrals of the Lagrange
+    basis (the reference integrates the same polynomials numerically)."""
 
     def __init__(self, order=4, **kw):
         super().__init__(**kw)
         self.order = int(order)
 
-    @torch.no_grad()
-    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, *, network=None, trace=None, **_):
-        n, sigmas, call, uc, x = self._setup(denoiser, x, cond, uc, num_steps, network)
-        sig_np = np.asarray(self.discretization(n, device="cpu"), dtype=np.float32)     # the reference's fp32 sigma table (sigmas.cpu().numpy())
-        ds = []
-        for i in range(n):
-            d1 = self._den(call, x, sigmas[i], cond, uc)
-            d = torch.empty_like(x) if len(ds) < self.order else ds.pop(0)
-            inv = 1.0 / sigmas[i]
-            k1, c1 = self._g(d1, x, -inv)
-            ops.lincomb(None, [x] + k1, [inv] + c1, d)
-            ds.append(d)
-            cur = min(i + 1, self.order)
-            coeffs = [linear_multistep_coeff(cur, sig_np, i, j) for j in range(cur)]
-            ops.lincomb(x, list(reversed(ds))[:cur], coeffs, x)
-            if trace is not None:
-                trace.append(x.clone())
-        return x
+    def _begin(self, run):
+        run.ds = []
+        run.sig_np = np.asarray(run.table, dtype=np.float32)      # the reference's fp32 sigma table (sigmas.cpu().numpy())
 
-
-def _capture_stream(dev):
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    if key not in _CAPTURE_STREAMS:
-        _CAPTURE_STREAMS[key] = torch.cuda.Stream(device=dev)
-    return _CAPTURE_STREAMS[key]
+    def _step(self, run, i):
+        ds = run.ds
+        d1 = self._den(run, run.x, run.sigmas[i])
+        d = torch.empty_like(run.x) if len(ds) < self.order else ds.pop(0)
+        inv = 1.0 / run.sigmas[i]
+        self._affine(run, inv, [(-inv, d1)], d)
+        ds.append(d)
+        cur = min(i + 1, self.order)
+        coeffs = [linear_multistep_coeff(cur, run.sig_np, i, j) for j in range(cur)]
+        ops.lincomb(run.x, list(reversed(ds))[:cur], coeffs, run.x)

@@ -46,6 +46,43 @@ def test_reference_lambda_is_recognised_and_nothing_looser():
     assert _find_pair(two_statements) == (None, None)     # STORE_FAST: not the reference's expression
 
 
+def test_a_closure_that_says_anything_more_runs_as_written():
+    """The four forms an opcode whitelist let through (an extra keyword, an extra positional, the two attributes swapped, the model
+    reached through the denoiser): each would have been replaced by the fused loop's own `den(net, ...)`.  And an argument layout of
+    its own: *args, a default."""
+    self = _Engine()
+    extra_kw = lambda input, sigma, c: self.denoiser(self.model, input, sigma, c, extra=True)
+    extra_pos = lambda input, sigma, c: self.denoiser(self.model, input, sigma, c, 0.5)
+    swapped_callee = lambda input, sigma, c: self.model(self.denoiser, input, sigma, c)
+    through_denoiser = lambda input, sigma, c: self.denoiser.model(input, sigma, c)
+    star_args = lambda input, sigma, c, *args: self.denoiser(self.model, input, sigma, c)
+    default_arg = lambda input, sigma, c=None: self.denoiser(self.model, input, sigma, c)
+    for f in (extra_kw, extra_pos, swapped_callee, through_denoiser, star_args, default_arg):
+        assert not _is_reference_lambda(f)
+        assert _find_pair(f) == (None, None)
+
+
+def test_the_callers_names_do_not_matter():
+    self = engine = _Engine()
+    additional_model_inputs = kw = {}
+    renamed_args = lambda x, s, cond: self.denoiser(self.model, x, s, cond, **additional_model_inputs)
+    renamed_cells = lambda input, sigma, c: engine.denoiser(engine.model, input, sigma, c, **kw)
+    renamed_both_plain = lambda x, s, cond: engine.denoiser(engine.model, x, s, cond)
+    for f in (renamed_args, renamed_cells, renamed_both_plain):
+        assert _is_reference_lambda(f)
+        assert _find_pair(f) == (engine.denoiser, engine.model)
+
+
+def test_recognition_names_no_instruction():
+    """the closure is recognised by equality with the module's own templates: its text lists no opcode"""
+    import re
+    from ln3diff_amd.sgm import sampling
+    with open(sampling.__file__) as f:
+        text = f.read()
+    assert not re.search(r"""['"](LOAD_|CALL)""", text)
+    assert '_engine_closures' in text and not hasattr(sampling, '_REF_LAMBDA_OPS') and not hasattr(sampling, '_CALL_OPS')
+
+
 def test_explicit_routes():
     e = _Engine()
     assert _find_pair(e.denoiser.bind(e.model)) == (e.denoiser, e.model)
