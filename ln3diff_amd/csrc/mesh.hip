@@ -11,6 +11,7 @@
 #include "common.h"
 #include "../../include/ln3d.h"
 #include "../../include/ln3d_meshclean.h"
+#include "../../include/ext/ln3d_meshsimplify.h"
 #include "mc_table.h"
 
 __constant__ int kTet[6][4] = {{0, 1, 3, 7}, {0, 2, 3, 7}, {0, 2, 6, 7}, {0, 4, 6, 7}, {0, 4, 5, 7}, {0, 1, 5, 7}};
@@ -324,5 +325,106 @@ extern "C" int ln3d_mesh_gather(const float* verts, const int64_t* faces, const 
   if (!verts || !faces || !keep_v || !vprefix || !keep_f || !fprefix || !verts_out || !faces_out || !meshclean_sizes_ok(nf, nv)) return LN3D_ERR_BAD_ARG;
   hipLaunchKernelGGL(meshclean_gather_kernel, meshclean_grid(nv > nf ? nv : nf), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)verts, faces,
                      keep_v, vprefix, keep_f, fprefix, nv, nf, (uint32_t*)verts_out, faces_out);
+  return ln3d_check_launch();
+}
+
+// ------------------------------------------------------------------ mesh simplification (include/ext/ln3d_meshsimplify.h)
+// Vertex clustering.  Everything but the representatives is integer work; the representatives are sums in one stated order with correctly
+// rounded operations, so every output is unique by definition.  The sorts, the unique and the prefix sums between the stages are the caller's.
+#define SIMPLIFY_QMAX 2097151ll                          // 2^21 - 1: the largest lattice coordinate and cluster number a key holds
+
+__device__ __forceinline__ int64_t simplify_cell_of(float x, float o, float cell) {
+  const float q = floorf(__fdiv_rn(x - o, cell));
+  return (int64_t)fminf(fmaxf(q, 0.0f), (float)SIMPLIFY_QMAX);     // fmaxf(NaN, 0) = 0: total
+}
+
+__global__ void simplify_keys_kernel(const float* verts, int64_t nv, float ox, float oy, float oz, float cell, int64_t* key) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= nv) return;
+  key[v] = (simplify_cell_of(verts[3 * v], ox, cell) << 42) | (simplify_cell_of(verts[3 * v + 1], oy, cell) << 21) |
+           simplify_cell_of(verts[3 * v + 2], oz, cell);
+}
+
+// One thread per cluster walks its row of the CSR.  The adds are sequential on purpose (the order is the definition): three independent
+// chains per thread, nothing to reassociate and no product to contract.
+__global__ void simplify_mean_kernel(const float* verts, const int64_t* order, const int64_t* start, int64_t nc, float* rep) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nc) return;
+  const int64_t b = start[k], e = start[k + 1];
+  float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+  for (int64_t i = b; i < e; ++i) {                      // terminates: i counts up to e
+    const int64_t v = order[i];
+    sx += verts[3 * v]; sy += verts[3 * v + 1]; sz += verts[3 * v + 2];
+  }
+  const float n = (float)(e - b);
+  rep[3 * k] = __fdiv_rn(sx, n); rep[3 * k + 1] = __fdiv_rn(sy, n); rep[3 * k + 2] = __fdiv_rn(sz, n);
+}
+
+__global__ void simplify_faces_kernel(const int64_t* faces, int64_t nf, const int64_t* cluster, int64_t* cfaces, int64_t* fkey) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= nf) return;
+  const int64_t a = cluster[faces[3 * f]], b = cluster[faces[3 * f + 1]], c = cluster[faces[3 * f + 2]];
+  cfaces[3 * f] = a; cfaces[3 * f + 1] = b; cfaces[3 * f + 2] = c;
+  const int64_t lo = min(a, min(b, c)), hi = max(a, max(b, c)), mid = a + b + c - lo - hi;
+  fkey[f] = (a == b || b == c || a == c) ? -1ll : ((lo << 42) | (mid << 21) | hi);
+}
+
+__global__ void simplify_first_kernel(const int64_t* sorted_key, const int64_t* perm, int64_t nf, int32_t* keep_f) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nf) return;
+  const int64_t k = sorted_key[i];
+  keep_f[perm[i]] = (k != -1ll && (i == 0 || sorted_key[i - 1] != k)) ? 1 : 0;      // perm is a permutation: every element is written
+}
+
+__global__ void simplify_zero_kernel(int32_t* keep_v, int64_t nc) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < nc) keep_v[c] = 0;
+}
+
+__global__ void simplify_used_kernel(const int64_t* cfaces, const int32_t* keep_f, int64_t nf, int32_t* keep_v) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= nf || !keep_f[f]) return;
+  keep_v[cfaces[3 * f]] = 1; keep_v[cfaces[3 * f + 1]] = 1; keep_v[cfaces[3 * f + 2]] = 1;      // every writer stores the same value
+}
+
+static inline bool simplify_count_ok(int64_t n) { return n >= 1 && n <= 0x7fffffffll; }
+static inline bool simplify_finite(float x) { return x - x == 0.0f; }
+
+extern "C" int ln3d_simplify_keys(const float* verts, int64_t nv, float origin_x, float origin_y, float origin_z, float cell, int64_t* key,
+                                  void* stream) {
+  if (!verts || !key || !simplify_count_ok(nv) || !simplify_finite(cell) || !(cell > 0.0f) || !simplify_finite(origin_x) ||
+      !simplify_finite(origin_y) || !simplify_finite(origin_z)) return LN3D_ERR_BAD_ARG;
+  hipLaunchKernelGGL(simplify_keys_kernel, meshclean_grid(nv), dim3(256), 0, (hipStream_t)stream, verts, nv, origin_x, origin_y, origin_z, cell, key);
+  return ln3d_check_launch();
+}
+
+extern "C" int ln3d_simplify_mean(const float* verts, const int64_t* order, const int64_t* start, int64_t nv, int64_t nc, float* rep, void* stream) {
+  if (!verts || !order || !start || !rep || !simplify_count_ok(nv) || !simplify_count_ok(nc) || nc > nv) return LN3D_ERR_BAD_ARG;
+  if (nc > SIMPLIFY_QMAX + 1) return LN3D_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(simplify_mean_kernel, meshclean_grid(nc), dim3(256), 0, (hipStream_t)stream, verts, order, start, nc, rep);
+  return ln3d_check_launch();
+}
+
+extern "C" int ln3d_simplify_faces(const int64_t* faces, int64_t nf, const int64_t* cluster, int64_t nv, int64_t nc, int64_t* cfaces, int64_t* fkey,
+                                   void* stream) {
+  if (!faces || !cluster || !cfaces || !fkey || !simplify_count_ok(nf) || !simplify_count_ok(nv) || !simplify_count_ok(nc) || nc > nv)
+    return LN3D_ERR_BAD_ARG;
+  if (nc > SIMPLIFY_QMAX + 1) return LN3D_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(simplify_faces_kernel, meshclean_grid(nf), dim3(256), 0, (hipStream_t)stream, faces, nf, cluster, cfaces, fkey);
+  return ln3d_check_launch();
+}
+
+extern "C" int ln3d_simplify_first(const int64_t* sorted_key, const int64_t* perm, int64_t nf, int32_t* keep_f, void* stream) {
+  if (!sorted_key || !perm || !keep_f || !simplify_count_ok(nf)) return LN3D_ERR_BAD_ARG;
+  hipLaunchKernelGGL(simplify_first_kernel, meshclean_grid(nf), dim3(256), 0, (hipStream_t)stream, sorted_key, perm, nf, keep_f);
+  return ln3d_check_launch();
+}
+
+extern "C" int ln3d_simplify_used(const int64_t* cfaces, const int32_t* keep_f, int64_t nf, int64_t nc, int32_t* keep_v, void* stream) {
+  if (!cfaces || !keep_f || !keep_v || !simplify_count_ok(nf) || !simplify_count_ok(nc)) return LN3D_ERR_BAD_ARG;
+  if (nc > SIMPLIFY_QMAX + 1) return LN3D_ERR_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(simplify_zero_kernel, meshclean_grid(nc), dim3(256), 0, s, keep_v, nc);
+  hipLaunchKernelGGL(simplify_used_kernel, meshclean_grid(nf), dim3(256), 0, s, cfaces, keep_f, nf, keep_v);
   return ln3d_check_launch();
 }

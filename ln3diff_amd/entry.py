@@ -10,6 +10,7 @@ DINO conditioners (--clip_checkpoint ...) or is synthesised; weights come from -
 """
 import argparse
 import json
+import math
 import os
 
 import numpy as np
@@ -103,7 +104,8 @@ def create_argparser(objaverse=True):
         export_mesh_normals=False,           # `vn` records (the density field's outward normals) in the exported meshes; needs --export_mesh
         save_normal_maps=False,              # normal_sample{i}.npy [V,3,R,R]: world-space surface normal maps next to the frames
         mesh_keep='all',                     # all | largest: which connected components of an exported mesh are written; needs --export_mesh
-        mesh_min_faces=0)                    # components of an exported mesh with fewer faces are dropped (floaters); needs --export_mesh
+        mesh_min_faces=0,                    # components of an exported mesh with fewer faces are dropped (floaters); needs --export_mesh
+        mesh_simplify_cell=0.0)              # > 0: an exported mesh is simplified by vertex clustering on cells of that many grid units; needs --export_mesh
     d.update(_IGNORED_DEFAULTS)
     d.update({k: v[0] for k, v in _CHECKED.items()})
     ap = argparse.ArgumentParser(allow_abbrev=False)
@@ -162,6 +164,11 @@ def validate(args):
         raise SystemExit(f"--mesh_min_faces {mesh_min_faces}: expected a non-negative face count")
     if (mesh_keep != 'all' or mesh_min_faces != 0) and not args.export_mesh:
         raise SystemExit("--mesh_keep / --mesh_min_faces: there is no mesh to clean without --export_mesh true")
+    mesh_simplify_cell = getattr(args, 'mesh_simplify_cell', 0.0)
+    if not math.isfinite(mesh_simplify_cell) or mesh_simplify_cell < 0:
+        raise SystemExit(f"--mesh_simplify_cell {mesh_simplify_cell}: expected a finite, non-negative cell size in grid units (0: off)")
+    if mesh_simplify_cell != 0 and not args.export_mesh:
+        raise SystemExit("--mesh_simplify_cell: there is no mesh to simplify without --export_mesh true")
     if getattr(args, 'save_normal_maps', False):
         world = int(os.environ.get('WORLD_SIZE', '1'))
         if world > 1 and args.num_samples % world != 0:
@@ -466,7 +473,7 @@ def run(args, objaverse=None):
         for k in ('export_mesh_normals', 'save_normal_maps'):        # recorded when set: a run without them writes the args.json it always wrote
             if not meta[k]:
                 del meta[k]
-        for k, default in (('mesh_keep', 'all'), ('mesh_min_faces', 0)):
+        for k, default in (('mesh_keep', 'all'), ('mesh_min_faces', 0), ('mesh_simplify_cell', 0.0)):
             if meta[k] == default:
                 del meta[k]
         with open(os.path.join(args.logdir, 'args.json'), 'w') as f:
@@ -537,7 +544,8 @@ def run(args, objaverse=None):
         for i in range(hi - lo):
             path = os.path.join(args.logdir, f'mesh_sample{lo + i}.obj')
             mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path,
-                           normals=args.export_mesh_normals, keep=args.mesh_keep, min_faces=args.mesh_min_faces)
+                           normals=args.export_mesh_normals, keep=args.mesh_keep, min_faces=args.mesh_min_faces,
+                           simplify_cell=args.mesh_simplify_cell)
             if not os.path.exists(path):
                 mesh_err = f"mesh export of sample {lo + i} produced no file at {path}"
                 break

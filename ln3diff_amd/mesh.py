@@ -4,7 +4,9 @@ coloured by re-querying the tri-plane, rotated -90 degrees about x, written as .
 The surface is classic marching cubes (what the reference's `mcubes.marching_cubes` is; method='cubes', the default) or marching
 tetrahedra (method='tetra'); both run on the GPU in two passes around a prefix sum and weld vertices by grid-edge id.
 Opt-in clean-up (no reference counterpart; include/ln3d_meshclean.h): connected components of the welded mesh on the device, then only the
-components with at least `min_faces` faces, or only the largest one, are kept - before the colour query, so discarded vertices cost nothing."""
+components with at least `min_faces` faces, or only the largest one, are kept - before the colour query, so discarded vertices cost nothing.
+Opt-in simplification (no reference counterpart; include/ext/ln3d_meshsimplify.h): vertex clustering on a lattice of `simplify_cell` grid units,
+behind the clean-up and before the colour query."""
 import math
 
 import numpy as np
@@ -85,11 +87,106 @@ def clean_mesh(verts, faces, keep='all', min_faces=0):
     return verts_out, faces_out
 
 
+SIMPLIFY_MAX_CELLS = 1 << 21                  # lattice cells per axis, and clusters, that a 63-bit key holds (include/ext/ln3d_meshsimplify.h)
+
+
+def _simplify_cell(cell):
+    """cell as the float32 the kernels divide by; None / 0 -> 0.0 (off); ValueError when it is negative, not finite or not a number"""
+    if cell is None:
+        return 0.0
+    try:
+        c = float(np.float32(cell))
+    except (TypeError, ValueError):
+        raise ValueError(f"cell {cell!r}: expected a positive finite number, or 0 / None for no simplification") from None
+    if not math.isfinite(c) or c < 0 or (c == 0 and cell != 0):
+        raise ValueError(f"cell {cell!r}: expected a positive finite number (in float32), or 0 / None for no simplification")
+    return c
+
+
 @torch.no_grad()
-def extract_isosurface(sigma, thr=10.0, method='cubes', keep='all', min_faces=0):
+def simplify_mesh(verts, faces, cell, origin=None, check=True):
+    """verts [Nv,3] f32, faces [Nf,3] int64 (device) -> (verts', faces'): the mesh simplified by vertex clustering on a lattice of cubic cells
+    of edge `cell` whose corner is `origin` (three numbers; None: the per-axis minimum of verts).  The definition (include/ext/
+    ln3d_meshsimplify.h; every output is unique, nothing depends on scheduling):
+      - a vertex falls into cell q_a = floor((x_a - origin_a) / cell) per axis, in float32;
+      - every occupied cell becomes one vertex, the float32 mean of its members summed in ascending vertex index;
+      - a face whose corners fall into fewer than three cells is dropped; of the faces that name the same three cells (in any order or
+        winding) the one with the smallest index survives, with its own corner order;
+      - cells that no surviving face names are dropped; vertices come out in ascending (q_x, q_y, q_z), faces in their input order.
+    cell None or 0 returns its arguments and launches nothing; an empty input, or one of which nothing survives, gives empty tensors.
+    Raises ValueError on a bad dtype or shape, a face index out of range, a non-finite vertex or origin, a cell that is not finite or is
+    negative, and a mesh that spans 2^21 cells or more on an axis (or reaches below an explicit origin).
+    NOT promised: the result can have non-manifold edges and folded-over triangles, convex regions are pulled inward by O(cell^2 *
+    curvature), and components that come within a cell of each other can merge.  No quadric-error placement, no smoothing.
+    The five stages are kernels; torch supplies unique (clusters), two stable sorts (members per cluster, duplicate faces), the prefix sums
+    and the read-backs: the face-index check, the bounds and finiteness of verts, the cluster count (inside unique), the surviving counts.
+    check=False skips the face-index check and its read-back: for a caller whose faces index verts by construction (extract_isosurface, whose
+    faces come out of its own weld and clean-up); dtype and shape are still checked."""
+    cell = _simplify_cell(cell)
+    if cell == 0.0:
+        return verts, faces
+    if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"verts: expected a float32 [Nv, 3] tensor, got {verts.dtype} {tuple(verts.shape)}")
+    if origin is not None:
+        origin = np.asarray(origin, dtype=np.float32).reshape(-1)
+        if origin.shape != (3,) or not np.isfinite(origin).all():
+            raise ValueError(f"origin {origin!r}: expected three finite numbers")
+    dev = verts.device
+    empty = lambda: (torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.long, device=dev))
+    nv, nf = verts.shape[0], faces.shape[0]
+    verts, faces = verts.contiguous(), faces.contiguous()
+    if check:
+        ops.check_faces(faces, nv)
+    elif faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces: expected an int64 [Nf, 3] tensor, got {faces.dtype} {tuple(faces.shape)}")
+    if nv == 0 or nf == 0:
+        return empty()
+    box = torch.cat([verts.amin(0), verts.amax(0), torch.isfinite(verts).all().float().reshape(1)]).cpu().numpy()      # one read-back
+    if not box[6]:
+        raise ValueError("verts: a coordinate is not finite")
+    lo, hi = box[:3], box[3:6]
+    if origin is None:
+        origin = lo
+    c32 = np.float32(cell)
+    with np.errstate(over='ignore', invalid='ignore'):
+        qlo, qhi = np.floor((lo - origin) / c32), np.floor((hi - origin) / c32)            # the kernel's arithmetic, monotone in x
+    if not (qlo >= 0).all() or not (qhi < SIMPLIFY_MAX_CELLS).all():
+        raise ValueError(f"verts span lattice cells {qlo.tolist()} to {qhi.tolist()} at cell {cell}: every axis must stay in [0, 2^21)")
+    key = torch.empty(nv, dtype=torch.int64, device=dev)
+    ops.simplify_keys(verts, origin, cell, key)
+    uniq, cluster, members = torch.unique(key, return_inverse=True, return_counts=True)
+    nc = uniq.shape[0]
+    order = torch.sort(cluster, stable=True)[1]
+    start = torch.zeros(nc + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(members, 0, out=start[1:])
+    rep = torch.empty(nc, 3, device=dev)
+    ops.simplify_mean(verts, order, start, rep, check=False)
+    cfaces = torch.empty(nf, 3, dtype=torch.int64, device=dev)
+    fkey = torch.empty(nf, dtype=torch.int64, device=dev)
+    ops.simplify_faces(faces, cluster, nc, cfaces, fkey, check=False)
+    sorted_key, perm = torch.sort(fkey, stable=True)
+    keep_f = torch.empty(nf, dtype=torch.int32, device=dev)
+    ops.simplify_first(sorted_key, perm, keep_f, check=False)
+    keep_v = torch.empty(nc, dtype=torch.int32, device=dev)
+    ops.simplify_used(cfaces, keep_f, keep_v, check=False)
+    vpre, fpre = torch.cumsum(keep_v.long(), 0), torch.cumsum(keep_f.long(), 0)
+    nv_out, nf_out = torch.stack([vpre[-1], fpre[-1]]).tolist()
+    if nf_out == 0:
+        return empty()
+    verts_out = torch.empty(nv_out, 3, device=dev)
+    faces_out = torch.empty(nf_out, 3, dtype=torch.int64, device=dev)
+    ops.mesh_gather(rep, cfaces, keep_v, vpre, keep_f, fpre, verts_out, faces_out, check=False)
+    return verts_out, faces_out
+
+
+@torch.no_grad()
+def extract_isosurface(sigma, thr=10.0, method='cubes', keep='all', min_faces=0, simplify_cell=0.0):
     """sigma [G,G,G] f32 device -> (verts [Nv,3] in grid coordinates, faces [Nf,3] int64).  Faces keep the emission order
-    (cells in x-major order, the case table's triangle order inside a cell).  keep / min_faces (opt-in): clean_mesh on the welded result."""
+    (cells in x-major order, the case table's triangle order inside a cell).  keep / min_faces (opt-in): clean_mesh on the welded result.
+    simplify_cell (opt-in, in grid units): simplify_mesh with origin (0, 0, 0) after the weld and after the clean-up, so floaters are judged
+    on the full-density mesh."""
     keep, min_faces = _clean_args(keep, min_faces)
+    simplify_cell = _simplify_cell(simplify_cell)
     count, emit = {'cubes': (ops.mcubes_count, ops.mcubes_emit), 'tetra': (ops.mesh_count, ops.mesh_emit)}[method]
     G = sigma.shape[0]
     dev = sigma.device
@@ -109,7 +206,8 @@ def extract_isosurface(sigma, thr=10.0, method='cubes', keep='all', min_faces=0)
     verts[inv] = pos                                                   # identical bits for every copy of a vertex
     faces = inv.view(ntri, 3)
     ok = (faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])
-    return clean_mesh(verts, faces[ok], keep, min_faces)
+    verts, faces = clean_mesh(verts, faces[ok], keep, min_faces)
+    return simplify_mesh(verts, faces, simplify_cell, (0.0, 0.0, 0.0), check=False)      # faces are the weld's own: in range by construction
 
 
 def rotation_matrix_x(deg):
@@ -137,7 +235,7 @@ def write_obj(path, v, f, c, n=None):
 
 @torch.no_grad()
 def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes', normals=False,
-                   keep='all', min_faces=0):
+                   keep='all', min_faces=0, simplify_cell=0.0):
     """nsr/train_util_diffusion.py:221-244: iso-surface of the sigma grid at `thr`, vertices mapped to the +-0.45 box, coloured
     by re-querying the tri-plane at the vertices (forward_points), rotated -90 degrees about x.
     Returns (verts [Nv,3] float32 numpy, faces [Nf,3] int64 numpy, colors [Nv,3] uint8 numpy); writes `path` when given.
@@ -145,9 +243,11 @@ def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0,
     (forward_points(with_grad=True), evaluated in box coordinates and rotated with the mesh); the return value is then the 4-tuple
     (verts, faces, colors, vn [Nv,3] float32 numpy) and the .obj carries `vn` records.
     keep / min_faces (opt-in; no reference counterpart): clean_mesh right after the weld, so only the surviving components are coloured (and
-    given normals) and written; what survives has the bits it has in the uncleaned mesh.  Nothing surviving writes an .obj with no records."""
+    given normals) and written; what survives has the bits it has in the uncleaned mesh.  Nothing surviving writes an .obj with no records.
+    simplify_cell (opt-in, in grid units; no reference counterpart): simplify_mesh behind the clean-up and before the query, so colours and `vn`
+    are the field's values AT THE NEW VERTICES and discarded vertices cost nothing.  See simplify_mesh for what clustering does not promise."""
     sigma = sigma.reshape(grid_size, grid_size, grid_size)
-    verts, faces = extract_isosurface(sigma, thr, method, keep, min_faces)
+    verts, faces = extract_isosurface(sigma, thr, method, keep, min_faces, simplify_cell)
     vtx = (verts / (grid_size - 1) * 2 - 1) * 0.45                       # g-objaverse scale
     pcl = dec_out.get('planes_channel_last')
     if pcl is None:
@@ -164,11 +264,11 @@ def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0,
 
 
 @torch.no_grad()
-def export_mesh(decoder, dec_out, path, grid_size=192, thr=10.0, sample_index=0, normals=False, keep='all', min_faces=0):
+def export_mesh(decoder, dec_out, path, grid_size=192, thr=10.0, sample_index=0, normals=False, keep='all', min_faces=0, simplify_cell=0.0):
     """decoder: the VAE decoder module; dec_out: its vit_decode_postprocess dict.  Writes `path` (.obj), with `vn` records when normals;
-    keep / min_faces: mesh_from_grid's."""
+    keep / min_faces / simplify_cell: mesh_from_grid's."""
     pcl = dec_out['planes_channel_last'][sample_index:sample_index + 1]
     grid = decoder.triplane_decode_grid({'planes_channel_last': pcl}, grid_size)
     v, f = mesh_from_grid(decoder, {'planes_channel_last': pcl}, grid['sigma'][0], grid_size, thr, 0, path, normals=normals, keep=keep,
-                          min_faces=min_faces)[:2]
+                          min_faces=min_faces, simplify_cell=simplify_cell)[:2]
     return v.shape[0], f.shape[0]

@@ -385,6 +385,87 @@ def mesh_gather(verts, faces, keep_v, vprefix, keep_f, fprefix, verts_out, faces
                                      _p(verts_out), _p(faces_out), _stream()), "mesh_gather")
 
 
+def check_index(t, n, what, shape=None):
+    """include/ext/ln3d_meshsimplify.h takes the values of its index arrays in [0, n) as a precondition: a contiguous int64 tensor (of
+    `shape`, when given) whose values all lie in that range, or ValueError (one read-back of the smallest and largest value)."""
+    if t.dtype != torch.int64 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{what}: expected a contiguous int64 tensor" + (f" of shape {tuple(shape)}" if shape is not None else "")
+                         + f", got {t.dtype} {tuple(t.shape)}")
+    if t.numel():
+        lo, hi = (int(x) for x in torch.aminmax(t))
+        if lo < 0 or hi >= n:
+            raise ValueError(f"{what}: values span [{lo}, {hi}], outside [0, {n})")
+    if not t.is_cuda:
+        raise RuntimeError(_NEED_DEVICE)
+
+
+def _buffer(t, dtype, shape, what):
+    """the kernels of include/ext/ln3d_meshsimplify.h write whole rows of the buffers they are given: a buffer of another dtype, a shorter one
+    or a strided view would be written past its end, so it is refused here (metadata only: no read-back)"""
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+
+def simplify_keys(verts, origin, cell, key):
+    """key [nv] int64 <- the packed lattice cell of every vertex (include/ext/ln3d_meshsimplify.h); verts [nv,3] f32; origin: three floats.
+    There is no index to check: the kernel clamps."""
+    _buffer(verts, torch.float32, (verts.shape[0], 3), "verts")
+    _buffer(key, torch.int64, (verts.shape[0],), "key")
+    ox, oy, oz = (float(o) for o in origin)
+    L.check(L.lib().ln3d_simplify_keys(_p(verts), verts.shape[0], ox, oy, oz, float(cell), _p(key), _stream()), "simplify_keys")
+
+
+def simplify_mean(verts, order, start, rep, check=True):
+    """rep [nc,3] f32 <- the mean of every cluster's members, summed in the order of its row of the CSR (order [nv], start [nc + 1] int64).
+    check=False: the caller has made order and start itself (a stable sort and the prefix sum of its counts)."""
+    nv, nc = verts.shape[0], start.shape[0] - 1
+    _buffer(verts, torch.float32, (nv, 3), "verts")
+    _buffer(order, torch.int64, (nv,), "order")
+    _buffer(start, torch.int64, (nc + 1,), "start")
+    _buffer(rep, torch.float32, (nc, 3), "rep")
+    if check:
+        check_index(order, nv, "order", (nv,))
+        check_index(start, nv + 1, "start")
+        if nc >= 1 and (int(start[0]) != 0 or int(start[-1]) != nv or bool((start[1:] < start[:-1]).any())):
+            raise ValueError("start: expected an ascending row-pointer array from 0 to nv")
+    L.check(L.lib().ln3d_simplify_mean(_p(verts), _p(order), _p(start), nv, nc, _p(rep), _stream()), "simplify_mean")
+
+
+def simplify_faces(faces, cluster, nc, cfaces, fkey, check=True):
+    """cfaces [nf,3] int64 <- cluster[faces]; fkey [nf] int64 <- -1 for a collapsed face, else its ascending corners packed 21 bits each"""
+    nv, nf = cluster.shape[0], faces.shape[0]
+    _buffer(faces, torch.int64, (nf, 3), "faces")
+    _buffer(cluster, torch.int64, (nv,), "cluster")
+    _buffer(cfaces, torch.int64, (nf, 3), "cfaces")
+    _buffer(fkey, torch.int64, (nf,), "fkey")
+    if check:
+        check_index(cluster, nc, "cluster")
+        check_faces(faces, nv)
+    L.check(L.lib().ln3d_simplify_faces(_p(faces), faces.shape[0], _p(cluster), nv, nc, _p(cfaces), _p(fkey), _stream()), "simplify_faces")
+
+
+def simplify_first(sorted_key, perm, keep_f, check=True):
+    """keep_f [nf] int32 <- 1 at the original index of every run head of the stably sorted keys whose key is not -1, 0 elsewhere"""
+    nf = sorted_key.shape[0]
+    _buffer(sorted_key, torch.int64, (nf,), "sorted_key")
+    _buffer(perm, torch.int64, (nf,), "perm")
+    _buffer(keep_f, torch.int32, (nf,), "keep_f")
+    if check:
+        check_index(perm, nf, "perm", (nf,))
+    L.check(L.lib().ln3d_simplify_first(_p(sorted_key), _p(perm), nf, _p(keep_f), _stream()), "simplify_first")
+
+
+def simplify_used(cfaces, keep_f, keep_v, check=True):
+    """keep_v [nc] int32 <- 1 for the clusters that a kept face names, 0 for the others"""
+    nc, nf = keep_v.shape[0], cfaces.shape[0]
+    _buffer(cfaces, torch.int64, (nf, 3), "cfaces")
+    _buffer(keep_f, torch.int32, (nf,), "keep_f")
+    _buffer(keep_v, torch.int32, (nc,), "keep_v")
+    if check:
+        check_faces(cfaces, nc)
+    L.check(L.lib().ln3d_simplify_used(_p(cfaces), _p(keep_f), cfaces.shape[0], nc, _p(keep_v), _stream()), "simplify_used")
+
+
 def lincomb(y, ks, cs, out):
     n = len(ks)
     arr_k = (C.c_void_p * n)(*[_p(k) for k in ks])
