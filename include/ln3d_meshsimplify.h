@@ -3,8 +3,8 @@
  * There is no reference counterpart (the reference writes the level set at the grid's full density and leaves reduction to trimesh or
  * MeshLab on the CPU); everything here is opt-in and changes no other output.  Same conventions as ln3d_meshclean.h (caller-owned device
  * pointers, stream as void*, 0 or a negative LN3D_ERR_* code, asynchronous on the stream, no allocation, no device-to-host read, a launch
- * count that does not depend on the data).  The entry points are an addition to ABI 10 of ln3d.h, which still describes every symbol it
- * described; they are bound from _lib.EXT_PROTOTYPES.
+ * count that does not depend on the data).  The entry points belong to ABI 10 of ln3d.h and, like every other export, are bound from
+ * _lib.PROTOTYPES.
  *
  * Arguments are checked before anything touches the device: a null buffer, a count (nv, nf, nc) below 1 or above 2^31 - 1, nc > nv, a
  * cell that is not finite or not > 0, or a non-finite origin returns LN3D_ERR_BAD_ARG; nc > 2^21 (three cluster numbers no longer fit
@@ -25,7 +25,7 @@
 #ifndef LN3D_MESHSIMPLIFY_H
 #define LN3D_MESHSIMPLIFY_H
 #include <stdint.h>
-#include "../ln3d.h"
+#include "ln3d.h"
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -1,5 +1,5 @@
 """ctypes binding of libln3d_hip.so (the C ABI of include/ln3d.h, include/ln3d_encoder.h, include/ln3d_shapenet.h, include/ln3d_mx.h, include/ln3d_ffhq.h,
-include/ln3d_planes16.h, include/ln3d_normals.h and include/ln3d_meshclean.h, plus the additions of include/ext/ln3d_meshsimplify.h in EXT_PROTOTYPES).
+include/ln3d_planes16.h, include/ln3d_normals.h, include/ln3d_meshclean.h and include/ln3d_meshsimplify.h).
 
 Every export is declared once, in PROTOTYPES: name -> (restype, argtypes), which lib() applies, so a call site passes plain Python values
 and a value of the wrong kind is a ctypes.ArgumentError.  One rule maps a C parameter to its argtype:
@@ -168,19 +168,14 @@ PROTOTYPES = {
     "ln3d_mesh_component_counts": _int(vp, i64, vp, i64, vp, vp, vp, vp),
     "ln3d_mesh_mark": _int(vp, i64, vp, vp, i64, i64, i32, vp, vp, vp, vp),
     "ln3d_mesh_gather": _int(vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp),
-}
-SYMBOLS = list(PROTOTYPES)
-
-# Additions to ABI 10 declared under include/ext/ (tests/test_abi_ext_cpu.py holds this table to those headers by the same rule).  They use
-# no struct and change no row above, so ABI_VERSION still describes every symbol it described.
-EXT_PROTOTYPES = {
-    # include/ext/ln3d_meshsimplify.h (mesh simplification by vertex clustering)
+    # include/ln3d_meshsimplify.h (mesh simplification by vertex clustering)
     "ln3d_simplify_keys": _int(vp, i64, f32, f32, f32, f32, vp, vp),
     "ln3d_simplify_mean": _int(vp, vp, vp, i64, i64, vp, vp),
     "ln3d_simplify_faces": _int(vp, i64, vp, i64, i64, vp, vp, vp),
     "ln3d_simplify_first": _int(vp, vp, i64, vp, vp),
     "ln3d_simplify_used": _int(vp, vp, i64, i64, vp, vp),
 }
+SYMBOLS = list(PROTOTYPES)
 
 _lib = None
 
@@ -199,7 +194,7 @@ def lib():
         # fail with "HIP kernel launch failed".
         import torch  # noqa: F401
         _lib = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(EXT_PROTOTYPES.items()):
+        for name, (restype, argtypes) in PROTOTYPES.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = restype, argtypes
     return _lib
@@ -207,7 +202,7 @@ def lib():
 
 def check_symbols():
     L = lib()
-    missing = [s for s in SYMBOLS + list(EXT_PROTOTYPES) if not hasattr(L, s)]
+    missing = [s for s in PROTOTYPES if not hasattr(L, s)]
     if missing:
         raise RuntimeError(f"libln3d_hip.so lacks symbols: {missing}")
     assert L.ln3d_abi_version() == ABI_VERSION

@@ -11,7 +11,7 @@
 #include "common.h"
 #include "../../include/ln3d.h"
 #include "../../include/ln3d_meshclean.h"
-#include "../../include/ext/ln3d_meshsimplify.h"
+#include "../../include/ln3d_meshsimplify.h"
 #include "mc_table.h"
 
 __constant__ int kTet[6][4] = {{0, 1, 3, 7}, {0, 2, 3, 7}, {0, 2, 6, 7}, {0, 4, 6, 7}, {0, 4, 5, 7}, {0, 1, 5, 7}};
@@ -143,34 +143,29 @@ __global__ void mcubes_emit_kernel(MeshP p, int64_t ncell, const int64_t* offset
     }
 }
 
-extern "C" int ln3d_mcubes_count(const float* sigma, int G, float thr, int32_t* counts, void* stream) {
-  if (!sigma || !counts || G < 2 || G > LN3D_MESH_MAX_GRID) return LN3D_ERR_BAD_ARG;
-  MeshP p{sigma, G, thr};
+static inline dim3 grid_1d(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }                          // one thread per element, blocks of 256
+static inline bool count_ok(int64_t n) { return n >= 1 && n <= 0x7fffffffll; }                               // a vertex, face or cluster count
+
+// The four iso-surface passes: one thread per cell of a grid with 2 <= G <= LN3D_MESH_MAX_GRID; `out` are the pass's own buffers.
+template <typename... Out>
+static int mesh_pass(void (*kernel)(MeshP, int64_t, Out...), const float* sigma, int G, float thr, void* stream, Out... out) {
+  if (!sigma || !(out && ...) || G < 2 || G > LN3D_MESH_MAX_GRID) return LN3D_ERR_BAD_ARG;
   const int64_t ncell = (int64_t)(G - 1) * (G - 1) * (G - 1);
-  hipLaunchKernelGGL(mcubes_count_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, ncell, counts);
-  return ln3d_check_launch();
-}
-extern "C" int ln3d_mcubes_emit(const float* sigma, int G, float thr, const int64_t* offsets, float* tri_pos, int64_t* tri_key, void* stream) {
-  if (!sigma || !offsets || !tri_pos || !tri_key || G < 2 || G > LN3D_MESH_MAX_GRID) return LN3D_ERR_BAD_ARG;
-  MeshP p{sigma, G, thr};
-  const int64_t ncell = (int64_t)(G - 1) * (G - 1) * (G - 1);
-  hipLaunchKernelGGL(mcubes_emit_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, ncell, offsets, tri_pos, tri_key);
+  hipLaunchKernelGGL(kernel, grid_1d(ncell), dim3(256), 0, (hipStream_t)stream, MeshP{sigma, G, thr}, ncell, out...);
   return ln3d_check_launch();
 }
 
+extern "C" int ln3d_mcubes_count(const float* sigma, int G, float thr, int32_t* counts, void* stream) {
+  return mesh_pass(mcubes_count_kernel, sigma, G, thr, stream, counts);
+}
+extern "C" int ln3d_mcubes_emit(const float* sigma, int G, float thr, const int64_t* offsets, float* tri_pos, int64_t* tri_key, void* stream) {
+  return mesh_pass(mcubes_emit_kernel, sigma, G, thr, stream, offsets, tri_pos, tri_key);
+}
 extern "C" int ln3d_mesh_count(const float* sigma, int G, float thr, int32_t* counts, void* stream) {
-  if (!sigma || !counts || G < 2 || G > LN3D_MESH_MAX_GRID) return LN3D_ERR_BAD_ARG;
-  MeshP p{sigma, G, thr};
-  const int64_t ncell = (int64_t)(G - 1) * (G - 1) * (G - 1);
-  hipLaunchKernelGGL(mesh_count_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, ncell, counts);
-  return ln3d_check_launch();
+  return mesh_pass(mesh_count_kernel, sigma, G, thr, stream, counts);
 }
 extern "C" int ln3d_mesh_emit(const float* sigma, int G, float thr, const int64_t* offsets, float* tri_pos, int64_t* tri_key, void* stream) {
-  if (!sigma || !offsets || !tri_pos || !tri_key || G < 2 || G > LN3D_MESH_MAX_GRID) return LN3D_ERR_BAD_ARG;
-  MeshP p{sigma, G, thr};
-  const int64_t ncell = (int64_t)(G - 1) * (G - 1) * (G - 1);
-  hipLaunchKernelGGL(mesh_emit_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, ncell, offsets, tri_pos, tri_key);
-  return ln3d_check_launch();
+  return mesh_pass(mesh_emit_kernel, sigma, G, thr, stream, offsets, tri_pos, tri_key);
 }
 
 // ------------------------------------------------------------------ mesh clean-up (include/ln3d_meshclean.h)
@@ -290,15 +285,14 @@ __global__ void meshclean_gather_kernel(const uint32_t* verts, const int64_t* fa
   }
 }
 
-static inline bool meshclean_sizes_ok(int64_t nf, int64_t nv) { return nv >= 1 && nv <= 0x7fffffffll && nf >= 1 && nf <= 0x7fffffffll; }
-static inline dim3 meshclean_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+static inline bool meshclean_sizes_ok(int64_t nf, int64_t nv) { return count_ok(nv) && count_ok(nf); }
 
 extern "C" int ln3d_mesh_components(const int64_t* faces, int64_t nf, int64_t nv, int32_t* label, void* stream) {
   if (!faces || !label || !meshclean_sizes_ok(nf, nv)) return LN3D_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(meshclean_init_kernel, meshclean_grid(nv), dim3(256), 0, s, label, nv);
-  hipLaunchKernelGGL(meshclean_hook_kernel, meshclean_grid(nf), dim3(256), 0, s, faces, nf, label);
-  hipLaunchKernelGGL(meshclean_flatten_kernel, meshclean_grid(nv), dim3(256), 0, s, label, nv);
+  hipLaunchKernelGGL(meshclean_init_kernel, grid_1d(nv), dim3(256), 0, s, label, nv);
+  hipLaunchKernelGGL(meshclean_hook_kernel, grid_1d(nf), dim3(256), 0, s, faces, nf, label);
+  hipLaunchKernelGGL(meshclean_flatten_kernel, grid_1d(nv), dim3(256), 0, s, label, nv);
   return ln3d_check_launch();
 }
 
@@ -306,16 +300,16 @@ extern "C" int ln3d_mesh_component_counts(const int64_t* faces, int64_t nf, cons
                                           uint64_t* best, void* stream) {
   if (!faces || !label || !nvert || !nface || !best || !meshclean_sizes_ok(nf, nv)) return LN3D_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(meshclean_zero_kernel, meshclean_grid(nv), dim3(256), 0, s, nvert, nface, (unsigned long long*)best, nv);
-  hipLaunchKernelGGL(meshclean_count_kernel, meshclean_grid(nv > nf ? nv : nf), dim3(256), 0, s, faces, nf, label, nv, nvert, nface);
-  hipLaunchKernelGGL(meshclean_best_kernel, meshclean_grid(nv), dim3(256), 0, s, label, nface, nv, (unsigned long long*)best);
+  hipLaunchKernelGGL(meshclean_zero_kernel, grid_1d(nv), dim3(256), 0, s, nvert, nface, (unsigned long long*)best, nv);
+  hipLaunchKernelGGL(meshclean_count_kernel, grid_1d(nv > nf ? nv : nf), dim3(256), 0, s, faces, nf, label, nv, nvert, nface);
+  hipLaunchKernelGGL(meshclean_best_kernel, grid_1d(nv), dim3(256), 0, s, label, nface, nv, (unsigned long long*)best);
   return ln3d_check_launch();
 }
 
 extern "C" int ln3d_mesh_mark(const int64_t* faces, int64_t nf, const int32_t* label, const int32_t* nface, int64_t nv, int64_t min_faces,
                               int largest_only, const uint64_t* best, int32_t* keep_v, int32_t* keep_f, void* stream) {
   if (!faces || !label || !nface || !best || !keep_v || !keep_f || !meshclean_sizes_ok(nf, nv) || min_faces < 0) return LN3D_ERR_BAD_ARG;
-  hipLaunchKernelGGL(meshclean_mark_kernel, meshclean_grid(nv > nf ? nv : nf), dim3(256), 0, (hipStream_t)stream, faces, nf, label, nface, nv,
+  hipLaunchKernelGGL(meshclean_mark_kernel, grid_1d(nv > nf ? nv : nf), dim3(256), 0, (hipStream_t)stream, faces, nf, label, nface, nv,
                      min_faces, largest_only, (const unsigned long long*)best, keep_v, keep_f);
   return ln3d_check_launch();
 }
@@ -323,12 +317,12 @@ extern "C" int ln3d_mesh_mark(const int64_t* faces, int64_t nf, const int32_t* l
 extern "C" int ln3d_mesh_gather(const float* verts, const int64_t* faces, const int32_t* keep_v, const int64_t* vprefix, const int32_t* keep_f,
                                 const int64_t* fprefix, int64_t nv, int64_t nf, float* verts_out, int64_t* faces_out, void* stream) {
   if (!verts || !faces || !keep_v || !vprefix || !keep_f || !fprefix || !verts_out || !faces_out || !meshclean_sizes_ok(nf, nv)) return LN3D_ERR_BAD_ARG;
-  hipLaunchKernelGGL(meshclean_gather_kernel, meshclean_grid(nv > nf ? nv : nf), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)verts, faces,
+  hipLaunchKernelGGL(meshclean_gather_kernel, grid_1d(nv > nf ? nv : nf), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)verts, faces,
                      keep_v, vprefix, keep_f, fprefix, nv, nf, (uint32_t*)verts_out, faces_out);
   return ln3d_check_launch();
 }
 
-// ------------------------------------------------------------------ mesh simplification (include/ext/ln3d_meshsimplify.h)
+// ------------------------------------------------------------------ mesh simplification (include/ln3d_meshsimplify.h)
 // Vertex clustering.  Everything but the representatives is integer work; the representatives are sums in one stated order with correctly
 // rounded operations, so every output is unique by definition.  The sorts, the unique and the prefix sums between the stages are the caller's.
 #define SIMPLIFY_QMAX 2097151ll                          // 2^21 - 1: the largest lattice coordinate and cluster number a key holds
@@ -387,44 +381,43 @@ __global__ void simplify_used_kernel(const int64_t* cfaces, const int32_t* keep_
   keep_v[cfaces[3 * f]] = 1; keep_v[cfaces[3 * f + 1]] = 1; keep_v[cfaces[3 * f + 2]] = 1;      // every writer stores the same value
 }
 
-static inline bool simplify_count_ok(int64_t n) { return n >= 1 && n <= 0x7fffffffll; }
 static inline bool simplify_finite(float x) { return x - x == 0.0f; }
 
 extern "C" int ln3d_simplify_keys(const float* verts, int64_t nv, float origin_x, float origin_y, float origin_z, float cell, int64_t* key,
                                   void* stream) {
-  if (!verts || !key || !simplify_count_ok(nv) || !simplify_finite(cell) || !(cell > 0.0f) || !simplify_finite(origin_x) ||
+  if (!verts || !key || !count_ok(nv) || !simplify_finite(cell) || !(cell > 0.0f) || !simplify_finite(origin_x) ||
       !simplify_finite(origin_y) || !simplify_finite(origin_z)) return LN3D_ERR_BAD_ARG;
-  hipLaunchKernelGGL(simplify_keys_kernel, meshclean_grid(nv), dim3(256), 0, (hipStream_t)stream, verts, nv, origin_x, origin_y, origin_z, cell, key);
+  hipLaunchKernelGGL(simplify_keys_kernel, grid_1d(nv), dim3(256), 0, (hipStream_t)stream, verts, nv, origin_x, origin_y, origin_z, cell, key);
   return ln3d_check_launch();
 }
 
 extern "C" int ln3d_simplify_mean(const float* verts, const int64_t* order, const int64_t* start, int64_t nv, int64_t nc, float* rep, void* stream) {
-  if (!verts || !order || !start || !rep || !simplify_count_ok(nv) || !simplify_count_ok(nc) || nc > nv) return LN3D_ERR_BAD_ARG;
+  if (!verts || !order || !start || !rep || !count_ok(nv) || !count_ok(nc) || nc > nv) return LN3D_ERR_BAD_ARG;
   if (nc > SIMPLIFY_QMAX + 1) return LN3D_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(simplify_mean_kernel, meshclean_grid(nc), dim3(256), 0, (hipStream_t)stream, verts, order, start, nc, rep);
+  hipLaunchKernelGGL(simplify_mean_kernel, grid_1d(nc), dim3(256), 0, (hipStream_t)stream, verts, order, start, nc, rep);
   return ln3d_check_launch();
 }
 
 extern "C" int ln3d_simplify_faces(const int64_t* faces, int64_t nf, const int64_t* cluster, int64_t nv, int64_t nc, int64_t* cfaces, int64_t* fkey,
                                    void* stream) {
-  if (!faces || !cluster || !cfaces || !fkey || !simplify_count_ok(nf) || !simplify_count_ok(nv) || !simplify_count_ok(nc) || nc > nv)
+  if (!faces || !cluster || !cfaces || !fkey || !count_ok(nf) || !count_ok(nv) || !count_ok(nc) || nc > nv)
     return LN3D_ERR_BAD_ARG;
   if (nc > SIMPLIFY_QMAX + 1) return LN3D_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(simplify_faces_kernel, meshclean_grid(nf), dim3(256), 0, (hipStream_t)stream, faces, nf, cluster, cfaces, fkey);
+  hipLaunchKernelGGL(simplify_faces_kernel, grid_1d(nf), dim3(256), 0, (hipStream_t)stream, faces, nf, cluster, cfaces, fkey);
   return ln3d_check_launch();
 }
 
 extern "C" int ln3d_simplify_first(const int64_t* sorted_key, const int64_t* perm, int64_t nf, int32_t* keep_f, void* stream) {
-  if (!sorted_key || !perm || !keep_f || !simplify_count_ok(nf)) return LN3D_ERR_BAD_ARG;
-  hipLaunchKernelGGL(simplify_first_kernel, meshclean_grid(nf), dim3(256), 0, (hipStream_t)stream, sorted_key, perm, nf, keep_f);
+  if (!sorted_key || !perm || !keep_f || !count_ok(nf)) return LN3D_ERR_BAD_ARG;
+  hipLaunchKernelGGL(simplify_first_kernel, grid_1d(nf), dim3(256), 0, (hipStream_t)stream, sorted_key, perm, nf, keep_f);
   return ln3d_check_launch();
 }
 
 extern "C" int ln3d_simplify_used(const int64_t* cfaces, const int32_t* keep_f, int64_t nf, int64_t nc, int32_t* keep_v, void* stream) {
-  if (!cfaces || !keep_f || !keep_v || !simplify_count_ok(nf) || !simplify_count_ok(nc)) return LN3D_ERR_BAD_ARG;
+  if (!cfaces || !keep_f || !keep_v || !count_ok(nf) || !count_ok(nc)) return LN3D_ERR_BAD_ARG;
   if (nc > SIMPLIFY_QMAX + 1) return LN3D_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(simplify_zero_kernel, meshclean_grid(nc), dim3(256), 0, s, keep_v, nc);
-  hipLaunchKernelGGL(simplify_used_kernel, meshclean_grid(nf), dim3(256), 0, s, cfaces, keep_f, nf, keep_v);
+  hipLaunchKernelGGL(simplify_zero_kernel, grid_1d(nc), dim3(256), 0, s, keep_v, nc);
+  hipLaunchKernelGGL(simplify_used_kernel, grid_1d(nf), dim3(256), 0, s, cfaces, keep_f, nf, keep_v);
   return ln3d_check_launch();
 }

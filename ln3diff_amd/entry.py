@@ -10,11 +10,12 @@ DINO conditioners (--clip_checkpoint ...) or is synthesised; weights come from -
 """
 import argparse
 import json
-import math
 import os
 
 import numpy as np
 import torch
+
+from .mesh import MeshPost, _clean_args, _simplify_cell, mesh_from_grid
 
 # --trainer_name -> engine (scripts/vit_triplane_diffusion_sample_objaverse.py:135-142, scripts/vit_triplane_diffusion_sample.py:236-242)
 TRAINERS = {
@@ -74,6 +75,12 @@ def str2bool(v):
     raise argparse.ArgumentTypeError('boolean value expected')
 
 
+# the flags of mesh.MeshPost's fields, in field order, with its defaults (no reference counterpart; all need --export_mesh true): `vn` records
+# with the density field's outward normals; all | largest: which connected components are written; components with fewer faces are dropped
+# (floaters); > 0: the mesh is simplified by vertex clustering on cells of that many grid units
+_MESH_FLAGS = dict(zip(('export_mesh_normals', 'mesh_keep', 'mesh_min_faces', 'mesh_simplify_cell'), MeshPost._field_defaults.values()))
+
+
 def add_dict_to_argparser(ap, d):            # guided_diffusion/script_util.py:712-722
     for k, v in d.items():
         t = str if v is None else (str2bool if isinstance(v, bool) else type(v))
@@ -101,17 +108,19 @@ def create_argparser(objaverse=True):
         ray_start=0.6, ray_end=1.8,          # nsr/script_util.py triplane_decoder_defaults; read by the ShapeNet decoder class only
         dit_precision='bf16',                # matmul precision of the T23D DiT (no reference counterpart): bf16 or the opt-in mxfp8
         plane_precision='fp32',              # texel storage of the renderer's tri-planes (no reference counterpart): fp32 or the opt-in fp16
-        export_mesh_normals=False,           # `vn` records (the density field's outward normals) in the exported meshes; needs --export_mesh
         save_normal_maps=False,              # normal_sample{i}.npy [V,3,R,R]: world-space surface normal maps next to the frames
-        mesh_keep='all',                     # all | largest: which connected components of an exported mesh are written; needs --export_mesh
-        mesh_min_faces=0,                    # components of an exported mesh with fewer faces are dropped (floaters); needs --export_mesh
-        mesh_simplify_cell=0.0)              # > 0: an exported mesh is simplified by vertex clustering on cells of that many grid units; needs --export_mesh
+        **_MESH_FLAGS)
     d.update(_IGNORED_DEFAULTS)
     d.update({k: v[0] for k, v in _CHECKED.items()})
     ap = argparse.ArgumentParser(allow_abbrev=False)
     add_dict_to_argparser(ap, d)
     ap.set_defaults(entry_objaverse=objaverse)             # which script's defaults these are (the default --prompt differs)
     return ap
+
+
+def _mesh_post(args):
+    """the launcher's mesh post-processing flags as a mesh.MeshPost; a flag that `args` lacks has its default"""
+    return MeshPost(*(getattr(args, flag, default) for flag, default in _MESH_FLAGS.items()))
 
 
 def validate(args):
@@ -155,19 +164,16 @@ def validate(args):
     plane_prec = getattr(args, 'plane_precision', 'fp32')
     if plane_prec not in PLANE_PRECISIONS:
         raise SystemExit(f"--plane_precision {plane_prec}: expected one of {list(PLANE_PRECISIONS)}")
-    if getattr(args, 'export_mesh_normals', False) and not args.export_mesh:
+    post = _mesh_post(args)
+    if post.normals and not args.export_mesh:
         raise SystemExit("--export_mesh_normals true: there is no mesh to put normals into without --export_mesh true")
-    mesh_keep, mesh_min_faces = getattr(args, 'mesh_keep', 'all'), getattr(args, 'mesh_min_faces', 0)
-    if mesh_keep not in ('all', 'largest'):
-        raise SystemExit(f"--mesh_keep {mesh_keep}: expected all or largest")
-    if mesh_min_faces < 0:
-        raise SystemExit(f"--mesh_min_faces {mesh_min_faces}: expected a non-negative face count")
-    if (mesh_keep != 'all' or mesh_min_faces != 0) and not args.export_mesh:
+    try:                                     # the library's own checks, so the launcher refuses exactly what mesh_from_grid would, before sampling
+        clean, cell = _clean_args(post.keep, post.min_faces), _simplify_cell(post.simplify_cell)
+    except ValueError as e:                  # "keep ...", "min_faces ..." or "simplify_cell ...: expected ..."
+        raise SystemExit(f"--mesh_{e}") from None
+    if clean != ('all', 0) and not args.export_mesh:
         raise SystemExit("--mesh_keep / --mesh_min_faces: there is no mesh to clean without --export_mesh true")
-    mesh_simplify_cell = getattr(args, 'mesh_simplify_cell', 0.0)
-    if not math.isfinite(mesh_simplify_cell) or mesh_simplify_cell < 0:
-        raise SystemExit(f"--mesh_simplify_cell {mesh_simplify_cell}: expected a finite, non-negative cell size in grid units (0: off)")
-    if mesh_simplify_cell != 0 and not args.export_mesh:
+    if cell != 0 and not args.export_mesh:
         raise SystemExit("--mesh_simplify_cell: there is no mesh to simplify without --export_mesh true")
     if getattr(args, 'save_normal_maps', False):
         world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -470,10 +476,7 @@ def run(args, objaverse=None):
     cond_all, cond_src = res[0], res[1]
     if rank == 0:
         meta = dict(vars(args), conditioning=cond_src, weights={k: (v or 'synthetic') for k, v in weights_from.items()})
-        for k in ('export_mesh_normals', 'save_normal_maps'):        # recorded when set: a run without them writes the args.json it always wrote
-            if not meta[k]:
-                del meta[k]
-        for k, default in (('mesh_keep', 'all'), ('mesh_min_faces', 0), ('mesh_simplify_cell', 0.0)):
+        for k, default in dict(_MESH_FLAGS, save_normal_maps=False).items():      # recorded when set: a run without them writes the args.json it always wrote
             if meta[k] == default:
                 del meta[k]
         with open(os.path.join(args.logdir, 'args.json'), 'w') as f:
@@ -535,7 +538,6 @@ def run(args, objaverse=None):
     if args.export_mesh and hi > lo:
         # meshes go with the SAMPLE shard; the file name carries the global sample id from the start (r2 wrote `sample{local}.obj`
         # on every rank and renamed afterwards: two ranks raced on the same names)
-        from .mesh import mesh_from_grid
         mine = lat_all[lo:hi].clone()
         mine *= args.triplane_scaling_divider
         d = {'latent_normalized_2Ddiffusion': mine}
@@ -543,9 +545,7 @@ def run(args, objaverse=None):
         grid = ae(latent=d, grid_size=args.mesh_grid, behaviour='triplane_decode_grid')
         for i in range(hi - lo):
             path = os.path.join(args.logdir, f'mesh_sample{lo + i}.obj')
-            mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path,
-                           normals=args.export_mesh_normals, keep=args.mesh_keep, min_faces=args.mesh_min_faces,
-                           simplify_cell=args.mesh_simplify_cell)
+            mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path, **_mesh_post(args)._asdict())
             if not os.path.exists(path):
                 mesh_err = f"mesh export of sample {lo + i} produced no file at {path}"
                 break

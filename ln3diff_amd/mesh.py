@@ -5,9 +5,10 @@ The surface is classic marching cubes (what the reference's `mcubes.marching_cub
 tetrahedra (method='tetra'); both run on the GPU in two passes around a prefix sum and weld vertices by grid-edge id.
 Opt-in clean-up (no reference counterpart; include/ln3d_meshclean.h): connected components of the welded mesh on the device, then only the
 components with at least `min_faces` faces, or only the largest one, are kept - before the colour query, so discarded vertices cost nothing.
-Opt-in simplification (no reference counterpart; include/ext/ln3d_meshsimplify.h): vertex clustering on a lattice of `simplify_cell` grid units,
+Opt-in simplification (no reference counterpart; include/ln3d_meshsimplify.h): vertex clustering on a lattice of `simplify_cell` grid units,
 behind the clean-up and before the colour query."""
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -18,12 +19,52 @@ from . import ops
 KEEP_MODES = ('all', 'largest')
 
 
+class MeshPost(NamedTuple):
+    """The opt-in post-processing of an exported mesh, as mesh_from_grid takes it; the layers above take the fields as mesh_<field> keywords
+    (from_kwargs).  A plain carrier: the values are checked where they are used (_clean_args, _simplify_cell), so not unless a mesh is made."""
+    normals: bool = False
+    keep: str = 'all'
+    min_faces: int = 0
+    simplify_cell: float = 0.0
+
+    @classmethod
+    def from_kwargs(cls, kw):
+        """{'mesh_<field>': value, ...} -> MeshPost; any other key is the TypeError of an unexpected keyword argument"""
+        for k in kw:
+            if not k.startswith('mesh_') or k[len('mesh_'):] not in cls._fields:
+                raise TypeError(f"got an unexpected keyword argument {k!r}")
+        return cls(**{k[len('mesh_'):]: v for k, v in kw.items()})
+
+
 def _clean_args(keep, min_faces):
     if keep not in KEEP_MODES:
         raise ValueError(f"keep {keep!r}: expected one of {list(KEEP_MODES)}")
     if int(min_faces) != min_faces or min_faces < 0:
         raise ValueError(f"min_faces {min_faces!r}: expected a non-negative integer")
     return keep, int(min_faces)
+
+
+def _check_verts(verts):
+    if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"verts: expected a float32 [Nv, 3] tensor, got {verts.dtype} {tuple(verts.shape)}")
+
+
+def _empty(dev):
+    return torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.long, device=dev)
+
+
+def _compact(verts, faces, keep_v, keep_f):
+    """the rows of verts and faces whose int32 mask is set, faces renumbered (ops.mesh_gather): two prefix sums and one read-back of the two
+    surviving counts; no surviving face gives the empty mesh"""
+    dev = verts.device
+    vpre, fpre = torch.cumsum(keep_v.long(), 0), torch.cumsum(keep_f.long(), 0)
+    nv_out, nf_out = torch.stack([vpre[-1], fpre[-1]]).tolist()
+    if nf_out == 0:
+        return _empty(dev)
+    verts_out = torch.empty(nv_out, 3, device=dev)
+    faces_out = torch.empty(nf_out, 3, dtype=torch.int64, device=dev)
+    ops.mesh_gather(verts, faces, keep_v, vpre, keep_f, fpre, verts_out, faces_out, check=False)
+    return verts_out, faces_out
 
 
 def _label_and_count(faces, nv):
@@ -64,30 +105,21 @@ def clean_mesh(verts, faces, keep='all', min_faces=0):
     keep, min_faces = _clean_args(keep, min_faces)
     if keep == 'all' and min_faces == 0:
         return verts, faces
-    if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
-        raise ValueError(f"verts: expected a float32 [Nv, 3] tensor, got {verts.dtype} {tuple(verts.shape)}")
+    _check_verts(verts)
     dev = verts.device
-    empty = lambda: (torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.long, device=dev))
     nv, nf = verts.shape[0], faces.shape[0]
     if nv == 0 or nf == 0:
-        return empty()
+        return _empty(dev)
     verts, faces = verts.contiguous(), faces.contiguous()
     ops.check_faces(faces, nv)
     label, _, nface, best = _label_and_count(faces, nv)
     keep_v = torch.empty(nv, dtype=torch.int32, device=dev)
     keep_f = torch.empty(nf, dtype=torch.int32, device=dev)
     ops.mesh_mark(faces, label, nface, min_faces, keep == 'largest', best, keep_v, keep_f, check=False)
-    vpre, fpre = torch.cumsum(keep_v.long(), 0), torch.cumsum(keep_f.long(), 0)
-    nv_out, nf_out = torch.stack([vpre[-1], fpre[-1]]).tolist()
-    if nf_out == 0:
-        return empty()
-    verts_out = torch.empty(nv_out, 3, device=dev)
-    faces_out = torch.empty(nf_out, 3, dtype=torch.int64, device=dev)
-    ops.mesh_gather(verts, faces, keep_v, vpre, keep_f, fpre, verts_out, faces_out, check=False)
-    return verts_out, faces_out
+    return _compact(verts, faces, keep_v, keep_f)
 
 
-SIMPLIFY_MAX_CELLS = 1 << 21                  # lattice cells per axis, and clusters, that a 63-bit key holds (include/ext/ln3d_meshsimplify.h)
+SIMPLIFY_MAX_CELLS = 1 << 21                  # lattice cells per axis, and clusters, that a 63-bit key holds (include/ln3d_meshsimplify.h)
 
 
 def _simplify_cell(cell):
@@ -97,16 +129,16 @@ def _simplify_cell(cell):
     try:
         c = float(np.float32(cell))
     except (TypeError, ValueError):
-        raise ValueError(f"cell {cell!r}: expected a positive finite number, or 0 / None for no simplification") from None
+        raise ValueError(f"simplify_cell {cell!r}: expected a positive finite number, or 0 / None for no simplification") from None
     if not math.isfinite(c) or c < 0 or (c == 0 and cell != 0):
-        raise ValueError(f"cell {cell!r}: expected a positive finite number (in float32), or 0 / None for no simplification")
+        raise ValueError(f"simplify_cell {cell!r}: expected a positive finite number (in float32), or 0 / None for no simplification")
     return c
 
 
 @torch.no_grad()
 def simplify_mesh(verts, faces, cell, origin=None, check=True):
     """verts [Nv,3] f32, faces [Nf,3] int64 (device) -> (verts', faces'): the mesh simplified by vertex clustering on a lattice of cubic cells
-    of edge `cell` whose corner is `origin` (three numbers; None: the per-axis minimum of verts).  The definition (include/ext/
+    of edge `cell` whose corner is `origin` (three numbers; None: the per-axis minimum of verts).  The definition (include/
     ln3d_meshsimplify.h; every output is unique, nothing depends on scheduling):
       - a vertex falls into cell q_a = floor((x_a - origin_a) / cell) per axis, in float32;
       - every occupied cell becomes one vertex, the float32 mean of its members summed in ascending vertex index;
@@ -125,14 +157,12 @@ def simplify_mesh(verts, faces, cell, origin=None, check=True):
     cell = _simplify_cell(cell)
     if cell == 0.0:
         return verts, faces
-    if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
-        raise ValueError(f"verts: expected a float32 [Nv, 3] tensor, got {verts.dtype} {tuple(verts.shape)}")
+    _check_verts(verts)
     if origin is not None:
         origin = np.asarray(origin, dtype=np.float32).reshape(-1)
         if origin.shape != (3,) or not np.isfinite(origin).all():
             raise ValueError(f"origin {origin!r}: expected three finite numbers")
     dev = verts.device
-    empty = lambda: (torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.long, device=dev))
     nv, nf = verts.shape[0], faces.shape[0]
     verts, faces = verts.contiguous(), faces.contiguous()
     if check:
@@ -140,7 +170,7 @@ def simplify_mesh(verts, faces, cell, origin=None, check=True):
     elif faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
         raise ValueError(f"faces: expected an int64 [Nf, 3] tensor, got {faces.dtype} {tuple(faces.shape)}")
     if nv == 0 or nf == 0:
-        return empty()
+        return _empty(dev)
     box = torch.cat([verts.amin(0), verts.amax(0), torch.isfinite(verts).all().float().reshape(1)]).cpu().numpy()      # one read-back
     if not box[6]:
         raise ValueError("verts: a coordinate is not finite")
@@ -169,14 +199,7 @@ def simplify_mesh(verts, faces, cell, origin=None, check=True):
     ops.simplify_first(sorted_key, perm, keep_f, check=False)
     keep_v = torch.empty(nc, dtype=torch.int32, device=dev)
     ops.simplify_used(cfaces, keep_f, keep_v, check=False)
-    vpre, fpre = torch.cumsum(keep_v.long(), 0), torch.cumsum(keep_f.long(), 0)
-    nv_out, nf_out = torch.stack([vpre[-1], fpre[-1]]).tolist()
-    if nf_out == 0:
-        return empty()
-    verts_out = torch.empty(nv_out, 3, device=dev)
-    faces_out = torch.empty(nf_out, 3, dtype=torch.int64, device=dev)
-    ops.mesh_gather(rep, cfaces, keep_v, vpre, keep_f, fpre, verts_out, faces_out, check=False)
-    return verts_out, faces_out
+    return _compact(rep, cfaces, keep_v, keep_f)
 
 
 @torch.no_grad()
@@ -197,7 +220,7 @@ def extract_isosurface(sigma, thr=10.0, method='cubes', keep='all', min_faces=0,
     offs = torch.cumsum(counts.long(), 0)
     ntri = int(offs[-1])
     if ntri == 0:
-        return torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.long, device=dev)
+        return _empty(dev)
     pos = torch.empty(ntri * 3, 3, device=dev)
     key = torch.empty(ntri * 3, dtype=torch.int64, device=dev)
     emit(sigma, G, thr, offs, pos, key)

@@ -338,17 +338,24 @@ def mcubes_emit(sigma, G, thr, offsets, tri_pos, tri_key):
     L.check(L.lib().ln3d_mcubes_emit(_p(sigma), G, thr, _p(offsets), _p(tri_pos), _p(tri_key), _stream()), "mcubes_emit")
 
 
-def check_faces(faces, nv):
-    """include/ln3d_meshclean.h takes face indices in [0, nv) as a precondition: an index outside that range must never reach a kernel, so
-    it is refused here (one read-back of the smallest and largest index)."""
-    if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous():
-        raise ValueError(f"faces: expected a contiguous int64 [Nf, 3] tensor, got {faces.dtype} {tuple(faces.shape)}")
-    if faces.shape[0]:
-        lo, hi = (int(x) for x in torch.aminmax(faces))
-        if lo < 0 or hi >= nv:
-            raise ValueError(f"faces: indices span [{lo}, {hi}], outside the {nv} vertices")
-    if not faces.is_cuda:
+def check_index(t, n, what, shape=None):
+    """include/ln3d_meshclean.h and include/ln3d_meshsimplify.h take the values of their index arrays in [0, n) as a precondition: a value
+    outside that range must never reach a kernel.  A contiguous int64 tensor (of `shape`, when given) whose values all lie in that range,
+    or ValueError (one read-back of the smallest and largest value); a host tensor that passes is refused like every other."""
+    if t.dtype != torch.int64 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{what}: expected a contiguous int64 tensor" + (f" of shape {tuple(shape)}" if shape is not None else "")
+                         + f", got {t.dtype} {tuple(t.shape)}")
+    if t.numel():
+        lo, hi = (int(x) for x in torch.aminmax(t))
+        if lo < 0 or hi >= n:
+            raise ValueError(f"{what}: values span [{lo}, {hi}], outside [0, {n})")
+    if not t.is_cuda:
         raise RuntimeError(_NEED_DEVICE)
+
+
+def check_faces(faces, nv):
+    """check_index for faces [Nf, 3] of a mesh with nv vertices"""
+    check_index(faces, nv, "faces", tuple(faces.shape[:1]) + (3,))
 
 
 def mesh_components(faces, nv, label, check=True):
@@ -385,29 +392,15 @@ def mesh_gather(verts, faces, keep_v, vprefix, keep_f, fprefix, verts_out, faces
                                      _p(verts_out), _p(faces_out), _stream()), "mesh_gather")
 
 
-def check_index(t, n, what, shape=None):
-    """include/ext/ln3d_meshsimplify.h takes the values of its index arrays in [0, n) as a precondition: a contiguous int64 tensor (of
-    `shape`, when given) whose values all lie in that range, or ValueError (one read-back of the smallest and largest value)."""
-    if t.dtype != torch.int64 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
-        raise ValueError(f"{what}: expected a contiguous int64 tensor" + (f" of shape {tuple(shape)}" if shape is not None else "")
-                         + f", got {t.dtype} {tuple(t.shape)}")
-    if t.numel():
-        lo, hi = (int(x) for x in torch.aminmax(t))
-        if lo < 0 or hi >= n:
-            raise ValueError(f"{what}: values span [{lo}, {hi}], outside [0, {n})")
-    if not t.is_cuda:
-        raise RuntimeError(_NEED_DEVICE)
-
-
 def _buffer(t, dtype, shape, what):
-    """the kernels of include/ext/ln3d_meshsimplify.h write whole rows of the buffers they are given: a buffer of another dtype, a shorter one
+    """the kernels of include/ln3d_meshsimplify.h write whole rows of the buffers they are given: a buffer of another dtype, a shorter one
     or a strided view would be written past its end, so it is refused here (metadata only: no read-back)"""
     if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
         raise ValueError(f"{what}: expected a contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
 
 
 def simplify_keys(verts, origin, cell, key):
-    """key [nv] int64 <- the packed lattice cell of every vertex (include/ext/ln3d_meshsimplify.h); verts [nv,3] f32; origin: three floats.
+    """key [nv] int64 <- the packed lattice cell of every vertex (include/ln3d_meshsimplify.h); verts [nv,3] f32; origin: three floats.
     There is no index to check: the kernel clamps."""
     _buffer(verts, torch.float32, (verts.shape[0], 3), "verts")
     _buffer(key, torch.int64, (verts.shape[0],), "key")

@@ -15,6 +15,7 @@ clamp range, ray-limit fix-up) per camera exactly as the loop has them.
 """
 import torch
 
+from .mesh import MeshPost
 from .sgm.sampling import DiscreteDenoiser, EulerEDMSampler, VanillaCFG
 
 TRIPLANE_SCALING_DIVIDER = 0.96806      # the released Objaverse runs (shell_scripts/final_release/inference/*.sh); a CLI flag there
@@ -23,16 +24,16 @@ TRIPLANE_SCALING_DIVIDER = 0.96806      # the released Objaverse runs (shell_scr
 @torch.no_grad()
 def render_video_given_triplane(planes, rec_model, cams, triplane_scaling_divider=TRIPLANE_SCALING_DIVIDER, latent_name='latent_normalized_2Ddiffusion',
                                 export_mesh=False, mesh_size=192, mesh_thres=10, mesh_path=None, resolution=None, jitter=None, u_fine=None,
-                                plane_precision=None, return_normals=False, mesh_normals=False, mesh_keep='all', mesh_min_faces=0, mesh_simplify_cell=0.0):
+                                plane_precision=None, return_normals=False, **mesh_post):
     """planes: sampled latent [B, 12, 32, 32] (scaled IN PLACE like the reference, :188); rec_model: `AE`; cams [V, 25] rendered
     for every sample.  plane_precision: 'fp32' | 'fp16' = the renderer's Triplane.set_plane_precision FOR THIS CALL (the renderer's own
     setting is restored on the way out; None: render with the setting it has); under 'fp16' the decoded planes are converted once and
     the mesh and every view read the f16 texels.  Returns {'latent_after_vit' (if produced), 'image_raw' [B,V,3,R,R], 'image_depth', 'weights_samples',
     'image_mask', 'mesh': [(verts, faces, colors)] when export_mesh}.  return_normals (opt-in) adds 'image_normal' [B,V,3,R,R], the
-    world-space surface normal maps of Triplane.forward(return_normals=True); mesh_normals (opt-in) makes every mesh a 4-tuple with
-    its vertex normals and writes them as `vn` records.  mesh_keep ('all' | 'largest') / mesh_min_faces (opt-in): mesh.clean_mesh on every
-    mesh before it is coloured - floaters below mesh_min_faces faces, or everything but the largest component, are dropped.
-    mesh_simplify_cell (opt-in, in grid units): mesh.simplify_mesh on every mesh behind the clean-up and before it is coloured."""
+    world-space surface normal maps of Triplane.forward(return_normals=True).  **mesh_post: mesh_normals, mesh_keep, mesh_min_faces and
+    mesh_simplify_cell (all opt-in), the fields of mesh.MeshPost, which mesh_from_grid documents: vertex normals (every mesh is then a 4-tuple),
+    floater clean-up and simplification of every mesh before it is coloured.  Any other keyword is a TypeError."""
+    post = MeshPost.from_kwargs(mesh_post)
     planes *= triplane_scaling_divider
     ddpm_latent = {latent_name: planes}
     ddpm_latent.update(rec_model(latent=ddpm_latent, behaviour='decode_after_vae_no_render'))
@@ -42,13 +43,13 @@ def render_video_given_triplane(planes, rec_model, cams, triplane_scaling_divide
         tp.set_plane_precision(plane_precision)
     try:
         return _render_video_decoded(ddpm_latent, planes, rec_model, cams, export_mesh, mesh_size, mesh_thres, mesh_path, resolution, jitter, u_fine,
-                                     return_normals, mesh_normals, mesh_keep, mesh_min_faces, mesh_simplify_cell)
+                                     return_normals, post)
     finally:
         tp.set_plane_precision(before)
 
 
 def _render_video_decoded(ddpm_latent, planes, rec_model, cams, export_mesh, mesh_size, mesh_thres, mesh_path, resolution, jitter, u_fine,
-                          return_normals=False, mesh_normals=False, mesh_keep='all', mesh_min_faces=0, mesh_simplify_cell=0.0):
+                          return_normals, post):
     tp = rec_model.decoder.triplane_decoder
     if ddpm_latent.get('planes_channel_last') is not None:
         ddpm_latent['planes_channel_last'] = tp.cast_planes(ddpm_latent['planes_channel_last'])
@@ -57,8 +58,7 @@ def _render_video_decoded(ddpm_latent, planes, rec_model, cams, export_mesh, mes
         from .mesh import mesh_from_grid
         grid_out = rec_model(latent=ddpm_latent, grid_size=mesh_size, behaviour='triplane_decode_grid')
         out['mesh'] = [mesh_from_grid(rec_model.decoder, ddpm_latent, grid_out['sigma'][i], mesh_size, mesh_thres, sample_index=i,
-                                      path=(mesh_path.format(i) if mesh_path else None), normals=mesh_normals, keep=mesh_keep,
-                                      min_faces=mesh_min_faces, simplify_cell=mesh_simplify_cell) for i in range(planes.shape[0])]
+                                      path=(mesh_path.format(i) if mesh_path else None), **post._asdict()) for i in range(planes.shape[0])]
     B, V = planes.shape[0], cams.shape[0]
     kw = {}
     if resolution is not None:
@@ -260,17 +260,14 @@ class FlowMatchingEngine:
     def render_video_given_triplane(self, planes, cams, **kw):
         return render_video_given_triplane(planes, self.rec_model, cams, self.triplane_scaling_divider, **kw)
 
-    # FlowMatchingEngine.eval_i23d_and_export (:684-760): image -> conditioner -> sample -> mesh + video
+    # FlowMatchingEngine.eval_i23d_and_export (:684-760): image -> conditioner -> sample -> mesh + video; **mesh_post: mesh.MeshPost's fields
     @torch.no_grad()
     def eval_i23d_and_export(self, inp_img, camera, num_steps=250, seed=42, mesh_size=192, mesh_thres=10, unconditional_guidance_scale=4.0,
-                             num_samples=1, export_mesh=True, resolution=None, mesh_path=None, plane_precision=None, mesh_keep='all',
-                             mesh_min_faces=0, mesh_simplify_cell=0.0):
+                             num_samples=1, export_mesh=True, resolution=None, mesh_path=None, plane_precision=None, **mesh_post):
         assert self.conditioner is not None, "construct the engine with conditioner=I23DConditioner(...)"
         cond = self.conditioner(inp_img)
-        samples, out = self.eval_cldm(cond, camera, num_samples, unconditional_guidance_scale, num_steps, seed, export_mesh,
-                                      resolution, mesh_size=mesh_size, mesh_thres=mesh_thres, mesh_path=mesh_path, plane_precision=plane_precision,
-                                      mesh_keep=mesh_keep, mesh_min_faces=mesh_min_faces, mesh_simplify_cell=mesh_simplify_cell)
-        return samples, out
+        return self.eval_cldm(cond, camera, num_samples, unconditional_guidance_scale, num_steps, seed, export_mesh, resolution, mesh_size=mesh_size,
+                              mesh_thres=mesh_thres, mesh_path=mesh_path, plane_precision=plane_precision, **mesh_post)
 
 
 I23DPipeline = FlowMatchingEngine
@@ -339,15 +336,14 @@ class GuidedDiffusionEngine:
 
 @torch.no_grad()
 def reconstruct(rec_model, img, cams, latent_dir=None, ins_names=None, sample_posterior=True, eps=None, export_mesh=False, mesh_size=192,
-                mesh_thres=10, mesh_path=None, resolution=None, jitter=None, u_fine=None, plane_precision=None, return_normals=False,
-                mesh_normals=False, mesh_keep='all', mesh_min_faces=0, mesh_simplify_cell=0.0):
+                mesh_thres=10, mesh_path=None, resolution=None, jitter=None, u_fine=None, plane_precision=None, return_normals=False, **mesh_post):
     """Posed views -> tri-plane latent -> renders (and meshes): TrainLoop.eval_novelview_loop(save_latent=True) of the VAE
     reconstruction launcher (vae_xl_reconstruction.sh; nsr/train_nv_util.py:1176-1213).  rec_model: `AE` with the released encoder;
     img [B*F, 10, 256, 256] (F = rec_model.encoder.num_frames views per object); cams [V, 25] rendered for every object.
     The latent is 'encoder_vae' (posterior sampled as the reference does, or the mode with sample_posterior=False; eps [B, 4, 3, H*W]
     overrides the CPU-generator draw).  latent_dir: writes <latent_dir>/<ins>/latent.npy = latent_normalized_2Ddiffusion[b] [12, 32, 32].
     The encoded latent is already in VAE space, so it is rendered with triplane_scaling_divider = 1.  Returns the
-    render_video_given_triplane dict plus 'latent' (the encoder_vae dict)."""
+    render_video_given_triplane dict plus 'latent' (the encoder_vae dict).  **mesh_post: render_video_given_triplane's (mesh.MeshPost)."""
     import os
     import numpy as np
     from .nsr.script_util import AE
@@ -370,7 +366,6 @@ def reconstruct(rec_model, img, cams, latent_dir=None, ins_names=None, sample_po
             np.save(os.path.join(latent_dir, name, 'latent.npy'), zc[b])
     out = render_video_given_triplane(z.clone(), rec_model, cams, triplane_scaling_divider=1.0, export_mesh=export_mesh, mesh_size=mesh_size,
                                       mesh_thres=mesh_thres, mesh_path=mesh_path, resolution=resolution, jitter=jitter, u_fine=u_fine,
-                                      plane_precision=plane_precision, return_normals=return_normals, mesh_normals=mesh_normals,
-                                      mesh_keep=mesh_keep, mesh_min_faces=mesh_min_faces, mesh_simplify_cell=mesh_simplify_cell)
+                                      plane_precision=plane_precision, return_normals=return_normals, **mesh_post)
     out['latent'] = lat
     return out

@@ -1,4 +1,4 @@
-"""Plain-numpy restatement of the mesh simplification of include/ext/ln3d_meshsimplify.h (csrc/mesh.hip: ln3d_simplify_keys, ln3d_simplify_mean,
+"""Plain-numpy restatement of the mesh simplification of include/ln3d_meshsimplify.h (csrc/mesh.hip: ln3d_simplify_keys, ln3d_simplify_mean,
 ln3d_simplify_faces, ln3d_simplify_first, ln3d_simplify_used, then ln3d_mesh_gather), no GPU, written from the definition with loops where the
 order matters, and the hand-made meshes that tests/test_mesh_simplify_cpu.py and tests/test_mesh_simplify_gpu.py share.  Every comparison
 against it is an equality: bit patterns for the representatives, integers elsewhere.

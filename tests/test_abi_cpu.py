@@ -1,7 +1,9 @@
 """C-ABI contract without a GPU: every entry point of include/ln3d.h and of the stage headers (ln3d_shapenet.h, ln3d_encoder.h,
 ln3d_ffhq.h, ln3d_mx.h) rejects missing buffers with LN3D_ERR_BAD_ARG BEFORE it touches the device (argument validation is not a
 compute call; nothing is launched here).  The tables must cover every `int ln3d_*(...)` declared in each header, so a new export
-without validation shows up as a failing test."""
+without validation shows up as a failing test.  The mesh simplification (ln3d_meshsimplify.h) is held to more: every entry point returns
+LN3D_ERR_BAD_ARG for each null buffer, each zero, negative or oversize count and each bad cell / origin, and LN3D_ERR_UNSUPPORTED for
+nc = 2^21 + 1, all on fake addresses that are never dereferenced."""
 import ctypes as C
 import os
 import re
@@ -250,3 +252,54 @@ def test_gate_residual_row_arguments_are_validated(hip_lib):
 def test_zero_sizes_are_bad_arguments(hip_lib):
     for name, args in ZERO_CALLS:
         assert getattr(hip_lib, name)(*args) == -1, (name, args)              # LN3D_ERR_BAD_ARG, before any launch
+
+
+# ---- the mesh simplification (include/ln3d_meshsimplify.h): name -> (a valid argument list on fake addresses, indices of its buffers,
+# indices of its counts)
+A = 0x10000                                  # a fake device address
+BIG = 1 << 31                                # one more than the largest count
+NAN, INF = float('nan'), float('inf')
+VALID = {
+    'ln3d_simplify_keys': ([A, 5, 0.0, -1.0, 2.0, 0.5, A, None], (0, 6), (1,)),
+    'ln3d_simplify_mean': ([A, A, A, 9, 4, A, None], (0, 1, 2, 5), (3, 4)),
+    'ln3d_simplify_faces': ([A, 7, A, 9, 4, A, A, None], (0, 2, 5, 6), (1, 3, 4)),
+    'ln3d_simplify_first': ([A, A, 7, A, None], (0, 1, 3), (2,)),
+    'ln3d_simplify_used': ([A, A, 7, 4, A, None], (0, 1, 4), (2, 3)),
+}
+NC_AT = {'ln3d_simplify_mean': 4, 'ln3d_simplify_faces': 4, 'ln3d_simplify_used': 3}          # where nc stands
+NV_AT = {'ln3d_simplify_mean': 3, 'ln3d_simplify_faces': 3}                                   # nc <= nv is checked: raise nv with it
+
+
+def _with(args, **at):
+    a = list(args)
+    for i, v in at.items():
+        a[int(i[1:])] = v
+    return a
+
+
+def test_every_entry_point_validates_before_it_launches(hip_lib):
+    assert set(VALID) == {'ln3d_simplify_faces', 'ln3d_simplify_first', 'ln3d_simplify_keys', 'ln3d_simplify_mean', 'ln3d_simplify_used'}
+    for name, (args, buffers, counts) in VALID.items():
+        fn = getattr(hip_lib, name)
+        for i in buffers:
+            assert fn(*_with(args, **{'i%d' % i: None})) == BAD_ARG, (name, 'null buffer', i)
+        for i in counts:
+            for bad in (0, -1, BIG, 1 << 40):
+                assert fn(*_with(args, **{'i%d' % i: bad})) == BAD_ARG, (name, 'count', i, bad)
+    keys, kargs = hip_lib.ln3d_simplify_keys, VALID['ln3d_simplify_keys'][0]
+    for cell in (0.0, -0.0, -1.0, NAN, INF, -INF):
+        assert keys(*_with(kargs, i5=cell)) == BAD_ARG, cell
+    for i in (2, 3, 4):
+        for o in (NAN, INF, -INF):
+            assert keys(*_with(kargs, **{'i%d' % i: o})) == BAD_ARG, (i, o)
+    # more clusters than vertices cannot be
+    assert hip_lib.ln3d_simplify_mean(*_with(VALID['ln3d_simplify_mean'][0], i3=4, i4=5)) == BAD_ARG
+    assert hip_lib.ln3d_simplify_faces(*_with(VALID['ln3d_simplify_faces'][0], i3=4, i4=5)) == BAD_ARG
+    # nc = 2^21 + 1: three cluster numbers no longer fit a face key; a null buffer still comes first
+    for name, at in NC_AT.items():
+        big = {'i%d' % at: (1 << 21) + 1}
+        if name in NV_AT:
+            big['i%d' % NV_AT[name]] = 1 << 22
+        assert getattr(hip_lib, name)(*_with(VALID[name][0], **big)) == UNSUPPORTED, name
+        assert getattr(hip_lib, name)(*_with(VALID[name][0], i0=None, **big)) == BAD_ARG, name
+    assert b'bad argument' in hip_lib.ln3d_strerror(BAD_ARG) and hip_lib.ln3d_strerror(UNSUPPORTED)

@@ -79,10 +79,11 @@ def test_prototype_table_equals_the_headers():
     assert set(declared) == set(_lib.PROTOTYPES), set(declared) ^ set(_lib.PROTOTYPES)
     for name, (restype, argtypes) in declared.items():
         assert (_lib.PROTOTYPES[name][0], tuple(_lib.PROTOTYPES[name][1])) == (restype, argtypes), name
-    assert list(_lib.SYMBOLS) == list(_lib.PROTOTYPES) and len(_lib.SYMBOLS) == 75
+    assert list(_lib.SYMBOLS) == list(_lib.PROTOTYPES) and len(_lib.SYMBOLS) == 80
+    assert {'ln3d_simplify_faces', 'ln3d_simplify_first', 'ln3d_simplify_keys', 'ln3d_simplify_mean', 'ln3d_simplify_used'} <= set(_lib.PROTOTYPES)
 
 
-def test_lib_applies_the_table(hip_lib):
+def test_lib_applies_the_table(hip_lib, monkeypatch):
     from ln3diff_amd import _lib
     for name, (restype, argtypes) in _lib.PROTOTYPES.items():
         fn = getattr(hip_lib, name)
@@ -90,6 +91,9 @@ def test_lib_applies_the_table(hip_lib):
     assert _lib.check_symbols() and hip_lib.ln3d_abi_version() == _lib.ABI_VERSION == 10
     assert hip_lib.ln3d_reload_env() is None
     assert isinstance(hip_lib.ln3d_strerror(-1), bytes)
+    monkeypatch.setitem(_lib.PROTOTYPES, 'ln3d_no_such_entry_point', _lib._int())
+    with pytest.raises(RuntimeError, match='ln3d_no_such_entry_point'):
+        _lib.check_symbols()
 
 
 def test_struct_layouts_and_constants_equal_the_compilers(tmp_path):

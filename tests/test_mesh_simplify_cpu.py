@@ -1,15 +1,18 @@
 """The numpy reference of the mesh simplification (tests/mesh_simplify_refs.py) against hand-written answers, its invariants on the iso-surfaces
 of the fields of tests/mesh_clean_refs.py, the recorded counts, and seeded faults that the comparisons of tests/test_mesh_simplify_gpu.py must
-catch.  No GPU, and no package code: these are the reference's own tests; tests/test_abi_ext_cpu.py and tests/test_mesh_simplify_gpu.py hold
-the package to it."""
+catch: the reference's own tests, to which tests/test_mesh_simplify_gpu.py holds the package.  Then, still without a GPU, the package's
+refusals: a host tensor never reaches the library through the ops wrappers, simplify_mesh refuses bad arguments before any launch, and
+the launcher refuses every cell that the library would.  (tests/test_abi_cpu.py has the entry points' own argument validation.)"""
 import numpy as np
 import pytest
+import torch
 
 import mesh_clean_refs as M
 import mesh_simplify_refs as S
 
 F32 = np.float32
 ZERO = (0.0, 0.0, 0.0)
+NAN, INF = float('nan'), float('inf')
 
 
 # ---------------------------------------------------------------- hand-made meshes, hand-written answers
@@ -138,3 +141,107 @@ def test_a_seeded_fault_in_each_stage_fails_the_comparison():
     last[s['perm'][-1]] = 1
     assert not np.array_equal(last, s['keep_f'])
     assert not np.array_equal(M.compact(s['rep'], s['cfaces'], s['keep_v'], last)[1], want_f)
+
+
+# ---------------------------------------------------------------- the package's refusals, without a library
+class _NoLibrary:
+    def __getattr__(self, name):
+        def fail(*a):
+            pytest.fail(f"{name} was reached with a host tensor")
+        return fail
+
+
+@pytest.mark.parametrize('check', [True, False])
+def test_host_tensors_never_reach_the_library(monkeypatch, check):
+    """the new wrappers turn tensors into addresses through ops._p only (and their checks refuse a host tensor themselves): with small CPU
+    tensors of the right dtypes, shapes and values each call raises before the (fake) library is touched"""
+    from ln3diff_amd import _lib, ops
+    monkeypatch.setattr(_lib, 'lib', lambda: _NoLibrary())
+    v = torch.rand(4, 3)
+    faces = torch.tensor([[0, 1, 2], [2, 1, 3]], dtype=torch.int64)
+    i64 = lambda *s: torch.zeros(*s, dtype=torch.int64)                                          # noqa: E731
+    i32 = lambda *s: torch.zeros(*s, dtype=torch.int32)                                          # noqa: E731
+    calls = [
+        lambda: ops.simplify_keys(v, (0.0, 0.0, 0.0), 1.0, i64(4)),
+        lambda: ops.simplify_mean(v, torch.arange(4), torch.tensor([0, 2, 4]), torch.zeros(2, 3), check=check),
+        lambda: ops.simplify_faces(faces, torch.tensor([0, 1, 1, 0]), 2, i64(2, 3), i64(2), check=check),
+        lambda: ops.simplify_first(i64(2), torch.arange(2), i32(2), check=check),
+        lambda: ops.simplify_used(faces, i32(2), i32(4), check=check),
+    ]
+    for call in calls:
+        with pytest.raises(RuntimeError, match="need device tensors"):
+            call()
+    with pytest.raises(RuntimeError, match="need device tensors"):
+        ops.check_index(torch.arange(3), 3, "index")
+    # the checks themselves: a value outside its range, a wrong dtype, a wrong shape - ValueError, wherever the tensor lives
+    with pytest.raises(ValueError):
+        ops.check_index(torch.arange(4), 3, "index")
+    with pytest.raises(ValueError):
+        ops.check_index(torch.tensor([-1, 0]), 3, "index")
+    with pytest.raises(ValueError):
+        ops.check_index(torch.arange(3, dtype=torch.int32), 3, "index")
+    with pytest.raises(ValueError):
+        ops.check_index(torch.arange(3), 3, "index", (4,))
+    with pytest.raises(ValueError):
+        ops.simplify_faces(faces, torch.tensor([0, 1, 2, 0]), 2, i64(2, 3), i64(2))             # cluster 2 of 2
+    with pytest.raises(ValueError):
+        ops.simplify_first(i64(2), torch.tensor([0, 2]), i32(2))                                 # perm 2 of 2
+    with pytest.raises(ValueError):
+        ops.simplify_used(faces, i32(2), i32(3))                                                 # corner 3 of 3 clusters
+    with pytest.raises(ValueError):
+        ops.simplify_mean(v, torch.tensor([0, 1, 2, 4]), torch.tensor([0, 2, 4]), torch.zeros(2, 3))      # order 4 of 4
+    # a buffer that the kernel would write past its end - another dtype, too short, strided - is refused from its metadata, checked or not
+    for bad in (lambda: ops.simplify_keys(v, (0.0, 0.0, 0.0), 1.0, i32(4)),
+                lambda: ops.simplify_keys(v, (0.0, 0.0, 0.0), 1.0, i64(3)),
+                lambda: ops.simplify_keys(v.double(), (0.0, 0.0, 0.0), 1.0, i64(4)),
+                lambda: ops.simplify_keys(torch.rand(4, 6)[:, ::2], (0.0, 0.0, 0.0), 1.0, i64(4)),
+                lambda: ops.simplify_mean(v, torch.arange(4), torch.tensor([0, 2, 4]), torch.zeros(1, 3), check=check),
+                lambda: ops.simplify_mean(v, torch.arange(4), torch.tensor([0, 2, 4]), torch.zeros(2, 3, dtype=torch.float64), check=check),
+                lambda: ops.simplify_faces(faces, torch.tensor([0, 1, 1, 0]), 2, i64(1, 3), i64(2), check=check),
+                lambda: ops.simplify_faces(faces, torch.tensor([0, 1, 1, 0]), 2, i64(2, 3), i32(2), check=check),
+                lambda: ops.simplify_first(i64(2), torch.arange(2), i64(2), check=check),
+                lambda: ops.simplify_first(i64(2), torch.arange(2), i32(1), check=check),
+                lambda: ops.simplify_used(faces, i32(1), i32(4), check=check),
+                lambda: ops.simplify_used(faces, i32(2), i64(4), check=check)):
+        with pytest.raises(ValueError):
+            bad()
+
+
+def test_simplify_mesh_refuses_bad_arguments_before_any_launch(monkeypatch):
+    from ln3diff_amd import _lib
+    from ln3diff_amd.mesh import simplify_mesh, _simplify_cell
+    monkeypatch.setattr(_lib, 'lib', lambda: _NoLibrary())
+    v = torch.rand(4, 3)
+    faces = torch.tensor([[0, 1, 2], [2, 1, 3]], dtype=torch.int64)
+    for cell in (-1.0, NAN, INF, 1e-60, 'two'):
+        with pytest.raises(ValueError):
+            simplify_mesh(v, faces, cell)
+    for cell in (None, 0, 0.0):
+        a, b = simplify_mesh(v, faces, cell)
+        assert a is v and b is faces and _simplify_cell(cell) == 0.0
+    with pytest.raises(ValueError):
+        simplify_mesh(v.double(), faces, 1.0)
+    with pytest.raises(ValueError):
+        simplify_mesh(v.reshape(3, 4), faces, 1.0)
+    with pytest.raises(ValueError):
+        simplify_mesh(v, faces.int(), 1.0)
+    with pytest.raises(ValueError):
+        simplify_mesh(v, faces + 2, 1.0)                                                         # index 5 of 4 vertices
+    for origin in ((0.0, 0.0), (0.0, NAN, 0.0), (INF, 0.0, 0.0)):
+        with pytest.raises(ValueError):
+            simplify_mesh(v, faces, 1.0, origin)
+
+
+def test_launcher_refuses_every_cell_that_simplify_mesh_refuses():
+    """validate() alone, before anything is built or sampled: 1e-60 is finite and positive as a double and 0 in float32"""
+    from ln3diff_amd.entry import create_argparser, validate
+    parse = lambda *flags: create_argparser(True).parse_known_args(list(flags))[0]              # noqa: E731
+    for cell in ('1e-60', '-1', 'nan', 'inf'):
+        with pytest.raises(SystemExit) as e:
+            validate(parse('--mesh_simplify_cell', cell, '--export_mesh', 'true'))
+        assert '--mesh_simplify_cell' in str(e.value), cell
+    with pytest.raises(SystemExit) as e:
+        validate(parse('--mesh_simplify_cell', '2'))
+    assert '--export_mesh true' in str(e.value)
+    a = parse('--mesh_simplify_cell', '2', '--export_mesh', 'true')
+    assert validate(a) == 'edm' and a.mesh_simplify_cell == 2.0 and validate(parse('--mesh_simplify_cell', '0')) == 'edm'

@@ -1,4 +1,4 @@
-"""Mesh simplification on the GPU (include/ext/ln3d_meshsimplify.h): the five entry points called through the C ABI on sentinel-filled, guarded
+"""Mesh simplification on the GPU (include/ln3d_meshsimplify.h): the five entry points called through the C ABI on sentinel-filled, guarded
 buffers and held to the numpy reference of tests/mesh_simplify_refs.py with equalities - bit patterns for the representatives, integers
 elsewhere; then the seams: simplify_mesh, extract_isosurface, mesh_from_grid, render_video_given_triplane and the launcher flag."""
 import json
@@ -439,6 +439,7 @@ def test_entry_point_mesh_simplify_flag(hip_lib, tmp_path):
         assert len(np.unique(f1)) == len(v1) and len(np.unique(np.sort(f1, 1), axis=0)) == len(f1)
         assert not ((f1[:, 0] == f1[:, 1]) | (f1[:, 1] == f1[:, 2]) | (f1[:, 0] == f1[:, 2])).any()
     off = base.replace("--export_mesh true", "--export_mesh false")
-    for flags in (off + "--mesh_simplify_cell 2", base + "--mesh_simplify_cell -1", base + "--mesh_simplify_cell nan", base + "--mesh_simplify_cell inf"):
+    for flags in (off + "--mesh_simplify_cell 2", base + "--mesh_simplify_cell -1", base + "--mesh_simplify_cell nan", base + "--mesh_simplify_cell inf",
+                  base + "--mesh_simplify_cell 1e-60"):                                          # positive, and 0 in the float32 the kernels divide by
         with pytest.raises(SystemExit):
             run(create_argparser(True).parse_args((flags + f" --logdir {tmp_path / 'no'}").split()))

@@ -1,4 +1,4 @@
-"""Times the mesh simplification of include/ext/ln3d_meshsimplify.h on a 192^3 grid and writes profiles/mesh_simplify.md.
+"""Times the mesh simplification of include/ln3d_meshsimplify.h on a 192^3 grid and writes profiles/mesh_simplify.md.
 
     python tools/mesh_simplify_bench.py [--out profiles/mesh_simplify.md] [--iters 20] [--grid 192] [--commit SHA]
 
