@@ -12,6 +12,7 @@
 #include "../../include/ln3d.h"
 #include "../../include/ln3d_meshclean.h"
 #include "../../include/ln3d_meshsimplify.h"
+#include "../../include/ext/ln3d_meshbake.h"
 #include "mc_table.h"
 
 __constant__ int kTet[6][4] = {{0, 1, 3, 7}, {0, 2, 3, 7}, {0, 2, 6, 7}, {0, 4, 6, 7}, {0, 4, 5, 7}, {0, 1, 5, 7}};
@@ -419,5 +420,68 @@ extern "C" int ln3d_simplify_used(const int64_t* cfaces, const int32_t* keep_f, 
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(simplify_zero_kernel, grid_1d(nc), dim3(256), 0, s, keep_v, nc);
   hipLaunchKernelGGL(simplify_used_kernel, grid_1d(nf), dim3(256), 0, s, cfaces, keep_f, nf, keep_v);
+  return ln3d_check_launch();
+}
+
+// ------------------------------------------------------------------ texture baking (include/ext/ln3d_meshbake.h)
+// The per-face atlas: which face owns a texel is integer work, the point on that face is six individually rounded fp32 operations per axis,
+// so both outputs are unique by definition.  (__fmul_rn and __fadd_rn are plain operators in this compiler's headers and a product next to
+// a sum is contracted into an fma, which rounds once instead of twice: the expression stands under `fp contract(off)` instead.)  The field is evaluated at the points
+// by the caller, through ln3d_query_points; the pack below turns its colours into the texture.
+#define BAKE_MAX_T 8192
+
+__device__ __forceinline__ float bake_affine(float v0, float v1, float v2, float s, float t) {
+#pragma clang fp contract(off)
+  const float e1 = v1 - v0, e2 = v2 - v0;
+  const float se1 = s * e1, te2 = t * e2;
+  const float a = v0 + se1;
+  return a + te2;
+}
+
+__global__ void bake_points_kernel(const float* verts, const int64_t* faces, int nf, int T, int n, int c, float* points, int32_t* owner) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);                       // T * T <= 2^26
+  if (i >= T * T) return;
+  const int x = i % T, y = i / T;
+  int f = -1, a = 0, b = 0;
+  if (x < n * c && y < n * c) {
+    const int kx = x / c, ky = y / c;
+    a = x - kx * c; b = y - ky * c;
+    f = 2 * (ky * n + kx) + (a + b <= c - 1 ? 0 : 1);                               // 2 n^2 <= 2^23
+    if (f >= nf) f = -1;
+  }
+  owner[i] = f;
+  float* p = points + 3 * (int64_t)i;
+  if (f < 0) { p[0] = 0.0f; p[1] = 0.0f; p[2] = 0.0f; return; }
+  const bool lower = (f & 1) == 0;
+  const float d = (float)(c - 3);
+  const float s = __fdiv_rn((float)(lower ? a : c - 1 - a), d), t = __fdiv_rn((float)(lower ? b : c - 1 - b), d);
+  const float* v0 = verts + 3 * faces[3 * (int64_t)f];
+  const float* v1 = verts + 3 * faces[3 * (int64_t)f + 1];
+  const float* v2 = verts + 3 * faces[3 * (int64_t)f + 2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    p[k] = bake_affine(v0[k], v1[k], v2[k], s, t);
+}
+
+__global__ void bake_pack_kernel(const float* rgb, const int32_t* owner, int64_t P, int fill, uint8_t* tex) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P) return;
+  const bool own = owner[i] >= 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k)                                                       // fmaxf(NaN, 0) = 0: a NaN colour is 0
+    tex[3 * i + k] = own ? (uint8_t)(int)(fminf(fmaxf(rgb[3 * i + k], 0.0f), 1.0f) * 255.0f) : (uint8_t)fill;
+}
+
+extern "C" int ln3d_bake_points(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, int T, int n, int c, float* points,
+                                int32_t* owner, void* stream) {
+  if (!verts || !faces || !points || !owner || !count_ok(nv) || !count_ok(nf) || T < 4 || T > BAKE_MAX_T || n < 1 || c < 4 ||
+      (int64_t)n * c > T || nf > 2 * (int64_t)n * n) return LN3D_ERR_BAD_ARG;
+  hipLaunchKernelGGL(bake_points_kernel, grid_1d((int64_t)T * T), dim3(256), 0, (hipStream_t)stream, verts, faces, (int)nf, T, n, c, points, owner);
+  return ln3d_check_launch();
+}
+
+extern "C" int ln3d_bake_pack(const float* rgb, const int32_t* owner, int64_t P, int fill, uint8_t* tex, void* stream) {
+  if (!rgb || !owner || !tex || !count_ok(P) || P > (int64_t)BAKE_MAX_T * BAKE_MAX_T || fill < 0 || fill > 255) return LN3D_ERR_BAD_ARG;
+  hipLaunchKernelGGL(bake_pack_kernel, grid_1d(P), dim3(256), 0, (hipStream_t)stream, rgb, owner, P, fill, tex);
   return ln3d_check_launch();
 }

@@ -6,8 +6,13 @@ tetrahedra (method='tetra'); both run on the GPU in two passes around a prefix s
 Opt-in clean-up (no reference counterpart; include/ln3d_meshclean.h): connected components of the welded mesh on the device, then only the
 components with at least `min_faces` faces, or only the largest one, are kept - before the colour query, so discarded vertices cost nothing.
 Opt-in simplification (no reference counterpart; include/ln3d_meshsimplify.h): vertex clustering on a lattice of `simplify_cell` grid units,
-behind the clean-up and before the colour query."""
+behind the clean-up and before the colour query.
+Opt-in texture baking (no reference counterpart; include/ext/ln3d_meshbake.h): textured_mesh_from_grid adds a per-face texture atlas, UVs,
+an .mtl and a .png to what mesh_from_grid makes; mesh_from_grid itself is unchanged."""
 import math
+import os
+import struct
+import zlib
 from typing import NamedTuple
 
 import numpy as np
@@ -238,22 +243,177 @@ def rotation_matrix_x(deg):
     return np.array([[1, 0, 0], [0, math.cos(a), -math.sin(a)], [0, math.sin(a), math.cos(a)]], dtype=np.float32)
 
 
+def _write_v(fh, v, c):
+    for i in range(v.shape[0]):
+        fh.write('v %.6f %.6f %.6f %.4f %.4f %.4f\n' % (v[i, 0], v[i, 1], v[i, 2], c[i, 0], c[i, 1], c[i, 2]))
+
+
+def _write_vn(fh, n):
+    for i in range(n.shape[0]):
+        fh.write('vn %.6f %.6f %.6f\n' % (n[i, 0], n[i, 1], n[i, 2]))
+
+
 def write_obj(path, v, f, c, n=None):
     """Wavefront .obj with per-vertex colours (what trimesh.Trimesh(vertex_colors=...).export(path, 'obj') writes).
     n [Nv,3]: per-vertex normals, written as `vn` records behind the vertices, every face corner then names its own vertex's normal
     (`f a//a b//b c//c`).  They are the outward normals -grad sigma / |grad sigma| of the density field (0 0 0 where it has none) and do
     NOT depend on the winding of the faces."""
     with open(path, 'w') as fh:
-        for i in range(v.shape[0]):
-            fh.write('v %.6f %.6f %.6f %.4f %.4f %.4f\n' % (v[i, 0], v[i, 1], v[i, 2], c[i, 0], c[i, 1], c[i, 2]))
+        _write_v(fh, v, c)
         if n is None:
             for t in f:
                 fh.write('f %d %d %d\n' % (t[0] + 1, t[1] + 1, t[2] + 1))
             return
-        for i in range(n.shape[0]):
-            fh.write('vn %.6f %.6f %.6f\n' % (n[i, 0], n[i, 1], n[i, 2]))
+        _write_vn(fh, n)
         for t in f:
             fh.write('f %d//%d %d//%d %d//%d\n' % (t[0] + 1, t[0] + 1, t[1] + 1, t[1] + 1, t[2] + 1, t[2] + 1))
+
+
+MATERIAL = 'baked'                            # the one material of a textured export
+
+
+def write_obj_textured(path, v, f, c, uv, n=None):
+    """`path` = <stem>.obj with the texture coordinates uv [Nf,3,2] of atlas_uvs, and <stem>.mtl beside it, which names <stem>.png (write_png
+    writes that).  The .obj holds, in order: `mtllib <stem>.mtl`; the `v` records of write_obj, byte for byte; its `vn` records when n is
+    given; 3 Nf `vt` records, corner j of face i being record 3 i + j + 1 (no two faces share one: every face has its own patch);
+    `usemtl baked`; the faces as `f a/t b/t c/t`, or `f a/t/a b/t/b c/t/c` with normals.  The .mtl holds `newmtl baked`, `Kd 1 1 1`,
+    `map_Kd <stem>.png`.  An empty mesh writes both files without records."""
+    stem = os.path.splitext(str(path))[0]
+    name = os.path.basename(stem)
+    with open(path, 'w') as fh:
+        fh.write('mtllib %s.mtl\n' % name)
+        _write_v(fh, v, c)
+        if n is not None:
+            _write_vn(fh, n)
+        for u in np.asarray(uv).reshape(-1, 2):
+            fh.write('vt %.8f %.8f\n' % (u[0], u[1]))
+        fh.write('usemtl %s\n' % MATERIAL)
+        for i, t in enumerate(f):
+            a, b, d = t[0] + 1, t[1] + 1, t[2] + 1
+            if n is None:
+                fh.write('f %d/%d %d/%d %d/%d\n' % (a, 3 * i + 1, b, 3 * i + 2, d, 3 * i + 3))
+            else:
+                fh.write('f %d/%d/%d %d/%d/%d %d/%d/%d\n' % (a, 3 * i + 1, a, b, 3 * i + 2, b, d, 3 * i + 3, d))
+    with open(stem + '.mtl', 'w') as fh:
+        fh.write('newmtl %s\nKd 1 1 1\nmap_Kd %s.png\n' % (MATERIAL, name))
+
+
+def write_png(path, tex):
+    """tex [H,W,3] uint8 -> an 8-bit RGB PNG (standard library only: one zlib stream, filter 0 on every row).  The rows are written FLIPPED:
+    the top row of the file is tex[H - 1], because v = 0 is the bottom of a texture and row 0 of the atlas holds v = 0.5 / H."""
+    tex = np.ascontiguousarray(tex)
+    if tex.dtype != np.uint8 or tex.ndim != 3 or tex.shape[2] != 3 or tex.shape[0] < 1 or tex.shape[1] < 1:
+        raise ValueError(f"tex: expected a uint8 [H, W, 3] array, got {tex.dtype} {tex.shape}")
+    h, w = tex.shape[:2]
+    rows = np.zeros((h, 1 + 3 * w), np.uint8)                           # a filter byte of 0 in front of every row
+    rows[:, 1:] = tex[::-1].reshape(h, 3 * w)
+
+    def chunk(kind, data):
+        return struct.pack('>I', len(data)) + kind + data + struct.pack('>I', zlib.crc32(kind + data) & 0xffffffff)
+    with open(path, 'wb') as fh:
+        fh.write(b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2, 0, 0, 0))
+                 + chunk(b'IDAT', zlib.compress(rows.tobytes(), 6)) + chunk(b'IEND', b''))
+
+
+# ------------------------------------------------------------------ texture baking (include/ext/ln3d_meshbake.h)
+ATLAS_MIN_SIZE, ATLAS_MAX_SIZE, ATLAS_MIN_CELL = 4, 8192, 4
+
+
+def _atlas_size(size):
+    if isinstance(size, bool) or int(size) != size or not ATLAS_MIN_SIZE <= size <= ATLAS_MAX_SIZE:
+        raise ValueError(f"texture size {size!r}: expected an integer in [{ATLAS_MIN_SIZE}, {ATLAS_MAX_SIZE}]")
+    return int(size)
+
+
+def atlas_layout(nf, size):
+    """The per-face atlas of nf >= 1 faces in a size x size texture -> (n, c): faces 2k and 2k + 1 share the square cell k of c x c texels
+    at ((k % n) * c, (k // n) * c); n is the smallest integer with n * n >= ceil(nf / 2) and c = size // n.  ValueError when c < 4, naming
+    the smallest sufficient size, 4 n (capacity: 2 (size // 4)^2 faces)."""
+    size = _atlas_size(size)
+    if int(nf) != nf or nf < 1:
+        raise ValueError(f"nf {nf!r}: expected a positive integer")
+    half = (int(nf) + 1) // 2
+    n = math.isqrt(half)
+    n += n * n < half
+    c = size // n
+    if c < ATLAS_MIN_CELL:
+        need = ATLAS_MIN_CELL * n
+        raise ValueError(f"texture size {size} is too small for {nf} faces (it holds {2 * (size // ATLAS_MIN_CELL) ** 2}): the smallest "
+                         f"sufficient size is {need}" + ("" if need <= ATLAS_MAX_SIZE else f", above the largest texture, {ATLAS_MAX_SIZE}")
+                         + "; a simplified mesh (simplify_cell, --mesh_simplify_cell) has fewer faces")
+    return n, c
+
+
+def atlas_uvs(nf, size):
+    """uv [nf,3,2] float32 of the face corners in the atlas of atlas_layout(nf, size), u to the right and v UP from the centre-(0.5, 0.5)
+    corner of texel (0, 0).  Cell-local, in texels: the lower (even) face has (0.5, 0.5) (c - 2.5, 0.5) (0.5, c - 2.5), the upper (odd) face
+    (c - 0.5, c - 0.5) (2.5, c - 0.5) (c - 0.5, 2.5), both counter-clockwise; uv = (cell origin + corner) / size, one float32 division of an
+    exact numerator.  nf = 0 gives an empty array."""
+    if nf == 0:
+        _atlas_size(size)
+        return np.zeros((0, 3, 2), np.float32)
+    n, c = atlas_layout(nf, size)
+    k = np.arange(nf) // 2
+    origin = np.stack([(k % n) * c, (k // n) * c], -1).astype(np.float32)                              # [nf, 2]
+    lower = np.array([[0.5, 0.5], [c - 2.5, 0.5], [0.5, c - 2.5]], np.float32)
+    upper = np.array([[c - 0.5, c - 0.5], [2.5, c - 0.5], [c - 0.5, 2.5]], np.float32)
+    corner = np.where((np.arange(nf) % 2 == 0)[:, None, None], lower[None], upper[None])
+    return ((origin[:, None, :] + corner) / np.float32(size)).astype(np.float32)
+
+
+@torch.no_grad()
+def bake_points(verts, faces, size):
+    """verts [Nv,3] f32, faces [Nf,3] int64 (device, Nf >= 1) -> (points [size*size,3] f32, owner [size*size] int32): for the texel with flat
+    index y * size + x the face that owns it (-1: nobody) and the point on that face's plane that the texel's centre maps to, (0, 0, 0)
+    for an unowned texel (ln3d_bake_points; the gutter texels extrapolate the face's affine map).  Raises ValueError on a bad dtype or
+    shape, a face index out of range and a size too small for Nf faces (atlas_layout)."""
+    _check_verts(verts)
+    verts, faces = verts.contiguous(), faces.contiguous()
+    n, c = atlas_layout(faces.shape[0], size)
+    ops.check_faces(faces, verts.shape[0])
+    T = int(size)
+    points = torch.empty(T * T, 3, device=verts.device)
+    owner = torch.empty(T * T, dtype=torch.int32, device=verts.device)
+    ops.bake_points(verts, faces, T, n, c, points, owner, check=False)
+    return points, owner
+
+
+@torch.no_grad()
+def bake_texture(decoder, planes_channel_last, verts_box, faces, size, fill=0):
+    """The colour of a mesh as a texture: decoder / planes_channel_last [1,3,H,W,C] as mesh_from_grid queries them, verts_box [Nv,3] f32 in
+    the box coordinates of that query, faces [Nf,3] int64 (device) -> (uv [Nf,3,2] float32 numpy: atlas_uvs, tex [size,size,3] uint8 numpy:
+    row y holds v = (y + 0.5) / size, so row 0 is the BOTTOM).  Every owned texel is forward_points' rgb at bake_points' point, clamped to
+    [0, 1], times 255, truncated - the rule of the vertex colours; an unowned texel is `fill` (0 .. 255).  One field sample per texel.  An
+    empty mesh gives a texture of `fill` and launches nothing."""
+    size = _atlas_size(size)
+    if isinstance(fill, bool) or int(fill) != fill or not 0 <= fill <= 255:
+        raise ValueError(f"fill {fill!r}: expected an integer in [0, 255]")
+    nf = faces.shape[0]
+    if nf == 0:
+        return atlas_uvs(0, size), np.full((size, size, 3), int(fill), np.uint8)
+    points, owner = bake_points(verts_box, faces, size)
+    rgb = decoder.forward_points(planes_channel_last, points[None])['rgb'][0].float().contiguous()
+    tex = torch.empty(size * size, 3, dtype=torch.uint8, device=points.device)
+    ops.bake_pack(rgb, owner, int(fill), tex)
+    return atlas_uvs(nf, size), tex.view(size, size, 3).cpu().numpy()
+
+
+def _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces, simplify_cell):
+    """what mesh_from_grid and textured_mesh_from_grid share: (the one sample's planes, the box-space vertices and the faces on the device,
+    then verts, faces, colors, vn as mesh_from_grid returns them; vn is None without normals)"""
+    sigma = sigma.reshape(grid_size, grid_size, grid_size)
+    verts, faces = extract_isosurface(sigma, thr, method, keep, min_faces, simplify_cell)
+    vtx = (verts / (grid_size - 1) * 2 - 1) * 0.45                       # g-objaverse scale
+    pcl = dec_out.get('planes_channel_last')
+    if pcl is None:
+        pcl = decoder.triplane_decoder.to_channel_last(dec_out['latent_after_vit'])        # f32, or f16 under set_plane_precision('fp16')
+    pcl = pcl[sample_index:sample_index + 1]
+    q = decoder.forward_points(pcl, vtx[None], with_grad=normals) if vtx.shape[0] else {'rgb': vtx[None], 'normal': vtx[None]}
+    colors = (q['rgb'][0].clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
+    v = (rotation_matrix_x(-90) @ vtx.cpu().numpy().T).T.astype(np.float32)
+    f = faces.cpu().numpy()
+    vn = (rotation_matrix_x(-90) @ q['normal'][0].cpu().numpy().T).T.astype(np.float32) if normals else None
+    return pcl, vtx, faces, v, f, colors, vn
 
 
 @torch.no_grad()
@@ -269,21 +429,33 @@ def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0,
     given normals) and written; what survives has the bits it has in the uncleaned mesh.  Nothing surviving writes an .obj with no records.
     simplify_cell (opt-in, in grid units; no reference counterpart): simplify_mesh behind the clean-up and before the query, so colours and `vn`
     are the field's values AT THE NEW VERTICES and discarded vertices cost nothing.  See simplify_mesh for what clustering does not promise."""
-    sigma = sigma.reshape(grid_size, grid_size, grid_size)
-    verts, faces = extract_isosurface(sigma, thr, method, keep, min_faces, simplify_cell)
-    vtx = (verts / (grid_size - 1) * 2 - 1) * 0.45                       # g-objaverse scale
-    pcl = dec_out.get('planes_channel_last')
-    if pcl is None:
-        pcl = decoder.triplane_decoder.to_channel_last(dec_out['latent_after_vit'])        # f32, or f16 under set_plane_precision('fp16')
-    pcl = pcl[sample_index:sample_index + 1]
-    q = decoder.forward_points(pcl, vtx[None], with_grad=normals) if vtx.shape[0] else {'rgb': vtx[None], 'normal': vtx[None]}
-    colors = (q['rgb'][0].clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
-    v = (rotation_matrix_x(-90) @ vtx.cpu().numpy().T).T.astype(np.float32)
-    f = faces.cpu().numpy()
-    vn = (rotation_matrix_x(-90) @ q['normal'][0].cpu().numpy().T).T.astype(np.float32) if normals else None
+    _, _, _, v, f, colors, vn = _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces,
+                                               simplify_cell)
     if path:
         write_obj(path, v, f, colors.astype(np.float32) / 255.0, vn)
     return (v, f, colors, vn) if normals else (v, f, colors)
+
+
+@torch.no_grad()
+def textured_mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes', texture_size=1024,
+                            normals=False, keep='all', min_faces=0, simplify_cell=0.0):
+    """mesh_from_grid plus a baked texture (opt-in; no reference counterpart): the same geometry, vertex colours and `vn`, bit for bit, for
+    the same options, then bake_texture of the faces at the box-space vertices (before the rotation, where the field lives) into a
+    texture_size x texture_size per-face atlas.  Returns mesh_from_grid's tuple with (uv [Nf,3,2] float32, tex [T,T,3] uint8) appended.
+    With `path` = <stem>.obj it writes <stem>.obj and <stem>.mtl (write_obj_textured) and <stem>.png (write_png).  A texture_size too
+    small for the extracted face count is a ValueError that names the smallest sufficient size (atlas_layout): simplify_cell is what makes
+    a mesh fit a small texture.
+    NOT promised: more than half of the atlas is unused; texel density is uniform per face, not per unit area; there is one field sample per
+    texel, no supersampling; there is no mip-safe padding beyond the 1 - 1.5 texel gutter; and the colours are the field's values on the
+    (possibly simplified) triangles, which lie off the level set by the simplifier's error."""
+    _atlas_size(texture_size)
+    pcl, vtx, faces, v, f, colors, vn = _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces,
+                                                       simplify_cell)
+    uv, tex = bake_texture(decoder, pcl, vtx, faces, texture_size)
+    if path:
+        write_obj_textured(path, v, f, colors.astype(np.float32) / 255.0, uv, vn)
+        write_png(os.path.splitext(str(path))[0] + '.png', tex)
+    return ((v, f, colors, vn) if normals else (v, f, colors)) + (uv, tex)
 
 
 @torch.no_grad()

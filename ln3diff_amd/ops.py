@@ -393,7 +393,7 @@ def mesh_gather(verts, faces, keep_v, vprefix, keep_f, fprefix, verts_out, faces
 
 
 def _buffer(t, dtype, shape, what):
-    """the kernels of include/ln3d_meshsimplify.h write whole rows of the buffers they are given: a buffer of another dtype, a shorter one
+    """the kernels of include/ln3d_meshsimplify.h and include/ext/ln3d_meshbake.h write whole rows of the buffers they are given: a buffer of another dtype, a shorter one
     or a strided view would be written past its end, so it is refused here (metadata only: no read-back)"""
     if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
         raise ValueError(f"{what}: expected a contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
@@ -457,6 +457,29 @@ def simplify_used(cfaces, keep_f, keep_v, check=True):
     if check:
         check_faces(cfaces, nc)
     L.check(L.lib().ln3d_simplify_used(_p(cfaces), _p(keep_f), cfaces.shape[0], nc, _p(keep_v), _stream()), "simplify_used")
+
+
+def bake_points(verts, faces, T, n, c, points, owner, check=True):
+    """points [T*T,3] f32, owner [T*T] int32 <- the point on its face and the face of every texel of the per-face atlas (T, n, c:
+    mesh.atlas_layout; include/ext/ln3d_meshbake.h); verts [nv,3] f32, faces [nf,3] int64.  check=False: the caller has already put these
+    faces through check_faces."""
+    nv, nf = verts.shape[0], faces.shape[0]
+    _buffer(verts, torch.float32, (nv, 3), "verts")
+    _buffer(faces, torch.int64, (nf, 3), "faces")
+    _buffer(points, torch.float32, (T * T, 3), "points")
+    _buffer(owner, torch.int32, (T * T,), "owner")
+    if check:
+        check_faces(faces, nv)
+    L.check(L.lib().ln3d_bake_points(_p(verts), nv, _p(faces), nf, T, n, c, _p(points), _p(owner), _stream()), "bake_points")
+
+
+def bake_pack(rgb, owner, fill, tex):
+    """tex [P,3] uint8 <- fill where owner [P] int32 is negative, elsewhere rgb [P,3] f32 clamped to [0, 1], times 255, truncated (NaN: 0)"""
+    P = owner.shape[0]
+    _buffer(rgb, torch.float32, (P, 3), "rgb")
+    _buffer(owner, torch.int32, (P,), "owner")
+    _buffer(tex, torch.uint8, (P, 3), "tex")
+    L.check(L.lib().ln3d_bake_pack(_p(rgb), _p(owner), P, int(fill), _p(tex), _stream()), "bake_pack")
 
 
 def lincomb(y, ks, cs, out):
