@@ -1,6 +1,6 @@
 """ctypes binding of libln3d_hip.so (the C ABI of include/ln3d.h, include/ln3d_encoder.h, include/ln3d_shapenet.h, include/ln3d_mx.h, include/ln3d_ffhq.h,
 include/ln3d_planes16.h, include/ln3d_normals.h, include/ln3d_meshclean.h and include/ln3d_meshsimplify.h, plus the additions of
-include/ext/ln3d_meshbake.h in EXT_PROTOTYPES).
+include/ext/ln3d_meshbake.h in EXT_PROTOTYPES and of every header under include/addons/ in ADDON_PROTOTYPES).
 
 Every export is declared once, in PROTOTYPES: name -> (restype, argtypes), which lib() applies, so a call site passes plain Python values
 and a value of the wrong kind is a ctypes.ArgumentError.  One rule maps a C parameter to its argtype:
@@ -179,13 +179,30 @@ PROTOTYPES = {
 SYMBOLS = list(PROTOTYPES)
 
 # Additions to ABI 10 declared under include/ext/ (tests/test_abi_ext_cpu.py holds this table to those headers by the same rule).  They use
-# no struct and no new constant and change no row above, so ABI_VERSION still describes every symbol it described.  The next change that
-# may touch tests/test_abi_types_cpu.py should fold the two tables together.
+# no struct and no new constant and change no row above, so ABI_VERSION still describes every symbol it described.  That test names this
+# table's two rows, as tests/test_abi_types_cpu.py counts the 80 above: both tables are frozen for as long as those files are, and nothing is
+# folded.  What comes later goes into ADDON_PROTOTYPES.
 EXT_PROTOTYPES = {
     # include/ext/ln3d_meshbake.h (texture baking of an exported mesh: per-face atlas)
     "ln3d_bake_points": _int(vp, i64, vp, i64, i32, i32, i32, vp, vp, vp),
     "ln3d_bake_pack": _int(vp, vp, i64, i32, vp, vp),
 }
+
+# Every later addition to ABI 10, declared under include/addons/ (one header per feature) by the rule of EXT_PROTOTYPES: no struct, no new
+# constant, no name of the tables above.  tests/test_mesh_smooth_cpu.py holds this table row for row to whatever headers that directory has
+# and names no entry and no count, so the next feature adds a header there and its rows here, not a fourth table.
+ADDON_PROTOTYPES = {
+    # include/addons/ln3d_meshsmooth.h (Taubin smoothing of an exported mesh)
+    "ln3d_smooth_edge_keys": _int(vp, i64, vp, vp),
+    "ln3d_smooth_halfedges": _int(vp, vp, i64, i64, vp, vp, vp),
+    "ln3d_smooth_step": _int(vp, vp, vp, vp, i64, i64, f32, vp, vp),
+}
+
+
+def _tables():
+    """every bound entry point: name -> (restype, argtypes), the three tables in order"""
+    return list(PROTOTYPES.items()) + list(EXT_PROTOTYPES.items()) + list(ADDON_PROTOTYPES.items())
+
 
 _lib = None
 
@@ -204,7 +221,7 @@ def lib():
         # fail with "HIP kernel launch failed".
         import torch  # noqa: F401
         _lib = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(EXT_PROTOTYPES.items()):
+        for name, (restype, argtypes) in _tables():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = restype, argtypes
     return _lib
@@ -212,7 +229,7 @@ def lib():
 
 def check_symbols():
     L = lib()
-    missing = [s for s in list(PROTOTYPES) + list(EXT_PROTOTYPES) if not hasattr(L, s)]
+    missing = [s for s, _ in _tables() if not hasattr(L, s)]
     if missing:
         raise RuntimeError(f"libln3d_hip.so lacks symbols: {missing}")
     assert L.ln3d_abi_version() == ABI_VERSION

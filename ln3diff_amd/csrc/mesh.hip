@@ -13,6 +13,7 @@
 #include "../../include/ln3d_meshclean.h"
 #include "../../include/ln3d_meshsimplify.h"
 #include "../../include/ext/ln3d_meshbake.h"
+#include "../../include/addons/ln3d_meshsmooth.h"
 #include "mc_table.h"
 
 __constant__ int kTet[6][4] = {{0, 1, 3, 7}, {0, 2, 3, 7}, {0, 2, 6, 7}, {0, 4, 6, 7}, {0, 4, 5, 7}, {0, 1, 5, 7}};
@@ -483,5 +484,80 @@ extern "C" int ln3d_bake_points(const float* verts, int64_t nv, const int64_t* f
 extern "C" int ln3d_bake_pack(const float* rgb, const int32_t* owner, int64_t P, int fill, uint8_t* tex, void* stream) {
   if (!rgb || !owner || !tex || !count_ok(P) || P > (int64_t)BAKE_MAX_T * BAKE_MAX_T || fill < 0 || fill > 255) return LN3D_ERR_BAD_ARG;
   hipLaunchKernelGGL(bake_pack_kernel, grid_1d(P), dim3(256), 0, (hipStream_t)stream, rgb, owner, P, fill, tex);
+  return ln3d_check_launch();
+}
+
+// ------------------------------------------------------------------ mesh smoothing (include/addons/ln3d_meshsmooth.h)
+// Taubin's lambda | mu passes over the vertex adjacency.  The adjacency is integer work (edge keys, the caller's unique and sort, half-edges);
+// a pass is a gather of one thread per vertex over its CSR row in ascending neighbour index, a short chain of individually rounded fp32
+// operations, so every output is unique by definition.  The array a pass gathers from (12 bytes a vertex) stays in L2.
+__global__ void smooth_edge_keys_kernel(const int64_t* faces, int64_t nf, int64_t* key) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= nf) return;
+  const int64_t v[3] = {faces[3 * f], faces[3 * f + 1], faces[3 * f + 2]};
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int64_t a = v[j], b = v[(j + 1) % 3];
+    key[3 * f + j] = a == b ? -1ll : ((min(a, b) << 32) | max(a, b));
+  }
+}
+
+__global__ void smooth_halfedges_kernel(const int64_t* edge, const int64_t* count, int64_t ne, int64_t nv, int64_t* dkey, int32_t* pinned) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= ne) return;
+  const int64_t k = edge[e], lo = k >> 32, hi = k & 0xffffffffll;
+  dkey[2 * e] = k; dkey[2 * e + 1] = (hi << 32) | lo;
+  if (count[e] == 1) {                                   // a boundary edge; every writer stores the same value
+    if (lo >= 0 && lo < nv) pinned[lo] = 1;
+    if (hi < nv) pinned[hi] = 1;
+  }
+}
+
+// x + f * (s / d - x) with four roundings (as bake_affine: the product next to the sum would otherwise be contracted into an fma)
+__device__ __forceinline__ float smooth_move(float x, float s, float d, float f) {
+#pragma clang fp contract(off)
+  const float m = __fdiv_rn(s, d);
+  const float e = m - x;
+  const float fe = f * e;
+  return x + fe;
+}
+
+__global__ void smooth_step_kernel(const float* vin, const int64_t* start, const int32_t* nbr, const int32_t* pinned, int64_t nv, int64_t nh,
+                                   float factor, float* vout) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nv) return;
+  const float x = vin[3 * i], y = vin[3 * i + 1], z = vin[3 * i + 2];
+  const int64_t b = max(start[i], (int64_t)0), e = min(start[i + 1], nh);
+  if (pinned[i] || e <= b) { vout[3 * i] = x; vout[3 * i + 1] = y; vout[3 * i + 2] = z; return; }
+  int64_t j = nbr[b];
+  float sx = vin[3 * j], sy = vin[3 * j + 1], sz = vin[3 * j + 2];
+  for (int64_t k = b + 1; k < e; ++k) {                  // terminates: k counts up to e; sequential on purpose (the order is the definition)
+    j = nbr[k];
+    sx += vin[3 * j]; sy += vin[3 * j + 1]; sz += vin[3 * j + 2];
+  }
+  const float d = (float)(e - b);
+  vout[3 * i] = smooth_move(x, sx, d, factor); vout[3 * i + 1] = smooth_move(y, sy, d, factor); vout[3 * i + 2] = smooth_move(z, sz, d, factor);
+}
+
+extern "C" int ln3d_smooth_edge_keys(const int64_t* faces, int64_t nf, int64_t* key, void* stream) {
+  if (!faces || !key || !count_ok(nf)) return LN3D_ERR_BAD_ARG;
+  hipLaunchKernelGGL(smooth_edge_keys_kernel, grid_1d(nf), dim3(256), 0, (hipStream_t)stream, faces, nf, key);
+  return ln3d_check_launch();
+}
+
+extern "C" int ln3d_smooth_halfedges(const int64_t* edge, const int64_t* count, int64_t ne, int64_t nv, int64_t* dkey, int32_t* pinned, void* stream) {
+  if (!edge || !count || !dkey || !pinned || !count_ok(ne) || !count_ok(nv)) return LN3D_ERR_BAD_ARG;
+  hipLaunchKernelGGL(smooth_halfedges_kernel, grid_1d(ne), dim3(256), 0, (hipStream_t)stream, edge, count, ne, nv, dkey, pinned);
+  return ln3d_check_launch();
+}
+
+extern "C" int ln3d_smooth_step(const float* verts_in, const int64_t* start, const int32_t* nbr, const int32_t* pinned, int64_t nv, int64_t n_halfedges,
+                                float factor, float* verts_out, void* stream) {
+  if (!verts_in || !start || !nbr || !pinned || !verts_out || !count_ok(nv) || !count_ok(n_halfedges) || !simplify_finite(factor))
+    return LN3D_ERR_BAD_ARG;
+  const uintptr_t in = (uintptr_t)verts_in, out = (uintptr_t)verts_out, bytes = (uintptr_t)nv * 3 * sizeof(float);
+  if ((in <= out ? out - in : in - out) < bytes) return LN3D_ERR_BAD_ARG;      // a pass reads the previous coordinates only
+  hipLaunchKernelGGL(smooth_step_kernel, grid_1d(nv), dim3(256), 0, (hipStream_t)stream, verts_in, start, nbr, pinned, nv, n_halfedges, factor,
+                     verts_out);
   return ln3d_check_launch();
 }

@@ -8,7 +8,9 @@ components with at least `min_faces` faces, or only the largest one, are kept - 
 Opt-in simplification (no reference counterpart; include/ln3d_meshsimplify.h): vertex clustering on a lattice of `simplify_cell` grid units,
 behind the clean-up and before the colour query.
 Opt-in texture baking (no reference counterpart; include/ext/ln3d_meshbake.h): textured_mesh_from_grid adds a per-face texture atlas, UVs,
-an .mtl and a .png to what mesh_from_grid makes; mesh_from_grid itself is unchanged."""
+an .mtl and a .png to what mesh_from_grid makes; mesh_from_grid itself is unchanged.
+Opt-in smoothing (no reference counterpart; include/addons/ln3d_meshsmooth.h): Taubin's lambda | mu passes over the extracted (cleaned,
+simplified) mesh in grid coordinates, before the box mapping, the colour / normal query and the bake."""
 import math
 import os
 import struct
@@ -154,7 +156,7 @@ def simplify_mesh(verts, faces, cell, origin=None, check=True):
     Raises ValueError on a bad dtype or shape, a face index out of range, a non-finite vertex or origin, a cell that is not finite or is
     negative, and a mesh that spans 2^21 cells or more on an axis (or reaches below an explicit origin).
     NOT promised: the result can have non-manifold edges and folded-over triangles, convex regions are pulled inward by O(cell^2 *
-    curvature), and components that come within a cell of each other can merge.  No quadric-error placement, no smoothing.
+    curvature), and components that come within a cell of each other can merge.  No quadric-error placement; smoothing is smooth_mesh's.
     The five stages are kernels; torch supplies unique (clusters), two stable sorts (members per cluster, duplicate faces), the prefix sums
     and the read-backs: the face-index check, the bounds and finiteness of verts, the cluster count (inside unique), the surviving counts.
     check=False skips the face-index check and its read-back: for a caller whose faces index verts by construction (extract_isosurface, whose
@@ -205,6 +207,117 @@ def simplify_mesh(verts, faces, cell, origin=None, check=True):
     keep_v = torch.empty(nc, dtype=torch.int32, device=dev)
     ops.simplify_used(cfaces, keep_f, keep_v, check=False)
     return _compact(rep, cfaces, keep_v, keep_f)
+
+
+# ------------------------------------------------------------------ smoothing (include/addons/ln3d_meshsmooth.h)
+SMOOTH_MAX_ITERS = 1000
+SMOOTH_LAMBDA, SMOOTH_MU = 0.5, -0.53
+
+
+def _smooth_args(iterations, lam=SMOOTH_LAMBDA, mu=SMOOTH_MU):
+    """-> (iterations as an int, None -> 0; lam and mu as the float32 values the kernel multiplies by); ValueError when iterations is no
+    integer in [0, 1000], lam (in float32) lies outside (0, 1] or mu outside [-1, 0]"""
+    if iterations is None:
+        iterations = 0
+    try:
+        ok = not isinstance(iterations, bool) and int(iterations) == iterations and 0 <= iterations <= SMOOTH_MAX_ITERS
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"smooth_iters {iterations!r}: expected an integer in [0, {SMOOTH_MAX_ITERS}], or None for no smoothing")
+    try:
+        lam32, mu32 = float(np.float32(lam)), float(np.float32(mu))
+    except (TypeError, ValueError):
+        lam32 = mu32 = math.nan
+    if not 0.0 < lam32 <= 1.0:
+        raise ValueError(f"smooth_lambda {lam!r}: expected a number in (0, 1] (in float32)")
+    if not -1.0 <= mu32 <= 0.0:
+        raise ValueError(f"smooth_mu {mu!r}: expected a number in [-1, 0] (in float32); 0 is plain Laplacian smoothing")
+    return int(iterations), lam32, mu32
+
+
+def _adjacency(faces, nv):
+    """faces [Nf >= 1, 3] int64 contiguous, already through ops.check_faces, nv >= 1 -> (start, nbr, pinned) of mesh_adjacency"""
+    dev = faces.device
+    nf = faces.shape[0]
+    pinned = torch.zeros(nv, dtype=torch.int32, device=dev)
+    key = torch.empty(3 * nf, dtype=torch.int64, device=dev)
+    ops.smooth_edge_keys(faces, nv, key, check=False)
+    edge, count = torch.unique(key, return_counts=True)                # ascending: a -1 (the a == b edges) comes first
+    skip = int(edge[0] < 0)                                            # one read-back
+    edge, count = edge[skip:], count[skip:]
+    ne = edge.shape[0]
+    if ne == 0:                                                        # every face is (a, a, a): nobody has a neighbour
+        return torch.zeros(nv + 1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev), pinned
+    dkey = torch.empty(2 * ne, dtype=torch.int64, device=dev)
+    ops.smooth_halfedges(edge, count, nv, dkey, pinned, check=False)
+    dkey = torch.sort(dkey)[0]                                         # distinct keys: ascending in (src, dst)
+    nbr = (dkey & 0xffffffff).to(torch.int32)
+    start = torch.searchsorted(dkey >> 32, torch.arange(nv + 1, device=dev))
+    return start, nbr, pinned
+
+
+@torch.no_grad()
+def mesh_adjacency(faces, num_verts):
+    """The diagnostic view of what smooth_mesh walks: faces [Nf,3] int64 device, num_verts -> (start [Nv+1] int64, nbr [2E] int32,
+    pinned [Nv] int32).  nbr[start[i]:start[i+1]] are the distinct vertices that share an edge with vertex i, ascending (an edge with two equal
+    ends is ignored); E is the number of distinct undirected edges.  pinned[i] is 1 when i is an end of a boundary edge - one that exactly one
+    face corner pair names, duplicate faces and opposite windings counted.  Raises ValueError on a face index outside [0, num_verts)."""
+    faces = faces.contiguous()
+    ops.check_faces(faces, num_verts)
+    dev = faces.device
+    if num_verts == 0 or faces.shape[0] == 0:
+        return (torch.zeros(num_verts + 1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
+                torch.zeros(num_verts, dtype=torch.int32, device=dev))
+    return _adjacency(faces, num_verts)
+
+
+@torch.no_grad()
+def smooth_mesh(verts, faces, iterations, lam=SMOOTH_LAMBDA, mu=SMOOTH_MU, check=True):
+    """verts [Nv,3] f32, faces [Nf,3] int64 (device) -> (verts', faces): the mesh after `iterations` iterations of Taubin's lambda | mu
+    smoothing with uniform weights.  The definition (include/addons/ln3d_meshsmooth.h; all arithmetic float32, every output is unique,
+    nothing depends on scheduling):
+      - every face contributes its three undirected edges {a, b}; an edge with a == b is ignored; duplicate faces and opposite windings
+        contribute the same edge again;
+      - the neighbours of vertex i are the DISTINCT vertices that share an edge with it, in ascending index j_1 < ... < j_d;
+      - an edge named by exactly one face corner pair is a boundary edge and both its ends are pinned; a pinned vertex never moves, and
+        neither does one with d = 0; edges named twice or more, non-manifold ones included, are interior;
+      - one pass with the factor f, per axis, for a free vertex: s = x[j_1], then s = fl(s + x[j_k]) for k = 2 .. d; m = fl(s / fl32(d));
+        e = fl(m - x_i); x_i' = fl(x_i + fl(f * e)) - every operation rounded once, no fused multiply-add; every pass reads the previous
+        pass's coordinates only;
+      - one iteration is a pass with lam, then a pass with mu; mu = 0 skips the second pass (plain Laplacian smoothing, which shrinks).
+    Faces, vertex count and vertex order are unchanged; `faces` is returned as given.  iterations None or 0 returns its arguments and
+    launches nothing, and so does a mesh without vertices or faces (nothing can move).  The adjacency is built once per call
+    (mesh_adjacency); each pass is one launch.
+    Raises ValueError on a bad dtype or shape, a face index out of range, a non-finite vertex (one read-back), iterations not an integer in
+    [0, 1000], lam not in (0, 1] and mu not in [-1, 0].
+    NOT promised: the weights are uniform, not cotangent, so vertices also drift along the surface; vertices move off the level set; features
+    sharper than the pass band are rounded; the volume is not preserved exactly; boundary loops stay jagged, because they are pinned.
+    check=False skips the face-index check and its read-back, for a caller whose faces index verts by construction (_coloured_mesh)."""
+    iterations, lam, mu = _smooth_args(iterations, lam, mu)
+    if iterations == 0:
+        return verts, faces
+    _check_verts(verts)
+    nv, nf = verts.shape[0], faces.shape[0]
+    cverts, cfaces = verts.contiguous(), faces.contiguous()
+    if check:
+        ops.check_faces(cfaces, nv)
+    elif faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces: expected an int64 [Nf, 3] tensor, got {faces.dtype} {tuple(faces.shape)}")
+    if nv == 0 or nf == 0:
+        return verts, faces
+    if not bool(torch.isfinite(cverts).all()):                          # one read-back
+        raise ValueError("verts: a coordinate is not finite")
+    start, nbr, pinned = _adjacency(cfaces, nv)
+    if nbr.shape[0] == 0:
+        return verts, faces
+    cur, spare = cverts, [torch.empty_like(cverts), torch.empty_like(cverts)]
+    for _ in range(iterations):
+        for factor in (lam, mu) if mu != 0.0 else (lam,):
+            out = spare[0] if cur is not spare[0] else spare[1]          # never the buffer the pass reads
+            ops.smooth_step(cur, start, nbr, pinned, factor, out, check=False)
+            cur = out
+    return cur, faces
 
 
 @torch.no_grad()
@@ -398,11 +511,15 @@ def bake_texture(decoder, planes_channel_last, verts_box, faces, size, fill=0):
     return atlas_uvs(nf, size), tex.view(size, size, 3).cpu().numpy()
 
 
-def _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces, simplify_cell):
+def _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces, simplify_cell,
+                   smooth=(0, SMOOTH_LAMBDA, SMOOTH_MU)):
     """what mesh_from_grid and textured_mesh_from_grid share: (the one sample's planes, the box-space vertices and the faces on the device,
-    then verts, faces, colors, vn as mesh_from_grid returns them; vn is None without normals)"""
+    then verts, faces, colors, vn as mesh_from_grid returns them; vn is None without normals).  smooth: (iterations, lam, mu) of smooth_mesh,
+    applied to the extracted mesh in grid coordinates, so everything behind it sees the smoothed positions."""
+    _smooth_args(*smooth)                                                # a bad value is refused before anything is extracted
     sigma = sigma.reshape(grid_size, grid_size, grid_size)
     verts, faces = extract_isosurface(sigma, thr, method, keep, min_faces, simplify_cell)
+    verts, faces = smooth_mesh(verts, faces, *smooth, check=False)       # faces are the extraction's own: in range by construction
     vtx = (verts / (grid_size - 1) * 2 - 1) * 0.45                       # g-objaverse scale
     pcl = dec_out.get('planes_channel_last')
     if pcl is None:
@@ -418,7 +535,7 @@ def _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method
 
 @torch.no_grad()
 def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes', normals=False,
-                   keep='all', min_faces=0, simplify_cell=0.0):
+                   keep='all', min_faces=0, simplify_cell=0.0, smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU):
     """nsr/train_util_diffusion.py:221-244: iso-surface of the sigma grid at `thr`, vertices mapped to the +-0.45 box, coloured
     by re-querying the tri-plane at the vertices (forward_points), rotated -90 degrees about x.
     Returns (verts [Nv,3] float32 numpy, faces [Nf,3] int64 numpy, colors [Nv,3] uint8 numpy); writes `path` when given.
@@ -428,9 +545,12 @@ def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0,
     keep / min_faces (opt-in; no reference counterpart): clean_mesh right after the weld, so only the surviving components are coloured (and
     given normals) and written; what survives has the bits it has in the uncleaned mesh.  Nothing surviving writes an .obj with no records.
     simplify_cell (opt-in, in grid units; no reference counterpart): simplify_mesh behind the clean-up and before the query, so colours and `vn`
-    are the field's values AT THE NEW VERTICES and discarded vertices cost nothing.  See simplify_mesh for what clustering does not promise."""
+    are the field's values AT THE NEW VERTICES and discarded vertices cost nothing.  See simplify_mesh for what clustering does not promise.
+    smooth_iters / smooth_lambda / smooth_mu (opt-in; no reference counterpart): smooth_mesh behind the clean-up and the simplification, in
+    grid coordinates, before the box mapping and the query, so colours and `vn` are the field's values AT THE SMOOTHED POSITIONS, which lie
+    off the level set; faces are unchanged.  0 iterations launches nothing.  See smooth_mesh for what smoothing does not promise."""
     _, _, _, v, f, colors, vn = _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces,
-                                               simplify_cell)
+                                               simplify_cell, (smooth_iters, smooth_lambda, smooth_mu))
     if path:
         write_obj(path, v, f, colors.astype(np.float32) / 255.0, vn)
     return (v, f, colors, vn) if normals else (v, f, colors)
@@ -438,7 +558,8 @@ def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0,
 
 @torch.no_grad()
 def textured_mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes', texture_size=1024,
-                            normals=False, keep='all', min_faces=0, simplify_cell=0.0):
+                            normals=False, keep='all', min_faces=0, simplify_cell=0.0, smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA,
+                            smooth_mu=SMOOTH_MU):
     """mesh_from_grid plus a baked texture (opt-in; no reference counterpart): the same geometry, vertex colours and `vn`, bit for bit, for
     the same options, then bake_texture of the faces at the box-space vertices (before the rotation, where the field lives) into a
     texture_size x texture_size per-face atlas.  Returns mesh_from_grid's tuple with (uv [Nf,3,2] float32, tex [T,T,3] uint8) appended.
@@ -447,10 +568,11 @@ def textured_mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample
     a mesh fit a small texture.
     NOT promised: more than half of the atlas is unused; texel density is uniform per face, not per unit area; there is one field sample per
     texel, no supersampling; there is no mip-safe padding beyond the 1 - 1.5 texel gutter; and the colours are the field's values on the
-    (possibly simplified) triangles, which lie off the level set by the simplifier's error."""
+    (possibly simplified, possibly smoothed: smooth_iters / smooth_lambda / smooth_mu are mesh_from_grid's) triangles, which lie off the
+    level set by the simplifier's and the smoother's error."""
     _atlas_size(texture_size)
     pcl, vtx, faces, v, f, colors, vn = _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces,
-                                                       simplify_cell)
+                                                       simplify_cell, (smooth_iters, smooth_lambda, smooth_mu))
     uv, tex = bake_texture(decoder, pcl, vtx, faces, texture_size)
     if path:
         write_obj_textured(path, v, f, colors.astype(np.float32) / 255.0, uv, vn)
@@ -459,11 +581,13 @@ def textured_mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample
 
 
 @torch.no_grad()
-def export_mesh(decoder, dec_out, path, grid_size=192, thr=10.0, sample_index=0, normals=False, keep='all', min_faces=0, simplify_cell=0.0):
+def export_mesh(decoder, dec_out, path, grid_size=192, thr=10.0, sample_index=0, normals=False, keep='all', min_faces=0, simplify_cell=0.0,
+                smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU):
     """decoder: the VAE decoder module; dec_out: its vit_decode_postprocess dict.  Writes `path` (.obj), with `vn` records when normals;
-    keep / min_faces / simplify_cell: mesh_from_grid's."""
+    keep / min_faces / simplify_cell / smooth_iters / smooth_lambda / smooth_mu: mesh_from_grid's."""
     pcl = dec_out['planes_channel_last'][sample_index:sample_index + 1]
     grid = decoder.triplane_decode_grid({'planes_channel_last': pcl}, grid_size)
     v, f = mesh_from_grid(decoder, {'planes_channel_last': pcl}, grid['sigma'][0], grid_size, thr, 0, path, normals=normals, keep=keep,
-                          min_faces=min_faces, simplify_cell=simplify_cell)[:2]
+                          min_faces=min_faces, simplify_cell=simplify_cell, smooth_iters=smooth_iters, smooth_lambda=smooth_lambda,
+                          smooth_mu=smooth_mu)[:2]
     return v.shape[0], f.shape[0]

@@ -482,6 +482,48 @@ def bake_pack(rgb, owner, fill, tex):
     L.check(L.lib().ln3d_bake_pack(_p(rgb), _p(owner), P, int(fill), _p(tex), _stream()), "bake_pack")
 
 
+def smooth_edge_keys(faces, nv, key, check=True):
+    """key [3 nf] int64 <- the undirected edge (lo << 32) | hi between corners j and (j + 1) % 3 of every face, -1 where they are equal
+    (include/addons/ln3d_meshsmooth.h); faces [nf,3] int64 of a mesh with nv vertices.  check=False: the caller has already put these faces
+    through check_faces."""
+    nf = faces.shape[0]
+    _buffer(faces, torch.int64, (nf, 3), "faces")
+    _buffer(key, torch.int64, (3 * nf,), "key")
+    if check:
+        check_faces(faces, nv)
+    L.check(L.lib().ln3d_smooth_edge_keys(_p(faces), nf, _p(key), _stream()), "smooth_edge_keys")
+
+
+def smooth_halfedges(edge, count, nv, dkey, pinned, check=True):
+    """dkey [2 ne] int64 <- every distinct edge of edge [ne] int64 in both directions, (src << 32) | dst; pinned [nv] int32, ZEROED BY THE
+    CALLER, <- 1 at both ends of every edge whose count [ne] int64 is 1.  check=False: the caller has made edge from smooth_edge_keys."""
+    ne = edge.shape[0]
+    _buffer(edge, torch.int64, (ne,), "edge")
+    _buffer(count, torch.int64, (ne,), "count")
+    _buffer(dkey, torch.int64, (2 * ne,), "dkey")
+    _buffer(pinned, torch.int32, (nv,), "pinned")
+    if check:
+        check_index(torch.stack([edge >> 32, edge & 0xffffffff]), nv, "edge (both ends)")
+    L.check(L.lib().ln3d_smooth_halfedges(_p(edge), _p(count), ne, nv, _p(dkey), _p(pinned), _stream()), "smooth_halfedges")
+
+
+def smooth_step(verts_in, start, nbr, pinned, factor, verts_out, check=True):
+    """verts_out [nv,3] f32 <- one smoothing pass of verts_in with `factor` over the CSR adjacency start [nv + 1] int64, nbr [nh] int32;
+    a vertex whose pinned [nv] int32 is set, or whose row is empty, is copied.  verts_out may not overlap verts_in.  check=False: the caller
+    has made start and nbr itself (mesh.mesh_adjacency)."""
+    nv, nh = verts_in.shape[0], nbr.shape[0]
+    _buffer(verts_in, torch.float32, (nv, 3), "verts_in")
+    _buffer(start, torch.int64, (nv + 1,), "start")
+    _buffer(nbr, torch.int32, (nh,), "nbr")
+    _buffer(pinned, torch.int32, (nv,), "pinned")
+    _buffer(verts_out, torch.float32, (nv, 3), "verts_out")
+    if check:
+        if int(start[0]) != 0 or int(start[-1]) != nh or bool((start[1:] < start[:-1]).any()):          # so every entry lies in [0, nh]
+            raise ValueError("start: expected an ascending row-pointer array from 0 to the number of half-edges")
+        check_index(nbr.long(), nv, "nbr")
+    L.check(L.lib().ln3d_smooth_step(_p(verts_in), _p(start), _p(nbr), _p(pinned), nv, nh, float(factor), _p(verts_out), _stream()), "smooth_step")
+
+
 def lincomb(y, ks, cs, out):
     n = len(ks)
     arr_k = (C.c_void_p * n)(*[_p(k) for k in ks])
