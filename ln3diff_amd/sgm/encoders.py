@@ -142,7 +142,11 @@ class FrozenCLIPEmbedder(_cache.PackedWeights, nn.Module):
         B, T = ids.shape
         D = P['tok'].shape[1]
         H = tm.heads
-        assert D // H in (64, 128), "attention kernel head sizes"
+        # refused before any launch: causal masking exists in the short-sequence attention kernel only, and the position table has
+        # one row per token
+        if D // H != 64 or T > 128 or T > P['pos'].shape[0]:
+            raise ValueError(f"FrozenCLIPEmbedder: the causal attention kernel serves 64-wide heads and at most 128 tokens, the position "
+                             f"table has {P['pos'].shape[0]} rows; got head size {D // H} ({D} / {H} heads) and {T} tokens")
         M = B * T
         ids_dev = ids.to(device=dev, dtype=torch.int32).contiguous()
         x = ws.get('x', (M, D), torch.float32)

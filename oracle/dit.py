@@ -121,6 +121,9 @@ class operand_rounding:
         queries of a wave when a tile of any of them outgrows it by more than 2^8 (the deferred re-base); bf16 rounding is not
         invariant under the factor 2^(m - max), so this decides which way each probability rounds.  The cross-attention that runs
         inside the query projection (LN3D_EPI_CROSS_ATTN, <= 96 keys) has all keys in one tile: m is the row maximum;
+      * the causal attention of the CLIP text tower (sdpa(causal=True): attn_short_kernel, Dh 64, <= 128 keys) is a single pass over all
+        keys like that epilogue: q stored bf16, the scale on the fp32 scores, m the row maximum over the UNMASKED keys, the row sum over
+        the unrounded P, a masked P exactly 0 (tests/cond_token_refs.py);
       * a cross-attention k-norm runs as a pass of its own over the bf16 keys the K projection wrote (_cross_kv): k is rounded in
         front of the norm as well as behind it.
     Not restated: the K-resident kernel (a head for every CU: none of the shapes these tests use), whose row sum is taken over the
@@ -167,30 +170,45 @@ def rms_norm(x, w, eps=1e-5):
     return x * w if w is not None else x
 
 
-def sdpa(q, k, v, one_tile=False):
-    """q,k,v [B,H,N,Dh]: softmax(q k^T / sqrt(Dh)) v, no mask, no dropout.  one_tile: the attention runs inside the query
-    projection's epilogue (all keys in one tile); only the kernel_arith restatement looks at it."""
+def _causal_masked(s):
+    """scores [.., Nq, Nk] with the keys behind each query (key > query) at -inf"""
+    future = torch.ones(s.shape[-2], s.shape[-1], dtype=torch.bool, device=s.device).triu(1)
+    return s.masked_fill(future, float('-inf'))
+
+
+def sdpa(q, k, v, one_tile=False, causal=False):
+    """q,k,v [B,H,N,Dh]: softmax(q k^T / sqrt(Dh)) v, no dropout; causal: query i sees keys 0..i (the CLIP text tower).  one_tile:
+    the attention runs inside the query projection's epilogue (all keys in one tile); only the kernel_arith restatement looks at it."""
     if OPERAND_ROUND[0] is None:
         s = (q @ k.transpose(-1, -2)) * (q.shape[-1] ** -0.5)
-        return torch.softmax(s, dim=-1) @ v
+        return torch.softmax(_causal_masked(s) if causal else s, dim=-1) @ v
     if KERNEL_ARITH[0]:
-        return _sdpa_kernel(q, k, v, one_tile)
+        return _sdpa_kernel(q, k, v, one_tile, causal)
     # the kernels' arithmetic: q pre-scaled then rounded, un-normalised probabilities rounded for the P.V product, fp32 row sum
     s = _r(q * (q.shape[-1] ** -0.5)) @ _r(k).transpose(-1, -2)
+    if causal:
+        s = _causal_masked(s)
     p = torch.exp(s - s.amax(-1, keepdim=True))
     return (_r(p) @ _r(v)) / p.sum(-1, keepdim=True)
 
 
-def _sdpa_kernel(q, k, v, one_tile):
+def _sdpa_kernel(q, k, v, one_tile, causal=False):
     """operand_rounding(kernel_arith=True): the softmax of attention.hip's ring / streaming kernels and of the cross-attention
-    epilogue, key tile by key tile with their running reference (see operand_rounding).  Scores are in log2 units."""
+    epilogue, key tile by key tile with their running reference (see operand_rounding).  Scores are in log2 units.  causal: the
+    short-sequence kernel (attn_short_kernel: Dh 64, <= 128 keys) - one pass over all keys, so the one_tile form with the masked scores
+    at -inf: the reference is the row maximum over the unmasked keys and a masked probability is exactly 0."""
     Dh, Nq, Nk = q.shape[-1], q.shape[-2], k.shape[-2]
     c = Dh ** -0.5 * 1.4426950408889634
+    if causal:
+        assert Dh == 64 and Nk <= 128, "causal masking exists in the short-sequence kernel only (Dh 64, <= 128 keys)"
+        one_tile = True
     stream = Dh == 64 and Nk % 256 == 0 and not one_tile
     if stream:
         s = _r(_r(q) * c) @ _r(k).transpose(-1, -2)
     else:
         s = (_r(q) @ _r(k).transpose(-1, -2)) * c
+    if causal:
+        s = _causal_masked(s)
     vr = _r(v)
     tile = Nk if one_tile else (32 if stream else 64)
     m, o, l = None, 0.0, 0.0
@@ -261,6 +279,13 @@ def gelu_erf_kernel(x):
         poly = poly * t + c
     hx = x * 0.5
     return hx * (u * poly) + hx
+
+
+def quick_gelu(x):
+    """x * sigmoid(1.702 x), the fc1 activation of the OpenAI CLIP towers.  Exact in every mode: common.h::quick_gelu
+    (x / (1 + __expf(-1.702 x))) is within fp32 ulps of it and the epilogue rounds the value to bf16 right behind it, so it is not
+    restated under kernel_arith (measured on the towers of tests/cond_token_refs.py: no case's rho needs it)."""
+    return x * torch.sigmoid(1.702 * x)
 
 
 def fused_mlp(sd, p, x):
