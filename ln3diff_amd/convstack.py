@@ -56,25 +56,32 @@ def pack_ln(norm, dev):
     return (f32(norm.weight - 1.0, dev), f32(norm.bias, dev), float(norm.eps))           # y = LN(x) (1 + (w - 1)) + b
 
 
+def pack_lin_any(w, b, dev):
+    """pack_lin for any input width (a multiple of 8).  ln3d_gemm_bf16 steps K by 64: a linear / 1x1 whose input width is no multiple of
+    64 is packed as the centre tap of a 3x3 (K = 9 cin, padded; it carries 'kpad') and runs on the im2col of its input - ConvStack.lin."""
+    q = pack_lin(w, b, dev)
+    if q['cin'] % 64:
+        w3 = torch.zeros(q['cout'], q['cin'], 3, 3)
+        w3[:, :, 1, 1] = w.detach().float().cpu().reshape(q['cout'], q['cin'])
+        q = pack_conv3(types.SimpleNamespace(weight=w3, bias=b), dev)
+    return q
+
+
 def pack_resblock(n1, c1, n2, c2, dev, shortcut=None, eps=None):
     q = {'n1': pack_gn(n1, dev, eps), 'c1': pack_conv3(c1, dev), 'n2': pack_gn(n2, dev, eps), 'c2': pack_conv3(c2, dev)}
     if shortcut is not None:
-        q['skip'] = pack_lin(shortcut.weight, shortcut.bias, dev)
-        if q['skip']['cin'] % 64:         # ln3d_gemm_bf16 steps K by 64: a narrower 1x1 runs as the centre tap of a 3x3 (K = 9 cin, padded)
-            w3 = torch.zeros(*shortcut.weight.shape[:2], 3, 3)
-            w3[:, :, 1, 1] = shortcut.weight.detach().float().cpu().reshape(w3.shape[:2])
-            q['skip'] = pack_conv3(types.SimpleNamespace(weight=w3, bias=shortcut.bias), dev)
+        q['skip'] = pack_lin_any(shortcut.weight, shortcut.bias, dev)
     return q
 
 
 def pack_out_proj(w, b, heads, dh, dev):
     """An attention's output projection as (plain, padded): the padded copy has zero columns where the MFMA route's output has its zero-
     padded head dims (None for head sizes that route never takes)."""
-    plain, w2 = pack_lin(w, b, dev), w.detach().reshape(w.shape[0], -1)
+    plain, w2 = pack_lin_any(w, b, dev), w.detach().reshape(w.shape[0], -1)
     if not mfma_head(dh):
         return plain, None
     wp = pad_head_columns(w2, heads, dh)
-    return plain, plain if wp is w2 else pack_lin(wp, b, dev)       # 64 / 72 / 80 / 128: nothing to pad, one copy serves both routes
+    return plain, plain if wp is w2 else pack_lin_any(wp, b, dev)   # 64 / 72 / 80 / 128: nothing to pad, one copy serves both routes
 
 
 def pack_transformer_block(b, heads, dh, cross, dev):
@@ -149,6 +156,19 @@ class ConvStack:
         ops.gemm(col, pc['w'], pc['b'], epi, out)
         return Ho, Wo
 
+    def kcols(self, a_bf, pl):
+        """the GEMM operand of a linear packed by pack_lin_any: a_bf itself, or (input width no multiple of 64) its rows as one-pixel
+        images through im2col - the centre tap, the other eight taps and the tail zero"""
+        if 'kpad' not in pl:
+            return a_bf
+        col = self.alloc('col', (a_bf.shape[0], pl['kpad']), torch.bfloat16)
+        ops.im2col3x3(a_bf, col, a_bf.shape[0], 1, 1, pl['cin'], 1, pl['kpad'])
+        return col
+
+    def lin(self, a_bf, pl, epi, out):
+        """out = (EPI_GATE_RES: out +=) a_bf @ w^T + b for pl = pack_lin_any(w, b)"""
+        ops.gemm(self.kcols(a_bf, pl), pl['w'], pl['b'], epi, out)
+
     def res(self, x, q, N, H, W, emb_silu=None, in_place=True):
         """One ResnetBlock.  in_place: the residual lands on x when no shortcut GEMM makes a new tensor (False: x is needed again)."""
         cin, cout, HW = q['c1']['cin'], q['c1']['cout'], H * W
@@ -180,6 +200,7 @@ class ConvStack:
         """Self-attention of B sequences of L tokens (rows of a_bf in sequence order) -> (bf16 [B*L, heads * head width], padded).
         padded: the MFMA route ran and the head width is attn_out_dim(dh): multiply by the padded output projection."""
         inner = heads * dh
+        a_bf = self.kcols(a_bf, q_qkv)
         if mfma_head(dh) and L >= MFMA_MIN_TOKENS and L % 32 == 0:
             # the fused q|k|v GEMM splits heads in its epilogue (q / k [B, H, L, Dp], V^T [B, H, Dp, L], head size zero-padded: exact, the
             # pad contributes 0 to q.k and meets zero columns of the padded projection); the scratch is keyed by dh because two head

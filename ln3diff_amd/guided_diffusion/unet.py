@@ -11,7 +11,8 @@ ln3diff_amd/convstack.py, with GroupNorm by ln3d_groupnorm_any.  What is the U-N
   ResBlock        the emb Linear, with `h + emb` or the scale / shift modulation folded into the second GroupNorm; never in place (the
                   input may be a saved skip activation)
   transformer     attn2 against the text context: q GEMM, k|v GEMM of the context, ln3d_attention_small
-  AttentionBlock  GroupNorm -> self-attention (qkv rows re-ordered at packing so heads are contiguous per q / k / v) -> proj
+  AttentionBlock  GroupNorm -> self-attention (qkv rows re-ordered at packing so heads are contiguous per q / k / v) -> proj; at a width
+                  that is no multiple of 64 (the GEMM's K step) qkv and proj run as the centre tap of a 3x3, like such a shortcut
 Not built (no released configuration uses them): class conditioning (num_classes), resblock_updown, dims != 2, use_fp16,
 predict_codebook_ids; they raise.
 """
@@ -21,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops, _cache
-from ..convstack import ConvStack, empty_alloc, pack_conv3, pack_gn, pack_lin, pack_out_proj, pack_resblock, pack_transformer
+from ..convstack import ConvStack, empty_alloc, pack_conv3, pack_gn, pack_lin, pack_lin_any, pack_out_proj, pack_resblock, pack_transformer
 from ..dit.dit_models_xformers import f32
 
 
@@ -249,7 +250,7 @@ class UNetModel(_cache.PackedWeights, nn.Module):
             # head is a contiguous column range of q, k and v
             idx = torch.arange(3 * C).reshape(nh, 3, ch).permute(1, 0, 2).reshape(-1)
             w = m.qkv.weight.detach().reshape(3 * C, C)[idx]
-            q = {'n': pack_gn(m.norm, dev), 'qkv': pack_lin(w, m.qkv.bias.detach()[idx], dev), 'heads': nh, 'dh': ch}
+            q = {'n': pack_gn(m.norm, dev), 'qkv': pack_lin_any(w, m.qkv.bias.detach()[idx], dev), 'heads': nh, 'dh': ch}    # any width % 32
             q['proj'], q['projp'] = pack_out_proj(m.proj_out.weight, m.proj_out.bias, nh, ch, dev)
             return ('attention', q)
         raise TypeError(type(m))
@@ -291,8 +292,7 @@ class UNetModel(_cache.PackedWeights, nn.Module):
         a = cs.gn(h, q['n'], N, HW, h.shape[1], False)
         s = h.clone()
         o, padded = cs.self_attend(a, q['qkv'], N, HW, q['heads'], q['dh'], 'u')
-        proj = q['projp' if padded else 'proj']
-        ops.gemm(o, proj['w'], proj['b'], ops.EPI_GATE_RES, s)
+        cs.lin(o, q['projp' if padded else 'proj'], ops.EPI_GATE_RES, s)
         return s
 
     def _run(self, layers, h, N, H, W, emb_silu, ctx_bf, Lc, x_cl=None):
@@ -333,29 +333,11 @@ class UNetModel(_cache.PackedWeights, nn.Module):
             raise ValueError("context %s: expected [%d, L, %d]" % (tuple(context.shape), x.shape[0], self.context_dim))
         if not x.is_cuda:
             raise RuntimeError("ln3diff_amd.UNetModel runs on the HIP device only (no CPU fallback)")
-        dev = x.device
-        P = self._ensure_packed(dev)
+        P = self._ensure_packed(x.device)
         B = x.shape[0]
-        if self.roll_out:                              # 'b (n c) h w -> b c h (n w)', n = 3
-            _, C3, Hh, Ww = x.shape
-            x = x.reshape(B, 3, C3 // 3, Hh, Ww).permute(0, 2, 3, 1, 4).reshape(B, C3 // 3, Hh, 3 * Ww)
-        x = x.contiguous().float()
-        _, Cin, H, W = x.shape
-        # time embedding: sincos(model_channels) -> Linear -> SiLU -> Linear; the ResBlocks consume SiLU(emb)
-        tf = self._new(B, self.model_channels, torch.bfloat16)
-        ops.timestep_embedding(timesteps.to(dev, torch.float32).contiguous(), tf, B, self.model_channels)
-        th = self._new(B, P['t0']['cout'], torch.bfloat16)
-        ops.gemm(tf, P['t0']['w'], P['t0']['b'], ops.EPI_SILU, th)
-        emb = self._new(B, P['t2']['cout'])
-        emb_silu = self._new(B, P['t2']['cout'], torch.bfloat16)
-        ops.gemm(th, P['t2']['w'], P['t2']['b'], ops.EPI_F32_SILU, emb, emb_silu)
-        ctx_bf, Lc = None, 0
-        if context is not None:
-            Lc = context.shape[1]
-            ctx_bf = self._cs.bf(context.to(dev).float().reshape(B * Lc, -1).contiguous())
-        cpad = P['inp'][0][0][1]['c']['cin']
-        x_cl = self._new(B * H * W, cpad, torch.bfloat16)
-        ops.nchw_to_cl_bf16(x, x_cl, B, Cin, H * W, cpad)
+        emb, emb_silu = self._time_embed(timesteps, B)
+        ctx_bf, Lc = self._context(context, B)
+        x_cl, H, W = self._stem_input(x)
         hs = []
         h = None
         for bi, layers in enumerate(P['inp']):
@@ -366,12 +348,50 @@ class UNetModel(_cache.PackedWeights, nn.Module):
             hp, _, _ = hs.pop()
             h = torch.cat([h, hp], dim=1)              # channel-last: the skip concat is along the last axis
             h, H, W = self._run(layers, h, B, H, W, emb_silu, ctx_bf, Lc)
+        return self._head(h, B, H, W)
+
+    # the named steps of forward (packed weights in place; tests/test_unet_pixels_gpu.py judges each against the float64 oracle)
+    def _time_embed(self, timesteps, B):
+        """sincos(model_channels) -> Linear -> SiLU -> Linear -> (emb f32 [B, 4 model_channels], SiLU(emb) bf16: what the ResBlocks consume)"""
+        P, dev = self._packed, self._packed['device']
+        tf = self._new(B, self.model_channels, torch.bfloat16)
+        ops.timestep_embedding(timesteps.to(dev, torch.float32).contiguous(), tf, B, self.model_channels)
+        th = self._new(B, P['t0']['cout'], torch.bfloat16)
+        ops.gemm(tf, P['t0']['w'], P['t0']['b'], ops.EPI_SILU, th)
+        emb = self._new(B, P['t2']['cout'])
+        emb_silu = self._new(B, P['t2']['cout'], torch.bfloat16)
+        ops.gemm(th, P['t2']['w'], P['t2']['b'], ops.EPI_F32_SILU, emb, emb_silu)
+        return emb, emb_silu
+
+    def _context(self, context, B):
+        """context [B, Lc, context_dim] or None -> (bf16 [B * Lc, context_dim] or None, Lc)"""
+        if context is None:
+            return None, 0
+        Lc = context.shape[1]
+        return self._cs.bf(context.to(self._packed['device']).float().reshape(B * Lc, -1).contiguous()), Lc
+
+    def _stem_input(self, x):
+        """x NCHW (roll_out: 'b (n c) h w -> b c h (n w)', n = 3) -> (bf16 channel-last [B*H*W, cin padded to 8], H, W)"""
+        B = x.shape[0]
+        if self.roll_out:
+            _, C3, Hh, Ww = x.shape
+            x = x.reshape(B, 3, C3 // 3, Hh, Ww).permute(0, 2, 3, 1, 4).reshape(B, C3 // 3, Hh, 3 * Ww)
+        x = x.contiguous().float()
+        _, Cin, H, W = x.shape
+        cpad = self._packed['inp'][0][0][1]['c']['cin']
+        x_cl = self._new(B * H * W, cpad, torch.bfloat16)
+        ops.nchw_to_cl_bf16(x, x_cl, B, Cin, H * W, cpad)
+        return x_cl, H, W
+
+    def _head(self, h, B, H, W):
+        """out.0 GroupNorm + SiLU -> out.2 conv -> NCHW f32 (roll_out: 'b c h (n w) -> b (n c) h w')"""
+        P = self._packed
         a = self._cs.gn(h, P['norm_out'], B, H * W, h.shape[1], True)
         o_cl = self._new(B * H * W, self.out_channels)
         self._cs.conv3(a, B, H, W, P['conv_out'], o_cl)
-        out = torch.empty(B, self.out_channels, H, W, device=dev, dtype=torch.float32)
+        out = torch.empty(B, self.out_channels, H, W, device=h.device, dtype=torch.float32)
         ops.cl_to_nchw_f32(o_cl, out, B, self.out_channels, H * W)
-        if self.roll_out:                              # 'b c h (n w) -> b (n c) h w'
+        if self.roll_out:
             out = out.reshape(B, self.out_channels, H, 3, W // 3).permute(0, 3, 1, 2, 4).reshape(B, 3 * self.out_channels, H, W // 3).contiguous()
         return out
 

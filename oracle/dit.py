@@ -125,7 +125,13 @@ class operand_rounding:
         keys like that epilogue: q stored bf16, the scale on the fp32 scores, m the row maximum over the UNMASKED keys, the row sum over
         the unrounded P, a masked P exactly 0 (tests/cond_token_refs.py);
       * a cross-attention k-norm runs as a pass of its own over the bf16 keys the K projection wrote (_cross_kv): k is rounded in
-        front of the norm as well as behind it.
+        front of the norm as well as behind it;
+      * the U-Net's self-attention (oracle/unet.py attend) hands the MFMA kernels heads zero-padded to 64 / 80 / 128 with the scale of
+        the TRUE head size (dit_models_xformers.self_attention_hip: scale=Dh ** -0.5, head_dim_pad=Dp): _sdpa_kernel(dh_true=...) takes
+        the padded width for the kernel choice (32 / 40 / 48 -> 64 over a multiple of 256 keys is the streaming kernel) and the true
+        one for the scale; below 256 tokens, at head sizes the MFMA route refuses and against a context it is attn_small_kernel
+        (csrc/unet_ops.hip:120-153): q / k / v in bf16, the scale on the fp32 scores (:136), the probabilities NOT rounded (:142,
+        :150), the output rounded to bf16 (:151).
     Not restated: the K-resident kernel (a head for every CU: none of the shapes these tests use), whose row sum is taken over the
     ROUNDED probabilities.
 
@@ -192,13 +198,15 @@ def sdpa(q, k, v, one_tile=False, causal=False):
     return (_r(p) @ _r(v)) / p.sum(-1, keepdim=True)
 
 
-def _sdpa_kernel(q, k, v, one_tile, causal=False):
+def _sdpa_kernel(q, k, v, one_tile, causal=False, dh_true=None):
     """operand_rounding(kernel_arith=True): the softmax of attention.hip's ring / streaming kernels and of the cross-attention
     epilogue, key tile by key tile with their running reference (see operand_rounding).  Scores are in log2 units.  causal: the
     short-sequence kernel (attn_short_kernel: Dh 64, <= 128 keys) - one pass over all keys, so the one_tile form with the masked scores
-    at -inf: the reference is the row maximum over the unmasked keys and a masked probability is exactly 0."""
+    at -inf: the reference is the row maximum over the unmasked keys and a masked probability is exactly 0.  dh_true: the heads are
+    zero-padded to the width the kernel runs at (the U-Net's 32 / 40 / 48 -> 64, 96 -> 128; self_attention_hip): the width handed in
+    chooses the kernel, the true one is the scale's."""
     Dh, Nq, Nk = q.shape[-1], q.shape[-2], k.shape[-2]
-    c = Dh ** -0.5 * 1.4426950408889634
+    c = (dh_true or Dh) ** -0.5 * 1.4426950408889634
     if causal:
         assert Dh == 64 and Nk <= 128, "causal masking exists in the short-sequence kernel only (Dh 64, <= 128 keys)"
         one_tile = True
