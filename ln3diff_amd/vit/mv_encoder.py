@@ -163,50 +163,69 @@ class Encoder(_cache.PackedWeights, nn.Module):
         if not x.is_cuda:
             raise RuntimeError("ln3diff_amd encoder runs on the HIP device only (no CPU fallback)")
 
+    def steps(self):
+        """The forward as ordered step names: conv_in, down{l} (the level's ResnetBlocks), down{l}_ds, mid_block_1, mid_attn_1,
+        mid_block_2, conv_out (norm_out + swish + conv_out)."""
+        names = ['conv_in']
+        for lvl, d in enumerate(self.down):
+            names.append(f'down{lvl}')
+            if hasattr(d, 'downsample'):
+                names.append(f'down{lvl}_ds')
+        return names + ['mid_block_1', 'mid_attn_1', 'mid_block_2', 'conv_out']
+
+    @torch.no_grad()
+    def _run_step(self, name, h, N, H, W):
+        """One step of steps() on h [N*H*W, C] f32 channel-last rows (conv_in: the NCHW input itself) -> (h, H, W).  A step without a
+        shortcut GEMM adds its residual onto h in place."""
+        dev = h.device
+        P = self._ensure_packed(dev)
+        cs = self._cs
+        new = lambda rows, cols, dtype=torch.float32: torch.empty(rows, cols, device=dev, dtype=dtype)
+        if name == 'conv_in':
+            pc = P['conv_in']
+            x_cl = new(N * H * W, pc['cin'], torch.bfloat16)
+            ops.nchw_to_cl_bf16(h.contiguous().float(), x_cl, N, h.shape[1], H * W, pc['cin'])
+            out = new(N * H * W, pc['cout'])
+            cs.conv3(x_cl, N, H, W, pc, out)
+            return out, H, W
+        if name.startswith('down'):
+            d = P['down'][int(name[4:].split('_')[0])]
+            if name.endswith('_ds'):                    # Downsample: pad (0,1,0,1), stride 2, padding 0
+                a = cs.bf(h)
+                out = new(N * ((H - 2) // 2 + 1) * ((W - 2) // 2 + 1), d['down']['cout'])
+                H, W = cs.conv3(a, N, H, W, d['down'], out, pad01=True)
+                return out, H, W
+            for q in d['blocks']:
+                h = cs.res(h, q, N, H, W)
+            return h, H, W
+        if name in ('mid_block_1', 'mid_block_2'):
+            return cs.res(h, P['mid1' if name == 'mid_block_1' else 'mid2'], N, H, W), H, W
+        if name == 'mid_attn_1':
+            att = P['attn']
+
+            def attn2(a, b):                            # within each frame
+                o, padded = cs.self_attend(a, b['qkv2'], N, H * W, att['heads'], att['dh'], 'f_')
+                return o, b['o2p' if padded else 'o2']
+            return cs.transformer(h, att, N, H, W, attn2, frames=self.num_frames), H, W
+        if name == 'conv_out':
+            a = cs.gn(h, P['norm_out'], N, H * W, h.shape[1], True)
+            out = new(N * H * W, P['conv_out']['cout'])
+            cs.conv3(a, N, H, W, P['conv_out'], out)
+            return out, H, W
+        raise KeyError(name)
+
     @torch.no_grad()
     def forward_frames(self, x, stages=None):
         """x [B*F, in_channels, S, S] -> conv_out per frame as [B*F, 2*z_channels, S/8, S/8] (an NCHW view of channel-last memory).
         stages: optional dict that receives NCHW copies of every stage (level outputs, middle before / after the attention)."""
-        F = self.num_frames
-        self._check_input(x, F)
-        dev = x.device
-        P = self._ensure_packed(dev)
-        N, Cin, H, W = x.shape
-        cs, pc = self._cs, P['conv_in']
-        new = lambda rows, cols, dtype=torch.float32: torch.empty(rows, cols, device=dev, dtype=dtype)
-        x_cl = new(N * H * W, pc['cin'], torch.bfloat16)
-        ops.nchw_to_cl_bf16(x.contiguous().float(), x_cl, N, Cin, H * W, pc['cin'])
-        h = new(N * H * W, pc['cout'])
-        cs.conv3(x_cl, N, H, W, pc, h)
-
-        def keep(name, t, H, W):
-            if stages is not None:
-                stages[name] = t.view(N, H, W, -1).permute(0, 3, 1, 2).contiguous()
-        keep('conv_in', h, H, W)
-        for lvl, d in enumerate(P['down']):
-            for q in d['blocks']:
-                h = cs.res(h, q, N, H, W)
-            keep(f'down{lvl}', h, H, W)
-            if d['down'] is not None:                   # Downsample: pad (0,1,0,1), stride 2, padding 0
-                a = cs.bf(h)
-                h = new(N * ((H - 2) // 2 + 1) * ((W - 2) // 2 + 1), d['down']['cout'])
-                H, W = cs.conv3(a, N, H, W, d['down'], h, pad01=True)
-                keep(f'down{lvl}_ds', h, H, W)
-        h = cs.res(h, P['mid1'], N, H, W)
-        keep('mid_block_1', h, H, W)
-        att = P['attn']
-
-        def attn2(a, b):                                # within each frame
-            o, padded = cs.self_attend(a, b['qkv2'], N, H * W, att['heads'], att['dh'], 'f_')
-            return o, b['o2p' if padded else 'o2']
-        h = cs.transformer(h, att, N, H, W, attn2, frames=F)
-        keep('mid_attn_1', h, H, W)
-        h = cs.res(h, P['mid2'], N, H, W)
-        keep('mid_block_2', h, H, W)
-        a = cs.gn(h, P['norm_out'], N, H * W, h.shape[1], True)
-        out = new(N * H * W, P['conv_out']['cout'])
-        cs.conv3(a, N, H, W, P['conv_out'], out)
-        return out.view(N, H, W, -1).permute(0, 3, 1, 2)
+        self._check_input(x, self.num_frames)
+        N, _, H, W = x.shape
+        h = x
+        for name in self.steps():
+            h, H, W = self._run_step(name, h, N, H, W)
+            if stages is not None and name != 'conv_out':
+                stages[name] = h.view(N, H, W, -1).permute(0, 3, 1, 2).contiguous()
+        return h.view(N, H, W, -1).permute(0, 3, 1, 2)
 
     @torch.no_grad()
     def forward(self, x, **kwargs):

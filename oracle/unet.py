@@ -205,7 +205,9 @@ def cross_attention(sd, pre, x, context, heads):
     return linear(o.permute(0, 2, 1, 3).reshape(B, N, inner), sd[pre + '.to_out.0.weight'], sd[pre + '.to_out.0.bias'])
 
 
-def spatial_transformer(sd, pre, x, context, p):
+def spatial_transformer(sd, pre, x, context, p, frames=1):
+    """frames: attn1 attends jointly over `frames` consecutive images ('(b f) l c -> b (f l) c': SpatialTransformer3D of the multi-view
+    VAE encoder, ldm/modules/attention.py:390-463); attn2 and the feed-forward stay per image."""
     B, C, H, W = x.shape
     h = _conv(sd, pre + '.proj_in', _gn(sd, pre + '.norm', x, 1e-6), padding=0)
     h = h.permute(0, 2, 3, 1).reshape(B, H * W, -1)
@@ -213,7 +215,8 @@ def spatial_transformer(sd, pre, x, context, p):
     for d in range(p['depth']):
         b = f'{pre}.transformer_blocks.{d}'
         ln = lambda n, t: F.layer_norm(t, (D,), sd[f'{b}.{n}.weight'], sd[f'{b}.{n}.bias'], 1e-5)
-        h = cross_attention(sd, b + '.attn1', ln('norm1', h), None, p['heads']) + h
+        joint = h.reshape(B // frames, frames * H * W, D)
+        h = (cross_attention(sd, b + '.attn1', ln('norm1', joint), None, p['heads']) + joint).reshape(B, H * W, D)
         h = cross_attention(sd, b + '.attn2', ln('norm2', h), context, p['heads']) + h
         g = linear(ln('norm3', h), sd[b + '.ff.net.0.proj.weight'], sd[b + '.ff.net.0.proj.bias'])
         a, gate = g.chunk(2, dim=-1)

@@ -10,7 +10,7 @@ import torch
 
 from conftest import ROOT, golden, load_synth, manifest, rel_l2
 from ln3diff_amd.synth import synth_input, synth_state_dict, orbit_cameras
-from oracle import dit as odit, samplers as osamp, render as orender, decoder as odec
+from oracle import dit as odit, samplers as osamp, render as orender, decoder as odec, encoder as oenc
 
 
 def _sd_from_manifest(g, key='manifest'):
@@ -213,6 +213,42 @@ def test_oracle_decode_tiny_matches_reference_golden():
     planes = odec.vae_decode(sd, latent, 2)
     assert rel_l2(planes[:, :, ::8, ::8], g['planes_sub']) < 1e-4
     assert abs(float(planes.std()) - float(g['planes_std'])) < 1e-4
+
+
+ENCODER_CFG = dict(ch=64, ch_mult=(1, 2, 4, 4), num_res_blocks=1, in_channels=10, z_channels=12, n_heads=8, d_head=64, num_frames=6)
+
+
+def test_oracle_encoder_small_matches_reference_golden_at_every_stage():
+    """oracle.encoder in fp32 against the reference's MVEncoderGSDynamicInp (tests/golden/make_golden_encoder.py), F = 6 at 64 x 64:
+    every stored stage at its stored stride, conv_out and the pooled h.  The stages are stored in fp16, whose own rounding is 2.1e-4 of
+    the tensor (measured: 2.05e-4 .. 2.09e-4 at every stage, against 1.1e-6 for the fp32 conv_out), so a stage is compared in the
+    format it is stored in: the oracle's stage rounded to fp16 like the golden.  Measured: 0 at the nine stages in front of the
+    attention (every fp16 number equal), 1.3e-5 / 1.7e-5 behind it."""
+    import json
+    g = golden('encoder_mv_small')
+    sd = synth_state_dict(manifest(g), 0)
+    taps = {}
+    with torch.no_grad():
+        y = oenc.forward(sd, ENCODER_CFG, synth_input('mv_small', (6, 10, 64, 64), 7), taps)
+        h = oenc.pooled(sd, ENCODER_CFG, synth_input('mv_small', (6, 10, 64, 64), 7))
+    steps = {k: tuple(v) for k, v in json.loads(bytes(g['stage_steps']).decode()).items()}
+    assert list(steps) == oenc.stages(ENCODER_CFG)[:-1] and int(g['n_params']) == sum(v.numel() for v in sd.values())
+    for k, (c, s) in steps.items():
+        want = torch.from_numpy(g['stage_' + k])
+        assert want.dtype == torch.float16
+        got = taps[k][1][:, ::c, ::s, ::s]
+        assert got.shape == want.shape and rel_l2(got.half().float(), want.float()) < 1e-4, (k, rel_l2(got.half().float(), want.float()))
+        assert rel_l2(got, want.float()) < 3e-4, k          # unrounded: the fp16 storage error itself
+    assert rel_l2(y, g['conv_out']) < 1e-4 and rel_l2(h, g['h']) < 1e-4
+
+
+def test_oracle_encoder_two_objects_matches_reference_golden():
+    """B = 2 objects x F = 6: the frame grouping of the joint attention and of the pooling"""
+    g = golden('encoder_mv_b2')
+    sd = synth_state_dict(manifest(g), 0)
+    with torch.no_grad():
+        h = oenc.pooled(sd, ENCODER_CFG, synth_input('mv_b2', (12, 10, 64, 64), 8))
+    assert h.shape == (2, 24, 8, 8) and rel_l2(h, g['h']) < 1e-4
 
 
 def test_oracle_ddim_matches_reference_golden():

@@ -361,14 +361,19 @@ def plan(lines, tmp_path):
     return [(ATTN_KERNELS[a] if a >= 0 else a, g != TILE_S128) for a, g in rows]
 
 
+def launch_line(who, dh, L, route, BH, rows, nmax, cus=CUS):
+    """one stated self-attention launch (and the widest GEMM beside it) as a plan() line, with the statement: (who, route, line)"""
+    from ln3diff_amd.dit.dit_models_xformers import attn_head_pad, attn_out_dim
+    Dp = attn_head_pad(dh)
+    return who, route, (Dp, dh if attn_out_dim(dh) != Dp else 0, L, BH, rows, nmax, 128, cus)
+
+
 def mfma_launches(cus=CUS):
     """every self-attention the cases state to be an MFMA launch, as plan() lines, with the statement: [(who, route, line)]"""
-    from ln3diff_amd.dit.dit_models_xformers import attn_head_pad, attn_out_dim
     out = []
 
     def add(who, dh, L, route, BH, rows, nmax):
-        Dp = attn_head_pad(dh)
-        out.append((who, route, (Dp, dh if attn_out_dim(dh) != Dp else 0, L, BH, rows, nmax, 128, cus)))
+        out.append(launch_line(who, dh, L, route, BH, rows, nmax, cus))
     for net in WALKED:
         B = len(TIMESTEPS)
         heads = {(p['ch'] // p['heads'], p['heads']) for _, layers in ounet.blocks(NETS[net]) for k, p in layers if k in ('attention', 'transformer')}
