@@ -196,6 +196,9 @@ ADDON_PROTOTYPES = {
     "ln3d_smooth_edge_keys": _int(vp, i64, vp, vp),
     "ln3d_smooth_halfedges": _int(vp, vp, i64, i64, vp, vp, vp),
     "ln3d_smooth_step": _int(vp, vp, vp, vp, i64, i64, f32, vp, vp),
+    # include/addons/ln3d_meshsnap.h (Newton projection of points onto a level set of the density field)
+    "ln3d_snap_points": _int(vp, i32, i32, vp, i64, vp, vp, vp, vp, f32, f32, i32, f32, f32, f32, vp, vp, vp, vp, vp),
+    "ln3d_snap_points_f16": _int(vp, i32, i32, vp, i64, vp, vp, vp, vp, f32, f32, i32, f32, f32, f32, vp, vp, vp, vp, vp),
 }
 
 

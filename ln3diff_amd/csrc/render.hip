@@ -27,6 +27,7 @@
 #include "../../include/ln3d.h"
 #include "../../include/ln3d_planes16.h"
 #include "../../include/ln3d_normals.h"
+#include "../../include/addons/ln3d_meshsnap.h"
 
 #define NS 64            // samples per pass (coarse == fine == 64, Objaverse preset)
 #define WAVE_LDS_BYTES 8192           // per wave: 64 points x (64 B hi + 64 B lo) feature rows; reused for cdf / merge arrays
@@ -1411,6 +1412,101 @@ extern "C" int ln3d_query_points_grad_f16(const void* planes, int H, int W, cons
                                           const float* dec_b0, const float* dec_w1, const float* dec_b1, float box_warp, float* sigma,
                                           float* grad, void* stream) {
   return query_points_grad_t<_Float16>(planes, H, W, points, P, dec_w0, dec_b0, dec_w1, dec_b1, box_warp, sigma, grad, stream);
+}
+
+// ------------------------------------------------------------------ level-set snapping (include/addons/ln3d_meshsnap.h)
+// One lane per point, the decoder staged once per block as above.  The loop of the header is turned inside out so that there is ONE
+// call site of sigma_grad_point (it is ~600 instructions and 64 live registers): the outer loop evaluates the pending point - the input
+// first, a candidate afterwards - and the inner loop spends iterations until it has the next candidate to evaluate or the lane is
+// done.  A finished lane leaves both loops, so a wave runs for as many evaluations as its slowest lane needs and not for iters + 1.
+// Everything outside sigma_grad_point is rounded once per operation (`fp contract(off)`; sigma_grad_point keeps its own contraction,
+// which clang records per instruction, so it computes here what it computes in query_points_grad_kernel).
+struct SnapP {
+  const float* pts; int64_t P;
+  const float* w0; const float* b0; const float* w1; const float* b1;
+  float level, tol, max_step, max_dist; int iters;
+  float* out; float* residual; int32_t* state; int32_t* evals;
+};
+
+__device__ __forceinline__ bool snap_finite(float x) { return x - x == 0.0f; }
+
+template <typename TX>
+__global__ __launch_bounds__(256) void snap_points_kernel(const TX* planes, int H, int W, float coord_scale, SnapP a) {
+#pragma clang fp contract(off)
+  __shared__ __attribute__((aligned(16))) float dl[NG_FLOATS];
+  stage_grad_decoder(dl, a.w0, a.b0, a.w1, a.b1);
+  const int64_t nt = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.P; i += nt) {
+    const float in0 = a.pts[3 * i], in1 = a.pts[3 * i + 1], in2 = a.pts[3 * i + 2];
+    float p0 = in0, p1 = in1, p2 = in2, r = 0.f, g0 = 0.f, g1 = 0.f, g2v = 0.f, f = 1.f;      // the best iterate, its residual and gradient
+    float c0 = in0, c1 = in1, c2 = in2;                                                          // the point to evaluate next
+    int it = 0, ne = 0;
+    const bool in_ok = snap_finite(in0) && snap_finite(in1) && snap_finite(in2);
+    bool first = true, stalled = false;
+#pragma unroll 1
+    for (;;) {                                               // terminates: every pass but the first spends at least one of `iters`
+      float sc, gc[3];
+      sigma_grad_point<TX>(planes, H, W, coord_scale, dl, c0, c1, c2, sc, gc);
+      const float rc = sc - a.level;
+      ++ne;
+      if (first || fabsf(rc) < fabsf(r)) { p0 = c0; p1 = c1; p2 = c2; r = rc; g0 = gc[0]; g1 = gc[1]; g2v = gc[2]; f = 1.f; }
+      else f *= 0.5f;
+      first = false;
+      bool go = false;
+#pragma unroll 1
+      while (it < a.iters) {                                 // terminates: it counts up
+        ++it;
+        const float gg = (g0 * g0 + g1 * g1) + g2v * g2v;
+        if (!in_ok || !snap_finite(r) || !snap_finite(gg) || gg == 0.f) { stalled = true; break; }
+        if (fabsf(r) <= a.tol) break;
+        const float len = __fdiv_rn(fabsf(r), __fsqrt_rn(gg));
+        const float al = f * fminf(1.0f, __fdiv_rn(a.max_step, len));
+        const float t = __fdiv_rn(al * r, gg);
+        c0 = p0 - t * g0; c1 = p1 - t * g1; c2 = p2 - t * g2v;
+        const float d0 = c0 - in0, d1 = c1 - in1, d2 = c2 - in2;
+        const float dist = __fsqrt_rn((d0 * d0 + d1 * d1) + d2 * d2);
+        if (!(dist <= a.max_dist)) { f *= 0.5f; continue; }  // too far (or not a number): no evaluation
+        go = true;
+        break;
+      }
+      if (!go) break;
+    }
+    a.out[3 * i] = p0; a.out[3 * i + 1] = p1; a.out[3 * i + 2] = p2;
+    a.residual[i] = r;
+    a.state[i] = fabsf(r) <= a.tol ? 0 : stalled ? 2 : 1;
+    a.evals[i] = ne;
+  }
+}
+
+template <typename TX>
+static int snap_points_t(const void* planes, int H, int W, const float* points_in, int64_t P, const float* dec_w0, const float* dec_b0,
+                         const float* dec_w1, const float* dec_b1, float box_warp, float level, int iters, float tol, float max_step,
+                         float max_dist, float* points_out, float* residual, int32_t* state, int32_t* evals, void* stream) {
+  if (!planes || !points_in || !points_out || !residual || !state || !evals || P < 1 || P > 0x7fffffffll) return LN3D_ERR_BAD_ARG;
+  if (!dec_w0 || !dec_b0 || !dec_w1 || !dec_b1 || !planes_ok(H, W, box_warp, (int)sizeof(TX))) return LN3D_ERR_BAD_ARG;
+  if (iters < 0 || iters > 64 || !(level - level == 0.f) || !(tol - tol == 0.f) || !(max_step - max_step == 0.f) ||
+      !(max_dist - max_dist == 0.f) || !(tol >= 0.f) || !(max_step > 0.f) || !(max_dist >= 0.f)) return LN3D_ERR_BAD_ARG;
+  const uintptr_t in = (uintptr_t)points_in, out = (uintptr_t)points_out, bytes = (uintptr_t)P * 3 * sizeof(float);
+  if ((in <= out ? out - in : in - out) < bytes) return LN3D_ERR_BAD_ARG;      // every lane compares with its input to the end
+  int64_t blocks = (P + 255) / 256;
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  const SnapP a{points_in, P, dec_w0, dec_b0, dec_w1, dec_b1, level, tol, max_step, max_dist, iters, points_out, residual, state, evals};
+  hipLaunchKernelGGL(snap_points_kernel<TX>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const TX*>(planes),
+                     H, W, (float)(2.0 / (double)box_warp), a);
+  return ln3d_check_launch();
+}
+extern "C" int ln3d_snap_points(const float* planes, int H, int W, const float* points_in, int64_t P, const float* dec_w0, const float* dec_b0,
+                                const float* dec_w1, const float* dec_b1, float box_warp, float level, int iters, float tol, float max_step,
+                                float max_dist, float* points_out, float* residual, int32_t* state, int32_t* evals, void* stream) {
+  return snap_points_t<float>(planes, H, W, points_in, P, dec_w0, dec_b0, dec_w1, dec_b1, box_warp, level, iters, tol, max_step, max_dist,
+                              points_out, residual, state, evals, stream);
+}
+extern "C" int ln3d_snap_points_f16(const void* planes_f16, int H, int W, const float* points_in, int64_t P, const float* dec_w0,
+                                    const float* dec_b0, const float* dec_w1, const float* dec_b1, float box_warp, float level, int iters,
+                                    float tol, float max_step, float max_dist, float* points_out, float* residual, int32_t* state,
+                                    int32_t* evals, void* stream) {
+  return snap_points_t<_Float16>(planes_f16, H, W, points_in, P, dec_w0, dec_b0, dec_w1, dec_b1, box_warp, level, iters, tol, max_step,
+                                 max_dist, points_out, residual, state, evals, stream);
 }
 
 // One lane per ray: p = o + (depth / wsum) d on the marcher's own ray, n = -grad sigma / |grad sigma| there.

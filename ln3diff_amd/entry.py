@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from .mesh import MeshPost, _atlas_size, _clean_args, _simplify_cell, _smooth_args, mesh_from_grid, textured_mesh_from_grid
+from .mesh import MeshPost, _atlas_size, _clean_args, _simplify_cell, _smooth_args, _snap_args, mesh_from_grid, textured_mesh_from_grid
 
 # --trainer_name -> engine (scripts/vit_triplane_diffusion_sample_objaverse.py:135-142, scripts/vit_triplane_diffusion_sample.py:236-242)
 TRAINERS = {
@@ -111,6 +111,7 @@ def create_argparser(objaverse=True):
         save_normal_maps=False,              # normal_sample{i}.npy [V,3,R,R]: world-space surface normal maps next to the frames
         mesh_texture_size=0,                 # > 0: every exported mesh gets a baked texture of that many texels a side (.mtl, .png); not a MeshPost field
         mesh_smooth_iters=0,                 # > 0: every exported mesh gets that many iterations of Taubin smoothing before it is coloured; not a MeshPost field
+        mesh_snap_iters=0,                   # > 0: the vertices of every exported mesh are put back on the level set (at most that many Newton iterations) before it is coloured; not a MeshPost field
         **_MESH_FLAGS)
     d.update(_IGNORED_DEFAULTS)
     d.update({k: v[0] for k, v in _CHECKED.items()})
@@ -192,6 +193,13 @@ def validate(args):
         raise SystemExit(f"--mesh_{e}") from None
     if smooth != 0 and not args.export_mesh:
         raise SystemExit("--mesh_smooth_iters: there is no mesh to smooth without --export_mesh true")
+    snap = getattr(args, 'mesh_snap_iters', 0)
+    try:                                     # the library's own check again
+        _snap_args(snap)
+    except ValueError as e:                  # "snap_iters ...: expected an integer in [0, 64]"
+        raise SystemExit(f"--mesh_{e}") from None
+    if snap != 0 and not args.export_mesh:
+        raise SystemExit("--mesh_snap_iters: there is no mesh to snap without --export_mesh true")
     if getattr(args, 'save_normal_maps', False):
         world = int(os.environ.get('WORLD_SIZE', '1'))
         if world > 1 and args.num_samples % world != 0:
@@ -493,7 +501,7 @@ def run(args, objaverse=None):
     cond_all, cond_src = res[0], res[1]
     if rank == 0:
         meta = dict(vars(args), conditioning=cond_src, weights={k: (v or 'synthetic') for k, v in weights_from.items()})
-        for k, default in dict(_MESH_FLAGS, save_normal_maps=False, mesh_texture_size=0, mesh_smooth_iters=0).items():      # recorded when set: a run without them writes the args.json it always wrote
+        for k, default in dict(_MESH_FLAGS, save_normal_maps=False, mesh_texture_size=0, mesh_smooth_iters=0, mesh_snap_iters=0).items():      # recorded when set: a run without them writes the args.json it always wrote
             if meta[k] == default:
                 del meta[k]
         with open(os.path.join(args.logdir, 'args.json'), 'w') as f:
@@ -561,17 +569,18 @@ def run(args, objaverse=None):
         d.update(ae(latent=d, behaviour='decode_after_vae_no_render'))
         grid = ae(latent=d, grid_size=args.mesh_grid, behaviour='triplane_decode_grid')
         smooth = dict(smooth_iters=args.mesh_smooth_iters) if getattr(args, 'mesh_smooth_iters', 0) else {}
+        snap = dict(snap_iters=args.mesh_snap_iters) if getattr(args, 'mesh_snap_iters', 0) else {}
         for i in range(hi - lo):
             path = os.path.join(args.logdir, f'mesh_sample{lo + i}.obj')
             if getattr(args, 'mesh_texture_size', 0):
                 try:
                     textured_mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path,
-                                            texture_size=args.mesh_texture_size, **smooth, **_mesh_post(args)._asdict())
+                                            texture_size=args.mesh_texture_size, **smooth, **snap, **_mesh_post(args)._asdict())
                 except ValueError as e:      # the texture cannot hold this sample's faces: known only once the surface is extracted
                     mesh_err = f"mesh export of sample {lo + i}: --mesh_texture_size {args.mesh_texture_size}: {e}"
                     break
             else:
-                mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path, **smooth, **_mesh_post(args)._asdict())
+                mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path, **smooth, **snap, **_mesh_post(args)._asdict())
             if not os.path.exists(path):
                 mesh_err = f"mesh export of sample {lo + i} produced no file at {path}"
                 break

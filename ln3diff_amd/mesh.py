@@ -10,7 +10,9 @@ behind the clean-up and before the colour query.
 Opt-in texture baking (no reference counterpart; include/ext/ln3d_meshbake.h): textured_mesh_from_grid adds a per-face texture atlas, UVs,
 an .mtl and a .png to what mesh_from_grid makes; mesh_from_grid itself is unchanged.
 Opt-in smoothing (no reference counterpart; include/addons/ln3d_meshsmooth.h): Taubin's lambda | mu passes over the extracted (cleaned,
-simplified) mesh in grid coordinates, before the box mapping, the colour / normal query and the bake."""
+simplified) mesh in grid coordinates, before the box mapping, the colour / normal query and the bake.
+Opt-in level-set snapping (no reference counterpart; include/addons/ln3d_meshsnap.h): a damped Newton projection of the box-space vertices
+onto sigma = thr, behind the smoothing and before the colour / normal query and the bake."""
 import math
 import os
 import struct
@@ -320,6 +322,68 @@ def smooth_mesh(verts, faces, iterations, lam=SMOOTH_LAMBDA, mu=SMOOTH_MU, check
     return cur, faces
 
 
+# ------------------------------------------------------------------ level-set snapping (include/addons/ln3d_meshsnap.h)
+SNAP_MAX_ITERS = ops.SNAP_MAX_ITERS
+
+
+def _snap_args(iterations, tol=None, max_move=None):
+    """-> (iterations as an int, None -> 0; tol or None; max_move in grid units as a float, or None); ValueError when iterations
+    is no integer in [0, 64], tol is given and not a finite number >= 0, or max_move is given and not a finite number > 0"""
+    if iterations is None:
+        iterations = 0
+    try:
+        ok = not isinstance(iterations, bool) and int(iterations) == iterations and 0 <= iterations <= SNAP_MAX_ITERS
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"snap_iters {iterations!r}: expected an integer in [0, {SNAP_MAX_ITERS}], or None for no snapping")
+    if tol is not None:
+        try:
+            t = float(np.float32(tol))
+        except (TypeError, ValueError):
+            t = math.nan
+        if not (math.isfinite(t) and t >= 0):
+            raise ValueError(f"snap_tol {tol!r}: expected a finite number >= 0 (in float32), or None for 1e-3 * max(1, |thr|)")
+    if max_move is not None:
+        try:
+            m = float(np.float32(max_move))
+        except (TypeError, ValueError):
+            m = math.nan
+        if not (math.isfinite(m) and m > 0):
+            raise ValueError(f"snap_max_move {max_move!r}: expected a finite number > 0 of grid cells (in float32), or None for max(1, simplify_cell)")
+        max_move = m
+    return int(iterations), tol, max_move
+
+
+@torch.no_grad()
+def snap_mesh(decoder, planes_channel_last, verts_box, level, iterations, tol=None, max_step=None, max_dist=None):
+    """verts_box [Nv,3] f32 (device, box / world coordinates), planes_channel_last [1,3,H,W,32] of ONE sample, decoder: the VAE decoder
+    module (its snap_points seam) -> (verts' [Nv,3], {'residual' [Nv] f32, 'state' [Nv] int32, 'evals' [Nv] int32}): every vertex put
+    onto sigma = level by at most `iterations` iterations of the damped Newton projection of include/addons/ln3d_meshsnap.h, one fused
+    launch with per-lane early exit.  verts' is the best iterate seen (|residual| never exceeds the input's), never farther than max_dist
+    from its start, each step at most max_step long (world units); residual = sigma(verts') - level as the kernel evaluates it; state 0 =
+    |residual| <= tol, 1 = out of iterations, 2 = stalled.  Vertex count and order never change, so faces stay valid as they are.
+    The defaults are choices, not measurements: tol None = 1e-3 * max(1, |level|); max_dist None = 0.02; max_step None = max_dist / 2.
+    iterations None or 0, or a mesh without vertices, returns verts_box itself with empty-handed diagnostics (residual None) and launches
+    nothing.  Raises ValueError on a bad dtype or shape, iterations not an integer in [0, 64], tol < 0, max_step <= 0, max_dist < 0 or
+    any of them not finite.
+    NOT promised: only vertices are put on the level set, triangle interiors are not; vertices move independently, so faces can fold or
+    flip and thin sheets can collapse onto each other; a vertex may land on a different sheet within max_dist; the field's gradient jumps
+    at texel centres, so convergence is not guaranteed - `state` says which vertices did not converge; and snapping partly undoes the
+    tangential regularity that smoothing produced."""
+    iterations, tol, _ = _snap_args(iterations, tol)
+    _check_verts(verts_box)
+    if max_dist is None:
+        max_dist = 0.02
+    if max_step is None:
+        max_step = max_dist / 2
+    nothing = {'residual': None, 'state': None, 'evals': None}
+    if iterations == 0 or verts_box.shape[0] == 0:
+        return verts_box, nothing
+    r = decoder.snap_points(planes_channel_last, verts_box[None], level, iterations, tol=tol, max_step=max_step, max_dist=max_dist)
+    return r['points'][0], {k: r[k][0] for k in nothing}
+
+
 @torch.no_grad()
 def extract_isosurface(sigma, thr=10.0, method='cubes', keep='all', min_faces=0, simplify_cell=0.0):
     """sigma [G,G,G] f32 device -> (verts [Nv,3] in grid coordinates, faces [Nf,3] int64).  Faces keep the emission order
@@ -512,11 +576,13 @@ def bake_texture(decoder, planes_channel_last, verts_box, faces, size, fill=0):
 
 
 def _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces, simplify_cell,
-                   smooth=(0, SMOOTH_LAMBDA, SMOOTH_MU)):
+                   smooth=(0, SMOOTH_LAMBDA, SMOOTH_MU), snap=(0, None, None)):
     """what mesh_from_grid and textured_mesh_from_grid share: (the one sample's planes, the box-space vertices and the faces on the device,
     then verts, faces, colors, vn as mesh_from_grid returns them; vn is None without normals).  smooth: (iterations, lam, mu) of smooth_mesh,
-    applied to the extracted mesh in grid coordinates, so everything behind it sees the smoothed positions."""
+    applied to the extracted mesh in grid coordinates, so everything behind it sees the smoothed positions.  snap: (iterations, tol, max_move
+    in grid units) of snap_mesh at level = thr, applied to the box-space vertices behind that and before the query."""
     _smooth_args(*smooth)                                                # a bad value is refused before anything is extracted
+    snap_iters, snap_tol, snap_move = _snap_args(*snap)
     sigma = sigma.reshape(grid_size, grid_size, grid_size)
     verts, faces = extract_isosurface(sigma, thr, method, keep, min_faces, simplify_cell)
     verts, faces = smooth_mesh(verts, faces, *smooth, check=False)       # faces are the extraction's own: in range by construction
@@ -525,6 +591,9 @@ def _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method
     if pcl is None:
         pcl = decoder.triplane_decoder.to_channel_last(dec_out['latent_after_vit'])        # f32, or f16 under set_plane_precision('fp16')
     pcl = pcl[sample_index:sample_index + 1]
+    if snap_iters:                                                       # one grid cell is 0.9 / (grid_size - 1) in the box
+        move = (snap_move if snap_move is not None else max(1.0, _simplify_cell(simplify_cell))) * 0.9 / (grid_size - 1)
+        vtx = snap_mesh(decoder, pcl, vtx.contiguous(), thr, snap_iters, snap_tol, max_step=move / 2, max_dist=move)[0]
     q = decoder.forward_points(pcl, vtx[None], with_grad=normals) if vtx.shape[0] else {'rgb': vtx[None], 'normal': vtx[None]}
     colors = (q['rgb'][0].clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
     v = (rotation_matrix_x(-90) @ vtx.cpu().numpy().T).T.astype(np.float32)
@@ -535,7 +604,8 @@ def _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method
 
 @torch.no_grad()
 def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes', normals=False,
-                   keep='all', min_faces=0, simplify_cell=0.0, smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU):
+                   keep='all', min_faces=0, simplify_cell=0.0, smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU,
+                   snap_iters=0, snap_tol=None, snap_max_move=None):
     """nsr/train_util_diffusion.py:221-244: iso-surface of the sigma grid at `thr`, vertices mapped to the +-0.45 box, coloured
     by re-querying the tri-plane at the vertices (forward_points), rotated -90 degrees about x.
     Returns (verts [Nv,3] float32 numpy, faces [Nf,3] int64 numpy, colors [Nv,3] uint8 numpy); writes `path` when given.
@@ -548,9 +618,14 @@ def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0,
     are the field's values AT THE NEW VERTICES and discarded vertices cost nothing.  See simplify_mesh for what clustering does not promise.
     smooth_iters / smooth_lambda / smooth_mu (opt-in; no reference counterpart): smooth_mesh behind the clean-up and the simplification, in
     grid coordinates, before the box mapping and the query, so colours and `vn` are the field's values AT THE SMOOTHED POSITIONS, which lie
-    off the level set; faces are unchanged.  0 iterations launches nothing.  See smooth_mesh for what smoothing does not promise."""
+    off the level set; faces are unchanged.  0 iterations launches nothing.  See smooth_mesh for what smoothing does not promise.
+    snap_iters / snap_tol / snap_max_move (opt-in; no reference counterpart): snap_mesh of the box-space vertices at level = thr, behind
+    the smoothing and before the query, so colours and `vn` are the field's values AT THE SNAPPED POSITIONS; faces, vertex count and order
+    never change.  snap_iters in [0, 64]; 0 launches nothing.  snap_max_move is the farthest a vertex may end from where it started, in
+    grid cells; a Newton step is at most half of it.  The defaults are choices, not measurements: snap_tol None = 1e-3 * max(1, |thr|),
+    snap_max_move None = max(1, simplify_cell).  See snap_mesh for what snapping does not promise."""
     _, _, _, v, f, colors, vn = _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces,
-                                               simplify_cell, (smooth_iters, smooth_lambda, smooth_mu))
+                                               simplify_cell, (smooth_iters, smooth_lambda, smooth_mu), (snap_iters, snap_tol, snap_max_move))
     if path:
         write_obj(path, v, f, colors.astype(np.float32) / 255.0, vn)
     return (v, f, colors, vn) if normals else (v, f, colors)
@@ -559,7 +634,7 @@ def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0,
 @torch.no_grad()
 def textured_mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes', texture_size=1024,
                             normals=False, keep='all', min_faces=0, simplify_cell=0.0, smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA,
-                            smooth_mu=SMOOTH_MU):
+                            smooth_mu=SMOOTH_MU, snap_iters=0, snap_tol=None, snap_max_move=None):
     """mesh_from_grid plus a baked texture (opt-in; no reference counterpart): the same geometry, vertex colours and `vn`, bit for bit, for
     the same options, then bake_texture of the faces at the box-space vertices (before the rotation, where the field lives) into a
     texture_size x texture_size per-face atlas.  Returns mesh_from_grid's tuple with (uv [Nf,3,2] float32, tex [T,T,3] uint8) appended.
@@ -569,10 +644,12 @@ def textured_mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample
     NOT promised: more than half of the atlas is unused; texel density is uniform per face, not per unit area; there is one field sample per
     texel, no supersampling; there is no mip-safe padding beyond the 1 - 1.5 texel gutter; and the colours are the field's values on the
     (possibly simplified, possibly smoothed: smooth_iters / smooth_lambda / smooth_mu are mesh_from_grid's) triangles, which lie off the
-    level set by the simplifier's and the smoother's error."""
+    level set by the simplifier's and the smoother's error.  snap_iters / snap_tol / snap_max_move (mesh_from_grid's) put the VERTICES
+    back on it before the bake; the interiors of the triangles stay where the flat faces are."""
     _atlas_size(texture_size)
     pcl, vtx, faces, v, f, colors, vn = _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces,
-                                                       simplify_cell, (smooth_iters, smooth_lambda, smooth_mu))
+                                                       simplify_cell, (smooth_iters, smooth_lambda, smooth_mu),
+                                                       (snap_iters, snap_tol, snap_max_move))
     uv, tex = bake_texture(decoder, pcl, vtx, faces, texture_size)
     if path:
         write_obj_textured(path, v, f, colors.astype(np.float32) / 255.0, uv, vn)
@@ -582,12 +659,12 @@ def textured_mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample
 
 @torch.no_grad()
 def export_mesh(decoder, dec_out, path, grid_size=192, thr=10.0, sample_index=0, normals=False, keep='all', min_faces=0, simplify_cell=0.0,
-                smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU):
+                smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU, snap_iters=0, snap_tol=None, snap_max_move=None):
     """decoder: the VAE decoder module; dec_out: its vit_decode_postprocess dict.  Writes `path` (.obj), with `vn` records when normals;
-    keep / min_faces / simplify_cell / smooth_iters / smooth_lambda / smooth_mu: mesh_from_grid's."""
+    keep / min_faces / simplify_cell / smooth_iters / smooth_lambda / smooth_mu / snap_iters / snap_tol / snap_max_move: mesh_from_grid's."""
     pcl = dec_out['planes_channel_last'][sample_index:sample_index + 1]
     grid = decoder.triplane_decode_grid({'planes_channel_last': pcl}, grid_size)
     v, f = mesh_from_grid(decoder, {'planes_channel_last': pcl}, grid['sigma'][0], grid_size, thr, 0, path, normals=normals, keep=keep,
                           min_faces=min_faces, simplify_cell=simplify_cell, smooth_iters=smooth_iters, smooth_lambda=smooth_lambda,
-                          smooth_mu=smooth_mu)[:2]
+                          smooth_mu=smooth_mu, snap_iters=snap_iters, snap_tol=snap_tol, snap_max_move=snap_max_move)[:2]
     return v.shape[0], f.shape[0]

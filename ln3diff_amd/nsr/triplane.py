@@ -213,6 +213,31 @@ class Triplane(_cache.PackedWeights, nn.Module):
         return ret
 
 
+    @torch.no_grad()
+    def snap_points(self, planes_channel_last_one, points, level, iters, tol=None, max_step=0.01, max_dist=0.02):
+        """points [P,3] against ONE tri-plane [3,H,W,32] (f32 or f16; cast_planes, the decoder and box_warp as query_points) ->
+        {'points': [P,3] f32, 'residual': [P] f32, 'state': [P] int32, 'evals': [P] int32}: the damped Newton projection of every point
+        onto sigma = level in at most `iters` (0 ... 64) iterations of ln3d_snap_points (opt-in; no reference counterpart; the loop and
+        what it does not promise: include/addons/ln3d_meshsnap.h).  'points' is the best iterate seen, never farther than max_dist from
+        its start, each Newton step at most max_step long (both in world units); 'residual' is sigma there minus level; 'state' 0 =
+        |residual| <= tol, 1 = out of iterations, 2 = stalled (no usable gradient); 'evals' the field evaluations spent.  tol None:
+        1e-3 * max(1, |level|) - like the defaults of max_step and max_dist a choice, not a measurement.  No point returns empty
+        tensors and launches nothing."""
+        dev = points.device
+        P = points.shape[0]
+        if tol is None:
+            tol = 1e-3 * max(1.0, abs(float(level)))
+        out = {'points': torch.empty(P, 3, device=dev), 'residual': torch.empty(P, device=dev),
+               'state': torch.empty(P, dtype=torch.int32, device=dev), 'evals': torch.empty(P, dtype=torch.int32, device=dev)}
+        if P == 0:
+            return out
+        H, W = planes_channel_last_one.shape[-3], planes_channel_last_one.shape[-2]
+        pcl, pts = self.cast_planes(planes_channel_last_one).contiguous(), points.contiguous().float()
+        ops.snap_points(pcl, H, W, pts, self._decoder_dev(dev), self.rendering_kwargs['box_warp'], level, iters, tol, max_step, max_dist,
+                        out['points'], out['residual'], out['state'], out['evals'])
+        return out
+
+
 def unit_outward(grad):
     """-g / |g| per row of [..., 3] (density falls towards the outside); 0 where g is 0 or not finite.  Scaled by the largest component
     first, like the kernel, so that the squares neither overflow nor vanish."""

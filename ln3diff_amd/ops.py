@@ -1,7 +1,9 @@
 """Thin torch-tensor wrappers over the C ABI (include/ln3d.h).  torch is used for device
 memory and streams only; every op below is a HIP kernel launch on torch's current stream."""
 import ctypes as C
+import math
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -522,6 +524,44 @@ def smooth_step(verts_in, start, nbr, pinned, factor, verts_out, check=True):
             raise ValueError("start: expected an ascending row-pointer array from 0 to the number of half-edges")
         check_index(nbr.long(), nv, "nbr")
     L.check(L.lib().ln3d_smooth_step(_p(verts_in), _p(start), _p(nbr), _p(pinned), nv, nh, float(factor), _p(verts_out), _stream()), "smooth_step")
+
+
+SNAP_MAX_ITERS = 64
+
+
+def snap_points(planes_cl, H, W, points_in, dec, box_warp, level, iters, tol, max_step, max_dist, points_out, residual, state, evals):
+    """points_out [P,3] f32, residual [P] f32, state [P] int32, evals [P] int32 <- the damped Newton projection of points_in [P,3] f32 onto
+    sigma = level of ONE tri-plane [3, H, W, 32] (torch.float32 or torch.float16 texels), at most `iters` iterations
+    (include/addons/ln3d_meshsnap.h).  points_out may not overlap points_in.  ValueError on a buffer of another dtype, shape or stride, iters
+    not an integer in [0, 64], a level / tol / max_step / max_dist that is not finite (in float32), tol < 0, max_step <= 0, max_dist < 0."""
+    P = points_in.shape[0]
+    _buffer(points_in, torch.float32, (P, 3), "points_in")
+    _buffer(points_out, torch.float32, (P, 3), "points_out")
+    _buffer(residual, torch.float32, (P,), "residual")
+    _buffer(state, torch.int32, (P,), "state")
+    _buffer(evals, torch.int32, (P,), "evals")
+    if planes_cl.dim() != 4 or tuple(planes_cl.shape) != (3, H, W, 32) or not planes_cl.is_contiguous():
+        raise ValueError(f"planes: expected one contiguous channel-last tri-plane of shape {(3, H, W, 32)}, got {tuple(planes_cl.shape)}")
+    if P < 1:
+        raise ValueError("points_in: expected at least one point")
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 0 <= iters <= SNAP_MAX_ITERS:
+        raise ValueError(f"iters {iters!r}: expected an integer in [0, {SNAP_MAX_ITERS}]")
+    vals = {}
+    for name, v in (("level", level), ("tol", tol), ("max_step", max_step), ("max_dist", max_dist)):
+        try:
+            with np.errstate(over='ignore'):
+                vals[name] = float(np.float32(v))
+        except (TypeError, ValueError):
+            vals[name] = math.nan
+        if not math.isfinite(vals[name]):
+            raise ValueError(f"{name} {v!r}: expected a finite number (in float32)")
+    if vals["tol"] < 0 or vals["max_step"] <= 0 or vals["max_dist"] < 0:
+        raise ValueError(f"expected tol >= 0, max_step > 0 and max_dist >= 0 (in float32), got {tol!r}, {max_step!r}, {max_dist!r}")
+    if points_out.data_ptr() == points_in.data_ptr():
+        raise ValueError("points_out: may not be the buffer of points_in")
+    L.check(_plane_entry(planes_cl, "snap_points")(_p(planes_cl), H, W, _p(points_in), P, *(_p(t) for t in dec), box_warp, vals["level"],
+                                                   int(iters), vals["tol"], vals["max_step"], vals["max_dist"], _p(points_out), _p(residual),
+                                                   _p(state), _p(evals), _stream()), "snap_points")
 
 
 def lincomb(y, ks, cs, out):

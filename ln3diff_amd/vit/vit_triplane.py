@@ -145,6 +145,13 @@ class _RendererSeams:
         return {k: torch.stack([o[k] for o in outs], 0) for k in outs[0]}
 
     @torch.no_grad()
+    def snap_points(self, planes_channel_last, points, level, iters, **kw):
+        """points [B,P,3] put onto sigma = level of planes_channel_last[n] (Triplane.snap_points; **kw: its tol, max_step, max_dist) ->
+        {'points': [B,P,3], 'residual', 'state', 'evals': [B,P]}"""
+        outs = [self.triplane_decoder.snap_points(planes_channel_last[n], points[n], level, iters, **kw) for n in range(points.shape[0])]
+        return {k: torch.stack([o[k] for o in outs], 0) for k in outs[0]}
+
+    @torch.no_grad()
     def triplane_decode_grid(self, vit_decode_out, grid_size, aabb=None, **kwargs):
         """vit_triplane.py:290-337, :2052: the grid spans sampler_bbox_min / max when the preset has them, else +- box_warp / 2 (ShapeNet)."""
         pcl = vit_decode_out.get('planes_channel_last')
