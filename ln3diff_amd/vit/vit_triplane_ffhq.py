@@ -173,20 +173,29 @@ class VAE_LDM_V4_vit3D_v3_conv3D_depth2_xformer_mha_PEinit_2d_sincos_uvit_RodinR
 
     def _conv_sr(self, up, res, planes_cl, B, r, R, Cm, Co):
         """Both roll-out convolutions as one launch of the fused implicit-GEMM kernel per object; names the stage 'x0' [B, 3, R, R, 32]."""
+        x0 = self._conv_x0(up, res, B, r, R, Cm, Co)
+        self._conv_planes(x0, planes_cl, B, R, Co)
+        return {'x0': x0}
+
+    def _conv_x0(self, up, res, B, r, R, Cm, Co):
+        """x0 = resize(res) + lrelu(conv3D_0(roll-out of the bf16 planes `up`))"""
         ws, P = self._ws, self._packed
-        N = B * 3
         rowm = ws.get('rowm0', (B, 3, R, Cm), torch.float32)
         colm = ws.get('colm0', (B, 3, R, Cm), torch.float32)
-        ops.rollout_means(up, rowm, colm, N, R, R, Cm)
+        ops.rollout_means(up, rowm, colm, B * 3, R, R, Cm)
         x0 = ws.get('x0', (B, 3, R, R, Co), torch.float32)
         for b in range(B):
             ops.conv3x3_rollout(up[b], rowm[b], colm[b], P['c0'][0], P['c0'][1], res[b], x0[b], R, R, Cm, Co, 0.01)
+        return x0
+
+    def _conv_planes(self, x0, planes_cl, B, R, Co):
+        """planes = x0 + lrelu(conv3D_1(roll-out of x0))"""
+        ws, P = self._ws, self._packed
         rowm1 = ws.get('rowm1', (B, 3, R, Co), torch.float32)
         colm1 = ws.get('colm1', (B, 3, R, Co), torch.float32)
-        ops.rollout_means(x0, rowm1, colm1, N, R, R, Co)
+        ops.rollout_means(x0, rowm1, colm1, B * 3, R, R, Co)
         for b in range(B):
             ops.conv3x3_rollout(x0[b], rowm1[b], colm1[b], P['c1'][0], P['c1'][1], x0[b], planes_cl[b], R, R, Co, Co, 0.01)
-        return {'x0': x0}
 
     # ------------------------------------------------------------------ reference-named stages
     @torch.no_grad()

@@ -189,8 +189,10 @@ def _pack_dino(b, dev, res_w=bf16):
 class _DinoTriplaneDecoderBase(_RendererSeams, _cache.PackedWeights, nn.Module):
     """Latent tokens -> DINOv2 blocks in fusion groups with UViT long skips -> decoder_pred -> unpatchify -> conv_sr -> tri-planes.
     A subclass gives its `superresolution` entries (_sr_modules), packs its token embedding, fusion groups and conv_sr convolutions
-    (_pack_sr, _pack_group), runs one fusion group (_group) and the two convolutions of conv_sr (_conv_sr); `_res_w` / `_res_gemm` are how
-    it carries and applies the weights of the projections that write the residual stream."""
+    (_pack_sr, _pack_group), runs one fusion group (_group) and the two convolutions of conv_sr (_conv_sr = _conv_x0 + _conv_planes);
+    `_res_w` / `_res_gemm` are how it carries and applies the weights of the projections that write the residual stream.  Every step of
+    the forward is a method of its own (_add_pos, _skip_step, _group, _final_norm, _pred, _unpatchify, _short_cut, _upsample), so that a
+    test can drive one step on an input of its choice; forward_vit_decoder and vit_decode_postprocess are those steps in order."""
     _res_w = staticmethod(bf16)
     _res_gemm = staticmethod(gate_res_gemm)
 
@@ -247,6 +249,23 @@ class _DinoTriplaneDecoderBase(_RendererSeams, _cache.PackedWeights, nn.Module):
         """DINOv2 block over each plane's N tokens (objects x planes = B*3 attention batches)."""
         vit_block_hip(self._ws, x, q, B * 3, N, H, self._packed['zeros'], 1e-6, ops.EPI_GELU_ERF, res_gemm=self._res_gemm)
 
+    def _add_pos(self, x, h):
+        """h [B*L, D] <- x [B, L, D] + pos_embed"""
+        B, L, D = x.shape
+        ops.add_table_rows(x.contiguous().float(), self._packed['pos'], h, 1, B, L * D)
+
+    def _skip_step(self, h, q, skip):
+        """h += skip_linear([h, skip]) as two projections onto the residual stream; skip: the bf16 copy of an earlier token state"""
+        M, D = h.shape
+        xb = self._ws.get('skip_x', (M, D), torch.bfloat16)
+        ops.cast_bf16(h, xb)
+        self._res_gemm(xb, q['skip_wx'], q['skip_b'], h)
+        self._res_gemm(skip, q['skip_ws'], None, h)
+
+    def _final_norm(self, h, out):
+        M, D = h.shape
+        ops.layernorm_f32(h, self._packed['norm'][0], self._packed['norm'][1], out, M, D, 1e-6)
+
     @torch.no_grad()
     def forward_vit_decoder(self, x, img_size=None):
         """x [B, 3*256, D] (ldm_upsample output) -> + pos_embed -> 6 fusion groups with UViT skips -> norm; returns f32 [B, 3*256, D].
@@ -258,7 +277,7 @@ class _DinoTriplaneDecoderBase(_RendererSeams, _cache.PackedWeights, nn.Module):
         B, L, D = x.shape
         H, N, M = P['H'], L // 3, B * L
         h = ws.get('x', (M, D), torch.float32)
-        ops.add_table_rows(x.contiguous().float(), P['pos'], h, 1, B, L * D)
+        self._add_pos(x, h)
         groups = P['groups']
         hook = self.__dict__.get('stage_hook')
         skips = []
@@ -270,18 +289,50 @@ class _DinoTriplaneDecoderBase(_RendererSeams, _cache.PackedWeights, nn.Module):
         push()
         for j, q in enumerate(groups):
             if j >= len(groups) // 2:
-                xb = ws.get('skip_x', (M, D), torch.bfloat16)
-                ops.cast_bf16(h, xb)
-                self._res_gemm(xb, q['skip_wx'], q['skip_b'], h)
-                self._res_gemm(skips.pop(), q['skip_ws'], None, h)
+                self._skip_step(h, q, skips.pop())
             self._group(h, q, B, N, H)
             if j < len(groups) // 2 - 1:
                 push()
             if hook is not None:
                 hook(f'blk{j}', h.view(B, L, D))
         out = torch.empty(B, L, D, device=x.device, dtype=torch.float32)
-        ops.layernorm_f32(h, P['norm'][0], P['norm'][1], out, M, D, 1e-6)
+        self._final_norm(h, out)
         return out
+
+    # ------------------------------------------------------------------ the steps of vit_decode_postprocess in front of conv_sr
+    def _pred(self, latent_from_vit):
+        """decoder_pred: f32 tokens [B, L, D] -> f32 [B*L, 16*Cm]"""
+        P, ws = self._packed, self._ws
+        B, L, D = latent_from_vit.shape
+        xb = ws.get('tok_bf', (B * L, D), torch.bfloat16)
+        ops.cast_bf16(latent_from_vit.contiguous(), xb)
+        pred = ws.get('pred', (B * L, P['dp_w'].shape[0]), torch.float32)
+        ops.gemm(xb, P['dp_w'], P['dp_b'], ops.EPI_F32, pred)
+        return pred
+
+    def _unpatchify(self, pred, B):
+        """unpatchify_triplane (p = 4): -> the low-resolution planes f32 [B*3, r, r, Cm] and short_cut's view of them, bf16 [B*3*r*r, Cm]"""
+        ws = self._ws
+        S, p, Cm = self.token_size, 4, self._packed['dp_w'].shape[0] // 16
+        r = S * p
+        lo = ws.get('lo', (B * 3, r, r, Cm), torch.float32)
+        mixed = ws.get('mixed', (B * 3 * r * r, Cm), torch.bfloat16)
+        ops.sr_unpatchify(pred, lo, mixed, B, S, p, Cm)
+        return lo, mixed
+
+    def _short_cut(self, mixed, B):
+        P = self._packed
+        r, Co = self.token_size * 4, P['sc_w'].shape[0]
+        res = self._ws.get('res', (B, 3, r, r, Co), torch.float32)
+        ops.gemm(mixed, P['sc_w'], P['sc_b'], ops.EPI_F32, res)
+        return res
+
+    def _upsample(self, lo, B, R):
+        """the transposed planes (the reference's permute(0, 1, 3, 2)) resized to R x R, bf16: the first convolution's operand"""
+        _, r, _, Cm = lo.shape
+        up = self._ws.get('up', (B, 3, R, R, Cm), torch.bfloat16)
+        ops.resize_bilinear_cl(lo, up, B * 3, r, r, R, R, Cm, transpose=True)
+        return up
 
     @torch.no_grad()
     def vit_decode_postprocess(self, latent_from_vit, ret_dict: dict, want_nchw=True, return_stages=False):
@@ -289,24 +340,16 @@ class _DinoTriplaneDecoderBase(_RendererSeams, _cache.PackedWeights, nn.Module):
         'latent_after_vit' [B, 96, R, R] (want_nchw), 'sr_w_code' and 'cls_token' (None) to ret_dict; return_stages also adds
         'decoder_pred' [B, 768, 2048], the low-resolution planes 'planes_lowres' [B, 3, 64, 64, 128] (channel-last) and whatever stages
         the class's _conv_sr names."""
-        P, ws = self._packed, self._ws
+        P = self._packed
         B, L, D = latent_from_vit.shape
         dev = latent_from_vit.device
         cs = self.superresolution['conv_sr']
         S, p, Cm = self.token_size, 4, P['dp_w'].shape[0] // 16
         r, R, Co = S * p, cs.input_resolution, cs.out_chans // 3
-        N = B * 3
-        xb = ws.get('tok_bf', (B * L, D), torch.bfloat16)
-        ops.cast_bf16(latent_from_vit.contiguous(), xb)
-        pred = ws.get('pred', (B * L, 16 * Cm), torch.float32)
-        ops.gemm(xb, P['dp_w'], P['dp_b'], ops.EPI_F32, pred)
-        lo = ws.get('lo', (N, r, r, Cm), torch.float32)
-        mixed = ws.get('mixed', (N * r * r, Cm), torch.bfloat16)
-        ops.sr_unpatchify(pred, lo, mixed, B, S, p, Cm)
-        res = ws.get('res', (B, 3, r, r, Co), torch.float32)
-        ops.gemm(mixed, P['sc_w'], P['sc_b'], ops.EPI_F32, res)
-        up = ws.get('up', (B, 3, R, R, Cm), torch.bfloat16)
-        ops.resize_bilinear_cl(lo, up, N, r, r, R, R, Cm, transpose=True)
+        pred = self._pred(latent_from_vit)
+        lo, mixed = self._unpatchify(pred, B)
+        res = self._short_cut(mixed, B)
+        up = self._upsample(lo, B, R)
         planes_cl = torch.empty(B, 3, R, R, Co, device=dev, dtype=torch.float32)
         stages = self._conv_sr(up, res, planes_cl, B, r, R, Cm, Co)
         ret_dict.update(dict(cls_token=None, planes_channel_last=planes_cl,
@@ -393,6 +436,12 @@ class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(_PosteriorSeams, _Din
 
     def _conv_sr(self, up, res, planes_cl, B, r, R, Cm, Co):
         """Both 3x3 group convolutions as im2col gathers + the MFMA GEMM, one object plane at a time."""
+        x0 = self._conv_x0(up, res, B, r, R, Cm, Co)
+        self._conv_planes(x0, planes_cl, B, R, Co)
+        return {}
+
+    def _conv_x0(self, up, res, B, r, R, Cm, Co):
+        """x0 = resize(res) + lrelu(conv3D_0(up)); the convolution's output stays in the scratch 't'"""
         P, ws = self._packed, self._ws
         N = B * 3
         up = up.view(N, R, R, Cm)
@@ -404,6 +453,13 @@ class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(_PosteriorSeams, _Din
             ops.gemm(col, w, b, ops.EPI_F32, t[n])
         x0 = ws.get('x0', (B, 3, R, R, Co), torch.float32)
         ops.resize_add_lrelu(res, t, x0, N, r, r, R, R, Co, 0.01)
+        return x0
+
+    def _conv_planes(self, x0, planes_cl, B, R, Co):
+        """planes = x0 + lrelu(conv3D_1(roll-out of x0)); the convolution's output stays in the scratch 't'"""
+        P, ws = self._packed, self._ws
+        N = B * 3
+        t = ws.get('t', (N, R * R, Co), torch.float32)
         rowm = ws.get('rowm', (B, 3, R, Co), torch.float32)
         colm = ws.get('colm', (B, 3, R, Co), torch.float32)
         ops.rollout_means(x0, rowm, colm, N, R, R, Co)
@@ -414,7 +470,6 @@ class RodinSR_256_fusionv5_ConvQuant_liteSR_dinoInit3DAttn(_PosteriorSeams, _Din
                 ops.im2col3x3_rollout(x0[b], rowm[b], colm[b], col, i, R, R, Co, P['c1_kpad'])
                 ops.gemm(col, w, bias, ops.EPI_F32, t[b * 3 + i])
         ops.resize_add_lrelu(x0, t, planes_cl, N, R, R, R, R, Co, 0.01)
-        return {}
 
     # ------------------------------------------------------------------ reference-named stages
     @torch.no_grad()

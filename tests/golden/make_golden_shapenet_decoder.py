@@ -14,6 +14,9 @@ Weights come from ln3diff_amd.synth.synth_vit_state_dict by state-dict name (see
                              attention re-orders query rows across objects when B > 1; decoding is per object)
   shapenet_dec_released.npz  D = 768, B = 1: ldm_upsample, ViT out, decoder_pred, latent_after_vit (sub-sampled), the shapenet64
                              render at 128 x 128 (one view, seeded ray noise) and a 64^3 grid query (sub-sampled)
+  shapenet_reparam_b2.npz    D = 128, B = 2: vae_reparameterization(tokens, sample_posterior=False) of the reference class: the encoder
+                             tokens [2, 256, 384] (fp16-exact values, stored as fp16), the mode latent [2, 12, 32, 32] and the
+                             soft-clamped log-variance [2, 4, 3, 1024] in fp32 (`--reparam-only` writes this file alone)
   shapenet_rendering_kwargs.json   rendering_options_defaults(opts) for the ShapeNet launchers' --cfg / --ray_start / --ray_end
 Every .npz carries the state-dict manifest; it is asserted equal to the package class's.
 """
@@ -161,7 +164,21 @@ def staged(dec, latent):
     return st, ret
 
 
+def reparam_fixture():
+    """the encoder side of the class: ldm_downsample -> unpatchify3D -> quant_conv posterior, mode"""
+    dec, shapes = build_ref(128, 2)
+    assert shapes == pkg_manifest(128, 2), "state-dict manifest differs from the package class (D = 128)"
+    tokens = synth_input('shapenet_enc_tokens', (2, 256, 384), 91).half()
+    with contextlib.redirect_stdout(io.StringIO()):
+        r = dec.vae_reparameterization(tokens.float(), False)
+    save('shapenet_reparam_b2', tokens=tokens, latent=r['latent_normalized_2Ddiffusion'], logvar=r['posterior'].logvar,
+         manifest=manifest_json(shapes))
+
+
 def main():
+    if '--reparam-only' in sys.argv:
+        return reparam_fixture()
+    reparam_fixture()
     rk = ref_rendering_kwargs()
     with open(os.path.join(HERE, 'shapenet_rendering_kwargs.json'), 'w') as f:
         json.dump({'flags': LAUNCHER_FLAGS, 'rendering_kwargs': rk}, f, indent=1, sort_keys=True)

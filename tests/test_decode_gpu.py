@@ -66,6 +66,38 @@ def test_vae_decode_backbone_vs_bf16_operand_oracle(hip_lib, tag, cfg, B):
     assert e_tok < 3e-3, e_tok
 
 
+TINY_TOKENS_MEASURED = 0.404     # worst per-token rho of the tiny DiT2 backbone on gfx950 (MI355X), B = 2
+
+
+def test_tiny_backbone_tokens_per_token(hip_lib):
+    """The whole-tensor 3e-3 above would hide one wrong token in 1536.  The tiny backbone (two DiT2 blocks: in-plane, then global
+    attention) judged per token by the criterion of tests/dit_token_refs.py against the float64 oracle and its
+    operand_rounding(bf16, kernel_arith=True) restatement, B = 2, every token counted; cap by the rule of stage_cap below."""
+    from dit_token_refs import to64, token_rho, worst_token, yardstick, YARD_MEDIAN, YARD_MAX
+    from ln3diff_amd.synth import synth_input
+    from oracle import decoder as odec, dit as odit
+    B, (hidden, depth, heads) = 2, (128, 2, 2)
+    assert B * 3 * heads < torch.cuda.get_device_properties(0).multi_processor_count          # never the K-resident attention kernel
+    dec = build_decoder(hidden, depth, heads)
+    sd, _ = load_synth(dec, 0)
+    dec = dec.cuda()
+    latent = synth_input('latent', (B, 12, 32, 32), 5)
+    tok = dec.vit_decode_backbone({'latent_normalized_2Ddiffusion': latent.cuda()}, 128).cpu()
+    with torch.no_grad():
+        y64 = odec.vae_decode(to64(sd), latent.double(), heads, return_tokens=True)
+        with odit.operand_rounding(torch.bfloat16, kernel_arith=True):
+            y16 = odec.vae_decode(to64(sd), latent.double(), heads, return_tokens=True)
+    med, mx = yardstick(y16, y64, None)
+    assert YARD_MEDIAN[0] <= med <= YARD_MEDIAN[1] and mx <= YARD_MAX, (med, mx)
+    rho, d = token_rho(tok.reshape(y16.shape), y16, y64, None)
+    assert rho.numel() == B * 768 and torch.isfinite(rho).all()
+    where, w = worst_token(rho)
+    cap = stage_cap(TINY_TOKENS_MEASURED)
+    print(f'tiny DiT2 tokens: worst token {where} rho = {w:.4g}, median rho {float(rho.median()):.3g}, tokens {rho.numel()}; yardstick median '
+          f'{med:.2e} (measured: worst {TINY_TOKENS_MEASURED}, cap {cap:g})')
+    assert w <= cap, (where, w, cap)
+
+
 # Per-pixel caps of the conv decoder's stages: the rule of tests/test_dit_tokens_gpu.py (twice the worst measured rho, rounded up to one
 # digit, never above 1.0), per stage.  measured: worst rho of every stage on gfx950 (MI355X)
 STAGE_MEASURED = {'mid.block_1.': 0.177, 'mid.block_2.': 0.161, 'up.3.block.0.': 0.183, 'up.2.block.0.': 0.212, 'up.0.block.0.': 0.220,
