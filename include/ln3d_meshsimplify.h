@@ -20,7 +20,9 @@
  *
  * What the whole does NOT promise: clustering can create non-manifold edges; it can fold triangles over; it pulls convex regions inward by
  * O(cell^2 * curvature) (a representative is the mean of points on the surface); and it merges components that come within a cell of
- * each other.  There is no quadric-error placement and no smoothing.
+ * each other.  There is no smoothing here.  The mean is the placement of THESE entry points; the opt-in quadric-error placement of the
+ * representatives, which keeps creases and corners, is two further entry points in addons/ln3d_meshquadric.h that run between
+ * ln3d_simplify_mean and the compaction and change coordinates only.
  */
 #ifndef LN3D_MESHSIMPLIFY_H
 #define LN3D_MESHSIMPLIFY_H

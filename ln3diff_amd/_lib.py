@@ -192,6 +192,9 @@ EXT_PROTOTYPES = {
 # constant, no name of the tables above.  tests/test_mesh_smooth_cpu.py holds this table row for row to whatever headers that directory has
 # and names no entry and no count, so the next feature adds a header there and its rows here, not a fourth table.
 ADDON_PROTOTYPES = {
+    # include/addons/ln3d_meshquadric.h (quadric-error placement of the simplification's representatives)
+    "ln3d_quadric_pairs": _int(vp, i64, i64, vp, vp),
+    "ln3d_quadric_place": _int(vp, i64, vp, i64, vp, i64, vp, i64, vp, f32, f32, f32, f32, vp, f32, vp, vp, vp),
     # include/addons/ln3d_meshsmooth.h (Taubin smoothing of an exported mesh)
     "ln3d_smooth_edge_keys": _int(vp, i64, vp, vp),
     "ln3d_smooth_halfedges": _int(vp, vp, i64, i64, vp, vp, vp),

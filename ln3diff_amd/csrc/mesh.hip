@@ -13,6 +13,7 @@
 #include "../../include/ln3d_meshclean.h"
 #include "../../include/ln3d_meshsimplify.h"
 #include "../../include/ext/ln3d_meshbake.h"
+#include "../../include/addons/ln3d_meshquadric.h"
 #include "../../include/addons/ln3d_meshsmooth.h"
 #include "mc_table.h"
 
@@ -559,5 +560,106 @@ extern "C" int ln3d_smooth_step(const float* verts_in, const int64_t* start, con
   if ((in <= out ? out - in : in - out) < bytes) return LN3D_ERR_BAD_ARG;      // a pass reads the previous coordinates only
   hipLaunchKernelGGL(smooth_step_kernel, grid_1d(nv), dim3(256), 0, (hipStream_t)stream, verts_in, start, nbr, pinned, nv, n_halfedges, factor,
                      verts_out);
+  return ln3d_check_launch();
+}
+
+// ------------------------------------------------------------------ quadric-error placement (include/addons/ln3d_meshquadric.h)
+// The opt-in second placement rule of the simplification.  The incidence is integer work (pair keys, the caller's sort and searchsorted); the
+// placement is one wavefront per cluster: 64 lanes gather 64 faces' corners at a time (at 45 faces per cluster on average one round; one lane
+// per cluster would walk 45 dependent gathers in a row and leave most of the device idle at 10^4 clusters), every lane sums its faces in
+// ascending order and a butterfly of fixed shape adds the 64 partial sums, so the bits depend on nothing but the input.
+#define QUADRIC_NONE 0x7fffffffffffffffll
+#define QUADRIC_FACE_MASK 0x7fffffffll
+
+__global__ void quadric_pairs_kernel(const int64_t* cfaces, int64_t nf, int64_t* key) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= nf) return;
+  const int64_t a = cfaces[3 * f], b = cfaces[3 * f + 1], c = cfaces[3 * f + 2];
+  key[3 * f] = (a << 31) | f;
+  key[3 * f + 1] = b != a ? ((b << 31) | f) : QUADRIC_NONE;
+  key[3 * f + 2] = (c != a && c != b) ? ((c << 31) | f) : QUADRIC_NONE;
+}
+
+// p_l <- p_l + p_(l xor s) for s = 32 ... 1: every lane ends with the same bits (the addition commutes), the whole wave takes part
+__device__ __forceinline__ float quadric_wave_sum(float v) {
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void quadric_place_kernel(const float* verts, const int64_t* faces, int64_t nf, const int64_t* skey,
+                                                            int64_t npairs, const int64_t* start, int64_t nc, const float* rep_mean, float ox,
+                                                            float oy, float oz, float cell, const int64_t* ckey, float eps, float* rep_out,
+                                                            int32_t* placed) {
+  const int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // four waves of 64 per block, one cluster each
+  if (k >= nc) return;                                                 // wave-uniform: the shuffles below see whole waves
+  const int lane = threadIdx.x & 63;
+  const float mx = rep_mean[3 * k], my = rep_mean[3 * k + 1], mz = rep_mean[3 * k + 2];
+  const int64_t b = max(start[k], (int64_t)0), e = min(start[k + 1], npairs);
+  float a00 = 0.0f, a01 = 0.0f, a02 = 0.0f, a11 = 0.0f, a12 = 0.0f, a22 = 0.0f, r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
+  for (int64_t i = b + lane; i < e; i += 64) {                         // terminates: i counts up to e
+    const int64_t key = skey[i], f = key & QUADRIC_FACE_MASK;
+    if ((key >> 31) != k || f >= nf) continue;                         // not a key of this row: skipped, never followed
+    const int64_t v0 = faces[3 * f], v1 = faces[3 * f + 1], v2 = faces[3 * f + 2];
+    const float ax = verts[3 * v0] - mx, ay = verts[3 * v0 + 1] - my, az = verts[3 * v0 + 2] - mz;
+    const float ux = (verts[3 * v1] - mx) - ax, uy = (verts[3 * v1 + 1] - my) - ay, uz = (verts[3 * v1 + 2] - mz) - az;
+    const float wx = (verts[3 * v2] - mx) - ax, wy = (verts[3 * v2 + 1] - my) - ay, wz = (verts[3 * v2 + 2] - mz) - az;
+    const float nx = uy * wz - uz * wy, ny = uz * wx - ux * wz, nz = ux * wy - uy * wx;
+    const float d = nx * ax + ny * ay + nz * az;
+    a00 += nx * nx; a01 += nx * ny; a02 += nx * nz; a11 += ny * ny; a12 += ny * nz; a22 += nz * nz;
+    r0 += d * nx; r1 += d * ny; r2 += d * nz;
+  }
+  a00 = quadric_wave_sum(a00); a01 = quadric_wave_sum(a01); a02 = quadric_wave_sum(a02);
+  a11 = quadric_wave_sum(a11); a12 = quadric_wave_sum(a12); a22 = quadric_wave_sum(a22);
+  r0 = quadric_wave_sum(r0); r1 = quadric_wave_sum(r1); r2 = quadric_wave_sum(r2);
+  if (lane != 0) return;
+  float x = mx, y = my, z = mz;
+  int ok = 0;
+  const float tr = a00 + a11 + a22;
+  if (tr > 0.0f) {                                                     // false for NaN too
+    const float lam = eps * tr;
+    const float d0 = a00 + lam;                                        // LDL^T of A + lam I: d0, d1, d2 >= lam up to rounding
+    const float l10 = a01 / d0, l20 = a02 / d0;
+    const float d1 = (a11 + lam) - l10 * a01;
+    const float t12 = a12 - l20 * a01;
+    const float l21 = t12 / d1;
+    const float d2 = (a22 + lam) - l20 * a02 - l21 * t12;
+    const float y1 = r1 - l10 * r0;
+    const float y2 = r2 - l20 * r0 - l21 * y1;
+    const float dz = y2 / d2;
+    const float dy = y1 / d1 - l21 * dz;
+    const float dx = r0 / d0 - l10 * dy - l20 * dz;
+    const float px = mx + dx, py = my + dy, pz = mz + dz;
+    const int64_t ck = ckey[k];
+    const float qx = (float)((ck >> 42) & SIMPLIFY_QMAX), qy = (float)((ck >> 21) & SIMPLIFY_QMAX), qz = (float)(ck & SIMPLIFY_QMAX);
+    ok = px - px == 0.0f && py - py == 0.0f && pz - pz == 0.0f &&
+         px >= fmaf(qx, cell, ox) && px <= fmaf(qx + 1.0f, cell, ox) && py >= fmaf(qy, cell, oy) && py <= fmaf(qy + 1.0f, cell, oy) &&
+         pz >= fmaf(qz, cell, oz) && pz <= fmaf(qz + 1.0f, cell, oz);
+    if (ok) { x = px; y = py; z = pz; }
+  }
+  rep_out[3 * k] = x; rep_out[3 * k + 1] = y; rep_out[3 * k + 2] = z;  // the mean's own bits when the placement is refused
+  placed[k] = ok;
+}
+
+extern "C" int ln3d_quadric_pairs(const int64_t* cfaces, int64_t nf, int64_t nc, int64_t* pair_key, void* stream) {
+  if (!cfaces || !pair_key || !count_ok(nf) || !count_ok(nc)) return LN3D_ERR_BAD_ARG;
+  if (nc > SIMPLIFY_QMAX + 1) return LN3D_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(quadric_pairs_kernel, grid_1d(nf), dim3(256), 0, (hipStream_t)stream, cfaces, nf, pair_key);
+  return ln3d_check_launch();
+}
+
+extern "C" int ln3d_quadric_place(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const int64_t* sorted_pair_key, int64_t npairs,
+                                  const int64_t* start, int64_t nc, const float* rep_mean, float origin_x, float origin_y, float origin_z,
+                                  float cell, const int64_t* cluster_cell_key, float eps, float* rep_out, int32_t* placed, void* stream) {
+  if (!verts || !faces || !sorted_pair_key || !start || !rep_mean || !cluster_cell_key || !rep_out || !placed || !count_ok(nv) ||
+      !count_ok(nf) || !count_ok(nc) || npairs < 1 || npairs > 3 * nf || nc > nv || !simplify_finite(cell) || !(cell > 0.0f) ||
+      !simplify_finite(origin_x) || !simplify_finite(origin_y) || !simplify_finite(origin_z) || !simplify_finite(eps) || !(eps > 0.0f) ||
+      !(eps <= 1.0f))
+    return LN3D_ERR_BAD_ARG;
+  if (nc > SIMPLIFY_QMAX + 1) return LN3D_ERR_UNSUPPORTED;
+  const uintptr_t in = (uintptr_t)rep_mean, out = (uintptr_t)rep_out, bytes = (uintptr_t)nc * 3 * sizeof(float);
+  if (in != out && (in < out ? out - in : in - out) < bytes) return LN3D_ERR_BAD_ARG;      // in place, or apart: a cluster reads its own mean only
+  hipLaunchKernelGGL(quadric_place_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, (hipStream_t)stream, verts, faces, nf, sorted_pair_key,
+                     npairs, start, nc, rep_mean, origin_x, origin_y, origin_z, cell, cluster_cell_key, eps, rep_out, placed);
   return ln3d_check_launch();
 }

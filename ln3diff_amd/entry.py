@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from .mesh import MeshPost, _atlas_size, _clean_args, _simplify_cell, _smooth_args, _snap_args, mesh_from_grid, textured_mesh_from_grid
+from .mesh import MeshPost, _atlas_size, _clean_args, _simplify_cell, _placement, _smooth_args, _snap_args, mesh_from_grid, textured_mesh_from_grid
 
 # --trainer_name -> engine (scripts/vit_triplane_diffusion_sample_objaverse.py:135-142, scripts/vit_triplane_diffusion_sample.py:236-242)
 TRAINERS = {
@@ -112,6 +112,7 @@ def create_argparser(objaverse=True):
         mesh_texture_size=0,                 # > 0: every exported mesh gets a baked texture of that many texels a side (.mtl, .png); not a MeshPost field
         mesh_smooth_iters=0,                 # > 0: every exported mesh gets that many iterations of Taubin smoothing before it is coloured; not a MeshPost field
         mesh_snap_iters=0,                   # > 0: the vertices of every exported mesh are put back on the level set (at most that many Newton iterations) before it is coloured; not a MeshPost field
+        mesh_simplify_placement='mean',      # 'quadric': the vertices of a simplified mesh are put where the planes of the faces around their cell meet, which keeps creases and corners (needs --mesh_simplify_cell); not a MeshPost field
         **_MESH_FLAGS)
     d.update(_IGNORED_DEFAULTS)
     d.update({k: v[0] for k, v in _CHECKED.items()})
@@ -200,6 +201,15 @@ def validate(args):
         raise SystemExit(f"--mesh_{e}") from None
     if snap != 0 and not args.export_mesh:
         raise SystemExit("--mesh_snap_iters: there is no mesh to snap without --export_mesh true")
+    place = getattr(args, 'mesh_simplify_placement', 'mean')
+    try:                                     # the library's own check again
+        _placement(place)
+    except ValueError as e:                  # "placement ...: expected one of ['mean', 'quadric']"
+        raise SystemExit(f"--mesh_simplify_{e}") from None
+    if place != 'mean' and not args.export_mesh:
+        raise SystemExit(f"--mesh_simplify_placement {place}: there is no mesh to simplify without --export_mesh true")
+    if place != 'mean' and cell == 0:
+        raise SystemExit(f"--mesh_simplify_placement {place}: there is nothing to place without --mesh_simplify_cell > 0")
     if getattr(args, 'save_normal_maps', False):
         world = int(os.environ.get('WORLD_SIZE', '1'))
         if world > 1 and args.num_samples % world != 0:
@@ -501,7 +511,7 @@ def run(args, objaverse=None):
     cond_all, cond_src = res[0], res[1]
     if rank == 0:
         meta = dict(vars(args), conditioning=cond_src, weights={k: (v or 'synthetic') for k, v in weights_from.items()})
-        for k, default in dict(_MESH_FLAGS, save_normal_maps=False, mesh_texture_size=0, mesh_smooth_iters=0, mesh_snap_iters=0).items():      # recorded when set: a run without them writes the args.json it always wrote
+        for k, default in dict(_MESH_FLAGS, save_normal_maps=False, mesh_texture_size=0, mesh_smooth_iters=0, mesh_snap_iters=0, mesh_simplify_placement='mean').items():      # recorded when set: a run without them writes the args.json it always wrote
             if meta[k] == default:
                 del meta[k]
         with open(os.path.join(args.logdir, 'args.json'), 'w') as f:
@@ -570,17 +580,18 @@ def run(args, objaverse=None):
         grid = ae(latent=d, grid_size=args.mesh_grid, behaviour='triplane_decode_grid')
         smooth = dict(smooth_iters=args.mesh_smooth_iters) if getattr(args, 'mesh_smooth_iters', 0) else {}
         snap = dict(snap_iters=args.mesh_snap_iters) if getattr(args, 'mesh_snap_iters', 0) else {}
+        place = dict(simplify_placement=args.mesh_simplify_placement) if getattr(args, 'mesh_simplify_placement', 'mean') != 'mean' else {}
         for i in range(hi - lo):
             path = os.path.join(args.logdir, f'mesh_sample{lo + i}.obj')
             if getattr(args, 'mesh_texture_size', 0):
                 try:
                     textured_mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path,
-                                            texture_size=args.mesh_texture_size, **smooth, **snap, **_mesh_post(args)._asdict())
+                                            texture_size=args.mesh_texture_size, **smooth, **snap, **place, **_mesh_post(args)._asdict())
                 except ValueError as e:      # the texture cannot hold this sample's faces: known only once the surface is extracted
                     mesh_err = f"mesh export of sample {lo + i}: --mesh_texture_size {args.mesh_texture_size}: {e}"
                     break
             else:
-                mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path, **smooth, **snap, **_mesh_post(args)._asdict())
+                mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path, **smooth, **snap, **place, **_mesh_post(args)._asdict())
             if not os.path.exists(path):
                 mesh_err = f"mesh export of sample {lo + i} produced no file at {path}"
                 break

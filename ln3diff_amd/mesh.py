@@ -6,7 +6,8 @@ tetrahedra (method='tetra'); both run on the GPU in two passes around a prefix s
 Opt-in clean-up (no reference counterpart; include/ln3d_meshclean.h): connected components of the welded mesh on the device, then only the
 components with at least `min_faces` faces, or only the largest one, are kept - before the colour query, so discarded vertices cost nothing.
 Opt-in simplification (no reference counterpart; include/ln3d_meshsimplify.h): vertex clustering on a lattice of `simplify_cell` grid units,
-behind the clean-up and before the colour query.
+behind the clean-up and before the colour query.  Its representatives are the means of their cells or, opt-in again (include/addons/
+ln3d_meshquadric.h), the quadric-error minimisers of the faces that touch the cell, which keep creases and corners.
 Opt-in texture baking (no reference counterpart; include/ext/ln3d_meshbake.h): textured_mesh_from_grid adds a per-face texture atlas, UVs,
 an .mtl and a .png to what mesh_from_grid makes; mesh_from_grid itself is unchanged.
 Opt-in smoothing (no reference counterpart; include/addons/ln3d_meshsmooth.h): Taubin's lambda | mu passes over the extracted (cleaned,
@@ -144,28 +145,27 @@ def _simplify_cell(cell):
     return c
 
 
-@torch.no_grad()
-def simplify_mesh(verts, faces, cell, origin=None, check=True):
-    """verts [Nv,3] f32, faces [Nf,3] int64 (device) -> (verts', faces'): the mesh simplified by vertex clustering on a lattice of cubic cells
-    of edge `cell` whose corner is `origin` (three numbers; None: the per-axis minimum of verts).  The definition (include/
-    ln3d_meshsimplify.h; every output is unique, nothing depends on scheduling):
-      - a vertex falls into cell q_a = floor((x_a - origin_a) / cell) per axis, in float32;
-      - every occupied cell becomes one vertex, the float32 mean of its members summed in ascending vertex index;
-      - a face whose corners fall into fewer than three cells is dropped; of the faces that name the same three cells (in any order or
-        winding) the one with the smallest index survives, with its own corner order;
-      - cells that no surviving face names are dropped; vertices come out in ascending (q_x, q_y, q_z), faces in their input order.
-    cell None or 0 returns its arguments and launches nothing; an empty input, or one of which nothing survives, gives empty tensors.
-    Raises ValueError on a bad dtype or shape, a face index out of range, a non-finite vertex or origin, a cell that is not finite or is
-    negative, and a mesh that spans 2^21 cells or more on an axis (or reaches below an explicit origin).
-    NOT promised: the result can have non-manifold edges and folded-over triangles, convex regions are pulled inward by O(cell^2 *
-    curvature), and components that come within a cell of each other can merge.  No quadric-error placement; smoothing is smooth_mesh's.
-    The five stages are kernels; torch supplies unique (clusters), two stable sorts (members per cluster, duplicate faces), the prefix sums
-    and the read-backs: the face-index check, the bounds and finiteness of verts, the cluster count (inside unique), the surviving counts.
-    check=False skips the face-index check and its read-back: for a caller whose faces index verts by construction (extract_isosurface, whose
-    faces come out of its own weld and clean-up); dtype and shape are still checked."""
-    cell = _simplify_cell(cell)
-    if cell == 0.0:
-        return verts, faces
+PLACEMENTS = ('mean', 'quadric')
+QUADRIC_EPS = 1e-3                            # the regularisation of the quadric placement, as a share of the trace: a choice, not a measurement
+
+
+def _placement(placement, eps=QUADRIC_EPS):
+    """-> (placement, eps as the float32 the kernel multiplies by); ValueError when placement is not one of PLACEMENTS or eps (in float32)
+    lies outside (0, 1]"""
+    if not isinstance(placement, str) or placement not in PLACEMENTS:
+        raise ValueError(f"placement {placement!r}: expected one of {list(PLACEMENTS)}")
+    try:
+        e = float(np.float32(eps))
+    except (TypeError, ValueError):
+        e = math.nan
+    if not 0.0 < e <= 1.0:
+        raise ValueError(f"quadric_eps {eps!r}: expected a number in (0, 1] (in float32)")
+    return placement, e
+
+
+def _simplify_clusters(verts, faces, cell, origin, check):
+    """the checks and the first three stages of simplify_mesh, cell > 0 -> None for an empty input, else (verts, faces contiguous, origin as
+    three float32, uniq [nc] int64: the clusters' cell keys ascending, rep [nc,3]: the means, cfaces [nf,3], fkey [nf])"""
     _check_verts(verts)
     if origin is not None:
         origin = np.asarray(origin, dtype=np.float32).reshape(-1)
@@ -179,7 +179,7 @@ def simplify_mesh(verts, faces, cell, origin=None, check=True):
     elif faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
         raise ValueError(f"faces: expected an int64 [Nf, 3] tensor, got {faces.dtype} {tuple(faces.shape)}")
     if nv == 0 or nf == 0:
-        return _empty(dev)
+        return None
     box = torch.cat([verts.amin(0), verts.amax(0), torch.isfinite(verts).all().float().reshape(1)]).cpu().numpy()      # one read-back
     if not box[6]:
         raise ValueError("verts: a coordinate is not finite")
@@ -203,12 +203,93 @@ def simplify_mesh(verts, faces, cell, origin=None, check=True):
     cfaces = torch.empty(nf, 3, dtype=torch.int64, device=dev)
     fkey = torch.empty(nf, dtype=torch.int64, device=dev)
     ops.simplify_faces(faces, cluster, nc, cfaces, fkey, check=False)
+    return verts, faces, origin, uniq, rep, cfaces, fkey
+
+
+def _quadric_place(verts, faces, cfaces, rep, origin, cell, uniq, eps):
+    """-> (rep_quadric [nc,3], placed [nc] int32) of include/addons/ln3d_meshquadric.h: the pair keys, their sort, the row pointers
+    (searchsorted, as _adjacency) and the placement; two launches, no read-back"""
+    dev = verts.device
+    nc = rep.shape[0]
+    pair_key = torch.empty(3 * faces.shape[0], dtype=torch.int64, device=dev)
+    ops.quadric_pairs(cfaces, nc, pair_key, check=False)
+    pair_key = torch.sort(pair_key)[0]                                 # distinct keys but for the INT64_MAX entries, which end up last
+    start = torch.searchsorted(pair_key >> 31, torch.arange(nc + 1, device=dev))
+    out = torch.empty_like(rep)
+    placed = torch.empty(nc, dtype=torch.int32, device=dev)
+    ops.quadric_place(verts, faces, pair_key, start, rep, origin, cell, uniq, eps, out, placed, check=False)
+    return out, placed
+
+
+@torch.no_grad()
+def simplify_mesh(verts, faces, cell, origin=None, check=True, placement='mean', quadric_eps=QUADRIC_EPS):
+    """verts [Nv,3] f32, faces [Nf,3] int64 (device) -> (verts', faces'): the mesh simplified by vertex clustering on a lattice of cubic cells
+    of edge `cell` whose corner is `origin` (three numbers; None: the per-axis minimum of verts).  The definition (include/
+    ln3d_meshsimplify.h; every output is unique, nothing depends on scheduling):
+      - a vertex falls into cell q_a = floor((x_a - origin_a) / cell) per axis, in float32;
+      - every occupied cell becomes one vertex, the float32 mean of its members summed in ascending vertex index;
+      - a face whose corners fall into fewer than three cells is dropped; of the faces that name the same three cells (in any order or
+        winding) the one with the smallest index survives, with its own corner order;
+      - cells that no surviving face names are dropped; vertices come out in ascending (q_x, q_y, q_z), faces in their input order.
+    placement='quadric' (opt-in; include/addons/ln3d_meshquadric.h) changes the second rule only: a cell's vertex is put where the summed
+    squared distance to the planes of ALL input faces with a corner in the cell (area-squared weights, collapsing and duplicate faces
+    included) is least, solved in float32 about the mean with the regularisation quadric_eps * trace, and accepted when it is finite and
+    lies in the closed cell; a cell whose solution is refused keeps the mean's bits.  Faces, vertex count and vertex order are exactly those
+    of 'mean'; creases and corners, which the mean chamfers by up to about 0.4 cells, are kept to about 1e-3 cells on a box.  It adds two
+    launches and one sort between the mean and the compaction; 'mean' launches nothing new.
+    cell None or 0 returns its arguments and launches nothing; an empty input, or one of which nothing survives, gives empty tensors.
+    Raises ValueError on a bad dtype or shape, a face index out of range, a non-finite vertex or origin, a cell that is not finite or is
+    negative, a mesh that spans 2^21 cells or more on an axis (or reaches below an explicit origin), a placement that is neither 'mean' nor
+    'quadric' and a quadric_eps outside (0, 1] - the last two before anything is launched.
+    NOT promised: the result can have non-manifold edges and folded-over triangles, under 'mean' convex regions are pulled inward by
+    O(cell^2 * curvature), and components that come within a cell of each other can merge.  'quadric' is a feature-preserving option, not a
+    better default: on smooth or noisy regions it is NOT closer to the surface than the mean (sphere of radius 60, cell 3: median distance
+    0.015 against 0.010; with sigma = 0.3 vertex noise 0.17 against 0.11), folds and non-manifold edges remain, bevels that marching cubes
+    already cut at grid resolution are only partly recovered, and quadric_eps trades crease sharpness against noise amplification (its
+    default 1e-3 is a choice, not a measurement).  Smoothing is smooth_mesh's.
+    The stages are kernels; torch supplies unique (clusters), the stable sorts (members per cluster, duplicate faces), the pair-key sort and
+    searchsorted of 'quadric', the prefix sums and the read-backs: the face-index check, the bounds and finiteness of verts, the cluster count
+    (inside unique), the surviving counts.
+    check=False skips the face-index check and its read-back: for a caller whose faces index verts by construction (extract_isosurface, whose
+    faces come out of its own weld and clean-up); dtype and shape are still checked."""
+    placement, quadric_eps = _placement(placement, quadric_eps)
+    cell = _simplify_cell(cell)
+    if cell == 0.0:
+        return verts, faces
+    dev = verts.device
+    front = _simplify_clusters(verts, faces, cell, origin, check)
+    if front is None:
+        return _empty(dev)
+    verts, faces, origin, uniq, rep, cfaces, fkey = front
+    nc, nf = rep.shape[0], faces.shape[0]
+    if placement == 'quadric':
+        rep = _quadric_place(verts, faces, cfaces, rep, origin, cell, uniq, quadric_eps)[0]
     sorted_key, perm = torch.sort(fkey, stable=True)
     keep_f = torch.empty(nf, dtype=torch.int32, device=dev)
     ops.simplify_first(sorted_key, perm, keep_f, check=False)
     keep_v = torch.empty(nc, dtype=torch.int32, device=dev)
     ops.simplify_used(cfaces, keep_f, keep_v, check=False)
     return _compact(rep, cfaces, keep_v, keep_f)
+
+
+@torch.no_grad()
+def simplify_placement(verts, faces, cell, origin=None, eps=QUADRIC_EPS):
+    """The diagnostic view of the two placements of simplify_mesh, before the compaction: verts [Nv,3] f32, faces [Nf,3] int64 (device),
+    cell > 0 -> (rep_mean [Nc,3] f32, rep_quadric [Nc,3] f32, placed [Nc] int32, cell_key [Nc] int64) for every occupied lattice cell in
+    ascending key q_x << 42 | q_y << 21 | q_z.  placed[k] = 1 where the quadric solution was accepted; where it is 0, rep_quadric[k] has
+    rep_mean[k]'s bits.  An empty input gives empty tensors.  Raises what simplify_mesh raises, and ValueError for cell None or 0."""
+    _, eps = _placement('quadric', eps)
+    cell = _simplify_cell(cell)
+    if cell == 0.0:
+        raise ValueError("cell: expected a positive finite number (there are no clusters without a lattice)")
+    dev = verts.device
+    front = _simplify_clusters(verts, faces, cell, origin, True)
+    if front is None:
+        return (torch.zeros(0, 3, device=dev), torch.zeros(0, 3, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
+                torch.zeros(0, dtype=torch.int64, device=dev))
+    verts, faces, origin, uniq, rep, cfaces, _ = front
+    quad, placed = _quadric_place(verts, faces, cfaces, rep, origin, cell, uniq, eps)
+    return rep, quad, placed, uniq
 
 
 # ------------------------------------------------------------------ smoothing (include/addons/ln3d_meshsmooth.h)
@@ -385,13 +466,14 @@ def snap_mesh(decoder, planes_channel_last, verts_box, level, iterations, tol=No
 
 
 @torch.no_grad()
-def extract_isosurface(sigma, thr=10.0, method='cubes', keep='all', min_faces=0, simplify_cell=0.0):
+def extract_isosurface(sigma, thr=10.0, method='cubes', keep='all', min_faces=0, simplify_cell=0.0, simplify_placement='mean'):
     """sigma [G,G,G] f32 device -> (verts [Nv,3] in grid coordinates, faces [Nf,3] int64).  Faces keep the emission order
     (cells in x-major order, the case table's triangle order inside a cell).  keep / min_faces (opt-in): clean_mesh on the welded result.
     simplify_cell (opt-in, in grid units): simplify_mesh with origin (0, 0, 0) after the weld and after the clean-up, so floaters are judged
-    on the full-density mesh."""
+    on the full-density mesh.  simplify_placement (opt-in): simplify_mesh's placement, 'mean' or 'quadric'; it changes coordinates only."""
     keep, min_faces = _clean_args(keep, min_faces)
     simplify_cell = _simplify_cell(simplify_cell)
+    simplify_placement = _placement(simplify_placement)[0]
     count, emit = {'cubes': (ops.mcubes_count, ops.mcubes_emit), 'tetra': (ops.mesh_count, ops.mesh_emit)}[method]
     G = sigma.shape[0]
     dev = sigma.device
@@ -412,7 +494,8 @@ def extract_isosurface(sigma, thr=10.0, method='cubes', keep='all', min_faces=0,
     faces = inv.view(ntri, 3)
     ok = (faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])
     verts, faces = clean_mesh(verts, faces[ok], keep, min_faces)
-    return simplify_mesh(verts, faces, simplify_cell, (0.0, 0.0, 0.0), check=False)      # faces are the weld's own: in range by construction
+    place = dict(placement=simplify_placement) if simplify_placement != 'mean' else {}
+    return simplify_mesh(verts, faces, simplify_cell, (0.0, 0.0, 0.0), check=False, **place)      # faces are the weld's own: in range by construction
 
 
 def rotation_matrix_x(deg):
@@ -576,15 +659,17 @@ def bake_texture(decoder, planes_channel_last, verts_box, faces, size, fill=0):
 
 
 def _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces, simplify_cell,
-                   smooth=(0, SMOOTH_LAMBDA, SMOOTH_MU), snap=(0, None, None)):
+                   smooth=(0, SMOOTH_LAMBDA, SMOOTH_MU), snap=(0, None, None), simplify_placement='mean'):
     """what mesh_from_grid and textured_mesh_from_grid share: (the one sample's planes, the box-space vertices and the faces on the device,
     then verts, faces, colors, vn as mesh_from_grid returns them; vn is None without normals).  smooth: (iterations, lam, mu) of smooth_mesh,
     applied to the extracted mesh in grid coordinates, so everything behind it sees the smoothed positions.  snap: (iterations, tol, max_move
-    in grid units) of snap_mesh at level = thr, applied to the box-space vertices behind that and before the query."""
+    in grid units) of snap_mesh at level = thr, applied to the box-space vertices behind that and before the query.  simplify_placement:
+    extract_isosurface's, handed on only when it is not 'mean'."""
     _smooth_args(*smooth)                                                # a bad value is refused before anything is extracted
     snap_iters, snap_tol, snap_move = _snap_args(*snap)
+    place = dict(simplify_placement=simplify_placement) if _placement(simplify_placement)[0] != 'mean' else {}
     sigma = sigma.reshape(grid_size, grid_size, grid_size)
-    verts, faces = extract_isosurface(sigma, thr, method, keep, min_faces, simplify_cell)
+    verts, faces = extract_isosurface(sigma, thr, method, keep, min_faces, simplify_cell, **place)
     verts, faces = smooth_mesh(verts, faces, *smooth, check=False)       # faces are the extraction's own: in range by construction
     vtx = (verts / (grid_size - 1) * 2 - 1) * 0.45                       # g-objaverse scale
     pcl = dec_out.get('planes_channel_last')
@@ -605,7 +690,7 @@ def _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method
 @torch.no_grad()
 def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes', normals=False,
                    keep='all', min_faces=0, simplify_cell=0.0, smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU,
-                   snap_iters=0, snap_tol=None, snap_max_move=None):
+                   snap_iters=0, snap_tol=None, snap_max_move=None, simplify_placement='mean'):
     """nsr/train_util_diffusion.py:221-244: iso-surface of the sigma grid at `thr`, vertices mapped to the +-0.45 box, coloured
     by re-querying the tri-plane at the vertices (forward_points), rotated -90 degrees about x.
     Returns (verts [Nv,3] float32 numpy, faces [Nf,3] int64 numpy, colors [Nv,3] uint8 numpy); writes `path` when given.
@@ -623,9 +708,14 @@ def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0,
     the smoothing and before the query, so colours and `vn` are the field's values AT THE SNAPPED POSITIONS; faces, vertex count and order
     never change.  snap_iters in [0, 64]; 0 launches nothing.  snap_max_move is the farthest a vertex may end from where it started, in
     grid cells; a Newton step is at most half of it.  The defaults are choices, not measurements: snap_tol None = 1e-3 * max(1, |thr|),
-    snap_max_move None = max(1, simplify_cell).  See snap_mesh for what snapping does not promise."""
+    snap_max_move None = max(1, simplify_cell).  See snap_mesh for what snapping does not promise.
+    simplify_placement (opt-in; no reference counterpart): 'quadric' puts every vertex of the simplified mesh where the planes of the faces
+    around its cell meet (simplify_mesh's placement) instead of at the mean of the cell, so creases and corners survive; faces, vertex count
+    and order are those of 'mean', and smoothing, snapping and the query follow as they do today, at the quadric positions.  Without
+    simplify_cell there is nothing to place.  See simplify_mesh for what it does not promise: on smooth regions it is no closer than the mean."""
     _, _, _, v, f, colors, vn = _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces,
-                                               simplify_cell, (smooth_iters, smooth_lambda, smooth_mu), (snap_iters, snap_tol, snap_max_move))
+                                               simplify_cell, (smooth_iters, smooth_lambda, smooth_mu), (snap_iters, snap_tol, snap_max_move),
+                                               simplify_placement)
     if path:
         write_obj(path, v, f, colors.astype(np.float32) / 255.0, vn)
     return (v, f, colors, vn) if normals else (v, f, colors)
@@ -634,7 +724,7 @@ def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0,
 @torch.no_grad()
 def textured_mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes', texture_size=1024,
                             normals=False, keep='all', min_faces=0, simplify_cell=0.0, smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA,
-                            smooth_mu=SMOOTH_MU, snap_iters=0, snap_tol=None, snap_max_move=None):
+                            smooth_mu=SMOOTH_MU, snap_iters=0, snap_tol=None, snap_max_move=None, simplify_placement='mean'):
     """mesh_from_grid plus a baked texture (opt-in; no reference counterpart): the same geometry, vertex colours and `vn`, bit for bit, for
     the same options, then bake_texture of the faces at the box-space vertices (before the rotation, where the field lives) into a
     texture_size x texture_size per-face atlas.  Returns mesh_from_grid's tuple with (uv [Nf,3,2] float32, tex [T,T,3] uint8) appended.
@@ -645,11 +735,11 @@ def textured_mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample
     texel, no supersampling; there is no mip-safe padding beyond the 1 - 1.5 texel gutter; and the colours are the field's values on the
     (possibly simplified, possibly smoothed: smooth_iters / smooth_lambda / smooth_mu are mesh_from_grid's) triangles, which lie off the
     level set by the simplifier's and the smoother's error.  snap_iters / snap_tol / snap_max_move (mesh_from_grid's) put the VERTICES
-    back on it before the bake; the interiors of the triangles stay where the flat faces are."""
+    back on it before the bake; the interiors of the triangles stay where the flat faces are.  simplify_placement is mesh_from_grid's."""
     _atlas_size(texture_size)
     pcl, vtx, faces, v, f, colors, vn = _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces,
                                                        simplify_cell, (smooth_iters, smooth_lambda, smooth_mu),
-                                                       (snap_iters, snap_tol, snap_max_move))
+                                                       (snap_iters, snap_tol, snap_max_move), simplify_placement)
     uv, tex = bake_texture(decoder, pcl, vtx, faces, texture_size)
     if path:
         write_obj_textured(path, v, f, colors.astype(np.float32) / 255.0, uv, vn)
@@ -659,12 +749,15 @@ def textured_mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample
 
 @torch.no_grad()
 def export_mesh(decoder, dec_out, path, grid_size=192, thr=10.0, sample_index=0, normals=False, keep='all', min_faces=0, simplify_cell=0.0,
-                smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU, snap_iters=0, snap_tol=None, snap_max_move=None):
+                smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU, snap_iters=0, snap_tol=None, snap_max_move=None,
+                simplify_placement='mean'):
     """decoder: the VAE decoder module; dec_out: its vit_decode_postprocess dict.  Writes `path` (.obj), with `vn` records when normals;
-    keep / min_faces / simplify_cell / smooth_iters / smooth_lambda / smooth_mu / snap_iters / snap_tol / snap_max_move: mesh_from_grid's."""
+    keep / min_faces / simplify_cell / smooth_iters / smooth_lambda / smooth_mu / snap_iters / snap_tol / snap_max_move /
+    simplify_placement: mesh_from_grid's (the last handed on only when it is not 'mean')."""
     pcl = dec_out['planes_channel_last'][sample_index:sample_index + 1]
     grid = decoder.triplane_decode_grid({'planes_channel_last': pcl}, grid_size)
+    place = dict(simplify_placement=simplify_placement) if _placement(simplify_placement)[0] != 'mean' else {}
     v, f = mesh_from_grid(decoder, {'planes_channel_last': pcl}, grid['sigma'][0], grid_size, thr, 0, path, normals=normals, keep=keep,
                           min_faces=min_faces, simplify_cell=simplify_cell, smooth_iters=smooth_iters, smooth_lambda=smooth_lambda,
-                          smooth_mu=smooth_mu, snap_iters=snap_iters, snap_tol=snap_tol, snap_max_move=snap_max_move)[:2]
+                          smooth_mu=smooth_mu, snap_iters=snap_iters, snap_tol=snap_tol, snap_max_move=snap_max_move, **place)[:2]
     return v.shape[0], f.shape[0]

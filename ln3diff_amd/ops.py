@@ -461,6 +461,50 @@ def simplify_used(cfaces, keep_f, keep_v, check=True):
     L.check(L.lib().ln3d_simplify_used(_p(cfaces), _p(keep_f), cfaces.shape[0], nc, _p(keep_v), _stream()), "simplify_used")
 
 
+def quadric_pairs(cfaces, nc, pair_key, check=True):
+    """pair_key [3 nf] int64 <- cfaces[f][j] << 31 | f for every corner j of face f whose cluster differs from the corners before it,
+    INT64_MAX for the others (include/addons/ln3d_meshquadric.h); cfaces [nf,3] int64 with every value in [0, nc).  check=False: the caller
+    has made cfaces itself (simplify_faces)."""
+    nf = cfaces.shape[0]
+    _buffer(cfaces, torch.int64, (nf, 3), "cfaces")
+    _buffer(pair_key, torch.int64, (3 * nf,), "pair_key")
+    if check:
+        check_faces(cfaces, nc)
+    L.check(L.lib().ln3d_quadric_pairs(_p(cfaces), nf, nc, _p(pair_key), _stream()), "quadric_pairs")
+
+
+def quadric_place(verts, faces, sorted_pair_key, start, rep_mean, origin, cell, cluster_cell_key, eps, rep_out, placed, check=True):
+    """rep_out [nc,3] f32, placed [nc] int32 <- the quadric-error placement of every cluster (include/addons/ln3d_meshquadric.h): the
+    minimiser of the summed squared distance to the planes of the cluster's faces, regularised with eps * trace, where it lies inside the
+    cluster's lattice cell (placed 1), rep_mean's bits elsewhere (placed 0).  verts [nv,3] f32, faces [nf,3] int64, sorted_pair_key [3 nf]
+    int64: quadric_pairs' keys in ascending order, start [nc + 1] int64: the row pointers into it, rep_mean [nc,3] f32, origin: three
+    floats, cluster_cell_key [nc] int64.  rep_out may be rep_mean itself and may not overlap it otherwise.  check=False: the caller has
+    put faces through check_faces and made the keys and start itself."""
+    nv, nf, nc, npairs = verts.shape[0], faces.shape[0], rep_mean.shape[0], sorted_pair_key.shape[0]
+    _buffer(verts, torch.float32, (nv, 3), "verts")
+    _buffer(faces, torch.int64, (nf, 3), "faces")
+    _buffer(sorted_pair_key, torch.int64, (3 * nf,), "sorted_pair_key")
+    _buffer(start, torch.int64, (nc + 1,), "start")
+    _buffer(rep_mean, torch.float32, (nc, 3), "rep_mean")
+    _buffer(cluster_cell_key, torch.int64, (nc,), "cluster_cell_key")
+    _buffer(rep_out, torch.float32, (nc, 3), "rep_out")
+    _buffer(placed, torch.int32, (nc,), "placed")
+    try:
+        e = float(np.float32(eps))
+    except (TypeError, ValueError):
+        e = math.nan
+    if not 0.0 < e <= 1.0:
+        raise ValueError(f"eps {eps!r}: expected a number in (0, 1] (in float32)")
+    if check:
+        check_faces(faces, nv)
+        check_index(start, npairs + 1, "start")
+        if nc >= 1 and bool((start[1:] < start[:-1]).any()):
+            raise ValueError("start: expected an ascending row-pointer array")
+    ox, oy, oz = (float(o) for o in origin)
+    L.check(L.lib().ln3d_quadric_place(_p(verts), nv, _p(faces), nf, _p(sorted_pair_key), npairs, _p(start), nc, _p(rep_mean), ox, oy, oz,
+                                       float(cell), _p(cluster_cell_key), e, _p(rep_out), _p(placed), _stream()), "quadric_place")
+
+
 def bake_points(verts, faces, T, n, c, points, owner, check=True):
     """points [T*T,3] f32, owner [T*T] int32 <- the point on its face and the face of every texel of the per-face atlas (T, n, c:
     mesh.atlas_layout; include/ext/ln3d_meshbake.h); verts [nv,3] f32, faces [nf,3] int64.  check=False: the caller has already put these

@@ -1,0 +1,218 @@
+"""Quadric-error placement on the GPU (include/addons/ln3d_meshquadric.h): ln3d_quadric_pairs exactly against the definition's loop,
+ln3d_quadric_place per cluster and axis against the float64 reference of tests/mesh_quadric_refs.py within POSITION_BOUND cells (calibrated in
+tests/test_mesh_quadric_cpu.py, where the fp32 restatement passes these same checks and four seeded faults fail them), `placed` against the
+reference's flag, the mean's bits where a placement is refused; then simplify_mesh / simplify_placement / extract_isosurface / mesh_from_grid
+with placement='quadric': same faces and vertex count as 'mean', creases of a box kept where the mean chamfers them."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import mesh_quadric_refs as R
+import mesh_simplify_refs as S
+
+pytestmark = pytest.mark.gpu
+
+ZERO = (0.0, 0.0, 0.0)
+PLACED = [n for n in R.cases() if n not in R.PAIRS_ONLY]
+
+
+def _dev(a, dtype):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).cuda()
+
+
+def _place(c, eps=R.EPS, in_place=False):
+    """one case through the two entry points as simplify_mesh drives them -> (rep [nc,3] float32, placed [nc] int32, pair_key [3 nf]) numpy"""
+    from ln3diff_amd import ops
+    st = c['st']
+    nc, nf = st['nc'], len(c['faces'])
+    verts, faces, cfaces = _dev(c['verts'], torch.float32), _dev(c['faces'], torch.int64), _dev(st['cfaces'], torch.int64)
+    key = torch.full((3 * nf,), -7, dtype=torch.int64, device='cuda')
+    ops.quadric_pairs(cfaces, nc, key)
+    skey = torch.sort(key)[0]
+    start = torch.searchsorted(skey >> 31, torch.arange(nc + 1, device='cuda'))
+    mean = _dev(st['rep'], torch.float32)
+    out = mean if in_place else torch.full((nc, 3), float('nan'), device='cuda')
+    placed = torch.full((nc,), -7, dtype=torch.int32, device='cuda')
+    ops.quadric_place(verts, faces, skey, start, mean, c['origin'], c['cell'], _dev(st['key_unique'], torch.int64), eps, out, placed)
+    return out.cpu().numpy(), placed.cpu().numpy(), key.cpu().numpy()
+
+
+@pytest.mark.parametrize('name', list(R.cases()))
+def test_pair_keys_equal_the_definition(hip_lib, name):
+    c = R.cases()[name]
+    key = _place(c)[2]
+    assert np.array_equal(key, R.pairs(c['st']['cfaces']))
+    if name == 'incidence':                                                               # two corners in one cluster, a collapsed face, three clusters
+        assert sorted((int(k >> 31), int(k & 0x7fffffff)) for k in key if k != R.NONE) == c['want']
+
+
+@pytest.mark.parametrize('name', PLACED)
+def test_placement_against_float64(hip_lib, name):
+    c = R.cases()[name]
+    rep, placed, _ = _place(c)
+    fails, fig = R.check_placement(c, rep, placed, small=name in R.SMALL)
+    print(f"[quadric] {name}: {fig}, bound {R.POSITION_BOUND:.3g}")
+    assert fails == [], (name, fails, fig)
+    again = _place(c)                                                                     # two runs, the same bits
+    assert np.array_equal(S.bits(again[0]), S.bits(rep)) and np.array_equal(again[1], placed)
+    inpl = _place(c, in_place=True)                                                       # rep_out == rep_mean is allowed
+    assert np.array_equal(S.bits(inpl[0]), S.bits(rep)) and np.array_equal(inpl[1], placed)
+
+
+def test_heavy_cluster_and_fallbacks(hip_lib):
+    C = R.cases()
+    rep, placed, _ = _place(C['fan3000'])                                                 # 3000 faces in one row: 47 rounds per lane
+    assert placed.tolist() == [1] and np.abs(rep[0] - np.float32([1.2, 1.1, 1.7])).max() < 2e-2
+    for name in ('zero_area', 'far_wedge'):                                               # trace == 0; the planes meet outside the cell
+        rep, placed, _ = _place(C[name])
+        assert placed.tolist() == [0] and np.array_equal(S.bits(rep), S.bits(C[name]['st']['rep'])), name
+    rep, placed, _ = _place(C['coplanar'])                                                # rank 1: accepted, and it stays in the plane
+    assert placed.tolist() == [1] and np.abs(rep.astype(np.float64) - C['coplanar']['ref']['x']).max() <= R.POSITION_BOUND * 2.0
+
+
+@pytest.mark.parametrize('name', ['ico2_c1.5', 'ico2_c4', 'ico4_c1.5', 'ico4_c4'])
+def test_energy_is_not_above_the_means(hip_lib, name):
+    """in float64 on the device output: the regularised minimiser never has more quadric energy than the mean it started from"""
+    c = R.cases()[name]
+    ref, cell = c['ref'], float(np.float32(c['cell']))
+    rep, placed, _ = _place(c)
+    on = placed != 0
+    dl = rep.astype(np.float64) - ref['mean']
+    grad = 2 * np.abs(np.einsum('kij,kj->ki', ref['A'], dl) - ref['r']).sum(1)
+    slack = R.POSITION_BOUND * cell * grad + 3 * ref['trace'] * (R.POSITION_BOUND * cell) ** 2
+    e = R.energy(ref, rep)                                                                # minus the mean's, which is the zero of R.energy
+    assert on.sum() >= 0.99 * len(on) and (e[on] <= slack[on]).all(), float((e - slack)[on].max())
+    assert (e[on] < 0).mean() > 0.5 or name.startswith('ico2')                            # and for most clusters it is lower (ico2: many cells hold one vertex, which stays)
+
+
+def test_box_creases_survive(hip_lib):
+    """the test that fails without the feature: the mean's representatives are up to 0.375 from the box, the quadric ones within 1e-2"""
+    from ln3diff_amd import mesh
+    c = R.cases()['box6']
+    lo, hi = c['box']
+    verts, faces = _dev(c['verts'], torch.float32), _dev(c['faces'], torch.int64)
+    vm, fm = mesh.simplify_mesh(verts, faces, 2.0, ZERO)
+    vq, fq = mesh.simplify_mesh(verts, faces, 2.0, ZERO, placement='quadric')
+    assert torch.equal(fm, fq) and vm.shape == vq.shape == (56, 3) and vq.dtype == torch.float32
+    d_mean, d_quad = R.box_distance(vm.cpu().numpy(), lo, hi).max(), R.box_distance(vq.cpu().numpy(), lo, hi).max()
+    print(f"[quadric] box6 on the device: largest distance from the box: mean {d_mean:.4g}, quadric {d_quad:.3g}")
+    assert d_quad <= 1e-2
+    assert not d_mean <= 1e-2 and d_mean > 0.37                                           # the same assertion on 'mean' fails
+    rep_mean, rep_quad, placed, cell_key = mesh.simplify_placement(verts, faces, 2.0, ZERO)
+    assert placed.dtype == torch.int32 and bool((placed == 1).all()) and np.array_equal(cell_key.cpu().numpy(), c['st']['key_unique'])
+    assert np.array_equal(S.bits(rep_mean.cpu().numpy()), S.bits(c['st']['rep']))         # ln3d_simplify_mean's output keeps its bits
+    assert torch.equal(rep_quad, vq) and torch.equal(rep_mean, vm)                        # every cluster of this mesh survives, in order
+    fails, fig = R.check_placement(c, rep_quad.cpu().numpy(), placed.cpu().numpy(), small=True)
+    assert fails == [], fails
+    soft = mesh.simplify_mesh(verts, faces, 2.0, ZERO, placement='quadric', quadric_eps=0.5)[0]
+    assert 1e-2 < R.box_distance(soft.cpu().numpy(), lo, hi).max() < d_mean               # eps trades sharpness away
+
+
+@pytest.mark.parametrize('name', ['box6', 'ico4_c1.5', 'small_clusters'])
+def test_placement_mean_is_the_call_without_the_argument(hip_lib, name):
+    from ln3diff_amd import mesh
+    c = R.cases()[name]
+    verts, faces = _dev(c['verts'], torch.float32), _dev(c['faces'], torch.int64)
+    a, b = mesh.simplify_mesh(verts, faces, c['cell'], ZERO), mesh.simplify_mesh(verts, faces, c['cell'], ZERO, placement='mean', quadric_eps=0.25)
+    assert torch.equal(a[1], b[1]) and np.array_equal(S.bits(a[0].cpu().numpy()), S.bits(b[0].cpu().numpy()))
+    want_v, want_f = S.simplify(c['verts'], c['faces'], c['cell'], ZERO)
+    assert np.array_equal(S.bits(a[0].cpu().numpy()), S.bits(want_v)) and np.array_equal(a[1].cpu().numpy(), want_f)
+    q = mesh.simplify_mesh(verts, faces, c['cell'], ZERO, placement='quadric')
+    assert torch.equal(q[1], a[1]) and q[0].shape == a[0].shape                           # only coordinates change
+    with pytest.raises(ValueError, match='placement'):
+        mesh.simplify_mesh(verts, faces, c['cell'], ZERO, placement='median')
+
+
+def test_wrapper_refuses_a_bad_start(hip_lib):
+    from ln3diff_amd import ops
+    c = R.cases()['incidence']
+    st = c['st']
+    verts, faces = _dev(c['verts'], torch.float32), _dev(c['faces'], torch.int64)
+    skey, mean, ck = torch.sort(_dev(R.pairs(st['cfaces']), torch.int64))[0], _dev(st['rep'], torch.float32), _dev(st['key_unique'], torch.int64)
+    out, placed = torch.empty(3, 3, device='cuda'), torch.empty(3, dtype=torch.int32, device='cuda')
+    for bad in ([0, 5, 3, 10], [0, 5, 8, 16], [-1, 5, 8, 10]):
+        with pytest.raises(ValueError, match='start'):
+            ops.quadric_place(verts, faces, skey, _dev(np.array(bad), torch.int64), mean, ZERO, 1.0, ck, 1e-3, out, placed)
+    with pytest.raises(ValueError, match='faces'):
+        ops.quadric_place(verts, faces + 5, skey, _dev(np.array([0, 5, 6, 10]), torch.int64), mean, ZERO, 1.0, ck, 1e-3, out, placed)
+
+
+# ---------------------------------------------------------------- through the extraction
+BOX_G, BOX_THR, BOX_C, BOX_H = 24, 10.0, (11.3, 11.45, 11.6), 6.2
+
+
+@functools.lru_cache(maxsize=None)
+def _box_field():
+    """thr + 4 (h - max |p - c|): the level set is the box of half-edge h about an off-lattice centre"""
+    g = np.arange(BOX_G, dtype=np.float64)
+    p = np.stack(np.meshgrid(g, g, g, indexing='ij'), -1)
+    return (BOX_THR + 4.0 * (BOX_H - np.abs(p - np.asarray(BOX_C)).max(-1))).astype(np.float32)
+
+
+def _corner_region(p):
+    """the points within one simplification cell (2) of two or three face planes of the box: its edges and corners"""
+    q = np.abs(np.asarray(p, dtype=np.float64) - np.asarray(BOX_C))
+    return (q > BOX_H - 2.0).sum(1) >= 2
+
+
+@functools.lru_cache(maxsize=None)
+def _box_reference():
+    """the float64 reference on the marching-cubes mesh of the field, computed on the CPU: (largest corner-region distance from the true box
+    under 'mean', under 'quadric', number of vertices, number of faces of the simplified mesh)"""
+    import mesh_clean_refs as M
+    import mesh_refs as MR
+    _, faces, pos, _ = MR.weld(MR.ref_cubes(_box_field(), BOX_THR, MR.load_mc_table()))
+    pos, faces = np.asarray(pos).astype(np.float32), faces.astype(np.int64)
+    st = S.stages(pos, faces, 2.0, ZERO)
+    st['key_unique'] = np.unique(st['key'])
+    ref = R.place64(pos, faces, st, 2.0)
+    lo, hi = np.asarray(BOX_C) - BOX_H, np.asarray(BOX_C) + BOX_H
+    vm, fm = M.compact(st['rep'], st['cfaces'], st['keep_v'], st['keep_f'])
+    vq, _ = M.compact(ref['rep'].astype(np.float32), st['cfaces'], st['keep_v'], st['keep_f'])
+    region = _corner_region(vm)
+    return float(R.box_distance(vm[region], lo, hi).max()), float(R.box_distance(vq[region], lo, hi).max()), len(vm), len(fm)
+
+
+def test_extract_isosurface_keeps_the_creases_of_a_box_field(hip_lib):
+    from ln3diff_amd.mesh import extract_isosurface
+    sigma = torch.from_numpy(_box_field()).cuda()
+    vm, fm = extract_isosurface(sigma, BOX_THR, simplify_cell=2.0)
+    vq, fq = extract_isosurface(sigma, BOX_THR, simplify_cell=2.0, simplify_placement='quadric')
+    assert torch.equal(fm, fq) and vm.shape == vq.shape and vm.shape[0] > 50              # same faces and vertex count
+    ref_mean, ref_quad, nv, nf = _box_reference()
+    assert (vm.shape[0], fm.shape[0]) == (nv, nf)
+    lo, hi = np.asarray(BOX_C) - BOX_H, np.asarray(BOX_C) + BOX_H
+    region = _corner_region(vm.cpu().numpy())
+    d_mean, d_quad = R.box_distance(vm.cpu().numpy()[region], lo, hi).max(), R.box_distance(vq.cpu().numpy()[region], lo, hi).max()
+    print(f"[quadric] box field 24^3, cell 2, {int(region.sum())} of {len(region)} vertices near an edge: largest distance from the box "
+          f"mean {d_mean:.4g} quadric {d_quad:.4g} (x{d_mean / d_quad:.2f}); float64 reference {ref_mean:.4g} / {ref_quad:.4g} (x{ref_mean / ref_quad:.2f})")
+    # marching cubes has already cut the edges of this box at grid resolution, so the planes around an edge cell are the bevel's too and only
+    # part of the crease comes back (what the header says it does not promise): the reference's own improvement is what the device is held to
+    assert ref_quad < ref_mean and d_quad < d_mean
+    assert d_mean / d_quad >= 1 + 0.5 * (ref_mean / ref_quad - 1) and d_mean - d_quad >= 0.5 * (ref_mean - ref_quad)
+
+
+def test_mesh_from_grid_colours_the_quadric_positions(hip_lib, tmp_path):
+    """extract -> smooth -> snap -> query as before: colours are the field's values AT the quadric positions"""
+    from ln3diff_amd.mesh import extract_isosurface, mesh_from_grid, rotation_matrix_x
+    from test_normals_gpu import _scene, _triplane, _Seams, _g
+    from test_normals_cpu import parse_obj
+    G = BOX_G
+    inp = _scene(91, sigma_bias=10.0)
+    dec = _Seams(_triplane(inp['dec']))
+    pcl = _g(inp['planes'][1:2])
+    d = {'planes_channel_last': pcl}
+    sigma = torch.from_numpy(_box_field()).cuda()
+    mean = mesh_from_grid(dec, d, sigma, G, thr=BOX_THR, simplify_cell=2.0)
+    assert all(np.array_equal(a, b) for a, b in zip(mean, mesh_from_grid(dec, d, sigma, G, thr=BOX_THR, simplify_cell=2.0, simplify_placement='mean')))
+    v, f, col = mesh_from_grid(dec, d, sigma, G, thr=BOX_THR, simplify_cell=2.0, simplify_placement='quadric', path=str(tmp_path / 'q.obj'))
+    gv, gf = extract_isosurface(sigma, BOX_THR, simplify_cell=2.0, simplify_placement='quadric')
+    vtx = (gv / (G - 1) * 2 - 1) * 0.45
+    rot = lambda a: (rotation_matrix_x(-90) @ a.cpu().numpy().T).T.astype(np.float32)      # noqa: E731
+    assert np.array_equal(f, gf.cpu().numpy()) and np.array_equal(f, mean[1]) and np.array_equal(S.bits(v), S.bits(rot(vtx)))
+    assert np.array_equal(col, (dec.forward_points(pcl, vtx[None])['rgb'][0].clamp(0, 1) * 255).to(torch.uint8).cpu().numpy())
+    assert v.shape == mean[0].shape and not np.array_equal(v, mean[0])
+    pv, _, pf, _ = parse_obj(tmp_path / 'q.obj')
+    assert len(pv) == len(v) and np.array_equal(pf, f)
