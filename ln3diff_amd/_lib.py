@@ -192,6 +192,13 @@ EXT_PROTOTYPES = {
 # constant, no name of the tables above.  tests/test_mesh_smooth_cpu.py holds this table row for row to whatever headers that directory has
 # and names no entry and no count, so the next feature adds a header there and its rows here, not a fourth table.
 ADDON_PROTOTYPES = {
+    # include/addons/ln3d_meshpack.h (the records of a binary PLY and the buffer sections of a GLB, packed on the device)
+    "ln3d_pack_ply_vertices": _int(vp, vp, vp, vp, i64, vp, vp),
+    "ln3d_pack_ply_faces": _int(vp, i64, vp, vp),
+    "ln3d_pack_gltf_vertices": _int(vp, vp, vp, vp, i64, vp, vp, vp, vp),
+    "ln3d_pack_gltf_indices": _int(vp, i64, vp, vp),
+    "ln3d_pack_gltf_corners": _int(vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp),
+    "ln3d_position_bounds": _int(vp, i64, vp, vp),
     # include/addons/ln3d_meshquadric.h (quadric-error placement of the simplification's representatives)
     "ln3d_quadric_pairs": _int(vp, i64, i64, vp, vp),
     "ln3d_quadric_place": _int(vp, i64, vp, i64, vp, i64, vp, i64, vp, f32, f32, f32, f32, vp, f32, vp, vp, vp),

@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from .mesh import MeshPost, _atlas_size, _clean_args, _simplify_cell, _placement, _smooth_args, _snap_args, mesh_from_grid, textured_mesh_from_grid
+from .mesh import MeshPost, _atlas_size, _clean_args, _mesh_format, _simplify_cell, _placement, _smooth_args, _snap_args, mesh_from_grid, textured_mesh_from_grid
 
 # --trainer_name -> engine (scripts/vit_triplane_diffusion_sample_objaverse.py:135-142, scripts/vit_triplane_diffusion_sample.py:236-242)
 TRAINERS = {
@@ -113,6 +113,7 @@ def create_argparser(objaverse=True):
         mesh_smooth_iters=0,                 # > 0: every exported mesh gets that many iterations of Taubin smoothing before it is coloured; not a MeshPost field
         mesh_snap_iters=0,                   # > 0: the vertices of every exported mesh are put back on the level set (at most that many Newton iterations) before it is coloured; not a MeshPost field
         mesh_simplify_placement='mean',      # 'quadric': the vertices of a simplified mesh are put where the planes of the faces around their cell meet, which keeps creases and corners (needs --mesh_simplify_cell); not a MeshPost field
+        mesh_format='obj',                   # 'ply' / 'glb': every exported mesh is written as mesh_sample{i}.ply / .glb, a binary file packed on the GPU, instead of the .obj text ('ply' carries vertex colours only: not with --mesh_texture_size); not a MeshPost field
         **_MESH_FLAGS)
     d.update(_IGNORED_DEFAULTS)
     d.update({k: v[0] for k, v in _CHECKED.items()})
@@ -210,6 +211,15 @@ def validate(args):
         raise SystemExit(f"--mesh_simplify_placement {place}: there is no mesh to simplify without --export_mesh true")
     if place != 'mean' and cell == 0:
         raise SystemExit(f"--mesh_simplify_placement {place}: there is nothing to place without --mesh_simplify_cell > 0")
+    fmt = getattr(args, 'mesh_format', 'obj')
+    try:                                     # the library's own check again
+        _mesh_format(fmt)
+    except ValueError as e:                  # "format ...: expected one of ['obj', 'ply', 'glb']"
+        raise SystemExit(f"--mesh_{e}") from None
+    if fmt != 'obj' and not args.export_mesh:
+        raise SystemExit(f"--mesh_format {fmt}: there is no mesh to write without --export_mesh true")
+    if fmt == 'ply' and tex != 0:
+        raise SystemExit("--mesh_format ply carries vertex colours only: a textured mesh (--mesh_texture_size) is written as obj or glb")
     if getattr(args, 'save_normal_maps', False):
         world = int(os.environ.get('WORLD_SIZE', '1'))
         if world > 1 and args.num_samples % world != 0:
@@ -511,7 +521,7 @@ def run(args, objaverse=None):
     cond_all, cond_src = res[0], res[1]
     if rank == 0:
         meta = dict(vars(args), conditioning=cond_src, weights={k: (v or 'synthetic') for k, v in weights_from.items()})
-        for k, default in dict(_MESH_FLAGS, save_normal_maps=False, mesh_texture_size=0, mesh_smooth_iters=0, mesh_snap_iters=0, mesh_simplify_placement='mean').items():      # recorded when set: a run without them writes the args.json it always wrote
+        for k, default in dict(_MESH_FLAGS, save_normal_maps=False, mesh_texture_size=0, mesh_smooth_iters=0, mesh_snap_iters=0, mesh_simplify_placement='mean', mesh_format='obj').items():      # recorded when set: a run without them writes the args.json it always wrote
             if meta[k] == default:
                 del meta[k]
         with open(os.path.join(args.logdir, 'args.json'), 'w') as f:
@@ -581,17 +591,19 @@ def run(args, objaverse=None):
         smooth = dict(smooth_iters=args.mesh_smooth_iters) if getattr(args, 'mesh_smooth_iters', 0) else {}
         snap = dict(snap_iters=args.mesh_snap_iters) if getattr(args, 'mesh_snap_iters', 0) else {}
         place = dict(simplify_placement=args.mesh_simplify_placement) if getattr(args, 'mesh_simplify_placement', 'mean') != 'mean' else {}
+        fmt = getattr(args, 'mesh_format', 'obj')
+        fmt_kw = dict(mesh_format=fmt) if fmt != 'obj' else {}
         for i in range(hi - lo):
-            path = os.path.join(args.logdir, f'mesh_sample{lo + i}.obj')
+            path = os.path.join(args.logdir, f'mesh_sample{lo + i}.{fmt}')
             if getattr(args, 'mesh_texture_size', 0):
                 try:
                     textured_mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path,
-                                            texture_size=args.mesh_texture_size, **smooth, **snap, **place, **_mesh_post(args)._asdict())
+                                            texture_size=args.mesh_texture_size, **smooth, **snap, **place, **fmt_kw, **_mesh_post(args)._asdict())
                 except ValueError as e:      # the texture cannot hold this sample's faces: known only once the surface is extracted
                     mesh_err = f"mesh export of sample {lo + i}: --mesh_texture_size {args.mesh_texture_size}: {e}"
                     break
             else:
-                mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path, **smooth, **snap, **place, **_mesh_post(args)._asdict())
+                mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path, **smooth, **snap, **place, **fmt_kw, **_mesh_post(args)._asdict())
             if not os.path.exists(path):
                 mesh_err = f"mesh export of sample {lo + i} produced no file at {path}"
                 break

@@ -13,7 +13,11 @@ an .mtl and a .png to what mesh_from_grid makes; mesh_from_grid itself is unchan
 Opt-in smoothing (no reference counterpart; include/addons/ln3d_meshsmooth.h): Taubin's lambda | mu passes over the extracted (cleaned,
 simplified) mesh in grid coordinates, before the box mapping, the colour / normal query and the bake.
 Opt-in level-set snapping (no reference counterpart; include/addons/ln3d_meshsnap.h): a damped Newton projection of the box-space vertices
-onto sigma = thr, behind the smoothing and before the colour / normal query and the bake."""
+onto sigma = thr, behind the smoothing and before the colour / normal query and the bake.
+Opt-in binary export (no reference counterpart; include/addons/ln3d_meshpack.h): mesh_format='ply' / 'glb' writes a binary little-endian
+PLY or a binary glTF 2.0 instead of the .obj text; the records and buffer sections are packed on the device from the tensors the colour
+query left there, and the host writes whole sections."""
+import json
 import math
 import os
 import struct
@@ -558,9 +562,9 @@ def write_obj_textured(path, v, f, c, uv, n=None):
         fh.write('newmtl %s\nKd 1 1 1\nmap_Kd %s.png\n' % (MATERIAL, name))
 
 
-def write_png(path, tex):
-    """tex [H,W,3] uint8 -> an 8-bit RGB PNG (standard library only: one zlib stream, filter 0 on every row).  The rows are written FLIPPED:
-    the top row of the file is tex[H - 1], because v = 0 is the bottom of a texture and row 0 of the atlas holds v = 0.5 / H."""
+def png_bytes(tex):
+    """tex [H,W,3] uint8 -> the bytes of an 8-bit RGB PNG (standard library only: one zlib stream, filter 0 on every row).  The rows are
+    FLIPPED: the top row of the image is tex[H - 1], because v = 0 is the bottom of a texture and row 0 of the atlas holds v = 0.5 / H."""
     tex = np.ascontiguousarray(tex)
     if tex.dtype != np.uint8 or tex.ndim != 3 or tex.shape[2] != 3 or tex.shape[0] < 1 or tex.shape[1] < 1:
         raise ValueError(f"tex: expected a uint8 [H, W, 3] array, got {tex.dtype} {tex.shape}")
@@ -570,9 +574,207 @@ def write_png(path, tex):
 
     def chunk(kind, data):
         return struct.pack('>I', len(data)) + kind + data + struct.pack('>I', zlib.crc32(kind + data) & 0xffffffff)
+    return (b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2, 0, 0, 0))
+            + chunk(b'IDAT', zlib.compress(rows.tobytes(), 6)) + chunk(b'IEND', b''))
+
+
+def write_png(path, tex):
+    """tex [H,W,3] uint8 -> `path`, the PNG of png_bytes"""
+    data = png_bytes(tex)
     with open(path, 'wb') as fh:
-        fh.write(b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2, 0, 0, 0))
-                 + chunk(b'IDAT', zlib.compress(rows.tobytes(), 6)) + chunk(b'IEND', b''))
+        fh.write(data)
+
+
+# ------------------------------------------------------------------ binary export (include/addons/ln3d_meshpack.h)
+MESH_FORMATS = ('obj', 'ply', 'glb')
+EXPORTER = 'ln3diff_amd'                      # the PLY comment and the glTF generator
+GLB_MAX_BYTES = 1 << 32                       # a GLB states its length in 32 bits
+
+
+def _mesh_format(fmt):
+    """-> fmt; ValueError when it is not one of MESH_FORMATS"""
+    if not isinstance(fmt, str) or fmt not in MESH_FORMATS:
+        raise ValueError(f"format {fmt!r}: expected one of {list(MESH_FORMATS)}")
+    return fmt
+
+
+def _export_args(verts, faces, rgb, normal, check):
+    """the device tensors a binary writer takes, contiguous -> (verts, faces, rgb, normal, rot9 on the device); ValueError on a bad dtype
+    or shape and, with check, on a face index out of range (one read-back)"""
+    _check_verts(verts)
+    nv = verts.shape[0]
+    verts, faces = verts.contiguous(), faces.contiguous()
+    if check:
+        ops.check_faces(faces, nv)
+    elif faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces: expected an int64 [Nf, 3] tensor, got {faces.dtype} {tuple(faces.shape)}")
+    for name, t in (('rgb', rgb), ('normal', normal)):
+        if t is not None and (t.dim() != 2 or tuple(t.shape) != (nv, 3)):
+            raise ValueError(f"{name}: expected a [{nv}, 3] tensor, got {tuple(t.shape)}")
+    rgb = rgb.float().contiguous()
+    normal = normal.float().contiguous() if normal is not None else None
+    rot9 = torch.from_numpy(rotation_matrix_x(-90).reshape(-1)).to(verts.device)
+    return verts, faces, rgb, normal, rot9
+
+
+def _host(t):
+    """a packed section on the host, as the bytes a file takes: one copy"""
+    return memoryview(t.cpu().numpy()).cast('B')
+
+
+def _ply_header(nv, nf, normals):
+    """the header of write_ply, every line ended by a newline"""
+    head = ['ply', 'format binary_little_endian 1.0', 'comment ' + EXPORTER, 'element vertex %d' % nv] + ['property float ' + a for a in 'xyz']
+    if normals:
+        head += ['property float n' + a for a in 'xyz']
+    head += ['property uchar ' + c for c in ('red', 'green', 'blue')] + ['element face %d' % nf, 'property list uchar int vertex_indices', 'end_header']
+    return ('\n'.join(head) + '\n').encode('ascii')
+
+
+@torch.no_grad()
+def write_ply(path, verts_box, faces, rgb, normal=None, check=True):
+    """A binary little-endian PLY with per-vertex colours, packed on the device (include/addons/ln3d_meshpack.h).  verts_box [Nv,3] f32 in
+    box coordinates, faces [Nf,3] int64, rgb [Nv,3] the query's colours, normal [Nv,3] the query's normals or None: DEVICE tensors.  What is
+    written: the positions rotation_matrix_x(-90) @ verts_box evaluated as (R0 x + R1 y) + R2 z in float32 without fma, the normals by the
+    same rule, the colours as trunc(clamp(c, 0, 1) * 255) - the values mesh_from_grid returns - and the indices as int32.  The header is
+    `ply / format binary_little_endian 1.0 / comment ln3diff_amd / element vertex Nv / property float x, y, z [, nx, ny, nz] / property uchar
+    red, green, blue / element face Nf / property list uchar int vertex_indices / end_header`; then Nv records of 15 (27) bytes and Nf of 13.
+    An empty mesh writes the header alone.  The host formats nothing per element: two launches, two copies, three writes.
+    check=False skips the face-index check and its read-back (mesh_from_grid, whose faces are the extraction's own)."""
+    verts_box, faces, rgb, normal, rot9 = _export_args(verts_box, faces, rgb, normal, check)
+    nv, nf = verts_box.shape[0], faces.shape[0]
+    dev = verts_box.device
+    vbytes, fbytes = nv * (15 if normal is None else 27), nf * 13
+    vbuf = fbuf = None
+    if nv:
+        vbuf = torch.empty((vbytes + 3) // 4 * 4, dtype=torch.uint8, device=dev)
+        ops.pack_ply_vertices(verts_box, normal, rgb, rot9, vbuf)
+    if nf:
+        fbuf = torch.empty((fbytes + 3) // 4 * 4, dtype=torch.uint8, device=dev)
+        ops.pack_ply_faces(faces, fbuf)
+    with open(path, 'wb') as fh:
+        fh.write(_ply_header(nv, nf, normal is not None))
+        if nv:
+            fh.write(_host(vbuf)[:vbytes])
+        if nf:
+            fh.write(_host(fbuf)[:fbytes])
+
+
+def _glb_json(views, nv_written, bounds, textured, nidx):
+    """the JSON of write_glb: views = [(name, byte length)] in buffer order -> (str, total buffer length); the key order is fixed here"""
+    F32, U8, U32, ARRAY, ELEMENT = 5126, 5121, 5125, 34962, 34963
+    accessors, buffer_views, attributes, offset, indices, image_view = [], [], {}, 0, None, None
+    for name, length in views:
+        view = {'buffer': 0, 'byteOffset': offset, 'byteLength': length}
+        if name != 'image':
+            view['target'] = ELEMENT if name == 'indices' else ARRAY
+        if name == 'POSITION':
+            acc = {'bufferView': len(buffer_views), 'componentType': F32, 'count': nv_written, 'type': 'VEC3',
+                   'min': [float(np.float32(b)) for b in bounds[:3]], 'max': [float(np.float32(b)) for b in bounds[3:]]}
+        elif name == 'NORMAL':
+            acc = {'bufferView': len(buffer_views), 'componentType': F32, 'count': nv_written, 'type': 'VEC3'}
+        elif name == 'COLOR_0':
+            acc = {'bufferView': len(buffer_views), 'componentType': U8, 'normalized': True, 'count': nv_written, 'type': 'VEC4'}
+        elif name == 'TEXCOORD_0':
+            acc = {'bufferView': len(buffer_views), 'componentType': F32, 'count': nv_written, 'type': 'VEC2'}
+        elif name == 'indices':
+            acc = {'bufferView': len(buffer_views), 'componentType': U32, 'count': nidx, 'type': 'SCALAR'}
+        else:
+            acc = None
+        if acc is not None:
+            if name == 'indices':
+                indices = len(accessors)
+            else:
+                attributes[name] = len(accessors)
+            accessors.append(acc)
+        else:
+            image_view = len(buffer_views)
+        buffer_views.append(view)
+        offset += (length + 3) // 4 * 4
+    primitive = {'attributes': attributes}
+    if indices is not None:
+        primitive['indices'] = indices
+    primitive.update(material=0, mode=4)
+    pbr = {'baseColorTexture': {'index': 0}} if textured else {}
+    pbr.update(metallicFactor=0.0, roughnessFactor=1.0)
+    doc = {'asset': {'version': '2.0', 'generator': EXPORTER}, 'scene': 0, 'scenes': [{'nodes': [0]}], 'nodes': [{'mesh': 0}],
+           'meshes': [{'primitives': [primitive]}], 'materials': [{'pbrMetallicRoughness': pbr, 'doubleSided': True}]}
+    if textured:
+        doc.update(textures=[{'sampler': 0, 'source': 0}], samplers=[{'magFilter': 9729, 'minFilter': 9729, 'wrapS': 33071, 'wrapT': 33071}],
+                   images=[{'bufferView': image_view, 'mimeType': 'image/png'}])
+    doc.update(accessors=accessors, bufferViews=buffer_views, buffers=[{'byteLength': offset}])
+    return doc, offset
+
+
+def _write_glb_file(path, doc, sections, bin_length):
+    """header, JSON chunk (padded with spaces), BIN chunk (every section padded with zeros to a multiple of 4); no BIN chunk without sections"""
+    text = json.dumps(doc, separators=(',', ':')).encode('ascii')
+    text += b' ' * (-len(text) % 4)
+    total = 12 + 8 + len(text) + ((8 + bin_length) if sections else 0)
+    if total >= GLB_MAX_BYTES:
+        raise ValueError(f"the GLB would be {total} bytes long: a GLB holds fewer than 2^32")
+    with open(path, 'wb') as fh:
+        fh.write(struct.pack('<4sII', b'glTF', 2, total) + struct.pack('<I4s', len(text), b'JSON') + text)
+        if sections:
+            fh.write(struct.pack('<I4s', bin_length, b'BIN\0'))
+            for data in sections:
+                fh.write(data)
+                if len(data) % 4:
+                    fh.write(b'\0' * (-len(data) % 4))
+
+
+@torch.no_grad()
+def write_glb(path, verts_box, faces, rgb, normal=None, uv=None, tex=None, check=True):
+    """A binary glTF 2.0 asset (.glb) whose buffer is packed on the device (include/addons/ln3d_meshpack.h).  verts_box [Nv,3] f32 in box
+    coordinates, faces [Nf,3] int64, rgb [Nv,3] the query's colours, normal [Nv,3] the query's normals or None: DEVICE tensors, with
+    write_ply's values.  One scene, one node, one mesh, one primitive in mode 4, one material (metallicFactor 0, roughnessFactor 1,
+    doubleSided: the winding of the faces is not promised).  The JSON has a fixed key order and separators, so equal meshes give equal bytes.
+    Without a texture the buffer holds POSITION f32 VEC3 [Nv], NORMAL [Nv] when given, COLOR_0 normalized UNSIGNED_BYTE VEC4 [Nv] (alpha
+    255) and the indices UNSIGNED_INT [3 Nf], each its own bufferView at a multiple of 4.
+    With uv [Nf,3,2] f32 (atlas_uvs) and tex [T,T,3] uint8 (bake_texture), numpy or tensors, the vertices are split per face corner, because
+    glTF has one index per vertex and every face owns its UV patch: POSITION [3 Nf], NORMAL [3 Nf] when given, TEXCOORD_0 f32 VEC2 [3 Nf] =
+    (u, 1 - v), corner 3 i + j holding vertex faces[i][j]; no indices and no COLOR_0 (glTF would multiply it into the texture); png_bytes(tex)
+    is one more bufferView, the image of the material's baseColorTexture.  There are no sibling files.
+    POSITION.min / max are the exact extremes of the written positions, as the repr of the float32 values widened to double.  An empty mesh
+    writes a valid asset with one empty scene and no buffer.  Raises ValueError on a bad dtype or shape, a face index out of range (check),
+    uv without tex or tex without uv, a position that is not finite, and a file of 2^32 bytes or more - all before the file is opened.
+    The host formats nothing per element: two or three launches, one copy per section and one write each."""
+    if (uv is None) != (tex is None):
+        raise ValueError("uv and tex: expected both (a textured asset) or neither")
+    verts_box, faces, rgb, normal, rot9 = _export_args(verts_box, faces, rgb, normal, check)
+    nv, nf = verts_box.shape[0], faces.shape[0]
+    dev = verts_box.device
+    textured = uv is not None
+    if textured:
+        uv = torch.as_tensor(uv).to(dev).contiguous()
+        if uv.dtype != torch.float32 or tuple(uv.shape) != (nf, 3, 2):
+            raise ValueError(f"uv: expected a float32 [{nf}, 3, 2] array, got {uv.dtype} {tuple(uv.shape)}")
+        image = png_bytes(tex.cpu().numpy() if torch.is_tensor(tex) else tex)
+    if nv == 0 or nf == 0:
+        _write_glb_file(path, {'asset': {'version': '2.0', 'generator': EXPORTER}, 'scene': 0, 'scenes': [{}]}, [], 0)
+        return
+    n = 3 * nf if textured else nv
+    pos = torch.empty(n, 3, device=dev)
+    nrm = torch.empty(n, 3, device=dev) if normal is not None else None
+    if textured:
+        last = torch.empty(n, 2, device=dev)
+        ops.pack_gltf_corners(verts_box, normal, faces, uv, rot9, pos, nrm, last, check=False)      # faces: checked above, or the caller's word
+    else:
+        last = torch.empty(n, 4, dtype=torch.uint8, device=dev)
+        idx = torch.empty(3 * nf, dtype=torch.int32, device=dev)
+        ops.pack_gltf_vertices(verts_box, normal, rgb, rot9, pos, nrm, last)
+        ops.pack_gltf_indices(faces, idx)
+    bounds = torch.empty(6, device=dev)
+    ops.position_bounds(pos, bounds)
+    bounds = bounds.cpu().numpy()                                        # the one read-back the JSON needs
+    if not np.isfinite(bounds).all():                                    # any position that is not finite shows in its axis' minimum or maximum
+        raise ValueError("verts: a written position is not finite")
+    named = [('POSITION', pos)] + ([('NORMAL', nrm)] if nrm is not None else []) + [('TEXCOORD_0' if textured else 'COLOR_0', last)]
+    if not textured:
+        named.append(('indices', idx))
+    sections = [(name, _host(t)) for name, t in named] + ([('image', image)] if textured else [])
+    doc, bin_length = _glb_json([(name, len(data)) for name, data in sections], n, bounds, textured, 3 * nf)
+    _write_glb_file(path, doc, [data for _, data in sections], bin_length)
 
 
 # ------------------------------------------------------------------ texture baking (include/ext/ln3d_meshbake.h)
@@ -661,7 +863,8 @@ def bake_texture(decoder, planes_channel_last, verts_box, faces, size, fill=0):
 def _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces, simplify_cell,
                    smooth=(0, SMOOTH_LAMBDA, SMOOTH_MU), snap=(0, None, None), simplify_placement='mean'):
     """what mesh_from_grid and textured_mesh_from_grid share: (the one sample's planes, the box-space vertices and the faces on the device,
-    then verts, faces, colors, vn as mesh_from_grid returns them; vn is None without normals).  smooth: (iterations, lam, mu) of smooth_mesh,
+    then verts, faces, colors, vn as mesh_from_grid returns them; vn is None without normals; last the query's own dict, whose 'rgb' and
+    'normal' [1,Nv,3] the binary writers take from the device).  smooth: (iterations, lam, mu) of smooth_mesh,
     applied to the extracted mesh in grid coordinates, so everything behind it sees the smoothed positions.  snap: (iterations, tol, max_move
     in grid units) of snap_mesh at level = thr, applied to the box-space vertices behind that and before the query.  simplify_placement:
     extract_isosurface's, handed on only when it is not 'mean'."""
@@ -684,13 +887,22 @@ def _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method
     v = (rotation_matrix_x(-90) @ vtx.cpu().numpy().T).T.astype(np.float32)
     f = faces.cpu().numpy()
     vn = (rotation_matrix_x(-90) @ q['normal'][0].cpu().numpy().T).T.astype(np.float32) if normals else None
-    return pcl, vtx, faces, v, f, colors, vn
+    return pcl, vtx, faces, v, f, colors, vn, q
+
+
+def _write_binary(mesh_format, path, vtx, faces, q, normals, uv=None, tex=None):
+    """the 'ply' / 'glb' branch of the two mesh functions: _coloured_mesh's device tensors go to the packers as they are"""
+    normal = q['normal'][0] if normals else None
+    if mesh_format == 'ply':
+        write_ply(path, vtx, faces, q['rgb'][0], normal, check=False)   # faces are the extraction's own: in range by construction
+    else:
+        write_glb(path, vtx, faces, q['rgb'][0], normal, uv, tex, check=False)
 
 
 @torch.no_grad()
 def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes', normals=False,
                    keep='all', min_faces=0, simplify_cell=0.0, smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU,
-                   snap_iters=0, snap_tol=None, snap_max_move=None, simplify_placement='mean'):
+                   snap_iters=0, snap_tol=None, snap_max_move=None, simplify_placement='mean', mesh_format='obj'):
     """nsr/train_util_diffusion.py:221-244: iso-surface of the sigma grid at `thr`, vertices mapped to the +-0.45 box, coloured
     by re-querying the tri-plane at the vertices (forward_points), rotated -90 degrees about x.
     Returns (verts [Nv,3] float32 numpy, faces [Nf,3] int64 numpy, colors [Nv,3] uint8 numpy); writes `path` when given.
@@ -712,19 +924,27 @@ def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0,
     simplify_placement (opt-in; no reference counterpart): 'quadric' puts every vertex of the simplified mesh where the planes of the faces
     around its cell meet (simplify_mesh's placement) instead of at the mean of the cell, so creases and corners survive; faces, vertex count
     and order are those of 'mean', and smoothing, snapping and the query follow as they do today, at the quadric positions.  Without
-    simplify_cell there is nothing to place.  See simplify_mesh for what it does not promise: on smooth regions it is no closer than the mean."""
-    _, _, _, v, f, colors, vn = _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces,
-                                               simplify_cell, (smooth_iters, smooth_lambda, smooth_mu), (snap_iters, snap_tol, snap_max_move),
-                                               simplify_placement)
-    if path:
+    simplify_cell there is nothing to place.  See simplify_mesh for what it does not promise: on smooth regions it is no closer than the mean.
+    mesh_format (opt-in; no reference counterpart): what `path` is written as - 'obj' (the default: exactly the text file above), 'ply'
+    (write_ply: binary little-endian, vertex colours, normals when asked for) or 'glb' (write_glb: binary glTF 2.0).  The two binary files are
+    packed on the device from the tensors the query left there and hold the returned values bit for bit; the returned tuple does not depend
+    on the format, and the extension of `path` is not interpreted.  A value that is none of the three is a ValueError before anything is
+    extracted."""
+    mesh_format = _mesh_format(mesh_format)
+    _, vtx, faces, v, f, colors, vn, q = _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces,
+                                                        simplify_cell, (smooth_iters, smooth_lambda, smooth_mu),
+                                                        (snap_iters, snap_tol, snap_max_move), simplify_placement)
+    if path and mesh_format == 'obj':
         write_obj(path, v, f, colors.astype(np.float32) / 255.0, vn)
+    elif path:
+        _write_binary(mesh_format, path, vtx, faces, q, normals)
     return (v, f, colors, vn) if normals else (v, f, colors)
 
 
 @torch.no_grad()
 def textured_mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes', texture_size=1024,
                             normals=False, keep='all', min_faces=0, simplify_cell=0.0, smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA,
-                            smooth_mu=SMOOTH_MU, snap_iters=0, snap_tol=None, snap_max_move=None, simplify_placement='mean'):
+                            smooth_mu=SMOOTH_MU, snap_iters=0, snap_tol=None, snap_max_move=None, simplify_placement='mean', mesh_format='obj'):
     """mesh_from_grid plus a baked texture (opt-in; no reference counterpart): the same geometry, vertex colours and `vn`, bit for bit, for
     the same options, then bake_texture of the faces at the box-space vertices (before the rotation, where the field lives) into a
     texture_size x texture_size per-face atlas.  Returns mesh_from_grid's tuple with (uv [Nf,3,2] float32, tex [T,T,3] uint8) appended.
@@ -735,29 +955,37 @@ def textured_mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample
     texel, no supersampling; there is no mip-safe padding beyond the 1 - 1.5 texel gutter; and the colours are the field's values on the
     (possibly simplified, possibly smoothed: smooth_iters / smooth_lambda / smooth_mu are mesh_from_grid's) triangles, which lie off the
     level set by the simplifier's and the smoother's error.  snap_iters / snap_tol / snap_max_move (mesh_from_grid's) put the VERTICES
-    back on it before the bake; the interiors of the triangles stay where the flat faces are.  simplify_placement is mesh_from_grid's."""
+    back on it before the bake; the interiors of the triangles stay where the flat faces are.  simplify_placement is mesh_from_grid's.
+    mesh_format (opt-in): 'glb' writes `path` alone, a binary glTF that embeds the .png and splits the vertices per face corner (write_glb:
+    3 Nf vertices, TEXCOORD_0 = (u, 1 - v), no vertex colours); the returned tuple is the same.  'ply' carries vertex colours only: with
+    a texture it is a ValueError before anything is extracted."""
     _atlas_size(texture_size)
-    pcl, vtx, faces, v, f, colors, vn = _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces,
-                                                       simplify_cell, (smooth_iters, smooth_lambda, smooth_mu),
-                                                       (snap_iters, snap_tol, snap_max_move), simplify_placement)
+    if _mesh_format(mesh_format) == 'ply':
+        raise ValueError("format 'ply' carries vertex colours only: a textured mesh is written as 'obj' or 'glb'")
+    pcl, vtx, faces, v, f, colors, vn, q = _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces,
+                                                          simplify_cell, (smooth_iters, smooth_lambda, smooth_mu),
+                                                          (snap_iters, snap_tol, snap_max_move), simplify_placement)
     uv, tex = bake_texture(decoder, pcl, vtx, faces, texture_size)
-    if path:
+    if path and mesh_format == 'obj':
         write_obj_textured(path, v, f, colors.astype(np.float32) / 255.0, uv, vn)
         write_png(os.path.splitext(str(path))[0] + '.png', tex)
+    elif path:
+        _write_binary(mesh_format, path, vtx, faces, q, normals, uv, tex)
     return ((v, f, colors, vn) if normals else (v, f, colors)) + (uv, tex)
 
 
 @torch.no_grad()
 def export_mesh(decoder, dec_out, path, grid_size=192, thr=10.0, sample_index=0, normals=False, keep='all', min_faces=0, simplify_cell=0.0,
                 smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU, snap_iters=0, snap_tol=None, snap_max_move=None,
-                simplify_placement='mean'):
+                simplify_placement='mean', mesh_format='obj'):
     """decoder: the VAE decoder module; dec_out: its vit_decode_postprocess dict.  Writes `path` (.obj), with `vn` records when normals;
     keep / min_faces / simplify_cell / smooth_iters / smooth_lambda / smooth_mu / snap_iters / snap_tol / snap_max_move /
-    simplify_placement: mesh_from_grid's (the last handed on only when it is not 'mean')."""
+    simplify_placement / mesh_format: mesh_from_grid's (the last two handed on only when they are not 'mean' / 'obj')."""
     pcl = dec_out['planes_channel_last'][sample_index:sample_index + 1]
     grid = decoder.triplane_decode_grid({'planes_channel_last': pcl}, grid_size)
     place = dict(simplify_placement=simplify_placement) if _placement(simplify_placement)[0] != 'mean' else {}
+    fmt = dict(mesh_format=mesh_format) if _mesh_format(mesh_format) != 'obj' else {}
     v, f = mesh_from_grid(decoder, {'planes_channel_last': pcl}, grid['sigma'][0], grid_size, thr, 0, path, normals=normals, keep=keep,
                           min_faces=min_faces, simplify_cell=simplify_cell, smooth_iters=smooth_iters, smooth_lambda=smooth_lambda,
-                          smooth_mu=smooth_mu, snap_iters=snap_iters, snap_tol=snap_tol, snap_max_move=snap_max_move, **place)[:2]
+                          smooth_mu=smooth_mu, snap_iters=snap_iters, snap_tol=snap_tol, snap_max_move=snap_max_move, **place, **fmt)[:2]
     return v.shape[0], f.shape[0]

@@ -570,6 +570,93 @@ def smooth_step(verts_in, start, nbr, pinned, factor, verts_out, check=True):
     L.check(L.lib().ln3d_smooth_step(_p(verts_in), _p(start), _p(nbr), _p(pinned), nv, nh, float(factor), _p(verts_out), _stream()), "smooth_step")
 
 
+# ------------------------------------------------------------------ binary mesh export (include/addons/ln3d_meshpack.h)
+def _pack_rows(xyz, normal, what="xyz"):
+    """xyz [n,3] f32 and, when given, normal of the same shape -> n"""
+    n = xyz.shape[0]
+    _buffer(xyz, torch.float32, (n, 3), what)
+    if normal is not None:
+        _buffer(normal, torch.float32, (n, 3), "normal")
+    return n
+
+
+def _pack_bytes(out, nbytes, what="out"):
+    """a uint8 buffer of exactly nbytes rounded up to a multiple of 4: the packers write whole words"""
+    _buffer(out, torch.uint8, ((nbytes + 3) // 4 * 4,), what)
+
+
+def pack_ply_vertices(xyz, normal, rgb, rot9, out):
+    """out [ceil(nv * S / 4) * 4] uint8 <- the nv vertex records of a binary little-endian PLY, S = 15 bytes each (3 f32 rot9 @ xyz, 3 uint8
+    colours) or 27 with normal (3 f32 rot9 @ normal between them); the pad bytes behind the last record are 0.  xyz, normal (or None), rgb
+    [nv,3] f32, rot9 [9] f32: a row-major 3 x 3 matrix."""
+    nv = _pack_rows(xyz, normal)
+    _buffer(rgb, torch.float32, (nv, 3), "rgb")
+    _buffer(rot9, torch.float32, (9,), "rot9")
+    _pack_bytes(out, nv * (15 if normal is None else 27))
+    L.check(L.lib().ln3d_pack_ply_vertices(_p(xyz), _p(normal), _p(rgb), _p(rot9), nv, _p(out), _stream()), "pack_ply_vertices")
+
+
+def pack_ply_faces(faces, out):
+    """out [ceil(nf * 13 / 4) * 4] uint8 <- the nf face records of a binary PLY: the byte 3 and three int32; faces [nf,3] int64.  Nothing is
+    gathered, so there is no index to check: the values are narrowed to 32 bits."""
+    nf = faces.shape[0]
+    _buffer(faces, torch.int64, (nf, 3), "faces")
+    _pack_bytes(out, nf * 13)
+    L.check(L.lib().ln3d_pack_ply_faces(_p(faces), nf, _p(out), _stream()), "pack_ply_faces")
+
+
+def pack_gltf_vertices(xyz, normal, rgb, rot9, pos_out, nrm_out, rgba_out):
+    """pos_out [nv,3] f32 <- rot9 @ xyz; nrm_out [nv,3] f32 <- rot9 @ normal (both None, or neither); rgba_out [nv,4] uint8 <- the colour
+    bytes of rgb [nv,3] f32 and 255"""
+    nv = _pack_rows(xyz, normal)
+    if (normal is None) != (nrm_out is None):
+        raise ValueError("normal and nrm_out: expected both or neither")
+    _buffer(rgb, torch.float32, (nv, 3), "rgb")
+    _buffer(rot9, torch.float32, (9,), "rot9")
+    _buffer(pos_out, torch.float32, (nv, 3), "pos_out")
+    if nrm_out is not None:
+        _buffer(nrm_out, torch.float32, (nv, 3), "nrm_out")
+    _buffer(rgba_out, torch.uint8, (nv, 4), "rgba_out")
+    L.check(L.lib().ln3d_pack_gltf_vertices(_p(xyz), _p(normal), _p(rgb), _p(rot9), nv, _p(pos_out), _p(nrm_out), _p(rgba_out), _stream()),
+            "pack_gltf_vertices")
+
+
+def pack_gltf_indices(faces, idx_out):
+    """idx_out [3 nf] int32 (read as uint32) <- faces [nf,3] int64, narrowed"""
+    nf = faces.shape[0]
+    _buffer(faces, torch.int64, (nf, 3), "faces")
+    _buffer(idx_out, torch.int32, (3 * nf,), "idx_out")
+    L.check(L.lib().ln3d_pack_gltf_indices(_p(faces), nf, _p(idx_out), _stream()), "pack_gltf_indices")
+
+
+def pack_gltf_corners(xyz, normal, faces, uv, rot9, pos_out, nrm_out, uv_out, check=True):
+    """The per-corner vertex sections of a textured GLB: pos_out [3 nf,3] f32 <- rot9 @ xyz[faces[i][j]] at corner 3 i + j; nrm_out likewise
+    from normal (both None, or neither); uv_out [3 nf,2] f32 <- (u, 1 - v) of uv [nf,3,2] f32.  check=False: the caller has already put these
+    faces through check_faces."""
+    nv, nf = _pack_rows(xyz, normal), faces.shape[0]
+    if (normal is None) != (nrm_out is None):
+        raise ValueError("normal and nrm_out: expected both or neither")
+    _buffer(faces, torch.int64, (nf, 3), "faces")
+    _buffer(uv, torch.float32, (nf, 3, 2), "uv")
+    _buffer(rot9, torch.float32, (9,), "rot9")
+    _buffer(pos_out, torch.float32, (3 * nf, 3), "pos_out")
+    if nrm_out is not None:
+        _buffer(nrm_out, torch.float32, (3 * nf, 3), "nrm_out")
+    _buffer(uv_out, torch.float32, (3 * nf, 2), "uv_out")
+    if check:
+        check_faces(faces, nv)
+    L.check(L.lib().ln3d_pack_gltf_corners(_p(xyz), _p(normal), _p(faces), _p(uv), _p(rot9), nv, nf, _p(pos_out), _p(nrm_out), _p(uv_out),
+                                           _stream()), "pack_gltf_corners")
+
+
+def position_bounds(pos, bounds6):
+    """bounds6 [6] f32 <- the per-axis minimum, then maximum, of pos [n,3] f32, which the caller has found finite"""
+    n = pos.shape[0]
+    _buffer(pos, torch.float32, (n, 3), "pos")
+    _buffer(bounds6, torch.float32, (6,), "bounds6")
+    L.check(L.lib().ln3d_position_bounds(_p(pos), n, _p(bounds6), _stream()), "position_bounds")
+
+
 SNAP_MAX_ITERS = 64
 
 
