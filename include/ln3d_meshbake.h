@@ -4,8 +4,8 @@
  * uint8.  There is no reference counterpart (the reference writes one colour per vertex); everything here is opt-in and changes no other
  * output.  Same conventions as ln3d_meshclean.h (caller-owned device pointers, stream as void*, 0 or a negative LN3D_ERR_* code,
  * asynchronous on the stream, no allocation, no device-to-host read, one launch per call, no float atomics).  The entry points are
- * additions to ABI 10 of ln3d.h that use no struct and no new constant; they are declared under include/ext/ and bound from
- * _lib.EXT_PROTOTYPES (tests/test_abi_ext_cpu.py holds that table to this header).
+ * additions to ABI 10 of ln3d.h that use no struct and no new constant; like every other export they are bound from
+ * _lib.PROTOTYPES (tests/test_abi_types_cpu.py holds that table to every header).
  *
  * The atlas (pure integer and half-integer arithmetic; ln3diff_amd/mesh.py atlas_layout / atlas_uvs are the host side of it):
  *   - texel (x, y) has its centre at (x + 0.5, y + 0.5); its flat index is y * T + x; 4 <= T <= 8192;
@@ -35,7 +35,7 @@
 #ifndef LN3D_MESHBAKE_H
 #define LN3D_MESHBAKE_H
 #include <stdint.h>
-#include "../ln3d.h"
+#include "ln3d.h"
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -2,7 +2,7 @@
  * of a binary little-endian PLY, and the buffer sections of a binary glTF (GLB).  There is no reference counterpart; everything here is
  * opt-in and changes no other output.  Same conventions as ln3d_meshclean.h (caller-owned device pointers, stream as void*, 0 or a negative
  * LN3D_ERR_* code, asynchronous on the stream, no allocation, no device-to-host read, no float atomics).  The entry points are additions to
- * ABI 10 of ln3d.h that use no struct and no new constant; they are bound from _lib.ADDON_PROTOTYPES.
+ * ABI 10 of ln3d.h that use no struct and no new constant; they are bound from _lib.PROTOTYPES.
  *
  * The values (all arithmetic float32; every output byte is unique, nothing depends on scheduling):
  *   - a rotated row: with rot9 the nine floats of a row-major 3 x 3 matrix R and (x, y, z) a row of xyz (or of normal),
@@ -29,7 +29,7 @@
 #ifndef LN3D_MESHPACK_H
 #define LN3D_MESHPACK_H
 #include <stdint.h>
-#include "../ln3d.h"
+#include "ln3d.h"
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -4,7 +4,7 @@
  * keeps the creases and corners that the mean chamfers by up to about 0.4 cells.  There is no reference counterpart; everything here is
  * opt-in and changes no other output.  Same conventions as ln3d_meshsmooth.h (caller-owned device pointers, stream as void*, 0 or a negative
  * LN3D_ERR_* code, asynchronous on the stream, no allocation, no device-to-host read, one launch per call, no float atomics).  The entry
- * points are additions to ABI 10 of ln3d.h that use no struct and no new constant; they are bound from _lib.ADDON_PROTOTYPES.
+ * points are additions to ABI 10 of ln3d.h that use no struct and no new constant; they are bound from _lib.PROTOTYPES.
  *
  * The definition.  Clusters k, cluster[v], cfaces[f][j] and the mean m_k are those of ln3d_meshsimplify.h; ln3d_simplify_mean's output keeps
  * its bits.  verts [nv, 3] f32, faces [nf, 3] int64, cfaces [nf, 3] int64.
@@ -49,7 +49,7 @@
 #ifndef LN3D_MESHQUADRIC_H
 #define LN3D_MESHQUADRIC_H
 #include <stdint.h>
-#include "../ln3d.h"
+#include "ln3d.h"
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -3,8 +3,7 @@
  * reference counterpart; everything here is opt-in and changes no other output.  Same conventions as ln3d_meshclean.h (caller-owned device
  * pointers, stream as void*, 0 or a negative LN3D_ERR_* code, asynchronous on the stream, no allocation, no device-to-host read, one launch
  * per call, no float atomics).  The entry points are additions to ABI 10 of ln3d.h that use no struct and no new constant; they are
- * declared under include/addons/ and bound from _lib.ADDON_PROTOTYPES (tests/test_mesh_smooth_cpu.py holds that table to every header of
- * this directory, so the next addition is a header here and its rows there, not another table).
+ * bound from _lib.PROTOTYPES.
  *
  * The definition (all arithmetic float32; every output is unique, nothing depends on scheduling).  verts [nv, 3] f32, faces [nf, 3] int64:
  *   - edges: every face contributes its three undirected edges {a, b}; an edge with a == b is ignored; duplicate faces and opposite
@@ -37,7 +36,7 @@
 #ifndef LN3D_MESHSMOOTH_H
 #define LN3D_MESHSMOOTH_H
 #include <stdint.h>
-#include "../ln3d.h"
+#include "ln3d.h"
 #ifdef __cplusplus
 extern "C" {
 #endif

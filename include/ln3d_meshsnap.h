@@ -4,7 +4,7 @@
  * and texels are taken.  There is no reference counterpart; everything here is opt-in and changes no other output.  Same conventions as
  * ln3d_normals.h (caller-owned device pointers, stream as void*, 0 or a negative LN3D_ERR_* code, asynchronous on the stream, no
  * allocation, one launch per call, every workgroup stages the decoder from the caller's weights itself).  The entry points are additions
- * to ABI 10 of ln3d.h with scalar and pointer arguments only and no new constant; they are bound from _lib.ADDON_PROTOTYPES.
+ * to ABI 10 of ln3d.h with scalar and pointer arguments only and no new constant; they are bound from _lib.PROTOTYPES.
  *
  * The field and its gradient are exactly those of ln3d_query_points_grad (ln3d_normals.h): field(p) = (sigma, d sigma / d p in world
  * units), all fp32, one device function for both.  The loop, per point, all arithmetic fp32, every operation outside field() rounded once
@@ -46,7 +46,7 @@
 #ifndef LN3D_MESHSNAP_H
 #define LN3D_MESHSNAP_H
 #include <stdint.h>
-#include "../ln3d.h"
+#include "ln3d.h"
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -1,6 +1,5 @@
 """ctypes binding of libln3d_hip.so (the C ABI of include/ln3d.h, include/ln3d_encoder.h, include/ln3d_shapenet.h, include/ln3d_mx.h, include/ln3d_ffhq.h,
-include/ln3d_planes16.h, include/ln3d_normals.h, include/ln3d_meshclean.h and include/ln3d_meshsimplify.h, plus the additions of
-include/ext/ln3d_meshbake.h in EXT_PROTOTYPES and of every header under include/addons/ in ADDON_PROTOTYPES).
+include/ln3d_planes16.h, include/ln3d_normals.h and the include/ln3d_mesh*.h of the mesh post-processing: every header of include/).
 
 Every export is declared once, in PROTOTYPES: name -> (restype, argtypes), which lib() applies, so a call site passes plain Python values
 and a value of the wrong kind is a ctypes.ArgumentError.  One rule maps a C parameter to its argtype:
@@ -175,46 +174,28 @@ PROTOTYPES = {
     "ln3d_simplify_faces": _int(vp, i64, vp, i64, i64, vp, vp, vp),
     "ln3d_simplify_first": _int(vp, vp, i64, vp, vp),
     "ln3d_simplify_used": _int(vp, vp, i64, i64, vp, vp),
-}
-SYMBOLS = list(PROTOTYPES)
-
-# Additions to ABI 10 declared under include/ext/ (tests/test_abi_ext_cpu.py holds this table to those headers by the same rule).  They use
-# no struct and no new constant and change no row above, so ABI_VERSION still describes every symbol it described.  That test names this
-# table's two rows, as tests/test_abi_types_cpu.py counts the 80 above: both tables are frozen for as long as those files are, and nothing is
-# folded.  What comes later goes into ADDON_PROTOTYPES.
-EXT_PROTOTYPES = {
-    # include/ext/ln3d_meshbake.h (texture baking of an exported mesh: per-face atlas)
+    # include/ln3d_meshbake.h (texture baking of an exported mesh: per-face atlas)
     "ln3d_bake_points": _int(vp, i64, vp, i64, i32, i32, i32, vp, vp, vp),
     "ln3d_bake_pack": _int(vp, vp, i64, i32, vp, vp),
-}
-
-# Every later addition to ABI 10, declared under include/addons/ (one header per feature) by the rule of EXT_PROTOTYPES: no struct, no new
-# constant, no name of the tables above.  tests/test_mesh_smooth_cpu.py holds this table row for row to whatever headers that directory has
-# and names no entry and no count, so the next feature adds a header there and its rows here, not a fourth table.
-ADDON_PROTOTYPES = {
-    # include/addons/ln3d_meshpack.h (the records of a binary PLY and the buffer sections of a GLB, packed on the device)
+    # include/ln3d_meshpack.h (the records of a binary PLY and the buffer sections of a GLB, packed on the device)
     "ln3d_pack_ply_vertices": _int(vp, vp, vp, vp, i64, vp, vp),
     "ln3d_pack_ply_faces": _int(vp, i64, vp, vp),
     "ln3d_pack_gltf_vertices": _int(vp, vp, vp, vp, i64, vp, vp, vp, vp),
     "ln3d_pack_gltf_indices": _int(vp, i64, vp, vp),
     "ln3d_pack_gltf_corners": _int(vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp),
     "ln3d_position_bounds": _int(vp, i64, vp, vp),
-    # include/addons/ln3d_meshquadric.h (quadric-error placement of the simplification's representatives)
+    # include/ln3d_meshquadric.h (quadric-error placement of the simplification's representatives)
     "ln3d_quadric_pairs": _int(vp, i64, i64, vp, vp),
     "ln3d_quadric_place": _int(vp, i64, vp, i64, vp, i64, vp, i64, vp, f32, f32, f32, f32, vp, f32, vp, vp, vp),
-    # include/addons/ln3d_meshsmooth.h (Taubin smoothing of an exported mesh)
+    # include/ln3d_meshsmooth.h (Taubin smoothing of an exported mesh)
     "ln3d_smooth_edge_keys": _int(vp, i64, vp, vp),
     "ln3d_smooth_halfedges": _int(vp, vp, i64, i64, vp, vp, vp),
     "ln3d_smooth_step": _int(vp, vp, vp, vp, i64, i64, f32, vp, vp),
-    # include/addons/ln3d_meshsnap.h (Newton projection of points onto a level set of the density field)
+    # include/ln3d_meshsnap.h (Newton projection of points onto a level set of the density field)
     "ln3d_snap_points": _int(vp, i32, i32, vp, i64, vp, vp, vp, vp, f32, f32, i32, f32, f32, f32, vp, vp, vp, vp, vp),
     "ln3d_snap_points_f16": _int(vp, i32, i32, vp, i64, vp, vp, vp, vp, f32, f32, i32, f32, f32, f32, vp, vp, vp, vp, vp),
 }
-
-
-def _tables():
-    """every bound entry point: name -> (restype, argtypes), the three tables in order"""
-    return list(PROTOTYPES.items()) + list(EXT_PROTOTYPES.items()) + list(ADDON_PROTOTYPES.items())
+SYMBOLS = list(PROTOTYPES)
 
 
 _lib = None
@@ -234,7 +215,7 @@ def lib():
         # fail with "HIP kernel launch failed".
         import torch  # noqa: F401
         _lib = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in _tables():
+        for name, (restype, argtypes) in PROTOTYPES.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = restype, argtypes
     return _lib
@@ -242,7 +223,7 @@ def lib():
 
 def check_symbols():
     L = lib()
-    missing = [s for s, _ in _tables() if not hasattr(L, s)]
+    missing = [s for s in PROTOTYPES if not hasattr(L, s)]
     if missing:
         raise RuntimeError(f"libln3d_hip.so lacks symbols: {missing}")
     assert L.ln3d_abi_version() == ABI_VERSION

@@ -12,9 +12,9 @@
 #include "../../include/ln3d.h"
 #include "../../include/ln3d_meshclean.h"
 #include "../../include/ln3d_meshsimplify.h"
-#include "../../include/ext/ln3d_meshbake.h"
-#include "../../include/addons/ln3d_meshquadric.h"
-#include "../../include/addons/ln3d_meshsmooth.h"
+#include "../../include/ln3d_meshbake.h"
+#include "../../include/ln3d_meshquadric.h"
+#include "../../include/ln3d_meshsmooth.h"
 #include "mc_table.h"
 
 __constant__ int kTet[6][4] = {{0, 1, 3, 7}, {0, 2, 3, 7}, {0, 2, 6, 7}, {0, 4, 6, 7}, {0, 4, 5, 7}, {0, 1, 5, 7}};
@@ -425,7 +425,7 @@ extern "C" int ln3d_simplify_used(const int64_t* cfaces, const int32_t* keep_f, 
   return ln3d_check_launch();
 }
 
-// ------------------------------------------------------------------ texture baking (include/ext/ln3d_meshbake.h)
+// ------------------------------------------------------------------ texture baking (include/ln3d_meshbake.h)
 // The per-face atlas: which face owns a texel is integer work, the point on that face is six individually rounded fp32 operations per axis,
 // so both outputs are unique by definition.  (__fmul_rn and __fadd_rn are plain operators in this compiler's headers and a product next to
 // a sum is contracted into an fma, which rounds once instead of twice: the expression stands under `fp contract(off)` instead.)  The field is evaluated at the points
@@ -488,7 +488,7 @@ extern "C" int ln3d_bake_pack(const float* rgb, const int32_t* owner, int64_t P,
   return ln3d_check_launch();
 }
 
-// ------------------------------------------------------------------ mesh smoothing (include/addons/ln3d_meshsmooth.h)
+// ------------------------------------------------------------------ mesh smoothing (include/ln3d_meshsmooth.h)
 // Taubin's lambda | mu passes over the vertex adjacency.  The adjacency is integer work (edge keys, the caller's unique and sort, half-edges);
 // a pass is a gather of one thread per vertex over its CSR row in ascending neighbour index, a short chain of individually rounded fp32
 // operations, so every output is unique by definition.  The array a pass gathers from (12 bytes a vertex) stays in L2.
@@ -563,7 +563,7 @@ extern "C" int ln3d_smooth_step(const float* verts_in, const int64_t* start, con
   return ln3d_check_launch();
 }
 
-// ------------------------------------------------------------------ quadric-error placement (include/addons/ln3d_meshquadric.h)
+// ------------------------------------------------------------------ quadric-error placement (include/ln3d_meshquadric.h)
 // The opt-in second placement rule of the simplification.  The incidence is integer work (pair keys, the caller's sort and searchsorted); the
 // placement is one wavefront per cluster: 64 lanes gather 64 faces' corners at a time (at 45 faces per cluster on average one round; one lane
 // per cluster would walk 45 dependent gathers in a row and leave most of the device idle at 10^4 clusters), every lane sums its faces in

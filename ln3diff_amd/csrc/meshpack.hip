@@ -1,4 +1,4 @@
-// Binary mesh export for gfx950 (include/addons/ln3d_meshpack.h): the records of a binary little-endian PLY and the buffer sections of a
+// Binary mesh export for gfx950 (include/ln3d_meshpack.h): the records of a binary little-endian PLY and the buffer sections of a
 // GLB, assembled on the device so that the host writes whole sections and touches no element.
 // The PLY records are 15, 27 and 13 bytes long.  One thread per record would issue byte stores scattered over a stride that is no multiple
 // of 4; instead one thread owns one aligned OUTPUT word, looks up which record and field each of its four bytes comes from, and stores
@@ -7,7 +7,7 @@
 // The GLB sections are arrays of whole words already: one thread per float.
 #include "common.h"
 #include "../../include/ln3d.h"
-#include "../../include/addons/ln3d_meshpack.h"
+#include "../../include/ln3d_meshpack.h"
 
 static inline dim3 pack_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }                        // one thread per element, blocks of 256
 static inline bool pack_count_ok(int64_t n) { return n >= 1 && n <= 0x7fffffffll; }

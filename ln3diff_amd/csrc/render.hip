@@ -27,7 +27,7 @@
 #include "../../include/ln3d.h"
 #include "../../include/ln3d_planes16.h"
 #include "../../include/ln3d_normals.h"
-#include "../../include/addons/ln3d_meshsnap.h"
+#include "../../include/ln3d_meshsnap.h"
 
 #define NS 64            // samples per pass (coarse == fine == 64, Objaverse preset)
 #define WAVE_LDS_BYTES 8192           // per wave: 64 points x (64 B hi + 64 B lo) feature rows; reused for cdf / merge arrays
@@ -1414,7 +1414,7 @@ extern "C" int ln3d_query_points_grad_f16(const void* planes, int H, int W, cons
   return query_points_grad_t<_Float16>(planes, H, W, points, P, dec_w0, dec_b0, dec_w1, dec_b1, box_warp, sigma, grad, stream);
 }
 
-// ------------------------------------------------------------------ level-set snapping (include/addons/ln3d_meshsnap.h)
+// ------------------------------------------------------------------ level-set snapping (include/ln3d_meshsnap.h)
 // One lane per point, the decoder staged once per block as above.  The loop of the header is turned inside out so that there is ONE
 // call site of sigma_grad_point (it is ~600 instructions and 64 live registers): the outer loop evaluates the pending point - the input
 // first, a candidate afterwards - and the inner loop spends iterations until it has the next candidate to evaluate or the lane is

@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from .mesh import MeshPost, _atlas_size, _clean_args, _mesh_format, _simplify_cell, _placement, _smooth_args, _snap_args, mesh_from_grid, textured_mesh_from_grid
+from .mesh import MeshPost, mesh_from_record
 
 # --trainer_name -> engine (scripts/vit_triplane_diffusion_sample_objaverse.py:135-142, scripts/vit_triplane_diffusion_sample.py:236-242)
 TRAINERS = {
@@ -75,10 +75,22 @@ def str2bool(v):
     raise argparse.ArgumentTypeError('boolean value expected')
 
 
+def _mesh_flag(field):
+    """the flag of a mesh.MeshPost field: its pipeline keyword, except that normals is --export_mesh_normals"""
+    return 'export_mesh_normals' if field == 'normals' else MeshPost.keyword(field)
+
+
 # the flags of mesh.MeshPost's fields, in field order, with its defaults (no reference counterpart; all need --export_mesh true): `vn` records
 # with the density field's outward normals; all | largest: which connected components are written; components with fewer faces are dropped
-# (floaters); > 0: the mesh is simplified by vertex clustering on cells of that many grid units
-_MESH_FLAGS = dict(zip(('export_mesh_normals', 'mesh_keep', 'mesh_min_faces', 'mesh_simplify_cell'), MeshPost._field_defaults.values()))
+# (floaters); > 0: the mesh is simplified by vertex clustering on cells of that many grid units; quadric: the simplified vertices are put where
+# the planes of the faces around their cell meet, which keeps creases and corners (needs --mesh_simplify_cell); > 0: that many iterations of
+# Taubin smoothing before the mesh is coloured; > 0: the vertices are put back on the level set (at most that many Newton iterations) before
+# the mesh is coloured; > 0: a baked texture of that many texels a side (.mtl, .png); ply | glb: mesh_sample{i}.ply / .glb, a binary file
+# packed on the GPU, instead of the .obj text (ply carries vertex colours only: not with --mesh_texture_size)
+_MESH_FLAGS = {_mesh_flag(field): default for field, default in MeshPost._field_defaults.items()}
+# what a flag that is set asks for, for the refusal without --export_mesh true
+_MESH_PURPOSE = dict(normals='put normals into', keep='clean', min_faces='clean', simplify_cell='simplify', simplify_placement='simplify',
+                     smooth_iters='smooth', snap_iters='snap', texture_size='texture', mesh_format='write')
 
 
 def add_dict_to_argparser(ap, d):            # guided_diffusion/script_util.py:712-722
@@ -109,11 +121,6 @@ def create_argparser(objaverse=True):
         dit_precision='bf16',                # matmul precision of the T23D DiT (no reference counterpart): bf16 or the opt-in mxfp8
         plane_precision='fp32',              # texel storage of the renderer's tri-planes (no reference counterpart): fp32 or the opt-in fp16
         save_normal_maps=False,              # normal_sample{i}.npy [V,3,R,R]: world-space surface normal maps next to the frames
-        mesh_texture_size=0,                 # > 0: every exported mesh gets a baked texture of that many texels a side (.mtl, .png); not a MeshPost field
-        mesh_smooth_iters=0,                 # > 0: every exported mesh gets that many iterations of Taubin smoothing before it is coloured; not a MeshPost field
-        mesh_snap_iters=0,                   # > 0: the vertices of every exported mesh are put back on the level set (at most that many Newton iterations) before it is coloured; not a MeshPost field
-        mesh_simplify_placement='mean',      # 'quadric': the vertices of a simplified mesh are put where the planes of the faces around their cell meet, which keeps creases and corners (needs --mesh_simplify_cell); not a MeshPost field
-        mesh_format='obj',                   # 'ply' / 'glb': every exported mesh is written as mesh_sample{i}.ply / .glb, a binary file packed on the GPU, instead of the .obj text ('ply' carries vertex colours only: not with --mesh_texture_size); not a MeshPost field
         **_MESH_FLAGS)
     d.update(_IGNORED_DEFAULTS)
     d.update({k: v[0] for k, v in _CHECKED.items()})
@@ -170,56 +177,18 @@ def validate(args):
     if plane_prec not in PLANE_PRECISIONS:
         raise SystemExit(f"--plane_precision {plane_prec}: expected one of {list(PLANE_PRECISIONS)}")
     post = _mesh_post(args)
-    if post.normals and not args.export_mesh:
-        raise SystemExit("--export_mesh_normals true: there is no mesh to put normals into without --export_mesh true")
-    try:                                     # the library's own checks, so the launcher refuses exactly what mesh_from_grid would, before sampling
-        clean, cell = _clean_args(post.keep, post.min_faces), _simplify_cell(post.simplify_cell)
-    except ValueError as e:                  # "keep ...", "min_faces ..." or "simplify_cell ...: expected ..."
-        raise SystemExit(f"--mesh_{e}") from None
-    if clean != ('all', 0) and not args.export_mesh:
-        raise SystemExit("--mesh_keep / --mesh_min_faces: there is no mesh to clean without --export_mesh true")
-    if cell != 0 and not args.export_mesh:
-        raise SystemExit("--mesh_simplify_cell: there is no mesh to simplify without --export_mesh true")
-    tex = getattr(args, 'mesh_texture_size', 0)
-    if tex != 0:
-        if not args.export_mesh:
-            raise SystemExit("--mesh_texture_size: there is no mesh to texture without --export_mesh true")
-        try:
-            _atlas_size(tex)
-        except ValueError as e:              # "texture size ...: expected an integer in [4, 8192]"
-            raise SystemExit(f"--mesh_texture_size: {e} (or 0 for no texture)") from None
-    smooth = getattr(args, 'mesh_smooth_iters', 0)
-    try:                                     # the library's own check again
-        _smooth_args(smooth)
-    except ValueError as e:                  # "smooth_iters ...: expected an integer in [0, 1000]"
-        raise SystemExit(f"--mesh_{e}") from None
-    if smooth != 0 and not args.export_mesh:
-        raise SystemExit("--mesh_smooth_iters: there is no mesh to smooth without --export_mesh true")
-    snap = getattr(args, 'mesh_snap_iters', 0)
-    try:                                     # the library's own check again
-        _snap_args(snap)
-    except ValueError as e:                  # "snap_iters ...: expected an integer in [0, 64]"
-        raise SystemExit(f"--mesh_{e}") from None
-    if snap != 0 and not args.export_mesh:
-        raise SystemExit("--mesh_snap_iters: there is no mesh to snap without --export_mesh true")
-    place = getattr(args, 'mesh_simplify_placement', 'mean')
-    try:                                     # the library's own check again
-        _placement(place)
-    except ValueError as e:                  # "placement ...: expected one of ['mean', 'quadric']"
-        raise SystemExit(f"--mesh_simplify_{e}") from None
-    if place != 'mean' and not args.export_mesh:
-        raise SystemExit(f"--mesh_simplify_placement {place}: there is no mesh to simplify without --export_mesh true")
-    if place != 'mean' and cell == 0:
-        raise SystemExit(f"--mesh_simplify_placement {place}: there is nothing to place without --mesh_simplify_cell > 0")
-    fmt = getattr(args, 'mesh_format', 'obj')
-    try:                                     # the library's own check again
-        _mesh_format(fmt)
-    except ValueError as e:                  # "format ...: expected one of ['obj', 'ply', 'glb']"
-        raise SystemExit(f"--mesh_{e}") from None
-    if fmt != 'obj' and not args.export_mesh:
-        raise SystemExit(f"--mesh_format {fmt}: there is no mesh to write without --export_mesh true")
-    if fmt == 'ply' and tex != 0:
+    if post.mesh_format == 'ply' and post.texture_size != 0:      # the library refuses it too; this names the flags
         raise SystemExit("--mesh_format ply carries vertex colours only: a textured mesh (--mesh_texture_size) is written as obj or glb")
+    try:                                     # the library's own checks, so the launcher refuses exactly what the mesh functions would, before sampling
+        post.check()
+    except ValueError as e:                  # "<field> <value>: expected ..."
+        field, _, rest = str(e).partition(' ')
+        raise SystemExit(f"--{_mesh_flag(field)} {rest}") from None
+    for field, purpose in _MESH_PURPOSE.items():
+        if getattr(post, field) != MeshPost._field_defaults[field] and not args.export_mesh:
+            raise SystemExit(f"--{_mesh_flag(field)}: there is no mesh to {purpose} without --export_mesh true")
+    if post.simplify_placement != 'mean' and not post.simplify_cell:
+        raise SystemExit(f"--mesh_simplify_placement {post.simplify_placement}: there is nothing to place without --mesh_simplify_cell > 0")
     if getattr(args, 'save_normal_maps', False):
         world = int(os.environ.get('WORLD_SIZE', '1'))
         if world > 1 and args.num_samples % world != 0:
@@ -521,7 +490,7 @@ def run(args, objaverse=None):
     cond_all, cond_src = res[0], res[1]
     if rank == 0:
         meta = dict(vars(args), conditioning=cond_src, weights={k: (v or 'synthetic') for k, v in weights_from.items()})
-        for k, default in dict(_MESH_FLAGS, save_normal_maps=False, mesh_texture_size=0, mesh_smooth_iters=0, mesh_snap_iters=0, mesh_simplify_placement='mean', mesh_format='obj').items():      # recorded when set: a run without them writes the args.json it always wrote
+        for k, default in dict(_MESH_FLAGS, save_normal_maps=False).items():      # recorded when set: a run without them writes the args.json it always wrote
             if meta[k] == default:
                 del meta[k]
         with open(os.path.join(args.logdir, 'args.json'), 'w') as f:
@@ -588,22 +557,17 @@ def run(args, objaverse=None):
         d = {'latent_normalized_2Ddiffusion': mine}
         d.update(ae(latent=d, behaviour='decode_after_vae_no_render'))
         grid = ae(latent=d, grid_size=args.mesh_grid, behaviour='triplane_decode_grid')
-        smooth = dict(smooth_iters=args.mesh_smooth_iters) if getattr(args, 'mesh_smooth_iters', 0) else {}
-        snap = dict(snap_iters=args.mesh_snap_iters) if getattr(args, 'mesh_snap_iters', 0) else {}
-        place = dict(simplify_placement=args.mesh_simplify_placement) if getattr(args, 'mesh_simplify_placement', 'mean') != 'mean' else {}
-        fmt = getattr(args, 'mesh_format', 'obj')
-        fmt_kw = dict(mesh_format=fmt) if fmt != 'obj' else {}
+        post = _mesh_post(args)
         for i in range(hi - lo):
-            path = os.path.join(args.logdir, f'mesh_sample{lo + i}.{fmt}')
-            if getattr(args, 'mesh_texture_size', 0):
-                try:
-                    textured_mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path,
-                                            texture_size=args.mesh_texture_size, **smooth, **snap, **place, **fmt_kw, **_mesh_post(args)._asdict())
-                except ValueError as e:      # the texture cannot hold this sample's faces: known only once the surface is extracted
-                    mesh_err = f"mesh export of sample {lo + i}: --mesh_texture_size {args.mesh_texture_size}: {e}"
-                    break
-            else:
-                mesh_from_grid(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, sample_index=i, path=path, **smooth, **snap, **place, **fmt_kw, **_mesh_post(args)._asdict())
+            path = os.path.join(args.logdir, f'mesh_sample{lo + i}.{post.mesh_format}')
+            try:
+                mesh_from_record(ae.decoder, d, grid['sigma'][i], args.mesh_grid, args.mesh_thres, i, path, post)
+            except ValueError as e:
+                if post.texture_size == 0:
+                    raise
+                # the texture cannot hold this sample's faces: known only once the surface is extracted
+                mesh_err = f"mesh export of sample {lo + i}: --mesh_texture_size {post.texture_size}: {e}"
+                break
             if not os.path.exists(path):
                 mesh_err = f"mesh export of sample {lo + i} produced no file at {path}"
                 break

@@ -6,15 +6,15 @@ tetrahedra (method='tetra'); both run on the GPU in two passes around a prefix s
 Opt-in clean-up (no reference counterpart; include/ln3d_meshclean.h): connected components of the welded mesh on the device, then only the
 components with at least `min_faces` faces, or only the largest one, are kept - before the colour query, so discarded vertices cost nothing.
 Opt-in simplification (no reference counterpart; include/ln3d_meshsimplify.h): vertex clustering on a lattice of `simplify_cell` grid units,
-behind the clean-up and before the colour query.  Its representatives are the means of their cells or, opt-in again (include/addons/
-ln3d_meshquadric.h), the quadric-error minimisers of the faces that touch the cell, which keep creases and corners.
-Opt-in texture baking (no reference counterpart; include/ext/ln3d_meshbake.h): textured_mesh_from_grid adds a per-face texture atlas, UVs,
+behind the clean-up and before the colour query.  Its representatives are the means of their cells or, opt-in again
+(include/ln3d_meshquadric.h), the quadric-error minimisers of the faces that touch the cell, which keep creases and corners.
+Opt-in texture baking (no reference counterpart; include/ln3d_meshbake.h): textured_mesh_from_grid adds a per-face texture atlas, UVs,
 an .mtl and a .png to what mesh_from_grid makes; mesh_from_grid itself is unchanged.
-Opt-in smoothing (no reference counterpart; include/addons/ln3d_meshsmooth.h): Taubin's lambda | mu passes over the extracted (cleaned,
+Opt-in smoothing (no reference counterpart; include/ln3d_meshsmooth.h): Taubin's lambda | mu passes over the extracted (cleaned,
 simplified) mesh in grid coordinates, before the box mapping, the colour / normal query and the bake.
-Opt-in level-set snapping (no reference counterpart; include/addons/ln3d_meshsnap.h): a damped Newton projection of the box-space vertices
+Opt-in level-set snapping (no reference counterpart; include/ln3d_meshsnap.h): a damped Newton projection of the box-space vertices
 onto sigma = thr, behind the smoothing and before the colour / normal query and the bake.
-Opt-in binary export (no reference counterpart; include/addons/ln3d_meshpack.h): mesh_format='ply' / 'glb' writes a binary little-endian
+Opt-in binary export (no reference counterpart; include/ln3d_meshpack.h): mesh_format='ply' / 'glb' writes a binary little-endian
 PLY or a binary glTF 2.0 instead of the .obj text; the records and buffer sections are packed on the device from the tensors the colour
 query left there, and the host writes whole sections."""
 import json
@@ -34,20 +34,44 @@ KEEP_MODES = ('all', 'largest')
 
 
 class MeshPost(NamedTuple):
-    """The opt-in post-processing of an exported mesh, as mesh_from_grid takes it; the layers above take the fields as mesh_<field> keywords
-    (from_kwargs).  A plain carrier: the values are checked where they are used (_clean_args, _simplify_cell), so not unless a mesh is made."""
+    """The opt-in options of an exported mesh, with their defaults: the keywords of mesh_from_grid and textured_mesh_from_grid, which document
+    them.  The layers above take them as the keywords of `keyword` (from_kwargs) and hand the record down; mesh_from_record makes a mesh from
+    it.  A plain carrier: the values are checked by `check`, which the mesh functions call, so not unless a mesh is made."""
     normals: bool = False
     keep: str = 'all'
     min_faces: int = 0
     simplify_cell: float = 0.0
+    simplify_placement: str = 'mean'
+    smooth_iters: int = 0
+    snap_iters: int = 0
+    texture_size: int = 0
+    mesh_format: str = 'obj'
+
+    @staticmethod
+    def keyword(field):
+        """the pipeline keyword of a field: mesh_<field>, except that a field that already begins with mesh_ is its own keyword"""
+        return field if field.startswith('mesh_') else 'mesh_' + field
 
     @classmethod
     def from_kwargs(cls, kw):
-        """{'mesh_<field>': value, ...} -> MeshPost; any other key is the TypeError of an unexpected keyword argument"""
+        """{keyword(field): value, ...} -> MeshPost; any other key is the TypeError of an unexpected keyword argument"""
+        fields = {cls.keyword(f): f for f in cls._fields}
         for k in kw:
-            if not k.startswith('mesh_') or k[len('mesh_'):] not in cls._fields:
+            if k not in fields:
                 raise TypeError(f"got an unexpected keyword argument {k!r}")
-        return cls(**{k[len('mesh_'):]: v for k, v in kw.items()})
+        return cls(**{fields[k]: v for k, v in kw.items()})
+
+    def check(self):
+        """every value check of the nine options, before anything is extracted; each ValueError begins with the name of its field"""
+        _clean_args(self.keep, self.min_faces)
+        _simplify_cell(self.simplify_cell)
+        _placement(self.simplify_placement)
+        _smooth_args(self.smooth_iters)
+        _snap_args(self.snap_iters)
+        if self.texture_size != 0:
+            _atlas_size(self.texture_size)
+        if _mesh_format(self.mesh_format) == 'ply' and self.texture_size != 0:
+            raise ValueError("mesh_format 'ply' carries vertex colours only: a textured mesh (texture_size) is written as 'obj' or 'glb'")
 
 
 def _clean_args(keep, min_faces):
@@ -61,6 +85,22 @@ def _clean_args(keep, min_faces):
 def _check_verts(verts):
     if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
         raise ValueError(f"verts: expected a float32 [Nv, 3] tensor, got {verts.dtype} {tuple(verts.shape)}")
+
+
+def _check_faces(faces, nv, check):
+    """dtype and shape always; with check also every index in [0, nv) (ops.check_faces: one read-back)"""
+    if check:
+        ops.check_faces(faces, nv)
+    elif faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces: expected an int64 [Nf, 3] tensor, got {faces.dtype} {tuple(faces.shape)}")
+
+
+def _float32(x):
+    """x as the float32 the kernels take, widened to a Python float; NaN when it is not a number"""
+    try:
+        return float(np.float32(x))
+    except (TypeError, ValueError):
+        return math.nan
 
 
 def _empty(dev):
@@ -157,11 +197,8 @@ def _placement(placement, eps=QUADRIC_EPS):
     """-> (placement, eps as the float32 the kernel multiplies by); ValueError when placement is not one of PLACEMENTS or eps (in float32)
     lies outside (0, 1]"""
     if not isinstance(placement, str) or placement not in PLACEMENTS:
-        raise ValueError(f"placement {placement!r}: expected one of {list(PLACEMENTS)}")
-    try:
-        e = float(np.float32(eps))
-    except (TypeError, ValueError):
-        e = math.nan
+        raise ValueError(f"simplify_placement {placement!r}: expected one of {list(PLACEMENTS)}")
+    e = _float32(eps)
     if not 0.0 < e <= 1.0:
         raise ValueError(f"quadric_eps {eps!r}: expected a number in (0, 1] (in float32)")
     return placement, e
@@ -178,10 +215,7 @@ def _simplify_clusters(verts, faces, cell, origin, check):
     dev = verts.device
     nv, nf = verts.shape[0], faces.shape[0]
     verts, faces = verts.contiguous(), faces.contiguous()
-    if check:
-        ops.check_faces(faces, nv)
-    elif faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"faces: expected an int64 [Nf, 3] tensor, got {faces.dtype} {tuple(faces.shape)}")
+    _check_faces(faces, nv, check)
     if nv == 0 or nf == 0:
         return None
     box = torch.cat([verts.amin(0), verts.amax(0), torch.isfinite(verts).all().float().reshape(1)]).cpu().numpy()      # one read-back
@@ -211,7 +245,7 @@ def _simplify_clusters(verts, faces, cell, origin, check):
 
 
 def _quadric_place(verts, faces, cfaces, rep, origin, cell, uniq, eps):
-    """-> (rep_quadric [nc,3], placed [nc] int32) of include/addons/ln3d_meshquadric.h: the pair keys, their sort, the row pointers
+    """-> (rep_quadric [nc,3], placed [nc] int32) of include/ln3d_meshquadric.h: the pair keys, their sort, the row pointers
     (searchsorted, as _adjacency) and the placement; two launches, no read-back"""
     dev = verts.device
     nc = rep.shape[0]
@@ -235,7 +269,7 @@ def simplify_mesh(verts, faces, cell, origin=None, check=True, placement='mean',
       - a face whose corners fall into fewer than three cells is dropped; of the faces that name the same three cells (in any order or
         winding) the one with the smallest index survives, with its own corner order;
       - cells that no surviving face names are dropped; vertices come out in ascending (q_x, q_y, q_z), faces in their input order.
-    placement='quadric' (opt-in; include/addons/ln3d_meshquadric.h) changes the second rule only: a cell's vertex is put where the summed
+    placement='quadric' (opt-in; include/ln3d_meshquadric.h) changes the second rule only: a cell's vertex is put where the summed
     squared distance to the planes of ALL input faces with a corner in the cell (area-squared weights, collapsing and duplicate faces
     included) is least, solved in float32 about the mean with the regularisation quadric_eps * trace, and accepted when it is finite and
     lies in the closed cell; a cell whose solution is refused keeps the mean's bits.  Faces, vertex count and vertex order are exactly those
@@ -296,7 +330,7 @@ def simplify_placement(verts, faces, cell, origin=None, eps=QUADRIC_EPS):
     return rep, quad, placed, uniq
 
 
-# ------------------------------------------------------------------ smoothing (include/addons/ln3d_meshsmooth.h)
+# ------------------------------------------------------------------ smoothing (include/ln3d_meshsmooth.h)
 SMOOTH_MAX_ITERS = 1000
 SMOOTH_LAMBDA, SMOOTH_MU = 0.5, -0.53
 
@@ -312,10 +346,7 @@ def _smooth_args(iterations, lam=SMOOTH_LAMBDA, mu=SMOOTH_MU):
         ok = False
     if not ok:
         raise ValueError(f"smooth_iters {iterations!r}: expected an integer in [0, {SMOOTH_MAX_ITERS}], or None for no smoothing")
-    try:
-        lam32, mu32 = float(np.float32(lam)), float(np.float32(mu))
-    except (TypeError, ValueError):
-        lam32 = mu32 = math.nan
+    lam32, mu32 = _float32(lam), _float32(mu)
     if not 0.0 < lam32 <= 1.0:
         raise ValueError(f"smooth_lambda {lam!r}: expected a number in (0, 1] (in float32)")
     if not -1.0 <= mu32 <= 0.0:
@@ -362,7 +393,7 @@ def mesh_adjacency(faces, num_verts):
 @torch.no_grad()
 def smooth_mesh(verts, faces, iterations, lam=SMOOTH_LAMBDA, mu=SMOOTH_MU, check=True):
     """verts [Nv,3] f32, faces [Nf,3] int64 (device) -> (verts', faces): the mesh after `iterations` iterations of Taubin's lambda | mu
-    smoothing with uniform weights.  The definition (include/addons/ln3d_meshsmooth.h; all arithmetic float32, every output is unique,
+    smoothing with uniform weights.  The definition (include/ln3d_meshsmooth.h; all arithmetic float32, every output is unique,
     nothing depends on scheduling):
       - every face contributes its three undirected edges {a, b}; an edge with a == b is ignored; duplicate faces and opposite windings
         contribute the same edge again;
@@ -387,10 +418,7 @@ def smooth_mesh(verts, faces, iterations, lam=SMOOTH_LAMBDA, mu=SMOOTH_MU, check
     _check_verts(verts)
     nv, nf = verts.shape[0], faces.shape[0]
     cverts, cfaces = verts.contiguous(), faces.contiguous()
-    if check:
-        ops.check_faces(cfaces, nv)
-    elif faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"faces: expected an int64 [Nf, 3] tensor, got {faces.dtype} {tuple(faces.shape)}")
+    _check_faces(cfaces, nv, check)
     if nv == 0 or nf == 0:
         return verts, faces
     if not bool(torch.isfinite(cverts).all()):                          # one read-back
@@ -407,7 +435,7 @@ def smooth_mesh(verts, faces, iterations, lam=SMOOTH_LAMBDA, mu=SMOOTH_MU, check
     return cur, faces
 
 
-# ------------------------------------------------------------------ level-set snapping (include/addons/ln3d_meshsnap.h)
+# ------------------------------------------------------------------ level-set snapping (include/ln3d_meshsnap.h)
 SNAP_MAX_ITERS = ops.SNAP_MAX_ITERS
 
 
@@ -423,17 +451,11 @@ def _snap_args(iterations, tol=None, max_move=None):
     if not ok:
         raise ValueError(f"snap_iters {iterations!r}: expected an integer in [0, {SNAP_MAX_ITERS}], or None for no snapping")
     if tol is not None:
-        try:
-            t = float(np.float32(tol))
-        except (TypeError, ValueError):
-            t = math.nan
+        t = _float32(tol)
         if not (math.isfinite(t) and t >= 0):
             raise ValueError(f"snap_tol {tol!r}: expected a finite number >= 0 (in float32), or None for 1e-3 * max(1, |thr|)")
     if max_move is not None:
-        try:
-            m = float(np.float32(max_move))
-        except (TypeError, ValueError):
-            m = math.nan
+        m = _float32(max_move)
         if not (math.isfinite(m) and m > 0):
             raise ValueError(f"snap_max_move {max_move!r}: expected a finite number > 0 of grid cells (in float32), or None for max(1, simplify_cell)")
         max_move = m
@@ -444,7 +466,7 @@ def _snap_args(iterations, tol=None, max_move=None):
 def snap_mesh(decoder, planes_channel_last, verts_box, level, iterations, tol=None, max_step=None, max_dist=None):
     """verts_box [Nv,3] f32 (device, box / world coordinates), planes_channel_last [1,3,H,W,32] of ONE sample, decoder: the VAE decoder
     module (its snap_points seam) -> (verts' [Nv,3], {'residual' [Nv] f32, 'state' [Nv] int32, 'evals' [Nv] int32}): every vertex put
-    onto sigma = level by at most `iterations` iterations of the damped Newton projection of include/addons/ln3d_meshsnap.h, one fused
+    onto sigma = level by at most `iterations` iterations of the damped Newton projection of include/ln3d_meshsnap.h, one fused
     launch with per-lane early exit.  verts' is the best iterate seen (|residual| never exceeds the input's), never farther than max_dist
     from its start, each step at most max_step long (world units); residual = sigma(verts') - level as the kernel evaluates it; state 0 =
     |residual| <= tol, 1 = out of iterations, 2 = stalled.  Vertex count and order never change, so faces stay valid as they are.
@@ -585,7 +607,7 @@ def write_png(path, tex):
         fh.write(data)
 
 
-# ------------------------------------------------------------------ binary export (include/addons/ln3d_meshpack.h)
+# ------------------------------------------------------------------ binary export (include/ln3d_meshpack.h)
 MESH_FORMATS = ('obj', 'ply', 'glb')
 EXPORTER = 'ln3diff_amd'                      # the PLY comment and the glTF generator
 GLB_MAX_BYTES = 1 << 32                       # a GLB states its length in 32 bits
@@ -594,7 +616,7 @@ GLB_MAX_BYTES = 1 << 32                       # a GLB states its length in 32 bi
 def _mesh_format(fmt):
     """-> fmt; ValueError when it is not one of MESH_FORMATS"""
     if not isinstance(fmt, str) or fmt not in MESH_FORMATS:
-        raise ValueError(f"format {fmt!r}: expected one of {list(MESH_FORMATS)}")
+        raise ValueError(f"mesh_format {fmt!r}: expected one of {list(MESH_FORMATS)}")
     return fmt
 
 
@@ -604,10 +626,7 @@ def _export_args(verts, faces, rgb, normal, check):
     _check_verts(verts)
     nv = verts.shape[0]
     verts, faces = verts.contiguous(), faces.contiguous()
-    if check:
-        ops.check_faces(faces, nv)
-    elif faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"faces: expected an int64 [Nf, 3] tensor, got {faces.dtype} {tuple(faces.shape)}")
+    _check_faces(faces, nv, check)
     for name, t in (('rgb', rgb), ('normal', normal)):
         if t is not None and (t.dim() != 2 or tuple(t.shape) != (nv, 3)):
             raise ValueError(f"{name}: expected a [{nv}, 3] tensor, got {tuple(t.shape)}")
@@ -633,7 +652,7 @@ def _ply_header(nv, nf, normals):
 
 @torch.no_grad()
 def write_ply(path, verts_box, faces, rgb, normal=None, check=True):
-    """A binary little-endian PLY with per-vertex colours, packed on the device (include/addons/ln3d_meshpack.h).  verts_box [Nv,3] f32 in
+    """A binary little-endian PLY with per-vertex colours, packed on the device (include/ln3d_meshpack.h).  verts_box [Nv,3] f32 in
     box coordinates, faces [Nf,3] int64, rgb [Nv,3] the query's colours, normal [Nv,3] the query's normals or None: DEVICE tensors.  What is
     written: the positions rotation_matrix_x(-90) @ verts_box evaluated as (R0 x + R1 y) + R2 z in float32 without fma, the normals by the
     same rule, the colours as trunc(clamp(c, 0, 1) * 255) - the values mesh_from_grid returns - and the indices as int32.  The header is
@@ -725,7 +744,7 @@ def _write_glb_file(path, doc, sections, bin_length):
 
 @torch.no_grad()
 def write_glb(path, verts_box, faces, rgb, normal=None, uv=None, tex=None, check=True):
-    """A binary glTF 2.0 asset (.glb) whose buffer is packed on the device (include/addons/ln3d_meshpack.h).  verts_box [Nv,3] f32 in box
+    """A binary glTF 2.0 asset (.glb) whose buffer is packed on the device (include/ln3d_meshpack.h).  verts_box [Nv,3] f32 in box
     coordinates, faces [Nf,3] int64, rgb [Nv,3] the query's colours, normal [Nv,3] the query's normals or None: DEVICE tensors, with
     write_ply's values.  One scene, one node, one mesh, one primitive in mode 4, one material (metallicFactor 0, roughnessFactor 1,
     doubleSided: the winding of the faces is not promised).  The JSON has a fixed key order and separators, so equal meshes give equal bytes.
@@ -777,13 +796,13 @@ def write_glb(path, verts_box, faces, rgb, normal=None, uv=None, tex=None, check
     _write_glb_file(path, doc, [data for _, data in sections], bin_length)
 
 
-# ------------------------------------------------------------------ texture baking (include/ext/ln3d_meshbake.h)
+# ------------------------------------------------------------------ texture baking (include/ln3d_meshbake.h)
 ATLAS_MIN_SIZE, ATLAS_MAX_SIZE, ATLAS_MIN_CELL = 4, 8192, 4
 
 
 def _atlas_size(size):
     if isinstance(size, bool) or int(size) != size or not ATLAS_MIN_SIZE <= size <= ATLAS_MAX_SIZE:
-        raise ValueError(f"texture size {size!r}: expected an integer in [{ATLAS_MIN_SIZE}, {ATLAS_MAX_SIZE}]")
+        raise ValueError(f"texture_size {size!r}: expected an integer in [{ATLAS_MIN_SIZE}, {ATLAS_MAX_SIZE}]")
     return int(size)
 
 
@@ -860,19 +879,19 @@ def bake_texture(decoder, planes_channel_last, verts_box, faces, size, fill=0):
     return atlas_uvs(nf, size), tex.view(size, size, 3).cpu().numpy()
 
 
-def _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces, simplify_cell,
-                   smooth=(0, SMOOTH_LAMBDA, SMOOTH_MU), snap=(0, None, None), simplify_placement='mean'):
-    """what mesh_from_grid and textured_mesh_from_grid share: (the one sample's planes, the box-space vertices and the faces on the device,
+def _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, post, smooth_tuning=(SMOOTH_LAMBDA, SMOOTH_MU),
+                   snap_tuning=(None, None)):
+    """the geometry and the colours of _mesh, post: a MeshPost -> (the one sample's planes, the box-space vertices and the faces on the device,
     then verts, faces, colors, vn as mesh_from_grid returns them; vn is None without normals; last the query's own dict, whose 'rgb' and
-    'normal' [1,Nv,3] the binary writers take from the device).  smooth: (iterations, lam, mu) of smooth_mesh,
-    applied to the extracted mesh in grid coordinates, so everything behind it sees the smoothed positions.  snap: (iterations, tol, max_move
-    in grid units) of snap_mesh at level = thr, applied to the box-space vertices behind that and before the query.  simplify_placement:
-    extract_isosurface's, handed on only when it is not 'mean'."""
+    'normal' [1,Nv,3] the binary writers take from the device).  smooth_tuning: (lam, mu) of smooth_mesh, which is applied to the extracted
+    mesh in grid coordinates, so everything behind it sees the smoothed positions.  snap_tuning: (tol, max_move in grid units) of snap_mesh
+    at level = thr, applied to the box-space vertices behind that and before the query."""
+    smooth = (post.smooth_iters, *smooth_tuning)
     _smooth_args(*smooth)                                                # a bad value is refused before anything is extracted
-    snap_iters, snap_tol, snap_move = _snap_args(*snap)
-    place = dict(simplify_placement=simplify_placement) if _placement(simplify_placement)[0] != 'mean' else {}
+    snap_iters, snap_tol, snap_move = _snap_args(post.snap_iters, *snap_tuning)
     sigma = sigma.reshape(grid_size, grid_size, grid_size)
-    verts, faces = extract_isosurface(sigma, thr, method, keep, min_faces, simplify_cell, **place)
+    place = dict(simplify_placement=post.simplify_placement) if post.simplify_placement != 'mean' else {}      # 'mean': the extraction is called as it always was
+    verts, faces = extract_isosurface(sigma, thr, method, post.keep, post.min_faces, post.simplify_cell, **place)
     verts, faces = smooth_mesh(verts, faces, *smooth, check=False)       # faces are the extraction's own: in range by construction
     vtx = (verts / (grid_size - 1) * 2 - 1) * 0.45                       # g-objaverse scale
     pcl = dec_out.get('planes_channel_last')
@@ -880,29 +899,44 @@ def _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method
         pcl = decoder.triplane_decoder.to_channel_last(dec_out['latent_after_vit'])        # f32, or f16 under set_plane_precision('fp16')
     pcl = pcl[sample_index:sample_index + 1]
     if snap_iters:                                                       # one grid cell is 0.9 / (grid_size - 1) in the box
-        move = (snap_move if snap_move is not None else max(1.0, _simplify_cell(simplify_cell))) * 0.9 / (grid_size - 1)
+        move = (snap_move if snap_move is not None else max(1.0, _simplify_cell(post.simplify_cell))) * 0.9 / (grid_size - 1)
         vtx = snap_mesh(decoder, pcl, vtx.contiguous(), thr, snap_iters, snap_tol, max_step=move / 2, max_dist=move)[0]
-    q = decoder.forward_points(pcl, vtx[None], with_grad=normals) if vtx.shape[0] else {'rgb': vtx[None], 'normal': vtx[None]}
+    q = decoder.forward_points(pcl, vtx[None], with_grad=post.normals) if vtx.shape[0] else {'rgb': vtx[None], 'normal': vtx[None]}
     colors = (q['rgb'][0].clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
     v = (rotation_matrix_x(-90) @ vtx.cpu().numpy().T).T.astype(np.float32)
     f = faces.cpu().numpy()
-    vn = (rotation_matrix_x(-90) @ q['normal'][0].cpu().numpy().T).T.astype(np.float32) if normals else None
+    vn = (rotation_matrix_x(-90) @ q['normal'][0].cpu().numpy().T).T.astype(np.float32) if post.normals else None
     return pcl, vtx, faces, v, f, colors, vn, q
 
 
-def _write_binary(mesh_format, path, vtx, faces, q, normals, uv=None, tex=None):
-    """the 'ply' / 'glb' branch of the two mesh functions: _coloured_mesh's device tensors go to the packers as they are"""
-    normal = q['normal'][0] if normals else None
-    if mesh_format == 'ply':
+def _mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, path, method, post, smooth_tuning, snap_tuning):
+    """the body of mesh_from_grid and textured_mesh_from_grid: post.texture_size != 0 bakes the texture and appends (uv, tex); post.mesh_format
+    selects the writer of `path`.  The binary writers get _coloured_mesh's device tensors as they are."""
+    post.check()
+    pcl, vtx, faces, v, f, colors, vn, q = _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, post, smooth_tuning, snap_tuning)
+    out = (v, f, colors, vn) if post.normals else (v, f, colors)
+    uv = tex = None
+    if post.texture_size != 0:
+        uv, tex = bake_texture(decoder, pcl, vtx, faces, post.texture_size)
+        out += (uv, tex)
+    normal = q['normal'][0] if post.normals else None
+    if not path:
+        pass
+    elif post.mesh_format == 'ply':
         write_ply(path, vtx, faces, q['rgb'][0], normal, check=False)   # faces are the extraction's own: in range by construction
-    else:
+    elif post.mesh_format == 'glb':
         write_glb(path, vtx, faces, q['rgb'][0], normal, uv, tex, check=False)
+    elif tex is None:
+        write_obj(path, v, f, colors.astype(np.float32) / 255.0, vn)
+    else:
+        write_obj_textured(path, v, f, colors.astype(np.float32) / 255.0, uv, vn)
+        write_png(os.path.splitext(str(path))[0] + '.png', tex)
+    return out
 
 
 @torch.no_grad()
-def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes', normals=False,
-                   keep='all', min_faces=0, simplify_cell=0.0, smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU,
-                   snap_iters=0, snap_tol=None, snap_max_move=None, simplify_placement='mean', mesh_format='obj'):
+def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes', smooth_lambda=SMOOTH_LAMBDA,
+                   smooth_mu=SMOOTH_MU, snap_tol=None, snap_max_move=None, **post):
     """nsr/train_util_diffusion.py:221-244: iso-surface of the sigma grid at `thr`, vertices mapped to the +-0.45 box, coloured
     by re-querying the tri-plane at the vertices (forward_points), rotated -90 degrees about x.
     Returns (verts [Nv,3] float32 numpy, faces [Nf,3] int64 numpy, colors [Nv,3] uint8 numpy); writes `path` when given.
@@ -929,22 +963,17 @@ def mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0,
     (write_ply: binary little-endian, vertex colours, normals when asked for) or 'glb' (write_glb: binary glTF 2.0).  The two binary files are
     packed on the device from the tensors the query left there and hold the returned values bit for bit; the returned tuple does not depend
     on the format, and the extension of `path` is not interpreted.  A value that is none of the three is a ValueError before anything is
-    extracted."""
-    mesh_format = _mesh_format(mesh_format)
-    _, vtx, faces, v, f, colors, vn, q = _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces,
-                                                        simplify_cell, (smooth_iters, smooth_lambda, smooth_mu),
-                                                        (snap_iters, snap_tol, snap_max_move), simplify_placement)
-    if path and mesh_format == 'obj':
-        write_obj(path, v, f, colors.astype(np.float32) / 255.0, vn)
-    elif path:
-        _write_binary(mesh_format, path, vtx, faces, q, normals)
-    return (v, f, colors, vn) if normals else (v, f, colors)
+    extracted.
+    **post: normals, keep, min_faces, simplify_cell, simplify_placement, smooth_iters, snap_iters and mesh_format, the fields of MeshPost
+    but texture_size (textured_mesh_from_grid's), with MeshPost's defaults; any other keyword is a TypeError."""
+    if 'texture_size' in post:
+        raise TypeError("mesh_from_grid() got an unexpected keyword argument 'texture_size'")
+    return _mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, path, method, MeshPost(**post), (smooth_lambda, smooth_mu), (snap_tol, snap_max_move))
 
 
 @torch.no_grad()
 def textured_mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample_index=0, path=None, method='cubes', texture_size=1024,
-                            normals=False, keep='all', min_faces=0, simplify_cell=0.0, smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA,
-                            smooth_mu=SMOOTH_MU, snap_iters=0, snap_tol=None, snap_max_move=None, simplify_placement='mean', mesh_format='obj'):
+                            smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU, snap_tol=None, snap_max_move=None, **post):
     """mesh_from_grid plus a baked texture (opt-in; no reference counterpart): the same geometry, vertex colours and `vn`, bit for bit, for
     the same options, then bake_texture of the faces at the box-space vertices (before the rotation, where the field lives) into a
     texture_size x texture_size per-face atlas.  Returns mesh_from_grid's tuple with (uv [Nf,3,2] float32, tex [T,T,3] uint8) appended.
@@ -958,34 +987,31 @@ def textured_mesh_from_grid(decoder, dec_out, sigma, grid_size, thr=10.0, sample
     back on it before the bake; the interiors of the triangles stay where the flat faces are.  simplify_placement is mesh_from_grid's.
     mesh_format (opt-in): 'glb' writes `path` alone, a binary glTF that embeds the .png and splits the vertices per face corner (write_glb:
     3 Nf vertices, TEXCOORD_0 = (u, 1 - v), no vertex colours); the returned tuple is the same.  'ply' carries vertex colours only: with
-    a texture it is a ValueError before anything is extracted."""
-    _atlas_size(texture_size)
-    if _mesh_format(mesh_format) == 'ply':
-        raise ValueError("format 'ply' carries vertex colours only: a textured mesh is written as 'obj' or 'glb'")
-    pcl, vtx, faces, v, f, colors, vn, q = _coloured_mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, method, normals, keep, min_faces,
-                                                          simplify_cell, (smooth_iters, smooth_lambda, smooth_mu),
-                                                          (snap_iters, snap_tol, snap_max_move), simplify_placement)
-    uv, tex = bake_texture(decoder, pcl, vtx, faces, texture_size)
-    if path and mesh_format == 'obj':
-        write_obj_textured(path, v, f, colors.astype(np.float32) / 255.0, uv, vn)
-        write_png(os.path.splitext(str(path))[0] + '.png', tex)
-    elif path:
-        _write_binary(mesh_format, path, vtx, faces, q, normals, uv, tex)
-    return ((v, f, colors, vn) if normals else (v, f, colors)) + (uv, tex)
+    a texture it is a ValueError before anything is extracted.
+    **post: mesh_from_grid's."""
+    _atlas_size(texture_size)                                            # 0 is no texture in the record: here it is refused like any other bad size
+    return _mesh(decoder, dec_out, sigma, grid_size, thr, sample_index, path, method, MeshPost(texture_size=texture_size, **post),
+                 (smooth_lambda, smooth_mu), (snap_tol, snap_max_move))
 
 
 @torch.no_grad()
-def export_mesh(decoder, dec_out, path, grid_size=192, thr=10.0, sample_index=0, normals=False, keep='all', min_faces=0, simplify_cell=0.0,
-                smooth_iters=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU, snap_iters=0, snap_tol=None, snap_max_move=None,
-                simplify_placement='mean', mesh_format='obj'):
-    """decoder: the VAE decoder module; dec_out: its vit_decode_postprocess dict.  Writes `path` (.obj), with `vn` records when normals;
-    keep / min_faces / simplify_cell / smooth_iters / smooth_lambda / smooth_mu / snap_iters / snap_tol / snap_max_move /
-    simplify_placement / mesh_format: mesh_from_grid's (the last two handed on only when they are not 'mean' / 'obj')."""
+def mesh_from_record(decoder, dec_out, sigma, grid_size, thr, sample_index, path, post):
+    """The mesh of one sample with the options of post, a MeshPost: textured_mesh_from_grid when post.texture_size is not 0, mesh_from_grid
+    otherwise (looked up when called).  The whole record is handed on; mesh_from_grid gets every field but texture_size."""
+    kw = post._asdict()
+    if post.texture_size != 0:
+        return textured_mesh_from_grid(decoder, dec_out, sigma, grid_size, thr, sample_index=sample_index, path=path, **kw)
+    del kw['texture_size']
+    return mesh_from_grid(decoder, dec_out, sigma, grid_size, thr, sample_index=sample_index, path=path, **kw)
+
+
+@torch.no_grad()
+def export_mesh(decoder, dec_out, path, grid_size=192, thr=10.0, sample_index=0, **kw):
+    """decoder: the VAE decoder module; dec_out: its vit_decode_postprocess dict.  Writes `path` (.obj, or what mesh_format says), with `vn`
+    records when normals; **kw: mesh_from_grid's options and tuning values (normals, keep, min_faces, simplify_cell, simplify_placement,
+    smooth_iters, smooth_lambda, smooth_mu, snap_iters, snap_tol, snap_max_move, mesh_format), handed on as they are.
+    Returns (number of vertices, number of faces)."""
     pcl = dec_out['planes_channel_last'][sample_index:sample_index + 1]
     grid = decoder.triplane_decode_grid({'planes_channel_last': pcl}, grid_size)
-    place = dict(simplify_placement=simplify_placement) if _placement(simplify_placement)[0] != 'mean' else {}
-    fmt = dict(mesh_format=mesh_format) if _mesh_format(mesh_format) != 'obj' else {}
-    v, f = mesh_from_grid(decoder, {'planes_channel_last': pcl}, grid['sigma'][0], grid_size, thr, 0, path, normals=normals, keep=keep,
-                          min_faces=min_faces, simplify_cell=simplify_cell, smooth_iters=smooth_iters, smooth_lambda=smooth_lambda,
-                          smooth_mu=smooth_mu, snap_iters=snap_iters, snap_tol=snap_tol, snap_max_move=snap_max_move, **place, **fmt)[:2]
+    v, f = mesh_from_grid(decoder, {'planes_channel_last': pcl}, grid['sigma'][0], grid_size, thr, 0, path, **kw)[:2]
     return v.shape[0], f.shape[0]

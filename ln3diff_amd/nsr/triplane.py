@@ -218,7 +218,7 @@ class Triplane(_cache.PackedWeights, nn.Module):
         """points [P,3] against ONE tri-plane [3,H,W,32] (f32 or f16; cast_planes, the decoder and box_warp as query_points) ->
         {'points': [P,3] f32, 'residual': [P] f32, 'state': [P] int32, 'evals': [P] int32}: the damped Newton projection of every point
         onto sigma = level in at most `iters` (0 ... 64) iterations of ln3d_snap_points (opt-in; no reference counterpart; the loop and
-        what it does not promise: include/addons/ln3d_meshsnap.h).  'points' is the best iterate seen, never farther than max_dist from
+        what it does not promise: include/ln3d_meshsnap.h).  'points' is the best iterate seen, never farther than max_dist from
         its start, each Newton step at most max_step long (both in world units); 'residual' is sigma there minus level; 'state' 0 =
         |residual| <= tol, 1 = out of iterations, 2 = stalled (no usable gradient); 'evals' the field evaluations spent.  tol None:
         1e-3 * max(1, |level|) - like the defaults of max_step and max_dist a choice, not a measurement.  No point returns empty

@@ -395,7 +395,7 @@ def mesh_gather(verts, faces, keep_v, vprefix, keep_f, fprefix, verts_out, faces
 
 
 def _buffer(t, dtype, shape, what):
-    """the kernels of include/ln3d_meshsimplify.h and include/ext/ln3d_meshbake.h write whole rows of the buffers they are given: a buffer of another dtype, a shorter one
+    """the kernels of include/ln3d_meshsimplify.h and include/ln3d_meshbake.h write whole rows of the buffers they are given: a buffer of another dtype, a shorter one
     or a strided view would be written past its end, so it is refused here (metadata only: no read-back)"""
     if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
         raise ValueError(f"{what}: expected a contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
@@ -463,7 +463,7 @@ def simplify_used(cfaces, keep_f, keep_v, check=True):
 
 def quadric_pairs(cfaces, nc, pair_key, check=True):
     """pair_key [3 nf] int64 <- cfaces[f][j] << 31 | f for every corner j of face f whose cluster differs from the corners before it,
-    INT64_MAX for the others (include/addons/ln3d_meshquadric.h); cfaces [nf,3] int64 with every value in [0, nc).  check=False: the caller
+    INT64_MAX for the others (include/ln3d_meshquadric.h); cfaces [nf,3] int64 with every value in [0, nc).  check=False: the caller
     has made cfaces itself (simplify_faces)."""
     nf = cfaces.shape[0]
     _buffer(cfaces, torch.int64, (nf, 3), "cfaces")
@@ -474,7 +474,7 @@ def quadric_pairs(cfaces, nc, pair_key, check=True):
 
 
 def quadric_place(verts, faces, sorted_pair_key, start, rep_mean, origin, cell, cluster_cell_key, eps, rep_out, placed, check=True):
-    """rep_out [nc,3] f32, placed [nc] int32 <- the quadric-error placement of every cluster (include/addons/ln3d_meshquadric.h): the
+    """rep_out [nc,3] f32, placed [nc] int32 <- the quadric-error placement of every cluster (include/ln3d_meshquadric.h): the
     minimiser of the summed squared distance to the planes of the cluster's faces, regularised with eps * trace, where it lies inside the
     cluster's lattice cell (placed 1), rep_mean's bits elsewhere (placed 0).  verts [nv,3] f32, faces [nf,3] int64, sorted_pair_key [3 nf]
     int64: quadric_pairs' keys in ascending order, start [nc + 1] int64: the row pointers into it, rep_mean [nc,3] f32, origin: three
@@ -507,7 +507,7 @@ def quadric_place(verts, faces, sorted_pair_key, start, rep_mean, origin, cell, 
 
 def bake_points(verts, faces, T, n, c, points, owner, check=True):
     """points [T*T,3] f32, owner [T*T] int32 <- the point on its face and the face of every texel of the per-face atlas (T, n, c:
-    mesh.atlas_layout; include/ext/ln3d_meshbake.h); verts [nv,3] f32, faces [nf,3] int64.  check=False: the caller has already put these
+    mesh.atlas_layout; include/ln3d_meshbake.h); verts [nv,3] f32, faces [nf,3] int64.  check=False: the caller has already put these
     faces through check_faces."""
     nv, nf = verts.shape[0], faces.shape[0]
     _buffer(verts, torch.float32, (nv, 3), "verts")
@@ -530,7 +530,7 @@ def bake_pack(rgb, owner, fill, tex):
 
 def smooth_edge_keys(faces, nv, key, check=True):
     """key [3 nf] int64 <- the undirected edge (lo << 32) | hi between corners j and (j + 1) % 3 of every face, -1 where they are equal
-    (include/addons/ln3d_meshsmooth.h); faces [nf,3] int64 of a mesh with nv vertices.  check=False: the caller has already put these faces
+    (include/ln3d_meshsmooth.h); faces [nf,3] int64 of a mesh with nv vertices.  check=False: the caller has already put these faces
     through check_faces."""
     nf = faces.shape[0]
     _buffer(faces, torch.int64, (nf, 3), "faces")
@@ -570,7 +570,7 @@ def smooth_step(verts_in, start, nbr, pinned, factor, verts_out, check=True):
     L.check(L.lib().ln3d_smooth_step(_p(verts_in), _p(start), _p(nbr), _p(pinned), nv, nh, float(factor), _p(verts_out), _stream()), "smooth_step")
 
 
-# ------------------------------------------------------------------ binary mesh export (include/addons/ln3d_meshpack.h)
+# ------------------------------------------------------------------ binary mesh export (include/ln3d_meshpack.h)
 def _pack_rows(xyz, normal, what="xyz"):
     """xyz [n,3] f32 and, when given, normal of the same shape -> n"""
     n = xyz.shape[0]
@@ -663,7 +663,7 @@ SNAP_MAX_ITERS = 64
 def snap_points(planes_cl, H, W, points_in, dec, box_warp, level, iters, tol, max_step, max_dist, points_out, residual, state, evals):
     """points_out [P,3] f32, residual [P] f32, state [P] int32, evals [P] int32 <- the damped Newton projection of points_in [P,3] f32 onto
     sigma = level of ONE tri-plane [3, H, W, 32] (torch.float32 or torch.float16 texels), at most `iters` iterations
-    (include/addons/ln3d_meshsnap.h).  points_out may not overlap points_in.  ValueError on a buffer of another dtype, shape or stride, iters
+    (include/ln3d_meshsnap.h).  points_out may not overlap points_in.  ValueError on a buffer of another dtype, shape or stride, iters
     not an integer in [0, 64], a level / tol / max_step / max_dist that is not finite (in float32), tol < 0, max_step <= 0, max_dist < 0."""
     P = points_in.shape[0]
     _buffer(points_in, torch.float32, (P, 3), "points_in")

@@ -15,50 +15,38 @@ clamp range, ray-limit fix-up) per camera exactly as the loop has them.
 """
 import torch
 
-from .mesh import MeshPost
+from .mesh import MeshPost, mesh_from_record
 from .sgm.sampling import DiscreteDenoiser, EulerEDMSampler, VanillaCFG
 
 TRIPLANE_SCALING_DIVIDER = 0.96806      # the released Objaverse runs (shell_scripts/final_release/inference/*.sh); a CLI flag there
 
 
-def _placement_kw(mesh_simplify_placement):
-    """the keyword that carries the opt-in placement one layer down: none for 'mean', so every layer then calls the next exactly as it did"""
-    return {} if mesh_simplify_placement == 'mean' else dict(mesh_simplify_placement=mesh_simplify_placement)
-
-
-def _format_kw(mesh_format):
-    """the same for the opt-in file format: none for 'obj'"""
-    return {} if mesh_format == 'obj' else dict(mesh_format=mesh_format)
-
-
 @torch.no_grad()
 def render_video_given_triplane(planes, rec_model, cams, triplane_scaling_divider=TRIPLANE_SCALING_DIVIDER, latent_name='latent_normalized_2Ddiffusion',
                                 export_mesh=False, mesh_size=192, mesh_thres=10, mesh_path=None, resolution=None, jitter=None, u_fine=None,
-                                plane_precision=None, return_normals=False, mesh_texture_size=0, mesh_smooth_iters=0, mesh_snap_iters=0, mesh_simplify_placement='mean', mesh_format='obj', **mesh_post):
+                                plane_precision=None, return_normals=False, **mesh_post):
     """planes: sampled latent [B, 12, 32, 32] (scaled IN PLACE like the reference, :188); rec_model: `AE`; cams [V, 25] rendered
     for every sample.  plane_precision: 'fp32' | 'fp16' = the renderer's Triplane.set_plane_precision FOR THIS CALL (the renderer's own
     setting is restored on the way out; None: render with the setting it has); under 'fp16' the decoded planes are converted once and
     the mesh and every view read the f16 texels.  Returns {'latent_after_vit' (if produced), 'image_raw' [B,V,3,R,R], 'image_depth', 'weights_samples',
     'image_mask', 'mesh': [(verts, faces, colors)] when export_mesh}.  return_normals (opt-in) adds 'image_normal' [B,V,3,R,R], the
-    world-space surface normal maps of Triplane.forward(return_normals=True).  **mesh_post: mesh_normals, mesh_keep, mesh_min_faces and
-    mesh_simplify_cell (all opt-in), the fields of mesh.MeshPost, which mesh_from_grid documents: vertex normals (every mesh is then a 4-tuple),
-    floater clean-up and simplification of every mesh before it is coloured.  Any other keyword is a TypeError.
-    mesh_texture_size (opt-in; ignored without export_mesh): > 0 makes every mesh with mesh.textured_mesh_from_grid instead, which appends
-    (uv, tex) to the tuple - a texture_size x texture_size per-face atlas - and writes an .mtl and a .png beside every mesh_path; 0 calls
-    mesh_from_grid exactly as before.
-    mesh_smooth_iters (opt-in; ignored without export_mesh): > 0 hands smooth_iters to whichever of the two makes the mesh - that many
-    iterations of mesh.smooth_mesh at its default lambda and mu, before the mesh is coloured; 0 hands nothing on.  Like mesh_texture_size it is
-    not a MeshPost field.
-    mesh_snap_iters (opt-in; ignored without export_mesh): > 0 hands snap_iters to whichever of the two makes the mesh - at most that many
-    iterations of mesh.snap_mesh at its default tolerance and reach, which put the vertices back on the level set before the mesh is
-    coloured; 0 hands nothing on.  Not a MeshPost field either.
-    mesh_simplify_placement (opt-in; ignored without export_mesh): 'quadric' hands simplify_placement='quadric' to whichever of the two makes
-    the mesh - the quadric-error placement of mesh.simplify_mesh, which keeps the creases that the cell means chamfer; 'mean' hands nothing
-    on.  Not a MeshPost field either; a value that is neither is the ValueError of the mesh function.
-    mesh_format (opt-in; ignored without export_mesh): 'ply' or 'glb' hands mesh_format to whichever of the two makes the mesh, which then
-    writes every mesh_path as a binary PLY or a binary glTF packed on the device instead of the .obj text (mesh.write_ply, mesh.write_glb;
-    'ply' with mesh_texture_size is the mesh function's ValueError); 'obj' hands nothing on.  Not a MeshPost field either; the meshes
-    returned do not depend on it, and the extension in mesh_path is the caller's."""
+    world-space surface normal maps of Triplane.forward(return_normals=True).
+    **mesh_post: the nine fields of mesh.MeshPost by their keywords (MeshPost.keyword), all opt-in, all ignored without export_mesh - a bad
+    value is the ValueError of the mesh function, so only when a mesh is made; any other keyword is a TypeError either way.  The record goes
+    to mesh.mesh_from_record for every sample; mesh_from_grid and textured_mesh_from_grid document what each option does:
+      mesh_normals            every mesh is the 4-tuple with vn, the field's unit outward normals at the vertices, and the file carries them
+      mesh_keep               'largest': only the connected component with the most faces is coloured and written
+      mesh_min_faces          components with fewer faces are dropped (floaters)
+      mesh_simplify_cell      > 0: vertex clustering on cells of that many grid units, before the mesh is coloured
+      mesh_simplify_placement 'quadric': the simplified vertices are the quadric-error minimisers, which keep creases; 'mean': the cell means
+      mesh_smooth_iters       > 0: that many iterations of mesh.smooth_mesh at its default lambda and mu, before the mesh is coloured
+      mesh_snap_iters         > 0: at most that many iterations of mesh.snap_mesh at its default tolerance and reach, which put the vertices
+                              back on the level set before the mesh is coloured
+      mesh_texture_size       > 0: every mesh is made by mesh.textured_mesh_from_grid, which appends (uv, tex) to the tuple - a per-face
+                              atlas of that many texels a side - and writes an .mtl and a .png beside every mesh_path
+      mesh_format             'ply' / 'glb': every mesh_path is written as a binary PLY or a binary glTF packed on the device instead of the
+                              .obj text ('ply' with mesh_texture_size is a ValueError); the meshes returned do not depend on it, and the
+                              extension in mesh_path is the caller's"""
     post = MeshPost.from_kwargs(mesh_post)
     planes *= triplane_scaling_divider
     ddpm_latent = {latent_name: planes}
@@ -69,27 +57,21 @@ def render_video_given_triplane(planes, rec_model, cams, triplane_scaling_divide
         tp.set_plane_precision(plane_precision)
     try:
         return _render_video_decoded(ddpm_latent, planes, rec_model, cams, export_mesh, mesh_size, mesh_thres, mesh_path, resolution, jitter, u_fine,
-                                     return_normals, post, mesh_texture_size, mesh_smooth_iters, mesh_snap_iters, mesh_simplify_placement, mesh_format)
+                                     return_normals, post)
     finally:
         tp.set_plane_precision(before)
 
 
 def _render_video_decoded(ddpm_latent, planes, rec_model, cams, export_mesh, mesh_size, mesh_thres, mesh_path, resolution, jitter, u_fine,
-                          return_normals, post, mesh_texture_size=0, mesh_smooth_iters=0, mesh_snap_iters=0, mesh_simplify_placement='mean', mesh_format='obj'):
+                          return_normals, post):
     tp = rec_model.decoder.triplane_decoder
     if ddpm_latent.get('planes_channel_last') is not None:
         ddpm_latent['planes_channel_last'] = tp.cast_planes(ddpm_latent['planes_channel_last'])
     out = {}
     if export_mesh:
-        from .mesh import mesh_from_grid, textured_mesh_from_grid
-        make, texture = (textured_mesh_from_grid, dict(texture_size=mesh_texture_size)) if mesh_texture_size else (mesh_from_grid, {})
-        smooth = dict(smooth_iters=mesh_smooth_iters) if mesh_smooth_iters else {}
-        snap = dict(snap_iters=mesh_snap_iters) if mesh_snap_iters else {}
-        place = dict(simplify_placement=mesh_simplify_placement) if mesh_simplify_placement != 'mean' else {}
-        fmt = _format_kw(mesh_format)                                    # the mesh functions' keyword has the same name
         grid_out = rec_model(latent=ddpm_latent, grid_size=mesh_size, behaviour='triplane_decode_grid')
-        out['mesh'] = [make(rec_model.decoder, ddpm_latent, grid_out['sigma'][i], mesh_size, mesh_thres, sample_index=i,
-                            path=(mesh_path.format(i) if mesh_path else None), **texture, **smooth, **snap, **place, **fmt, **post._asdict()) for i in range(planes.shape[0])]
+        out['mesh'] = [mesh_from_record(rec_model.decoder, ddpm_latent, grid_out['sigma'][i], mesh_size, mesh_thres, i,
+                                        mesh_path.format(i) if mesh_path else None, post) for i in range(planes.shape[0])]
     B, V = planes.shape[0], cams.shape[0]
     kw = {}
     if resolution is not None:
@@ -203,16 +185,16 @@ class T23DPipeline:
 
     # DiffusionEngineLSGM.eval_cldm (:410-480): one condition x num_samples, then the video of every sample
     @torch.no_grad()
-    def eval_cldm(self, cond, cams, num_samples=1, resolution=None, export_mesh=False, seed=41, mesh_smooth_iters=0, mesh_snap_iters=0, mesh_simplify_placement='mean', mesh_format='obj', **render_kw):
+    def eval_cldm(self, cond, cams, num_samples=1, resolution=None, export_mesh=False, seed=41, **render_kw):
         assert cond['crossattn'].shape[0] == 1
         c = {k: v.repeat_interleave(num_samples, 0) for k, v in cond.items()}
         latent = self.sample(c, None, batch_size=num_samples, seed=seed)
         return latent, self.render_video_given_triplane(latent.clone(), cams[:40], resolution=resolution, export_mesh=export_mesh,
-                                                        mesh_smooth_iters=mesh_smooth_iters, mesh_snap_iters=mesh_snap_iters, **_placement_kw(mesh_simplify_placement), **_format_kw(mesh_format), **render_kw)
+                                                        **render_kw)
 
     @torch.no_grad()
-    def render_video_given_triplane(self, planes, cams, mesh_smooth_iters=0, mesh_snap_iters=0, mesh_simplify_placement='mean', mesh_format='obj', **kw):
-        return render_video_given_triplane(planes, self.rec_model, cams, self.triplane_scaling_divider, mesh_smooth_iters=mesh_smooth_iters, mesh_snap_iters=mesh_snap_iters, **_placement_kw(mesh_simplify_placement), **_format_kw(mesh_format), **kw)
+    def render_video_given_triplane(self, planes, cams, **kw):
+        return render_video_given_triplane(planes, self.rec_model, cams, self.triplane_scaling_divider, **kw)
 
     @torch.no_grad()
     def decode(self, latent, want_nchw=False):
@@ -281,27 +263,25 @@ class FlowMatchingEngine:
     # FlowMatchingEngine.eval_cldm (:554-682): one condition x num_samples; camera[:24]
     @torch.no_grad()
     def eval_cldm(self, cond, camera, num_samples=1, unconditional_guidance_scale=4.0, num_steps=250, seed=42, export_mesh=False,
-                  resolution=None, mesh_smooth_iters=0, mesh_snap_iters=0, mesh_simplify_placement='mean', mesh_format='obj', **render_kw):
+                  resolution=None, **render_kw):
         assert cond['crossattn'].shape[0] == 1
         c = {k: v.repeat_interleave(num_samples, 0) for k, v in cond.items()}
         samples = self.sample(c, None, batch_size=num_samples, cfg_scale=unconditional_guidance_scale, num_steps=num_steps, seed=seed)
         return samples, render_video_given_triplane(samples.clone(), self.rec_model, camera[:24], self.triplane_scaling_divider,
-                                                    export_mesh=export_mesh, resolution=resolution, mesh_smooth_iters=mesh_smooth_iters, mesh_snap_iters=mesh_snap_iters, **_placement_kw(mesh_simplify_placement), **_format_kw(mesh_format), **render_kw)
+                                                    export_mesh=export_mesh, resolution=resolution, **render_kw)
 
     @torch.no_grad()
-    def render_video_given_triplane(self, planes, cams, mesh_smooth_iters=0, mesh_snap_iters=0, mesh_simplify_placement='mean', mesh_format='obj', **kw):
-        return render_video_given_triplane(planes, self.rec_model, cams, self.triplane_scaling_divider, mesh_smooth_iters=mesh_smooth_iters, mesh_snap_iters=mesh_snap_iters, **_placement_kw(mesh_simplify_placement), **_format_kw(mesh_format), **kw)
+    def render_video_given_triplane(self, planes, cams, **kw):
+        return render_video_given_triplane(planes, self.rec_model, cams, self.triplane_scaling_divider, **kw)
 
     # FlowMatchingEngine.eval_i23d_and_export (:684-760): image -> conditioner -> sample -> mesh + video; **mesh_post: mesh.MeshPost's fields
     @torch.no_grad()
     def eval_i23d_and_export(self, inp_img, camera, num_steps=250, seed=42, mesh_size=192, mesh_thres=10, unconditional_guidance_scale=4.0,
-                             num_samples=1, export_mesh=True, resolution=None, mesh_path=None, plane_precision=None, mesh_texture_size=0,
-                             mesh_smooth_iters=0, mesh_snap_iters=0, mesh_simplify_placement='mean', mesh_format='obj', **mesh_post):
+                             num_samples=1, export_mesh=True, resolution=None, mesh_path=None, plane_precision=None, **mesh_post):
         assert self.conditioner is not None, "construct the engine with conditioner=I23DConditioner(...)"
         cond = self.conditioner(inp_img)
         return self.eval_cldm(cond, camera, num_samples, unconditional_guidance_scale, num_steps, seed, export_mesh, resolution, mesh_size=mesh_size,
-                              mesh_thres=mesh_thres, mesh_path=mesh_path, plane_precision=plane_precision, mesh_texture_size=mesh_texture_size,
-                              mesh_smooth_iters=mesh_smooth_iters, mesh_snap_iters=mesh_snap_iters, **_placement_kw(mesh_simplify_placement), **_format_kw(mesh_format), **mesh_post)
+                              mesh_thres=mesh_thres, mesh_path=mesh_path, plane_precision=plane_precision, **mesh_post)
 
 
 I23DPipeline = FlowMatchingEngine
@@ -353,35 +333,31 @@ class GuidedDiffusionEngine:
 
     @torch.no_grad()
     def eval_cldm(self, cond, camera, use_ddim=False, unconditional_guidance_scale=1.0, export_mesh=False, resolution=None,
-                  overwrite_diff_inp_size=None, mesh_smooth_iters=0, mesh_snap_iters=0, mesh_simplify_placement='mean', mesh_format='obj', **render_kw):
+                  overwrite_diff_inp_size=None, **render_kw):
         latent = self.sample(cond, use_ddim=use_ddim, unconditional_guidance_scale=unconditional_guidance_scale,
                              overwrite_diff_inp_size=overwrite_diff_inp_size)
         return latent, render_video_given_triplane(latent.clone(), self.rec_model, camera, self.triplane_scaling_divider,
-                                                   export_mesh=export_mesh, resolution=resolution, mesh_smooth_iters=mesh_smooth_iters, mesh_snap_iters=mesh_snap_iters, **_placement_kw(mesh_simplify_placement), **_format_kw(mesh_format), **render_kw)
+                                                   export_mesh=export_mesh, resolution=resolution, **render_kw)
 
     @torch.no_grad()
-    def render_video_given_triplane(self, planes, cams, mesh_smooth_iters=0, mesh_snap_iters=0, mesh_simplify_placement='mean', mesh_format='obj', **kw):
-        return render_video_given_triplane(planes, self.rec_model, cams, self.triplane_scaling_divider, mesh_smooth_iters=mesh_smooth_iters, mesh_snap_iters=mesh_snap_iters, **_placement_kw(mesh_simplify_placement), **_format_kw(mesh_format), **kw)
+    def render_video_given_triplane(self, planes, cams, **kw):
+        return render_video_given_triplane(planes, self.rec_model, cams, self.triplane_scaling_divider, **kw)
 
     @torch.no_grad()
-    def eval_ddpm_sample(self, camera, mesh_smooth_iters=0, mesh_snap_iters=0, mesh_simplify_placement='mean', mesh_format='obj', **kw):
-        return self.eval_cldm(None, camera, mesh_smooth_iters=mesh_smooth_iters, mesh_snap_iters=mesh_snap_iters, **_placement_kw(mesh_simplify_placement), **_format_kw(mesh_format), **kw)
+    def eval_ddpm_sample(self, camera, **kw):
+        return self.eval_cldm(None, camera, **kw)
 
 
 @torch.no_grad()
 def reconstruct(rec_model, img, cams, latent_dir=None, ins_names=None, sample_posterior=True, eps=None, export_mesh=False, mesh_size=192,
-                mesh_thres=10, mesh_path=None, resolution=None, jitter=None, u_fine=None, plane_precision=None, return_normals=False,
-                mesh_texture_size=0, mesh_smooth_iters=0, mesh_snap_iters=0, mesh_simplify_placement='mean', mesh_format='obj', **mesh_post):
+                mesh_thres=10, mesh_path=None, resolution=None, jitter=None, u_fine=None, plane_precision=None, return_normals=False, **mesh_post):
     """Posed views -> tri-plane latent -> renders (and meshes): TrainLoop.eval_novelview_loop(save_latent=True) of the VAE
     reconstruction launcher (vae_xl_reconstruction.sh; nsr/train_nv_util.py:1176-1213).  rec_model: `AE` with the released encoder;
     img [B*F, 10, 256, 256] (F = rec_model.encoder.num_frames views per object); cams [V, 25] rendered for every object.
     The latent is 'encoder_vae' (posterior sampled as the reference does, or the mode with sample_posterior=False; eps [B, 4, 3, H*W]
     overrides the CPU-generator draw).  latent_dir: writes <latent_dir>/<ins>/latent.npy = latent_normalized_2Ddiffusion[b] [12, 32, 32].
     The encoded latent is already in VAE space, so it is rendered with triplane_scaling_divider = 1.  Returns the
-    render_video_given_triplane dict plus 'latent' (the encoder_vae dict).  **mesh_post, mesh_texture_size and mesh_smooth_iters:
-    render_video_given_triplane's (mesh.MeshPost; the opt-in baked texture; the opt-in smoothing), and so are mesh_snap_iters (the opt-in
-    level-set snapping), mesh_simplify_placement (the opt-in quadric-error placement of the simplification) and mesh_format (the opt-in
-    binary PLY / GLB files)."""
+    render_video_given_triplane dict plus 'latent' (the encoder_vae dict).  **mesh_post: render_video_given_triplane's (the fields of mesh.MeshPost)."""
     import os
     import numpy as np
     from .nsr.script_util import AE
@@ -404,7 +380,6 @@ def reconstruct(rec_model, img, cams, latent_dir=None, ins_names=None, sample_po
             np.save(os.path.join(latent_dir, name, 'latent.npy'), zc[b])
     out = render_video_given_triplane(z.clone(), rec_model, cams, triplane_scaling_divider=1.0, export_mesh=export_mesh, mesh_size=mesh_size,
                                       mesh_thres=mesh_thres, mesh_path=mesh_path, resolution=resolution, jitter=jitter, u_fine=u_fine,
-                                      plane_precision=plane_precision, return_normals=return_normals, mesh_texture_size=mesh_texture_size,
-                                      mesh_smooth_iters=mesh_smooth_iters, mesh_snap_iters=mesh_snap_iters, **_placement_kw(mesh_simplify_placement), **_format_kw(mesh_format), **mesh_post)
+                                      plane_precision=plane_precision, return_normals=return_normals, **mesh_post)
     out['latent'] = lat
     return out

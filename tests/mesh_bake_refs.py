@@ -1,4 +1,4 @@
-"""numpy reference of the texture bake (include/ext/ln3d_meshbake.h): the per-face atlas layout, the UV corners, the owner of every texel,
+"""numpy reference of the texture bake (include/ln3d_meshbake.h): the per-face atlas layout, the UV corners, the owner of every texel,
 the point every owned texel maps to (float32, one rounding per operation, which is what the kernel promises) and the uint8 pack; and the
 bilinear look-up a renderer does, with its taps laid open.  Written from the header's definition, texel by texel, not from mesh.py."""
 import numpy as np

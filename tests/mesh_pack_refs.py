@@ -1,4 +1,4 @@
-"""Plain-numpy restatement of the binary mesh export of include/addons/ln3d_meshpack.h (csrc/meshpack.hip: ln3d_pack_ply_vertices,
+"""Plain-numpy restatement of the binary mesh export of include/ln3d_meshpack.h (csrc/meshpack.hip: ln3d_pack_ply_vertices,
 ln3d_pack_ply_faces, ln3d_pack_gltf_vertices, ln3d_pack_gltf_indices, ln3d_pack_gltf_corners, ln3d_position_bounds) and two minimal readers
 of the files that mesh.write_ply and mesh.write_glb write, which share no code with the writers (struct, json and numpy only).
 

@@ -1,4 +1,4 @@
-"""The quadric-error placement of include/addons/ln3d_meshquadric.h (csrc/mesh.hip: ln3d_quadric_pairs, ln3d_quadric_place) without a GPU:
+"""The quadric-error placement of include/ln3d_meshquadric.h (csrc/mesh.hip: ln3d_quadric_pairs, ln3d_quadric_place) without a GPU:
 the float64 reference of the definition (place64), an fp32 numpy restatement that sums in the kernel's stated order (place32, with the
 seeded faults of tests/test_mesh_quadric_cpu.py), the inputs that the CPU and the GPU test share, and the checks both apply (check_placement).
 The clusters, cfaces and means are those of tests/mesh_simplify_refs.py.

@@ -1,4 +1,4 @@
-"""Plain-numpy restatement of the mesh smoothing of include/addons/ln3d_meshsmooth.h (csrc/mesh.hip: ln3d_smooth_edge_keys,
+"""Plain-numpy restatement of the mesh smoothing of include/ln3d_meshsmooth.h (csrc/mesh.hip: ln3d_smooth_edge_keys,
 ln3d_smooth_halfedges, ln3d_smooth_step), no GPU, written from the definition - a counter of undirected edges, sets of neighbours, a
 sequential float32 loop per vertex - and the hand-made meshes that tests/test_mesh_smooth_cpu.py and tests/test_mesh_smooth_gpu.py share.
 Every comparison against it is an equality: bit patterns for the coordinates, integers elsewhere.

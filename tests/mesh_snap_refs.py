@@ -1,4 +1,4 @@
-"""Float64 restatement of the level-set snapping of include/addons/ln3d_meshsnap.h (csrc/render.hip: ln3d_snap_points) on top of
+"""Float64 restatement of the level-set snapping of include/ln3d_meshsnap.h (csrc/render.hip: ln3d_snap_points) on top of
 normal_refs.sigma_and_grad, first-order bounds for what an fp32 evaluation of the same loop may return, an fp32 torch stand-in of the loop
 with seeded faults, and the checks that tests/test_mesh_snap_gpu.py applies to the kernel and tests/test_mesh_snap_cpu.py to the stand-in.
 

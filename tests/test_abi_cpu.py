@@ -8,6 +8,7 @@ import ctypes as C
 import os
 import re
 
+from abi_args import BAD_ARG, UNSUPPORTED, refuses_null_buffers_and_bad_counts, with_args as _with
 from conftest import ROOT
 
 N = None
@@ -167,7 +168,6 @@ def _render_args(**kw):
     return a
 
 
-BAD_ARG, UNSUPPORTED = -1, -3
 RENDER_ROWS = [
     (dict(H=0), BAD_ARG), (dict(H=-1), BAD_ARG), (dict(W=0), BAD_ARG), (dict(W=-8), BAD_ARG),
     (dict(H=1 << 15, W=1 << 15), BAD_ARG),                                        # 32-bit tap offsets
@@ -257,7 +257,6 @@ def test_zero_sizes_are_bad_arguments(hip_lib):
 # ---- the mesh simplification (include/ln3d_meshsimplify.h): name -> (a valid argument list on fake addresses, indices of its buffers,
 # indices of its counts)
 A = 0x10000                                  # a fake device address
-BIG = 1 << 31                                # one more than the largest count
 NAN, INF = float('nan'), float('inf')
 VALID = {
     'ln3d_simplify_keys': ([A, 5, 0.0, -1.0, 2.0, 0.5, A, None], (0, 6), (1,)),
@@ -270,22 +269,10 @@ NC_AT = {'ln3d_simplify_mean': 4, 'ln3d_simplify_faces': 4, 'ln3d_simplify_used'
 NV_AT = {'ln3d_simplify_mean': 3, 'ln3d_simplify_faces': 3}                                   # nc <= nv is checked: raise nv with it
 
 
-def _with(args, **at):
-    a = list(args)
-    for i, v in at.items():
-        a[int(i[1:])] = v
-    return a
-
-
 def test_every_entry_point_validates_before_it_launches(hip_lib):
     assert set(VALID) == {'ln3d_simplify_faces', 'ln3d_simplify_first', 'ln3d_simplify_keys', 'ln3d_simplify_mean', 'ln3d_simplify_used'}
     for name, (args, buffers, counts) in VALID.items():
-        fn = getattr(hip_lib, name)
-        for i in buffers:
-            assert fn(*_with(args, **{'i%d' % i: None})) == BAD_ARG, (name, 'null buffer', i)
-        for i in counts:
-            for bad in (0, -1, BIG, 1 << 40):
-                assert fn(*_with(args, **{'i%d' % i: bad})) == BAD_ARG, (name, 'count', i, bad)
+        refuses_null_buffers_and_bad_counts(getattr(hip_lib, name), name, args, buffers, counts)
     keys, kargs = hip_lib.ln3d_simplify_keys, VALID['ln3d_simplify_keys'][0]
     for cell in (0.0, -0.0, -1.0, NAN, INF, -INF):
         assert keys(*_with(kargs, i5=cell)) == BAD_ARG, cell

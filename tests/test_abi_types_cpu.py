@@ -1,6 +1,7 @@
 """The ctypes binding against the headers, without a GPU.  ln3diff_amd/_lib.py declares every export once (PROTOTYPES: restype and
 argtypes) and mirrors six argument structs by hand; nothing at run time reads include/.  Here the headers are parsed and
-  - every `int | void | const char* ln3d_*(...)` maps, by the one rule of _lib's docstring, to exactly its PROTOTYPES row;
+  - every `int | void | const char* ln3d_*(...)` of every header maps, by the one rule of _lib's docstring, to exactly its PROTOTYPES
+    row, the rows of a header stand in its declaration order, and include/ has no subdirectory that this file would not read;
   - a C probe compiled with the build's compiler prints sizeof / offsetof of the six structs and the values of the header's constants,
     which must be the Structure classes' layouts and _lib's constants;
   - ops._p, the one place a tensor becomes an address, refuses a host tensor before the library is reached;
@@ -42,11 +43,14 @@ def _ctype(decl, lib):
     return SCALARS[ctype]
 
 
-def _declared_prototypes(lib):
+def _declared_prototypes(lib, by_header=None):
+    """{name: (restype, argtypes)} of every header; by_header, a dict, gets {header path: [its names in declaration order]}"""
     out = {}
     for path in HEADERS:
+        names = [] if by_header is None else by_header.setdefault(path, [])
         for ret, name, params in re.findall(r'\b(int|void|const\s+char\s*\*)\s*(ln3d_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', _source(path)):
             assert name not in out, f"{name} declared twice"
+            names.append(name)
             params = params.strip()
             out[name] = (RESTYPES[re.sub(r'\s*\*', '*', ' '.join(ret.split()))],
                          () if params == 'void' else tuple(_ctype(p, lib) for p in params.split(',')))
@@ -75,11 +79,15 @@ def _constants():
 
 def test_prototype_table_equals_the_headers():
     from ln3diff_amd import _lib
-    declared = _declared_prototypes(_lib)
+    by_header = {}
+    declared = _declared_prototypes(_lib, by_header)
     assert set(declared) == set(_lib.PROTOTYPES), set(declared) ^ set(_lib.PROTOTYPES)
+    assert not [e.name for e in os.scandir(os.path.join(ROOT, 'include')) if e.is_dir()]      # one folder: HEADERS is every header
+    for path, names in by_header.items():                                                  # row for row, in the order the header declares them
+        assert [n for n in _lib.PROTOTYPES if n in set(names)] == names, path
     for name, (restype, argtypes) in declared.items():
         assert (_lib.PROTOTYPES[name][0], tuple(_lib.PROTOTYPES[name][1])) == (restype, argtypes), name
-    assert list(_lib.SYMBOLS) == list(_lib.PROTOTYPES) and len(_lib.SYMBOLS) == 80
+    assert list(_lib.SYMBOLS) == list(_lib.PROTOTYPES) and len(_lib.SYMBOLS) == 95
     assert {'ln3d_simplify_faces', 'ln3d_simplify_first', 'ln3d_simplify_keys', 'ln3d_simplify_mean', 'ln3d_simplify_used'} <= set(_lib.PROTOTYPES)
 
 

@@ -1,11 +1,12 @@
-"""The host side of the texture bake (include/ext/ln3d_meshbake.h), without a GPU:
+"""The host side of the texture bake (include/ln3d_meshbake.h), without a GPU:
   - mesh.atlas_layout / atlas_uvs equal the reference of tests/mesh_bake_refs.py, at the edges of the capacity too;
   - the property the layout exists for, for every cell size c = 4 ... 13: a bilinear look-up at the corners, the edge midpoints and random
     points of a face's UV triangle has its non-zero taps in texels that face owns (exact arithmetic: dyadic weights, half-integer corners);
   - an affine field baked unquantised at the reference's points comes back from the bilinear look-up to 1e-6;
   - write_png decodes (by an inverse written here, and by Pillow where it imports) to the flipped array; write_obj_textured parses back;
-  - mesh_texture_size, from every public entry of pipeline down: 0 calls mesh_from_grid with the four MeshPost keywords only, 64 calls
-    textured_mesh_from_grid with texture_size=64 plus the four, and without export_mesh neither is called."""
+  - both entry points return LN3D_ERR_BAD_ARG for each null buffer, each zero, negative or oversize count and each bad (T, n, c, nf)
+    combination, all on fake addresses that are never dereferenced (validation precedes every launch).
+(mesh_texture_size from every public entry of pipeline down, and the launcher flag: tests/test_mesh_options_cpu.py.)"""
 import struct
 import zlib
 
@@ -14,6 +15,7 @@ import pytest
 import torch
 
 import mesh_bake_refs as R
+from abi_args import BAD_ARG, refuses_null_buffers_and_bad_counts, with_args as _with
 
 
 # ---------------------------------------------------------------- layout
@@ -198,141 +200,6 @@ def test_write_obj_textured_parses_back(tmp_path, normals):
     assert parse_textured(tmp_path / 'none.obj')['order'] == ['mtllib', 'usemtl'] and (tmp_path / 'none.mtl').exists()
 
 
-# ---------------------------------------------------------------- the option, from every entry down (the recorder idea of test_mesh_options_cpu)
-B, V, G, RES = 2, 2, 8, 4
-FOUR = dict(normals=False, keep='all', min_faces=0, simplify_cell=0.0)
-
-
-class _Planes:
-    plane_precision = 'fp32'
-    neural_rendering_resolution = RES
-
-    def set_plane_precision(self, p):
-        self.plane_precision = p
-
-    def cast_planes(self, x):
-        return x
-
-
-class _Decoder:
-    triplane_decoder = _Planes()
-
-    def vit_decode_backbone(self, ret_dict, img_size):
-        return ret_dict
-
-    def vit_decode_postprocess(self, latent, ret_dict):
-        return {'planes_channel_last': torch.zeros(B, 3, 4, 4, 2)}
-
-    def triplane_decode(self, latent, c, return_raw_only=False, **kw):
-        r = kw.get('neural_rendering_resolution', RES)
-        z = lambda ch: torch.zeros(c.shape[0], ch, r, r)                              # noqa: E731
-        return {'image_raw': z(3), 'image_depth': z(1), 'weights_samples': z(1), 'image_mask': z(1)}
-
-    def triplane_decode_grid(self, latent, grid_size):
-        return {'sigma': torch.zeros(B, grid_size ** 3, 1)}
-
-    def vae_reparameterization(self, h, sample, eps=None, num_frames=None):
-        return {'latent_normalized_2Ddiffusion': torch.zeros(B, 12, 4, 4)}
-
-
-class _Encoder:
-    num_frames = 1
-
-    def forward_frames(self, img):
-        return img
-
-
-def _entries():
-    from ln3diff_amd import pipeline as P
-    from ln3diff_amd.nsr.script_util import AE
-    ae = AE(None, _Decoder(), RES)
-    ae.encoder = _Encoder()
-    lat = lambda: torch.zeros(B, 12, 4, 4)                                            # noqa: E731
-    cams, cond, common = torch.zeros(V, 25), {'crossattn': torch.zeros(1, 1, 1)}, dict(mesh_size=G, resolution=RES)
-    t23d, flow, gd = P.T23DPipeline(None, ae), P.FlowMatchingEngine(None, ae, conditioner=lambda img: cond), P.GuidedDiffusionEngine(None, ae, None)
-    for eng in (t23d, flow, gd):
-        eng.sample = lambda *a, **k: lat()
-    return {
-        'render_video_given_triplane': lambda e, **kw: P.render_video_given_triplane(lat(), ae, cams, export_mesh=e, **common, **kw),
-        'T23DPipeline.eval_cldm': lambda e, **kw: t23d.eval_cldm(cond, cams, num_samples=B, export_mesh=e, **common, **kw),
-        'T23DPipeline.render_video_given_triplane': lambda e, **kw: t23d.render_video_given_triplane(lat(), cams, export_mesh=e, **common, **kw),
-        'FlowMatchingEngine.eval_cldm': lambda e, **kw: flow.eval_cldm(cond, cams, num_samples=B, export_mesh=e, **common, **kw),
-        'FlowMatchingEngine.eval_i23d_and_export': lambda e, **kw: flow.eval_i23d_and_export(None, cams, num_samples=B, export_mesh=e, **common, **kw),
-        'FlowMatchingEngine.render_video_given_triplane': lambda e, **kw: flow.render_video_given_triplane(lat(), cams, export_mesh=e, **common, **kw),
-        'GuidedDiffusionEngine.eval_cldm': lambda e, **kw: gd.eval_cldm(cond, cams, export_mesh=e, **common, **kw),
-        'GuidedDiffusionEngine.eval_ddpm_sample': lambda e, **kw: gd.eval_ddpm_sample(cams, export_mesh=e, **common, **kw),
-        'GuidedDiffusionEngine.render_video_given_triplane': lambda e, **kw: gd.render_video_given_triplane(lat(), cams, export_mesh=e, **common, **kw),
-        'reconstruct': lambda e, **kw: P.reconstruct(ae, torch.zeros(B, 10, 4, 4), cams, export_mesh=e, **common, **kw),
-    }
-
-
-ENTRIES = ['render_video_given_triplane', 'T23DPipeline.eval_cldm', 'T23DPipeline.render_video_given_triplane', 'FlowMatchingEngine.eval_cldm',
-           'FlowMatchingEngine.eval_i23d_and_export', 'FlowMatchingEngine.render_video_given_triplane', 'GuidedDiffusionEngine.eval_cldm',
-           'GuidedDiffusionEngine.eval_ddpm_sample', 'GuidedDiffusionEngine.render_video_given_triplane', 'reconstruct']
-
-
-@pytest.fixture
-def recorder(monkeypatch):
-    from ln3diff_amd import mesh
-    calls = {'plain': [], 'textured': []}
-    e3, ef = np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int64)
-
-    def plain(decoder, dec_out, sigma, grid_size, thr=10.0, **kw):
-        calls['plain'].append(kw)
-        return e3, ef, e3.astype(np.uint8)
-
-    def textured(decoder, dec_out, sigma, grid_size, thr=10.0, **kw):
-        calls['textured'].append(kw)
-        return e3, ef, e3.astype(np.uint8), np.zeros((0, 3, 2), np.float32), np.zeros((kw['texture_size'],) * 2 + (3,), np.uint8)
-    monkeypatch.setattr(mesh, 'mesh_from_grid', plain)
-    monkeypatch.setattr(mesh, 'textured_mesh_from_grid', textured)
-    return calls
-
-
-def _strip(kw):
-    return {k: v for k, v in kw.items() if k not in ('sample_index', 'path')}
-
-
-@pytest.mark.parametrize('entry', ENTRIES)
-def test_mesh_texture_size_selects_the_function(recorder, entry):
-    assert list(_entries()) == ENTRIES
-    call = _entries()[entry]
-    out = lambda o: o[1] if isinstance(o, tuple) else o                               # noqa: E731
-    for given in ({}, dict(mesh_texture_size=0)):
-        o = out(call(True, **given))
-        assert [_strip(kw) for kw in recorder['plain']] == [FOUR] * B and recorder['textured'] == [] and all(len(m) == 3 for m in o['mesh'])
-        assert [kw['sample_index'] for kw in recorder['plain']] == list(range(B))
-        del recorder['plain'][:]
-    o = out(call(True, mesh_texture_size=64, mesh_keep='largest', mesh_simplify_cell=2.5))
-    assert recorder['plain'] == [] and [kw['sample_index'] for kw in recorder['textured']] == list(range(B))
-    assert [_strip(kw) for kw in recorder['textured']] == [dict(FOUR, keep='largest', simplify_cell=2.5, texture_size=64)] * B
-    assert len(o['mesh']) == B and all(len(m) == 5 and m[4].shape == (64, 64, 3) for m in o['mesh'])
-    del recorder['textured'][:]
-    o = out(call(False, mesh_texture_size=64))
-    assert 'mesh' not in o and recorder == {'plain': [], 'textured': []}
-    o = out(call(False, mesh_texture_size='bogus'))                                   # ignored without export_mesh
-    assert 'mesh' not in o and recorder == {'plain': [], 'textured': []}
-
-
-def test_mesh_texture_size_is_not_a_meshpost_field():
-    from ln3diff_amd import mesh
-    from ln3diff_amd.entry import _MESH_FLAGS, create_argparser, validate
-    assert 'texture_size' not in mesh.MeshPost._fields and 'mesh_texture_size' not in _MESH_FLAGS
-    with pytest.raises(TypeError, match='mesh_texture_size'):
-        mesh.MeshPost.from_kwargs(dict(mesh_texture_size=64))
-    parse = lambda s: create_argparser(True).parse_args(s.split())                    # noqa: E731
-    assert parse("").mesh_texture_size == 0
-    validate(parse("--export_mesh true --mesh_texture_size 256"))
-    validate(parse("--export_mesh true --mesh_texture_size 4"))
-    validate(parse("--export_mesh true --mesh_texture_size 8192"))
-    validate(parse("--mesh_texture_size 0"))
-    with pytest.raises(SystemExit, match='export_mesh'):
-        validate(parse("--mesh_texture_size 256"))
-    for bad in ('3', '9000', '-1'):
-        with pytest.raises(SystemExit, match='mesh_texture_size'):
-            validate(parse(f"--export_mesh true --mesh_texture_size {bad}"))
-
-
 def test_bake_wrappers_refuse_bad_buffers_and_host_tensors(monkeypatch):
     from ln3diff_amd import _lib, mesh, ops
 
@@ -364,3 +231,32 @@ def test_bake_wrappers_refuse_bad_buffers_and_host_tensors(monkeypatch):
             bad()
     uv, t = mesh.bake_texture(None, None, v[:0], f[:0], 8, fill=7)                    # an empty mesh: nothing is asked of anybody
     assert uv.shape == (0, 3, 2) and t.shape == (8, 8, 3) and (t == 7).all()
+
+
+# ---------------------------------------------------------------- entry points on fake addresses
+P = 0x10000                                  # a fake device address
+# name -> (a valid argument list on fake addresses, indices of its buffers, indices of its int64 counts)
+VALID = {
+    'ln3d_bake_points': ([P, 9, P, 7, 11, 2, 5, P, P, None], (0, 2, 7, 8), (1, 3)),             # verts nv faces nf T n c points owner stream
+    'ln3d_bake_pack': ([P, P, 121, 0, P, None], (0, 1, 4), (2,)),                               # rgb owner P fill tex stream
+}
+
+
+def test_every_entry_point_validates_before_it_launches(hip_lib):
+    from ln3diff_amd import _lib
+    assert set(VALID) <= set(_lib.PROTOTYPES)
+    for name, (args, buffers, counts) in VALID.items():
+        assert len(args) == len(_lib.PROTOTYPES[name][1])
+        refuses_null_buffers_and_bad_counts(getattr(hip_lib, name), name, args, buffers, counts)
+    points, pargs = hip_lib.ln3d_bake_points, VALID['ln3d_bake_points'][0]
+    # (T, n, c, nf): T outside [4, 8192]; n < 1; c < 4; n * c > T; nf > 2 n^2 - each with the other values as sane as they can be
+    for T, n, c, nf in ((3, 1, 3, 1), (3, 1, 4, 1), (0, 1, 4, 1), (-8, 1, 4, 1), (8193, 1, 4, 1), (16384, 2048, 4, 2), (1 << 30, 1, 4, 1),
+                        (11, 0, 5, 1), (11, -2, 5, 1), (11, 2, 3, 7), (11, 2, 0, 7), (11, 2, -5, 7), (11, 2, 6, 7), (11, 3, 4, 7),
+                        (8192, 1 << 16, 1 << 16, 7),                                     # n * c overflows an int
+                        (11, 2, 5, 9), (4, 1, 4, 3), (64, 1, 64, 3), (8192, 2048, 4, 2 * 2048 * 2048 + 1)):
+        assert points(*_with(pargs, i3=nf, i4=T, i5=n, i6=c)) == BAD_ARG, (T, n, c, nf)
+    pack, kargs = hip_lib.ln3d_bake_pack, VALID['ln3d_bake_pack'][0]
+    for fill in (-1, 256, 1 << 20):
+        assert pack(*_with(kargs, i3=fill)) == BAD_ARG, fill
+    assert pack(*_with(kargs, i2=8192 * 8192 + 1)) == BAD_ARG
+    assert b'bad argument' in hip_lib.ln3d_strerror(BAD_ARG)

@@ -1,4 +1,4 @@
-"""Texture baking on the GPU (include/ext/ln3d_meshbake.h): the two entry points called through the C ABI on sentinel-filled, guarded buffers
+"""Texture baking on the GPU (include/ln3d_meshbake.h): the two entry points called through the C ABI on sentinel-filled, guarded buffers
 and held to the numpy reference of tests/mesh_bake_refs.py by equality of bits; the whole bake through a stub field (an affine function,
 which a bilinear look-up must give back) and through the real point query, f32 and f16 texels; then the seams: textured_mesh_from_grid
 against mesh_from_grid, render_video_given_triplane and the launcher flag."""

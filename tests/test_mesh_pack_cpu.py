@@ -1,4 +1,4 @@
-"""The binary mesh export of include/addons/ln3d_meshpack.h without a GPU:
+"""The binary mesh export of include/ln3d_meshpack.h without a GPU:
   - the numpy restatement (tests/mesh_pack_refs.py) against the rules it restates, and hand-made meshes through mesh.write_ply /
     mesh.write_glb - with the six packers replaced by the restatement, so that everything the HOST does (headers, JSON, chunks, padding,
     the order of the writes) is the product's - and back through the two readers of that file;
@@ -8,8 +8,8 @@
     tests/test_mesh_pack_gpu.py must catch, on the inputs those tests use;
   - every new entry point validates its arguments on fake addresses before it launches.  (That a null `normal` is ACCEPTED cannot be shown
     here: an accepted call launches.  The GPU tests run every packer with and without normals.)
-  - mesh_format from every public entry of pipeline down to mesh_from_grid / textured_mesh_from_grid, handed on only when it is not 'obj';
-    the launcher flag and its refusals."""
+  - mesh_format selects the writer of the two mesh functions and nothing else.
+(mesh_format from every public entry of pipeline down, and the launcher flag and its refusals: tests/test_mesh_options_cpu.py.)"""
 import json
 import struct
 
@@ -18,11 +18,10 @@ import pytest
 import torch
 
 import mesh_pack_refs as R
-from test_abi_cpu import BAD_ARG
-from test_mesh_bake_cpu import B, ENTRIES, FOUR, _entries, _strip, decode_png, recorder          # noqa: F401  (recorder is a fixture)
+from abi_args import BAD_ARG, BIG, with_args as _with
+from test_mesh_bake_cpu import decode_png
 
 P, Q = 0x10000, 0x4000000                    # two fake device addresses, 64 MiB apart
-BIG = 1 << 31                                # one more than the largest count
 
 
 # ---------------------------------------------------------------- the restatement's own rules
@@ -324,19 +323,12 @@ VALID = {
 }
 
 
-def _with(args, **at):
-    a = list(args)
-    for i, v in at.items():
-        a[int(i[1:])] = v
-    return a
-
-
 def test_every_pack_entry_point_validates_before_it_launches(hip_lib):
     from ln3diff_amd import _lib
-    assert list(_lib.ADDON_PROTOTYPES)[:len(VALID)] == list(VALID)                          # in front of the rows that were there
+    assert set(VALID) <= set(_lib.PROTOTYPES)
     for name, (args, buffers, pair, counts, aligned) in VALID.items():
         fn = getattr(hip_lib, name)
-        assert len(args) == len(_lib.ADDON_PROTOTYPES[name][1])
+        assert len(args) == len(_lib.PROTOTYPES[name][1])
         for i in buffers:
             assert fn(*_with(args, **{'i%d' % i: None})) == BAD_ARG, (name, 'null buffer', i)
         if pair is not None:                  # both or neither: one without the other is refused
@@ -393,31 +385,6 @@ def test_pack_wrappers_refuse_bad_buffers_and_host_tensors(monkeypatch):
             bad()
 
 
-# ---------------------------------------------------------------- plumbing
-@pytest.mark.parametrize('entry', ENTRIES)
-def test_mesh_format_reaches_the_mesh_functions(recorder, entry):                          # noqa: F811
-    assert list(_entries()) == ENTRIES
-    call = _entries()[entry]
-    out = lambda o: o[1] if isinstance(o, tuple) else o                                   # noqa: E731
-    for given in ({}, dict(mesh_format='obj')):                                           # absent or 'obj': exactly today's four keywords
-        out(call(True, **given))
-        assert [_strip(kw) for kw in recorder['plain']] == [FOUR] * B and recorder['textured'] == []
-        del recorder['plain'][:]
-    for fmt in ('ply', 'glb'):
-        out(call(True, mesh_format=fmt, mesh_keep='largest'))
-        assert [_strip(kw) for kw in recorder['plain']] == [dict(FOUR, keep='largest', mesh_format=fmt)] * B and recorder['textured'] == []
-        del recorder['plain'][:]
-    out(call(True, mesh_format='glb', mesh_texture_size=64, mesh_smooth_iters=2, mesh_path='m{}.glb'))
-    assert [_strip(kw) for kw in recorder['textured']] == [dict(FOUR, texture_size=64, smooth_iters=2, mesh_format='glb')] * B and recorder['plain'] == []
-    assert [kw['path'] for kw in recorder['textured']] == ['m%d.glb' % i for i in range(B)]    # the extension is the caller's
-    del recorder['textured'][:]
-    o = out(call(False, mesh_format='bogus'))                                              # ignored without export_mesh
-    assert 'mesh' not in o and recorder == {'plain': [], 'textured': []}
-    with pytest.raises(TypeError, match='mesh_formats'):
-        call(True, mesh_formats='glb')                                                     # misspelt
-    assert recorder == {'plain': [], 'textured': []}
-
-
 class _Field:
     def forward_points(self, pcl, pts, with_grad=False):
         return {'rgb': torch.full_like(pts, 0.5), 'normal': torch.zeros_like(pts)}
@@ -472,25 +439,4 @@ def test_the_format_selects_the_writer_and_nothing_else(monkeypatch, tmp_path):
     mesh.export_mesh(_Field(), d, 'e.obj', grid_size=G)
     mesh.export_mesh(_Field(), d, 'e.obj', grid_size=G, mesh_format='obj')
     mesh.export_mesh(_Field(), d, 'e.glb', grid_size=G, mesh_format='glb')
-    assert ['mesh_format' in kw for kw in seen] == [False, False, True] and seen[2]['mesh_format'] == 'glb'
-    assert mesh.MeshPost._fields == ('normals', 'keep', 'min_faces', 'simplify_cell')
-    with pytest.raises(TypeError, match='mesh_format'):
-        mesh.MeshPost.from_kwargs(dict(mesh_format='glb'))
-
-
-def test_launcher_flag():
-    from ln3diff_amd.entry import _MESH_FLAGS, create_argparser, validate
-    for objaverse in (True, False):
-        parse = lambda s: create_argparser(objaverse).parse_args(s.split())                # noqa: E731
-        assert parse("").mesh_format == 'obj' and 'mesh_format' not in _MESH_FLAGS
-        for ok in ("--export_mesh true --mesh_format ply", "--export_mesh true --mesh_format glb", "--export_mesh true --mesh_format obj",
-                   "--mesh_format obj", "--export_mesh true --mesh_format glb --mesh_texture_size 256",
-                   "--export_mesh true --mesh_format obj --mesh_texture_size 256", "--export_mesh true --mesh_format ply --export_mesh_normals true"):
-            validate(parse(ok))
-        for fmt in ('ply', 'glb'):
-            with pytest.raises(SystemExit, match='export_mesh'):
-                validate(parse(f"--mesh_format {fmt}"))
-        with pytest.raises(SystemExit, match="mesh_format 'stl'.*obj.*ply.*glb"):
-            validate(parse("--export_mesh true --mesh_format stl"))
-        with pytest.raises(SystemExit, match='mesh_format ply.*mesh_texture_size'):
-            validate(parse("--export_mesh true --mesh_format ply --mesh_texture_size 256"))
+    assert [kw.get('mesh_format') for kw in seen] == [None, 'obj', 'glb']                  # handed on as given: mesh_from_grid has the default

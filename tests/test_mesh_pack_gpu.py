@@ -1,4 +1,4 @@
-"""The binary mesh export of include/addons/ln3d_meshpack.h on the GPU (csrc/meshpack.hip):
+"""The binary mesh export of include/ln3d_meshpack.h on the GPU (csrc/meshpack.hip):
   - the six packers against the numpy restatement (tests/mesh_pack_refs.py), byte for byte, at nv, nf in {1, 2, 3, 4, 5, 63, 64, 65, 257, 1000}
     (every phase of the 4-record period of the PLY words, a partial last word, wave and block edges, more than one block), with and without
     normals, rotated by a RANDOM matrix (the real rotation cannot show a fused multiply-add: tests/test_mesh_pack_cpu.py), on positions

@@ -1,4 +1,4 @@
-"""The quadric-error placement of include/addons/ln3d_meshquadric.h without a GPU:
+"""The quadric-error placement of include/ln3d_meshquadric.h without a GPU:
   - what the float64 reference achieves (the figures the feature was proposed with): creases of a box to 1e-3 cells where the mean is 0.4
     cells off, every cluster inside its cell, and NO gain on a sphere, clean or noisy;
   - the calibration of mesh_quadric_refs.POSITION_BOUND: the fp32 restatement against float64 over every input of the GPU test, times 4;
@@ -14,12 +14,10 @@ import torch
 
 import mesh_quadric_refs as R
 import mesh_simplify_refs as S
-from test_abi_cpu import BAD_ARG, UNSUPPORTED
-from test_mesh_bake_cpu import B, ENTRIES, FOUR, _entries, _strip, recorder          # noqa: F401  (recorder is a fixture)
+from abi_args import BAD_ARG, BIG, UNSUPPORTED, with_args as _with
 
 HOST_SPREAD = 0.25               # relative: the maximum over clusters of a rounding error moves with the host's float32 / LAPACK details
 P0, Q0 = 0x10000, 0x4000000      # two fake device addresses, 64 MiB apart
-BIG = 1 << 31
 PLACED = [n for n in R.cases() if n not in R.PAIRS_ONLY]
 
 
@@ -146,13 +144,6 @@ def _place_args():
     return [P0, 20, P0 + 0x1000, 10, P0 + 0x2000, 30, P0 + 0x3000, 4, P0 + 0x4000, 0.0, 0.5, -1.0, 2.0, P0 + 0x5000, 1e-3, Q0, Q0 + 0x1000, None]
 
 
-def _with(args, **at):
-    a = list(args)
-    for i, v in at.items():
-        a[int(i[1:])] = v
-    return a
-
-
 def test_quadric_pairs_validates_before_it_launches(hip_lib):
     fn, args = hip_lib.ln3d_quadric_pairs, _pairs_args()
     for i in (0, 3):
@@ -184,30 +175,6 @@ def test_quadric_place_validates_before_it_launches(hip_lib):
     for shift in (4, 12 * 4 - 4, -(12 * 4 - 4)):                                          # rep_out overlaps rep_mean: nc = 4 rows of 12 bytes
         assert fn(*_with(args, i15=args[8] + shift)) == BAD_ARG, shift
     assert b'bad argument' in hip_lib.ln3d_strerror(BAD_ARG)
-
-
-# ---------------------------------------------------------------- plumbing
-@pytest.mark.parametrize('entry', ENTRIES)
-def test_mesh_simplify_placement_reaches_the_mesh_functions(recorder, entry):           # noqa: F811
-    assert list(_entries()) == ENTRIES
-    call = _entries()[entry]
-    out = lambda o: o[1] if isinstance(o, tuple) else o                                   # noqa: E731
-    for given in ({}, dict(mesh_simplify_placement='mean')):                              # absent or 'mean': exactly today's four keywords
-        out(call(True, **given))
-        assert [_strip(kw) for kw in recorder['plain']] == [FOUR] * B and recorder['textured'] == []
-        del recorder['plain'][:]
-    out(call(True, mesh_simplify_placement='quadric', mesh_simplify_cell=2.0))
-    assert [_strip(kw) for kw in recorder['plain']] == [dict(FOUR, simplify_cell=2.0, simplify_placement='quadric')] * B and recorder['textured'] == []
-    del recorder['plain'][:]
-    out(call(True, mesh_simplify_placement='quadric', mesh_snap_iters=8, mesh_smooth_iters=3, mesh_texture_size=64))
-    assert [_strip(kw) for kw in recorder['textured']] == [dict(FOUR, texture_size=64, smooth_iters=3, snap_iters=8, simplify_placement='quadric')] * B
-    assert recorder['plain'] == []
-    del recorder['textured'][:]
-    o = out(call(False, mesh_simplify_placement='bogus'))                                 # ignored without export_mesh
-    assert 'mesh' not in o and recorder == {'plain': [], 'textured': []}
-    with pytest.raises(TypeError, match='mesh_simplify_placment'):
-        call(True, mesh_simplify_placment='quadric')                                      # misspelt
-    assert recorder == {'plain': [], 'textured': []}
 
 
 class _Field:
@@ -310,9 +277,6 @@ def test_the_default_call_launches_nothing_new(monkeypatch):
     with pytest.raises(ValueError, match='quadric_eps'):
         mesh.simplify_placement(v, f, 2.0, eps=-1.0)
     assert mesh.PLACEMENTS == ('mean', 'quadric') and mesh.QUADRIC_EPS == 1e-3
-    assert mesh.MeshPost._fields == ('normals', 'keep', 'min_faces', 'simplify_cell')
-    with pytest.raises(TypeError, match='mesh_simplify_placement'):
-        mesh.MeshPost.from_kwargs(dict(mesh_simplify_placement='quadric'))
     # 'mean' reaches none of the two new wrappers: the stages it launches are the ones it always launched
     called = []
     for name in ('quadric_pairs', 'quadric_place'):
@@ -320,24 +284,6 @@ def test_the_default_call_launches_nothing_new(monkeypatch):
     with pytest.raises(RuntimeError, match='need device tensors'):                        # host tensors: refused at the first stage
         mesh.simplify_mesh(v, f, 2.0, placement='mean', check=False)
     assert called == []
-
-
-def test_launcher_flag():
-    from ln3diff_amd.entry import _MESH_FLAGS, create_argparser, validate
-    for objaverse in (True, False):                                                       # both launchers
-        parse = lambda s: create_argparser(objaverse).parse_args(s.split())               # noqa: E731
-        assert parse("").mesh_simplify_placement == 'mean' and 'mesh_simplify_placement' not in _MESH_FLAGS
-        validate(parse("--export_mesh true --mesh_simplify_cell 2 --mesh_simplify_placement quadric"))
-        validate(parse("--export_mesh true --mesh_simplify_cell 2 --mesh_simplify_placement mean"))
-        validate(parse("--mesh_simplify_placement mean"))
-        with pytest.raises(SystemExit, match='export_mesh'):
-            validate(parse("--mesh_simplify_cell 0 --mesh_simplify_placement quadric"))
-        with pytest.raises(SystemExit, match='mesh_simplify_cell'):
-            validate(parse("--export_mesh true --mesh_simplify_placement quadric"))
-        with pytest.raises(SystemExit, match='mesh_simplify_cell'):
-            validate(parse("--export_mesh true --mesh_simplify_cell 0 --mesh_simplify_placement quadric"))
-        with pytest.raises(SystemExit, match='mesh_simplify_placement'):
-            validate(parse("--export_mesh true --mesh_simplify_cell 2 --mesh_simplify_placement median"))
 
 
 def test_wrappers_refuse_bad_buffers(monkeypatch):

@@ -1,4 +1,4 @@
-"""Quadric-error placement on the GPU (include/addons/ln3d_meshquadric.h): ln3d_quadric_pairs exactly against the definition's loop,
+"""Quadric-error placement on the GPU (include/ln3d_meshquadric.h): ln3d_quadric_pairs exactly against the definition's loop,
 ln3d_quadric_place per cluster and axis against the float64 reference of tests/mesh_quadric_refs.py within POSITION_BOUND cells (calibrated in
 tests/test_mesh_quadric_cpu.py, where the fp32 restatement passes these same checks and four seeded faults fail them), `placed` against the
 reference's flag, the mean's bits where a placement is refused; then simplify_mesh / simplify_placement / extract_isosurface / mesh_from_grid

@@ -1,30 +1,20 @@
-"""The mesh smoothing of include/addons/ln3d_meshsmooth.h without a GPU:
+"""The mesh smoothing of include/ln3d_meshsmooth.h without a GPU:
   - the numpy reference (tests/mesh_smooth_refs.py) against what the definition promises - which vertices are pinned, that pinned vertices
     keep their bits, that Taubin's passes keep the volume where Laplacian smoothing loses it, that the roughness falls - and seeded faults
     that the equalities of tests/test_mesh_smooth_gpu.py must catch;
-  - the addon ABI table: every prototype of include/addons/*.h maps, by the one rule of tests/test_abi_types_cpu.py, to exactly its row of
-    _lib.ADDON_PROTOTYPES (no list of names and no count here: the next header is covered as it is), the three tables are disjoint, lib()
-    applies the table, check_symbols() covers it, and every entry point validates on fake addresses before it launches;
-  - mesh_smooth_iters from every public entry of pipeline down to mesh_from_grid / textured_mesh_from_grid, handed on only when non-zero;
-    smooth_mesh between the extraction and the query; the launcher flag; the ValueErrors of smooth_mesh and of the ops wrappers."""
-import glob
+  - every entry point validates on fake addresses before it launches (the prototype table against the header: tests/test_abi_types_cpu.py);
+  - smooth_mesh between the extraction and the query; the ValueErrors of smooth_mesh and of the ops wrappers.
+(mesh_smooth_iters from every public entry of pipeline down, and the launcher flag: tests/test_mesh_options_cpu.py.)"""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import mesh_smooth_refs as R
-from conftest import ROOT
-from test_abi_cpu import BAD_ARG
-from test_abi_types_cpu import RESTYPES, _ctype, _source
-from test_mesh_bake_cpu import B, ENTRIES, FOUR, _entries, _strip, recorder          # noqa: F401  (recorder is a fixture)
+from abi_args import BAD_ARG, refuses_null_buffers_and_bad_counts, with_args as _with
 
-ADDON_HEADERS = sorted(glob.glob(os.path.join(ROOT, 'include', 'addons', '*.h')))
 P, Q = 0x10000, 0x4000000                    # two fake device addresses, 64 MiB apart
-BIG = 1 << 31                                # one more than the largest count
 
 
 # ---------------------------------------------------------------- the reference's own properties
@@ -93,43 +83,7 @@ def test_every_seeded_fault_changes_bits():
     assert not np.array_equal(R.bits(a), R.bits(b)) and np.isfinite(a).all() and np.isfinite(b).all()
 
 
-# ---------------------------------------------------------------- the addon ABI table
-def _declared(lib):
-    out = {}
-    for path in ADDON_HEADERS:
-        src = _source(path)
-        assert 'struct' not in src, f"{path}: the additions use no struct"
-        assert not re.search(r'LN3D_(ERR|EPI)_\w+\s*=|#define\s+LN3D_(ERR|EPI)_', src), f"{path}: the additions define no constant"
-        for ret, name, params in re.findall(r'\b(int|void|const\s+char\s*\*)\s*(ln3d_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', src):
-            assert name not in out, f"{name} declared twice"
-            params = params.strip()
-            out[name] = (RESTYPES[re.sub(r'\s*\*', '*', ' '.join(ret.split()))],
-                         () if params == 'void' else tuple(_ctype(p, lib) for p in params.split(',')))
-    return out
-
-
-def test_addon_table_equals_the_addon_headers():
-    from ln3diff_amd import _lib
-    declared = _declared(_lib)
-    assert ADDON_HEADERS and declared and list(declared) == list(_lib.ADDON_PROTOTYPES), set(declared) ^ set(_lib.ADDON_PROTOTYPES)      # row for row
-    for name, (restype, argtypes) in declared.items():
-        assert (_lib.ADDON_PROTOTYPES[name][0], tuple(_lib.ADDON_PROTOTYPES[name][1])) == (restype, argtypes), name
-    tables = [set(_lib.PROTOTYPES), set(_lib.EXT_PROTOTYPES), set(_lib.ADDON_PROTOTYPES)]
-    assert len(set.union(*tables)) == sum(len(t) for t in tables) and _lib.ABI_VERSION == 10
-    assert 'ln3d_smooth_step' in _lib.ADDON_PROTOTYPES                                    # this feature's rows are among them
-
-
-def test_lib_applies_the_addon_table(hip_lib, monkeypatch):
-    from ln3diff_amd import _lib
-    for name, (restype, argtypes) in _lib.ADDON_PROTOTYPES.items():
-        fn = getattr(hip_lib, name)
-        assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes), name
-    assert _lib.check_symbols()
-    monkeypatch.setitem(_lib.ADDON_PROTOTYPES, 'ln3d_no_such_addon', _lib._int())
-    with pytest.raises(RuntimeError, match='ln3d_no_such_addon'):
-        _lib.check_symbols()
-
-
+# ---------------------------------------------------------------- entry points on fake addresses
 # name -> (a valid argument list on fake addresses, indices of its buffers, indices of its int64 counts)
 VALID = {
     'ln3d_smooth_edge_keys': ([P, 7, Q, None], (0, 2), (1,)),                                                # faces nf key stream
@@ -138,21 +92,9 @@ VALID = {
 }
 
 
-def _with(args, **at):
-    a = list(args)
-    for i, v in at.items():
-        a[int(i[1:])] = v
-    return a
-
-
 def test_every_smooth_entry_point_validates_before_it_launches(hip_lib):
     for name, (args, buffers, counts) in VALID.items():
-        fn = getattr(hip_lib, name)
-        for i in buffers:
-            assert fn(*_with(args, **{'i%d' % i: None})) == BAD_ARG, (name, 'null buffer', i)
-        for i in counts:
-            for bad in (0, -1, BIG, 1 << 40):
-                assert fn(*_with(args, **{'i%d' % i: bad})) == BAD_ARG, (name, 'count', i, bad)
+        refuses_null_buffers_and_bad_counts(getattr(hip_lib, name), name, args, buffers, counts)
     step, sargs = hip_lib.ln3d_smooth_step, VALID['ln3d_smooth_step'][0]
     for factor in (float('nan'), float('inf'), -float('inf')):
         assert step(*_with(sargs, i6=factor)) == BAD_ARG, factor
@@ -160,29 +102,6 @@ def test_every_smooth_entry_point_validates_before_it_launches(hip_lib):
     for shift in (4, 12 * 5 - 4, -(12 * 5 - 4)):                                           # ... or overlap: nv = 5 rows of 12 bytes
         assert step(*_with(sargs, i7=P + shift)) == BAD_ARG, shift
     assert b'bad argument' in hip_lib.ln3d_strerror(BAD_ARG)
-
-
-# ---------------------------------------------------------------- plumbing
-@pytest.mark.parametrize('entry', ENTRIES)
-def test_mesh_smooth_iters_reaches_the_mesh_functions(recorder, entry):                  # noqa: F811
-    assert list(_entries()) == ENTRIES
-    call = _entries()[entry]
-    out = lambda o: o[1] if isinstance(o, tuple) else o                                   # noqa: E731
-    for given in ({}, dict(mesh_smooth_iters=0)):                                         # absent or 0: exactly today's four keywords
-        out(call(True, **given))
-        assert [_strip(kw) for kw in recorder['plain']] == [FOUR] * B and recorder['textured'] == []
-        del recorder['plain'][:]
-    out(call(True, mesh_smooth_iters=4, mesh_keep='largest'))
-    assert [_strip(kw) for kw in recorder['plain']] == [dict(FOUR, keep='largest', smooth_iters=4)] * B and recorder['textured'] == []
-    del recorder['plain'][:]
-    out(call(True, mesh_smooth_iters=4, mesh_texture_size=64))
-    assert [_strip(kw) for kw in recorder['textured']] == [dict(FOUR, texture_size=64, smooth_iters=4)] * B and recorder['plain'] == []
-    del recorder['textured'][:]
-    o = out(call(False, mesh_smooth_iters='bogus'))                                       # ignored without export_mesh
-    assert 'mesh' not in o and recorder == {'plain': [], 'textured': []}
-    with pytest.raises(TypeError, match='mesh_smooth_iter'):
-        call(True, mesh_smooth_iter=4)                                                    # misspelt
-    assert recorder == {'plain': [], 'textured': []}
 
 
 class _Field:
@@ -243,23 +162,6 @@ def test_the_default_call_launches_nothing_new(monkeypatch):
         assert a is v and b is f
     a, b = mesh.smooth_mesh(v[:0], f[:0], 3, check=False)                                 # an empty mesh returns empty
     assert a.shape == (0, 3) and b.shape == (0, 3)
-    assert mesh.MeshPost._fields == ('normals', 'keep', 'min_faces', 'simplify_cell')
-    with pytest.raises(TypeError, match='mesh_smooth_iters'):
-        mesh.MeshPost.from_kwargs(dict(mesh_smooth_iters=3))
-
-
-def test_launcher_flag():
-    from ln3diff_amd.entry import _MESH_FLAGS, create_argparser, validate
-    parse = lambda s: create_argparser(True).parse_args(s.split())                        # noqa: E731
-    assert parse("").mesh_smooth_iters == 0 and 'mesh_smooth_iters' not in _MESH_FLAGS
-    validate(parse("--export_mesh true --mesh_smooth_iters 10"))
-    validate(parse("--export_mesh true --mesh_smooth_iters 1000"))
-    validate(parse("--mesh_smooth_iters 0"))
-    with pytest.raises(SystemExit, match='export_mesh'):
-        validate(parse("--mesh_smooth_iters 10"))
-    for bad in ('1001', '-1'):
-        with pytest.raises(SystemExit, match='mesh_smooth_iters'):
-            validate(parse(f"--export_mesh true --mesh_smooth_iters {bad}"))
 
 
 def test_smooth_mesh_refuses_bad_arguments(monkeypatch):

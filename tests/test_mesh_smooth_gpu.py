@@ -1,4 +1,4 @@
-"""Mesh smoothing on the GPU (include/addons/ln3d_meshsmooth.h), held to the numpy reference of tests/mesh_smooth_refs.py with equalities -
+"""Mesh smoothing on the GPU (include/ln3d_meshsmooth.h), held to the numpy reference of tests/mesh_smooth_refs.py with equalities -
 integers for the adjacency, bit patterns for the coordinates: the three entry points on sentinel-filled buffers with guard rows before and
 behind, mesh_adjacency and smooth_mesh on the smallest meshes at which each part of the definition can go wrong, then the seams:
 mesh_from_grid, textured_mesh_from_grid, render_video_given_triplane and the launcher flag."""

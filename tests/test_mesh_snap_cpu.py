@@ -1,4 +1,4 @@
-"""The level-set snapping of include/addons/ln3d_meshsnap.h without a GPU:
+"""The level-set snapping of include/ln3d_meshsnap.h without a GPU:
   - the calibration of the sigma bound of the all-fp32 path (mesh_snap_refs.SIGMA_BOUND_ULPS);
   - the fp32 stand-in of the loop passes every check tests/test_mesh_snap_gpu.py makes, on exactly that test's cases, and every seeded
     fault fails at least one of them;
@@ -16,12 +16,10 @@ import torch
 
 import mesh_snap_refs as R
 import normal_refs as nr
-from test_abi_cpu import BAD_ARG
-from test_mesh_bake_cpu import B, ENTRIES, FOUR, _entries, _strip, recorder          # noqa: F401  (recorder is a fixture)
+from abi_args import BAD_ARG, BIG, with_args as _with
 
 HOST_SPREAD = 0.25               # relative: a maximum over points of an error a few ulps of sigma large moves in steps of a quarter of itself
 P0, Q0 = 0x10000, 0x4000000      # two fake device addresses, 64 MiB apart
-BIG = 1 << 31
 
 
 # ---------------------------------------------------------------- calibration
@@ -108,13 +106,6 @@ def _valid():
             Q0, Q0 + 4096, Q0 + 8192, Q0 + 12288, None]
 
 
-def _with(args, **at):
-    a = list(args)
-    for i, v in at.items():
-        a[int(i[1:])] = v
-    return a
-
-
 @pytest.mark.parametrize('name', ['ln3d_snap_points', 'ln3d_snap_points_f16'])
 def test_snap_entry_points_validate_before_they_launch(hip_lib, name):
     fn, args = getattr(hip_lib, name), _valid()
@@ -136,29 +127,6 @@ def test_snap_entry_points_validate_before_they_launch(hip_lib, name):
     for shift in (4, 12 * 5 - 4, -(12 * 5 - 4)):                                           # ... or overlap: P = 5 rows of 12 bytes
         assert fn(*_with(args, i15=args[3] + shift)) == BAD_ARG, shift
     assert b'bad argument' in hip_lib.ln3d_strerror(BAD_ARG)
-
-
-# ---------------------------------------------------------------- plumbing
-@pytest.mark.parametrize('entry', ENTRIES)
-def test_mesh_snap_iters_reaches_the_mesh_functions(recorder, entry):                    # noqa: F811
-    assert list(_entries()) == ENTRIES
-    call = _entries()[entry]
-    out = lambda o: o[1] if isinstance(o, tuple) else o                                   # noqa: E731
-    for given in ({}, dict(mesh_snap_iters=0)):                                           # absent or 0: exactly today's four keywords
-        out(call(True, **given))
-        assert [_strip(kw) for kw in recorder['plain']] == [FOUR] * B and recorder['textured'] == []
-        del recorder['plain'][:]
-    out(call(True, mesh_snap_iters=4, mesh_keep='largest'))
-    assert [_strip(kw) for kw in recorder['plain']] == [dict(FOUR, keep='largest', snap_iters=4)] * B and recorder['textured'] == []
-    del recorder['plain'][:]
-    out(call(True, mesh_snap_iters=8, mesh_smooth_iters=3, mesh_texture_size=64))
-    assert [_strip(kw) for kw in recorder['textured']] == [dict(FOUR, texture_size=64, smooth_iters=3, snap_iters=8)] * B and recorder['plain'] == []
-    del recorder['textured'][:]
-    o = out(call(False, mesh_snap_iters='bogus'))                                         # ignored without export_mesh
-    assert 'mesh' not in o and recorder == {'plain': [], 'textured': []}
-    with pytest.raises(TypeError, match='mesh_snap_iter'):
-        call(True, mesh_snap_iter=4)                                                      # misspelt
-    assert recorder == {'plain': [], 'textured': []}
 
 
 class _Field:
@@ -231,23 +199,6 @@ def test_the_default_call_launches_nothing_new():
         assert a is v and diag == {'residual': None, 'state': None, 'evals': None}
     a, diag = mesh.snap_mesh(NoDecoder(), None, v[:0], 10.0, 8)                           # an empty mesh returns empty
     assert a.shape == (0, 3) and diag['state'] is None
-    assert mesh.MeshPost._fields == ('normals', 'keep', 'min_faces', 'simplify_cell')
-    with pytest.raises(TypeError, match='mesh_snap_iters'):
-        mesh.MeshPost.from_kwargs(dict(mesh_snap_iters=3))
-
-
-def test_launcher_flag():
-    from ln3diff_amd.entry import _MESH_FLAGS, create_argparser, validate
-    parse = lambda s: create_argparser(True).parse_args(s.split())                        # noqa: E731
-    assert parse("").mesh_snap_iters == 0 and 'mesh_snap_iters' not in _MESH_FLAGS
-    validate(parse("--export_mesh true --mesh_snap_iters 4"))
-    validate(parse("--export_mesh true --mesh_snap_iters 64 --mesh_smooth_iters 10"))
-    validate(parse("--mesh_snap_iters 0"))
-    with pytest.raises(SystemExit, match='export_mesh'):
-        validate(parse("--mesh_snap_iters 4"))
-    for bad in ('65', '-1'):
-        with pytest.raises(SystemExit, match='mesh_snap_iters'):
-            validate(parse(f"--export_mesh true --mesh_snap_iters {bad}"))
 
 
 def test_wrappers_refuse_bad_arguments(monkeypatch):

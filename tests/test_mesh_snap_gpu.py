@@ -1,4 +1,4 @@
-"""Level-set snapping on the GPU (include/addons/ln3d_meshsnap.h): ln3d_snap_points and its f16 twin against the float64 loop of
+"""Level-set snapping on the GPU (include/ln3d_meshsnap.h): ln3d_snap_points and its f16 twin against the float64 loop of
 tests/mesh_snap_refs.py - the checks are that file's, the ones tests/test_mesh_snap_cpu.py shows an fp32 stand-in to pass and every seeded
 fault to fail - on sentinel-tailed buffers, then the seams: Triplane.snap_points, mesh.snap_mesh, mesh_from_grid,
 textured_mesh_from_grid, render_video_given_triplane and the launcher flag.

@@ -1,4 +1,4 @@
-"""Times the texture bake of include/ext/ln3d_meshbake.h on the level set of a 192^3 grid and writes profiles/mesh_bake.md.
+"""Times the texture bake of include/ln3d_meshbake.h on the level set of a 192^3 grid and writes profiles/mesh_bake.md.
 
     python tools/mesh_bake_bench.py [--out profiles/mesh_bake.md] [--iters 10] [--grid 192] [--commit SHA]
 

@@ -1,4 +1,4 @@
-"""Times the mesh export - the .obj text, and the binary PLY and GLB of include/addons/ln3d_meshpack.h - and writes profiles/mesh_export.md.
+"""Times the mesh export - the .obj text, and the binary PLY and GLB of include/ln3d_meshpack.h - and writes profiles/mesh_export.md.
 
     python tools/mesh_export_bench.py [--out profiles/mesh_export.md] [--windows 5] [--calls 3] [--grid 192] [--dir DIR] [--commit SHA]
     python tools/mesh_export_bench.py --obj-only --tree PATH        # the .obj rows alone, with the package of another checkout (the parent)
@@ -164,7 +164,7 @@ def main():
             if args.obj_only:
                 continue
             # ---- the export step alone: the device tensors mesh_from_grid holds at that point, and the arrays it returns
-            _, vtx, faces, v2, f2, c2, _, q = mesh._coloured_mesh(dec, d, sigma, G, thr, 0, 'cubes', False, 'all', 0, cell)
+            _, vtx, faces, v2, f2, c2, _, q = mesh._coloured_mesh(dec, d, sigma, G, thr, 0, 'cubes', mesh.MeshPost(simplify_cell=cell))
             rgb = q['rgb'][0]
             mesh.write_ply(path('dev.ply'), vtx, faces, rgb, check=False)
             numpy_ply(path('np.ply'), v2, f2, c2)

@@ -9,7 +9,7 @@ launches drain (launch throughput), an upper bound on the kernel's own time, not
 with and without simplification (without an .obj, and once with one) are timed with a host clock around calls that end in a device
 synchronise, because they contain read-backs.  The device result is compared with the numpy reference of tests/mesh_simplify_refs.py at a
 small grid before anything is reported.
---placement quadric measures the opt-in quadric-error placement (include/addons/ln3d_meshquadric.h) INSTEAD: per cell size simplify_mesh as a
+--placement quadric measures the opt-in quadric-error placement (include/ln3d_meshquadric.h) INSTEAD: per cell size simplify_mesh as a
 whole with placement='mean' and with placement='quadric' in alternating windows of `iters` calls in this one process (host clock, median and
 range over the windows), and the steps the option adds (the two kernels, the pair-key sort and searchsorted) with device events; nothing of
 the default report is measured or written, and --out then defaults to profiles/mesh_quadric_times.md."""

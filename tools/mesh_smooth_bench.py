@@ -1,4 +1,4 @@
-"""Times the mesh smoothing of include/addons/ln3d_meshsmooth.h on the level set of a 192^3 grid and writes profiles/mesh_smooth.md.
+"""Times the mesh smoothing of include/ln3d_meshsmooth.h on the level set of a 192^3 grid and writes profiles/mesh_smooth.md.
 
     python tools/mesh_smooth_bench.py [--out profiles/mesh_smooth.md] [--iters 20] [--grid 192] [--commit SHA]
 

@@ -1,4 +1,4 @@
-"""Times the level-set snapping of include/addons/ln3d_meshsnap.h on the level set of a 192^3 grid and writes profiles/mesh_snap.md.
+"""Times the level-set snapping of include/ln3d_meshsnap.h on the level set of a 192^3 grid and writes profiles/mesh_snap.md.
 
     python tools/mesh_snap_bench.py [--out profiles/mesh_snap.md] [--reps 7] [--calls 10] [--grid 192] [--commit SHA]
 
