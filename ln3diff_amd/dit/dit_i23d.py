@@ -15,12 +15,17 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .dit_models_xformers import (CaptionEmbedder, ImageCondDiTBlock, ImageCondDiTBlockPixelArtRMSNorm, RMSNormP, T2IFinalLayer, bf16, f32,
-                                  self_attention_hip, pack_caption, attn_head_pad, attn_out_dim)
-from .dit_trilatent import DiT_TriLatent
+from .dit_base import DiT
+from .dit_models_xformers import (CaptionEmbedder, ImageCondDiTBlock, ImageCondDiTBlockPixelArtRMSNorm, Mlp, PixelArtTextCondDiTBlock,
+                                  RMSNormP, T2IFinalLayer, bf16, f32, pack_caption, attn_head_pad)
 
 
-class DiT_I23D_PixelArt(DiT_TriLatent):
+class DiT_I23D_PixelArt(DiT):
+    # the prompt-side modules of the class, in state-dict order behind final_layer ('clip_text_proj': in front of the blocks).
+    # clip_spatial_proj is present in the single-view checkpoints and unused by their forward.
+    PROMPT_MODULES = ('dino_proj', 'clip_spatial_proj', 'adaLN_modulation', 'cap_embedder', 'attention_y_norm')
+    _norm_kind = (1, 1e-5)             # pre-norms: RMSNorm(eps 1e-5) with a weight; the plain DiT_I23D uses affine-free LayerNorm
+
     def __init__(self, input_size=32, patch_size=2, in_channels=4, hidden_size=1152, depth=28, num_heads=16, mlp_ratio=4,
                  class_dropout_prob=0.1, num_classes=1000, learn_sigma=True, mixing_logit_init=-3, mixed_prediction=True,
                  context_dim=False, pooling_ctx_dim=768, roll_out=False, vit_blk=ImageCondDiTBlockPixelArtRMSNorm,
@@ -29,28 +34,27 @@ class DiT_I23D_PixelArt(DiT_TriLatent):
                          class_dropout_prob, num_classes, learn_sigma, mixing_logit_init, mixed_prediction, context_dim,
                          roll_out, vit_blk, T2IFinalLayer)
         self.clip_ctx_dim = 1024
-        del self.clip_text_proj
-        self.dino_proj = CaptionEmbedder(context_dim, hidden_size)
-        self.clip_spatial_proj = CaptionEmbedder(1024, hidden_size)     # present in the checkpoint, unused by forward
-        self.adaLN_modulation = nn.Sequential(nn.SiLU(), nn.Linear(hidden_size, 6 * hidden_size, bias=True))
-        self.cap_embedder = nn.Sequential(nn.LayerNorm(pooling_ctx_dim), nn.Linear(pooling_ctx_dim, hidden_size))
-        self.attention_y_norm = RMSNormP(1024)
+        make = {'dino_proj': lambda: CaptionEmbedder(context_dim, hidden_size),
+                'clip_spatial_proj': lambda: CaptionEmbedder(1024, hidden_size),
+                'adaLN_modulation': lambda: nn.Sequential(nn.SiLU(), nn.Linear(hidden_size, 6 * hidden_size, bias=True)),
+                'cap_embedder': lambda: nn.Sequential(nn.LayerNorm(pooling_ctx_dim), nn.Linear(pooling_ctx_dim, hidden_size)),
+                'attention_y_norm': lambda: RMSNormP(1024)}
+        for name in self.PROMPT_MODULES:
+            if name in make:
+                setattr(self, name, make[name]())
         self.pooling_ctx_dim = pooling_ctx_dim
 
+    APPEND_PROJ = 'dino_proj'          # the CaptionEmbedder whose output tokens are appended to the self-attention sequence (None: none)
     _uc_first = False                  # the flow-matching engine's [c, uc] order: the unconditional samples trail
 
-    def _append_proj(self):
-        """CaptionEmbedder whose output tokens are appended to the self-attention sequence."""
-        return self.dino_proj
-
     def _pack_prompt(self, P, device):
-        if hasattr(self, 'cap_embedder'):
+        if 'cap_embedder' in self.PROMPT_MODULES:
             P['cap_ln_w'], P['cap_ln_b'] = f32(self.cap_embedder[0].weight, device), f32(self.cap_embedder[0].bias, device)
             P['cap_w'], P['cap_b'] = bf16(self.cap_embedder[1].weight, device), f32(self.cap_embedder[1].bias, device)
-        if hasattr(self, 'attention_y_norm'):
+        if 'attention_y_norm' in self.PROMPT_MODULES:
             P['ynorm_w'] = f32(self.attention_y_norm.weight, device)
-        if self._append_proj() is not None:
-            pack_caption(P, 'd', self._append_proj(), device)
+        if self.APPEND_PROJ is not None:
+            pack_caption(P, 'd', getattr(self, self.APPEND_PROJ), device)
         P['fin_sst'] = f32(self.final_layer.scale_shift_table, device)          # [2, D]
         P['zeros'] = torch.zeros(max(self.embed_dim, self.pooling_ctx_dim), device=device)
 
@@ -81,96 +85,54 @@ class DiT_I23D_PixelArt(DiT_TriLatent):
             raise ValueError(f"context['crossattn'] must be [B, L, {want}] (CLIP {C1} || DINO) and context['vector'] [B, {self.pooling_ctx_dim}]; "
                              f"got {tuple(ca.shape)} / {tuple(vec.shape)}")
         cls = self._cls_token(vec)
-        # CLIP tokens: the model's attention_y_norm once for every layer (dit_i23d.py:247); DINO tokens: tanh-GELU MLP
-        clip_n = self._ws.get('clip_n', (Bn * Lc, C1), torch.bfloat16)
-        ops.norm_modulate(ca[..., :C1].contiguous().float(), clip_n, Bn * Lc, C1, kind=1, eps=1e-5, weight=self._packed['ynorm_w'])
+        # CLIP tokens: the model's attention_y_norm once for every layer (dit_i23d.py:247), or without one (the plain DiT_I23D) each
+        # BLOCK's own in front of its K / V GEMM; DINO tokens: tanh-GELU MLP
+        clip, own_norm = ca[..., :C1], 'attention_y_norm' not in self.PROMPT_MODULES
+        if not own_norm:
+            clip = self._ws.get('clip_n', (Bn * Lc, C1), torch.bfloat16)
+            ops.norm_modulate(ca[..., :C1].contiguous().float(), clip, Bn * Lc, C1, kind=1, eps=1e-5, weight=self._packed['ynorm_w'])
         dino = self._appended_tokens(ca[..., C1:])
-        k_all, vt_all, lpad = self._cross_kv(clip_n, Bn, Lc)
+        k_all, vt_all, lpad = self._cross_kv(clip, Bn, Lc, block_norm=own_norm)
         return self._finish_context({'k': k_all, 'vt': vt_all, 'Lc': Lc, 'lpad': lpad, 'Bn': Bn, 'cls': cls, 'dino': dino}, ca[..., :C1])
 
-    @torch.no_grad()
-    def forward(self, x, timesteps=None, context=None, y=None, get_attr='', context_cache=None, in_scale=None, **kwargs):
-        if get_attr != '':
-            return getattr(self, get_attr)
-        if not x.is_cuda:
-            raise RuntimeError("ln3diff_amd.DiT_I23D_PixelArt runs on the HIP device only (no CPU fallback)")
-        dev = x.device
-        self._ensure_packed(dev)
-        P, ws = self._packed, self._ws
-        cc = context_cache if context_cache is not None else self.prepare_context(context)
-        self._check_prepared(cc, 'prepare_context')
-        D, H, depth = self.embed_dim, self.num_heads, self.depth
-        Bn, Bx = timesteps.shape[0], x.shape[0]
-        assert cc['Bn'] == Bn
-        S, p, C = self.input_size, self.patch_size, self.in_channels
-        N = self._num_tokens(x)
-        Ld = cc['dino'].shape[1]
-        NA = N + Ld
-        M = Bn * N
+    def _multiview_context(self, mv, cls, appended):
+        """the prepared context of the multi-view classes: cross-attention over the flattened DINO features mv [B, V, L, C], raw"""
+        Bn, Lk = mv.shape[0], mv.shape[1] * mv.shape[2]
+        mvb = self._ws.get('mv_in', (Bn * Lk, mv.shape[3]), torch.bfloat16)
+        ops.cast_bf16(mv.reshape(Bn * Lk, mv.shape[3]).contiguous().float(), mvb)
+        k_all, vt_all, lpad = self._cross_kv(mvb, Bn, Lk)
+        return self._finish_context({'k': k_all, 'vt': vt_all, 'Lc': Lk, 'lpad': lpad, 'Bn': Bn, 'cls': cls, 'dino': appended}, mv.reshape(Bn, Lk, -1))
 
-        t32 = timesteps.to(device=dev, dtype=torch.float32).contiguous()
-        tf = ws.get('tfreq', (Bn, 256), torch.bfloat16)
-        ops.timestep_embedding(t32, tf, Bn, 256)
-        th = ws.get('th', (Bn, D), torch.bfloat16)
-        ops.gemm(tf, P['t_w0'], P['t_b0'], ops.EPI_SILU, th)
-        temb = ws.get('temb', (Bn, D), torch.float32)
-        ops.gemm(th, P['t_w2'], P['t_b2'], ops.EPI_F32, temb)
-        tsum = ws.get('tsum', (Bn, D), torch.float32)                  # t = t_embedder(timesteps) + cap token
-        tsilu = ws.get('tsilu', (Bn, D), torch.bfloat16)
+    # ------------------------------------------------------------------ the hooks of the forward template (dit_base.DiT.forward)
+    def _conditioning(self, timesteps, cc, opts):
+        """t = t_embedder(timesteps) + the pooled token: (SiLU(t) bf16, the adaLN GEMM's operand; t fp32 for the T2IFinalLayer)"""
+        Bn, D = timesteps.shape[0], self.embed_dim
+        temb, tsilu = self._timestep_embed(timesteps, '', silu=False)
+        tsum = self._ws.get('tsum', (Bn, D), torch.float32)
         ops.add_act_cast(temb, cc['cls'], tsilu, tsum, Bn * D, 1)
-        mod_of, ld = self._modulation(tsilu, Bn)
-        nk, neps = self._norm_kind
+        return tsilu, tsum
 
-        xt = self._embed_tokens(x, in_scale, Bx, Bn, N)
-        akv = self._appended_kv(cc, Bn, N) if Ld else None             # per-layer K / V^T of the appended tokens, once per prompt
-        if akv is None:
-            ha = ws.get('ha', (Bn, NA, D), torch.bfloat16)
-            if getattr(self, '_ha_src', None) is not cc['dino'] or getattr(self, '_ha_buf', None) is not ha:
-                ha[:, N:].copy_(cc['dino'])                            # appended DINO tokens: constant per prompt, and the
-                self._ha_src, self._ha_buf = cc['dino'], ha            # norm kernel only ever writes rows < N of each sample
-        hb = ws.get('h', (M, D), torch.bfloat16)
-        xb = ws.get('xb', (M, D), torch.bfloat16)
-        qc = ws.get('qc', (Bn, H, N, 64), torch.bfloat16)
-        oc = ws.get('oc', (M, H * 64), torch.bfloat16)
-        f1 = ws.get('f1', (M, P['blocks'][0]['fc1_w'].shape[0]), torch.bfloat16)
-        probe = getattr(self, '_fc1_probe', None)
-        fold = cc.get('fold', 0)                                       # trailing samples with a constant cross-attention output
-        Bc = Bn - fold
-        Mc = Bc * N
-        fuse_cq = ops.heads_norm_fusable(Mc, H * 64, N, 64)
-        for i, q in enumerate(P['blocks']):
-            mi = mod_of(i)
-            if akv is not None:
-                # queries / keys / values of the x tokens only (M rows instead of Bn * NA: the appended quarter of the joint
-                # sequence never changes); their K / V^T rows land in front of the cached ones of this layer
-                sa_k, sa_vt, npad, Dp = akv
-                ops.norm_modulate(xt, hb, M, D, kind=nk, eps=neps, weight=q['n1'], shift=mi[:, 0:], scale=mi[:, D:], mod_rows=N, mod_ld=ld)
-                qs = ws.get('sa_q', (Bn, H, npad, Dp), torch.bfloat16, zero=True, extent=N)
-                Do = attn_out_dim(D // H)
-                ao = ws.get('sa_o', (M, H * Do), torch.bfloat16)
-                ops.gemm(hb, q['qkv_w'], q['qkv_b'], ops.EPI_HEADS, qs, sa_k[i], sa_vt[i], M=M, tokens=N, tok_pad=npad, heads=H,
-                         head_dim=D // H, transpose_mask=0b100, head_dim_pad=Dp, head_norm0=q['qn'], head_norm1=q['kn'])
-                ops.attention(qs, sa_k[i], sa_vt[i], ao, Bn, H, N, npad, NA, npad, Dp, scale=(D // H) ** -0.5,
-                              dh_true=(D // H) if Do != Dp else 0)
-            else:
-                ops.norm_modulate(xt, ha, M, D, kind=nk, eps=neps, weight=q['n1'], shift=mi[:, 0:], scale=mi[:, D:], mod_rows=N,
-                                  mod_ld=ld, rows_in=N, rows_out=NA)
-                ao = self_attention_hip(ws, 'sa_', ha, Bn, NA, D, H, q['qkv_w'], q['qkv_b'], q['qn'], q['kn'], nq=N)
-            ops.gemm(ao, q['proj_w'], q['proj_b'], ops.EPI_GATE_RES, xt, xb, gate=mi[:, 2 * D:], gate_rows=N, gate_ld=ld,
-                     res_bias=cc['const'][i] if fold else None, res_bias_ld=D)
-            if q['cqn'] is not None and fuse_cq:        # qk_norm of the cross-attention query inside the projection's epilogue
-                ops.gemm(xb, q['cq_w'], None, ops.EPI_HEADS, qc, M=Mc, tokens=N, tok_pad=N, heads=H, head_dim=64, head_norm0=q['cqn'])
-            else:
-                ops.gemm(xb, q['cq_w'], None, ops.EPI_HEADS, qc, M=Mc, tokens=N, tok_pad=N, heads=H, head_dim=64)
-                if q['cqn'] is not None:
-                    ops.rmsnorm_heads(qc, q['cqn'], Bc * H * N, 64)
-            ops.attention(qc, cc['k'][i], cc['vt'][i], oc, Bc, H, N, N, cc['Lc'], cc['lpad'], 64)
-            ops.gemm(oc, q['co_w'], q['co_b'], ops.EPI_GATE_RES, xt, M=Mc)
-            ops.norm_modulate(xt, hb, M, D, kind=nk, eps=neps, weight=q['n2'], shift=mi[:, 3 * D:], scale=mi[:, 4 * D:],
-                              mod_rows=N, mod_ld=ld)
-            self._fc1(probe, i, hb, q, f1)
-            ops.gemm(f1, q['fc2_w'], q['fc2_b'], ops.EPI_GATE_RES, xt, gate=mi[:, 5 * D:], gate_rows=N, gate_ld=ld)
-        return self._output(xt, tsum, Bn, N)
+    def _modulation(self, tsilu, Bn, opts):
+        """(i -> [Bn, 6D] view of block i's shift/scale/gate rows, row stride): t2i blocks = shared adaLN(t) + scale_shift_table[i]"""
+        P, ws, D, depth = self._packed, self._ws, self.embed_dim, self.depth
+        t0 = ws.get('t0', (Bn, 6 * D), torch.float32)
+        ops.gemm(tsilu, P['ada_w'], P['ada_b'], ops.EPI_F32, t0)
+        mod = ws.get('modb', (depth, Bn, 6 * D), torch.float32)
+        ops.add_table_rows(t0, P['sst'], mod, depth, Bn, 6 * D)
+        return (lambda i: mod[i]), 6 * D
+
+    def _appended(self, cc, Bn, N):
+        """The tokens appended to the self-attention sequence: their per-layer K / V^T, cached once per prompt (_appended_kv), or
+        failing that the joint-sequence buffer [Bn, N + Ld, D] whose rows [N, N + Ld) of every sample hold them."""
+        Ld = cc['dino'].shape[1]
+        akv = self._appended_kv(cc, Bn, N) if Ld else None
+        if akv is not None:
+            return (akv[0], akv[1], N + Ld), None
+        ha = self._ws.get('ha', (Bn, N + Ld, self.embed_dim), torch.bfloat16)
+        if getattr(self, '_ha_src', None) is not cc['dino'] or getattr(self, '_ha_buf', None) is not ha:
+            ha[:, N:].copy_(cc['dino'])                            # appended DINO tokens: constant per prompt, and the
+            self._ha_src, self._ha_buf = cc['dino'], ha            # norm kernel only ever writes rows < N of each sample
+        return None, ha
 
     APPEND_CACHE_MAX_BYTES = 16 << 30
 
@@ -222,30 +184,7 @@ class DiT_I23D_PixelArt(DiT_TriLatent):
         cc['akv'] = (sa_k, sa_vt, npad, Dp)
         return cc['akv']
 
-    _norm_kind = (1, 1e-5)             # pre-norms: RMSNorm(eps 1e-5) with a weight; the plain DiT_I23D uses affine-free LayerNorm
-
-    def _modulation(self, tsilu, Bn):
-        """(i -> [Bn, 6D] view of block i's shift/scale/gate rows, row stride): t2i blocks = shared adaLN(t) + scale_shift_table[i]"""
-        P, ws, D, depth = self._packed, self._ws, self.embed_dim, self.depth
-        t0 = ws.get('t0', (Bn, 6 * D), torch.float32)
-        ops.gemm(tsilu, P['ada_w'], P['ada_b'], ops.EPI_F32, t0)
-        mod = ws.get('modb', (depth, Bn, 6 * D), torch.float32)
-        ops.add_table_rows(t0, P['sst'], mod, depth, Bn, 6 * D)
-        return (lambda i: mod[i]), 6 * D
-
-    # ---- the two ends of forward that the point-cloud variant replaces
-    def _num_tokens(self, x):
-        return 3 * (self.input_size // self.patch_size) ** 2
-
-    def _embed_tokens(self, x, in_scale, Bx, Bn, N):
-        """patchify + shared conv patch-embed + positional embedding -> fp32 tokens [Bn*N, D]"""
-        P, D = self._packed, self.embed_dim
-        xt = self._ws.get('x', (Bn * N, D), torch.float32)
-        ops.patch_embed(x.contiguous().float(), in_scale, P['pe_w'], P['pe_b'], P['pos'], xt, Bx, Bn, self.in_channels, self.input_size,
-                        self.patch_size, D)
-        return xt
-
-    def _output(self, xt, tsum, Bn, N):
+    def _output(self, xt, tsum, mod_of, ld, Bn, N):
         """T2IFinalLayer (LN, scale_shift_table + t, Linear) + unpatchify -> [Bn, 3*C_out, S, S]"""
         P, D, S = self._packed, self.embed_dim, self.input_size
         out = torch.empty(Bn, self.out_channels * 3, S, S, dtype=torch.float32, device=xt.device)
@@ -265,22 +204,20 @@ class DiT_I23D(DiT_I23D_PixelArt):
     dit_i23d.DiT_models): ImageCondDiTBlock blocks - every block has its OWN adaLN (no shared adaLN / scale_shift_table),
     affine-free LayerNorm(eps 1e-6) pre-norms and its own attention_y_norm for the CLIP tokens; the pooled token is
     clip_text_proj(context['vector']) (CaptionEmbedder, tanh-GELU MLP); T2IFinalLayer.  Runs on the same block machinery as the
-    PixArt variant: only the modulation source, the pre-norm kind and the prompt-side preparation differ."""
+    PixArt variant: only the modulation source, the pre-norm kind, the pooled token and where the CLIP tokens are normed differ."""
 
+    PROMPT_MODULES = ('clip_text_proj', 'dino_proj', 'clip_spatial_proj')
     _norm_kind = (0, 1e-6)
 
     def __init__(self, input_size=32, patch_size=2, in_channels=4, hidden_size=1152, depth=28, num_heads=16, mlp_ratio=4,
                  class_dropout_prob=0.1, num_classes=1000, learn_sigma=True, mixing_logit_init=-3, mixed_prediction=True,
                  context_dim=False, pooling_ctx_dim=768, roll_out=False, vit_blk=ImageCondDiTBlock, final_layer_blk=T2IFinalLayer):
-        DiT_TriLatent.__init__(self, input_size, patch_size, in_channels, hidden_size, depth, num_heads, mlp_ratio, class_dropout_prob,
-                               num_classes, learn_sigma, mixing_logit_init, mixed_prediction, context_dim, roll_out, vit_blk,
-                               T2IFinalLayer)
-        self.clip_ctx_dim = 1024
-        self.dino_proj = CaptionEmbedder(context_dim, hidden_size)
-        self.clip_spatial_proj = CaptionEmbedder(1024, hidden_size)     # present in the checkpoint, unused by forward
-        self.pooling_ctx_dim = self.clip_text_proj.y_proj.fc1.in_features
+        # the pooled vector goes through clip_text_proj, whose input width is context_dim
+        super().__init__(input_size, patch_size, in_channels, hidden_size, depth, num_heads, mlp_ratio, class_dropout_prob,
+                         num_classes, learn_sigma, mixing_logit_init, mixed_prediction, context_dim, context_dim, roll_out, vit_blk,
+                         T2IFinalLayer)
 
-    def _modulation(self, tsilu, Bn):
+    def _modulation(self, tsilu, Bn, opts):
         P, ws, D, depth = self._packed, self._ws, self.embed_dim, self.depth
         mod = ws.get('modall', (Bn, depth * 6 * D), torch.float32)
         ops.gemm(tsilu, P['ada_w'], P['ada_b'], ops.EPI_F32, mod)
@@ -290,21 +227,6 @@ class DiT_I23D(DiT_I23D_PixelArt):
         """clip_text_proj(context['vector']): Linear -> tanh-GELU -> Linear, fp32 out (dit_i23d.py:112)"""
         return self._caption_mlp(vec, 'c', torch.empty(vec.shape[0], self.embed_dim, device=vec.device, dtype=torch.float32))
 
-    @torch.no_grad()
-    def prepare_context(self, context):
-        ca, vec = context['crossattn'], context['vector']
-        self._ensure_packed(ca.device)
-        Bn, Lc, _ = ca.shape
-        C1 = self.clip_ctx_dim
-        want = C1 + self.dino_proj.y_proj.fc1.in_features
-        if ca.shape[-1] != want or vec.shape[-1] != self.pooling_ctx_dim:
-            raise ValueError(f"context['crossattn'] must be [B, L, {want}] (CLIP {C1} || DINO) and context['vector'] [B, {self.pooling_ctx_dim}]; "
-                             f"got {tuple(ca.shape)} / {tuple(vec.shape)}")
-        cls = self._cls_token(vec)
-        dino = self._appended_tokens(ca[..., C1:])
-        k_all, vt_all, lpad = self._cross_kv(ca[..., :C1], Bn, Lc, block_norm=True)      # the BLOCK's attention_y_norm
-        return self._finish_context({'k': k_all, 'vt': vt_all, 'Lc': Lc, 'lpad': lpad, 'Bn': Bn, 'cls': cls, 'dino': dino}, ca[..., :C1])
-
 
 class DiT_I23D_PixelArt_MVCond(DiT_I23D_PixelArt):
     """Multi-view image conditioned variant (reference dit/dit_i23d.py:293-384): the projected CLIP spatial tokens
@@ -312,12 +234,9 @@ class DiT_I23D_PixelArt_MVCond(DiT_I23D_PixelArt):
     [B, V, L, C] are the cross-attention context (raw: no attention_y_norm, no projection); `dino_proj` does not exist.
     Same blocks / kernels as the single-view model: only the prompt-side preparation differs."""
 
-    def __init__(self, *a, **k):
-        super().__init__(*a, **k)
-        del self.dino_proj
+    PROMPT_MODULES = ('clip_spatial_proj', 'adaLN_modulation', 'cap_embedder', 'attention_y_norm')
 
-    def _append_proj(self):
-        return self.clip_spatial_proj
+    APPEND_PROJ = 'clip_spatial_proj'
 
     @torch.no_grad()
     def prepare_context(self, context):
@@ -326,15 +245,8 @@ class DiT_I23D_PixelArt_MVCond(DiT_I23D_PixelArt):
             raise ValueError(f"MVCond context: 'crossattn' [B, L, {self.clip_spatial_proj.y_proj.fc1.in_features}] (CLIP spatial tokens), "
                              f"'concat' [B, V, L, C] (multi-view DINO); got {tuple(ca.shape)} / {tuple(mv.shape)}")
         self._ensure_packed(ca.device)
-        ws = self._ws
-        Bn = ca.shape[0]
         cls = self._cls_token(vec)
-        appended = self._appended_tokens(ca)
-        Lk = mv.shape[1] * mv.shape[2]
-        mvb = ws.get('mv_in', (Bn * Lk, mv.shape[3]), torch.bfloat16)
-        ops.cast_bf16(mv.reshape(Bn * Lk, mv.shape[3]).contiguous().float(), mvb)
-        k_all, vt_all, lpad = self._cross_kv(mvb, Bn, Lk)
-        return self._finish_context({'k': k_all, 'vt': vt_all, 'Lc': Lk, 'lpad': lpad, 'Bn': Bn, 'cls': cls, 'dino': appended}, mv.reshape(Bn, Lk, -1))
+        return self._multiview_context(mv, cls, self._appended_tokens(ca))
 
 
 class DiT_I23D_PixelArt_MVCond_noClip(DiT_I23D_PixelArt):
@@ -343,13 +255,9 @@ class DiT_I23D_PixelArt_MVCond_noClip(DiT_I23D_PixelArt):
     (ImageCondDiTBlockPixelArtNoclip), cross-attention over the flattened multi-view DINO features context['concat'];
     dino_proj, clip_spatial_proj and cap_embedder do not exist."""
 
-    def __init__(self, *a, **k):
-        super().__init__(*a, **k)
-        del self.dino_proj
-        del self.clip_spatial_proj, self.cap_embedder
+    PROMPT_MODULES = ('adaLN_modulation', 'attention_y_norm')
 
-    def _append_proj(self):
-        return None
+    APPEND_PROJ = None
 
     @torch.no_grad()
     def prepare_context(self, context):
@@ -357,12 +265,7 @@ class DiT_I23D_PixelArt_MVCond_noClip(DiT_I23D_PixelArt):
         dev = mv.device
         self._ensure_packed(dev)
         Bn, D = mv.shape[0], self.embed_dim
-        Lk = mv.shape[1] * mv.shape[2]
-        mvb = self._ws.get('mv_in', (Bn * Lk, mv.shape[3]), torch.bfloat16)
-        ops.cast_bf16(mv.reshape(Bn * Lk, mv.shape[3]).contiguous().float(), mvb)
-        k_all, vt_all, lpad = self._cross_kv(mvb, Bn, Lk)
-        return self._finish_context({'k': k_all, 'vt': vt_all, 'Lc': Lk, 'lpad': lpad, 'Bn': Bn, 'cls': torch.zeros(Bn, D, device=dev),
-                              'dino': torch.zeros(Bn, 0, D, device=dev, dtype=torch.bfloat16)}, mv.reshape(Bn, Lk, -1))
+        return self._multiview_context(mv, torch.zeros(Bn, D, device=dev), torch.zeros(Bn, 0, D, device=dev, dtype=torch.bfloat16))
 
 
 class DiT_TriLatent_PixelArt(DiT_I23D_PixelArt):
@@ -373,21 +276,18 @@ class DiT_TriLatent_PixelArt(DiT_I23D_PixelArt):
     Runs on the I23D block machinery: nothing is appended to the self-attention sequence, the per-block normalised context's
     K / V^T are computed once per prompt."""
 
+    PROMPT_MODULES = ('adaLN_modulation', 'cap_embedder')
+
     def __init__(self, input_size=32, patch_size=2, in_channels=4, hidden_size=1152, depth=28, num_heads=16, mlp_ratio=4,
                  class_dropout_prob=0.1, num_classes=1000, learn_sigma=True, mixing_logit_init=-3, mixed_prediction=True,
                  context_dim=False, roll_out=False, vit_blk=None, final_layer_blk=T2IFinalLayer):
-        from .dit_models_xformers import PixelArtTextCondDiTBlock
-        DiT_TriLatent.__init__(self, input_size, patch_size, in_channels, hidden_size, depth, num_heads, mlp_ratio, class_dropout_prob,
-                               num_classes, learn_sigma, mixing_logit_init, mixed_prediction, context_dim, roll_out,
-                               PixelArtTextCondDiTBlock, T2IFinalLayer)
-        del self.clip_text_proj
-        self.adaLN_modulation = nn.Sequential(nn.SiLU(), nn.Linear(hidden_size, 6 * hidden_size, bias=True))
-        self.cap_embedder = nn.Sequential(nn.LayerNorm(context_dim), nn.Linear(context_dim, hidden_size))
-        self.pooling_ctx_dim = context_dim
+        # the text context is both the cross-attention tokens and (pooled) the cap_embedder's input
+        super().__init__(input_size, patch_size, in_channels, hidden_size, depth, num_heads, mlp_ratio, class_dropout_prob,
+                         num_classes, learn_sigma, mixing_logit_init, mixed_prediction, context_dim, context_dim, roll_out,
+                         PixelArtTextCondDiTBlock, T2IFinalLayer)
         self.clip_ctx_dim = context_dim
 
-    def _append_proj(self):
-        return None
+    APPEND_PROJ = None
 
     @torch.no_grad()
     def prepare_context(self, context):
@@ -422,11 +322,8 @@ class DiT_pcd_I23D_PixelArt_MVCond(DiT_I23D_PixelArt_MVCond):
     On the HIP path the embedder runs as two GEMMs with the input channels zero-padded to the GEMM's K granule, and the final
     Linear as a bf16 GEMM (the output width is padded to a multiple of 4 and sliced)."""
 
-    def __init__(self, *a, **k):
-        super().__init__(*a, **k)
-        from .dit_models_xformers import Mlp
+    def _build_embedder(self):
         self.x_embedder = Mlp(self.in_channels, self.embed_dim, self.embed_dim)
-        del self.pos_embed
 
     def _pack_embedder(self, P, device):
         C, D = self.in_channels, self.embed_dim
@@ -463,7 +360,7 @@ class DiT_pcd_I23D_PixelArt_MVCond(DiT_I23D_PixelArt_MVCond):
         ops.gemm(h1, P['xe_w2'], P['xe_b2'], ops.EPI_F32, xt)
         return xt
 
-    def _output(self, xt, tsum, Bn, N):
+    def _output(self, xt, tsum, mod_of, ld, Bn, N):
         P, ws, D = self._packed, self._ws, self.embed_dim
         yb = ws.get('pcd_fin', (Bn * N, D), torch.bfloat16)
         ops.norm_modulate(xt, yb, Bn * N, D, kind=0, eps=1e-6, shift=tsum, scale=tsum, mod_rows=N, mod_ld=D,

@@ -298,28 +298,30 @@ def pad_head_columns(w, H, Dh):
     return out.reshape(w.shape[0], H * Dp)
 
 
-def self_attention_hip(ws, tag, h_bf16, B, N, D, H, qkv_w, qkv_b, qn=None, kn=None, nq=None):
+def self_attention_hip(ws, tag, h_bf16, B, N, D, H, qkv_w, qkv_b, qn=None, kn=None, nq=None, kv=None):
     """h [B*N, D] bf16, or an ops.MX with qkv_w one too (the MX-FP8 QKV GEMM) -> attention output bf16 [B*nq, H*attn_out_dim] (nq <= N
-    query rows kept).  For head sizes other than
+    query rows kept).  kv = (k, vt): h holds only the nq leading rows of every sample, the other rows' K / V^T are already in the
+    caller's [B, H, npad, Dp] / [B, H, Dp, npad] buffers (with their qk-norm, so qn / kn run fused).  For head sizes other than
     64/128 the QKV epilogue writes into 128-wide zero-initialised heads (exact: the extra dims contribute 0 to q.k); the kernel
     skips the padding for the sizes it knows (DiT-XL/2's 72: compact output, unpadded proj weight), otherwise it produces 0 output
     columns, which meet zero columns of the padded proj weight."""
     Dh = D // H
     Dp = attn_head_pad(Dh)
     nq = N if nq is None else nq
+    T = N if kv is None else nq        # rows of h per sample
     npad = (N + 63) // 64 * 64
-    q = ws.get(tag + 'q', (B, H, npad, Dp), torch.bfloat16, zero=True, extent=N)
-    k = ws.get(tag + 'k', (B, H, npad, Dp), torch.bfloat16, zero=True, extent=N)
-    vt = ws.get(tag + 'vt', (B, H, Dp, npad), torch.bfloat16, zero=True, extent=N)
+    q = ws.get(tag + 'q', (B, H, npad, Dp), torch.bfloat16, zero=True, extent=T)
+    k, vt = kv if kv is not None else (ws.get(tag + 'k', (B, H, npad, Dp), torch.bfloat16, zero=True, extent=N),
+                                       ws.get(tag + 'vt', (B, H, Dp, npad), torch.bfloat16, zero=True, extent=N))
     Do = attn_out_dim(Dh)
     o = ws.get(tag + 'o', (B * nq, H * Do), torch.bfloat16)
     if isinstance(h_bf16, ops.MX):
         fused = False                  # the MX GEMM's head split has no fused qk-norm
-        ops.gemm_mx(h_bf16, qkv_w, qkv_b, ops.EPI_HEADS, q, k, vt, M=B * N, tokens=N, tok_pad=npad, heads=H, head_dim=Dh,
+        ops.gemm_mx(h_bf16, qkv_w, qkv_b, ops.EPI_HEADS, q, k, vt, M=B * T, tokens=T, tok_pad=npad, heads=H, head_dim=Dh,
                     transpose_mask=0b100, head_dim_pad=Dp)
     else:
-        fused = qn is not None and ops.heads_norm_fusable(B * N, qkv_w.shape[0], N, Dh, Dp)
-        ops.gemm(h_bf16, qkv_w, qkv_b, ops.EPI_HEADS, q, k, vt, M=B * N, tokens=N, tok_pad=npad, heads=H, head_dim=Dh,
+        fused = qn is not None and (kv is not None or ops.heads_norm_fusable(B * N, qkv_w.shape[0], N, Dh, Dp))
+        ops.gemm(h_bf16, qkv_w, qkv_b, ops.EPI_HEADS, q, k, vt, M=B * T, tokens=T, tok_pad=npad, heads=H, head_dim=Dh,
                  transpose_mask=0b100, head_dim_pad=Dp, head_norm0=qn if fused else None, head_norm1=kn if fused else None)
     if qn is not None and not fused:
         ops.rmsnorm_heads(q, qn, B * H * npad, Dp, true_dim=Dh)      # qn / kn: [Dp] (zero beyond Dh when padded)
