@@ -1,6 +1,7 @@
-// Channel-last helpers for the conv decoder of the tri-plane VAE (ldm Decoder): GroupNorm(+swish),
-// im2col for 3x3 convs (optionally fused with the nearest-2x upsample), layout conversion; and for the multi-view encoder
-// (include/ln3d_encoder.h): the pad-(0,1,0,1) stride-2 im2col of its Downsample, frame pooling and the fused posterior.
+// Channel-last helpers for the conv decoder of the tri-plane VAE (ldm Decoder): GroupNorm(+swish), layout conversion, and the one
+// im2col kernel for every 3x3 conv of a bf16 channel-last image: pad 1 with an optional nearest-2x upsample (this decoder), pad 1
+// with a stride (the U-Net's Downsample) and pad (0,1,0,1) stride 2 (the multi-view encoder's Downsample).  For the encoder
+// (include/ln3d_encoder.h) also frame pooling and the fused posterior.
 // The convolutions themselves run on the MFMA GEMM (gemm_bf16.hip) with fused bias / residual epilogues.
 #include "common.h"
 #include "../../include/ln3d.h"
@@ -99,34 +100,56 @@ extern "C" int ln3d_groupnorm_swish(const float* x, const float* w, const float*
   return ln3d_check_launch();
 }
 
-// ------------------------------------------------------------------ im2col 3x3 pad 1 (channel-last bf16), optional nearest-2x upsample
-// col[(n*Ho*Wo + oy*Wo + ox), (ky*3+kx)*C + c] = x[n, (oy+ky-1)/up, (ox+kx-1)/up, c] (0 outside), zero pad to Kpad
-__global__ void im2col3x3_kernel(const bf16_t* x, bf16_t* col, int H, int W, int C, int up, int Kpad, int64_t total8) {
+// ------------------------------------------------------------------ im2col 3x3 (channel-last bf16): one kernel, three fronts
+// col[(n*Ho*Wo + oy*Wo + ox), (ky*3+kx)*C + c] = x[n, (oy*STRIDE+ky-PAD)/UP, (ox*STRIDE+kx-PAD)/UP, c] where that position lies inside the
+// nearest-upsampled H*UP x W*UP image, 0 outside (PAD rows / columns in front, one behind); zero pad to Kpad.  (UP, STRIDE, PAD) are
+// compile-time: the plain kernel before this one divided by a run-time `up` and the strided one multiplied by a run-time `stride`, and
+// neither should pay for the other's parameter.
+template <int UP, int STRIDE, int PAD>
+__global__ void im2col3x3_kernel(const bf16_t* x, bf16_t* col, int H, int W, int C, int Ho, int Wo, int Kpad, int64_t total8) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // one 16-B (8 x bf16) piece
   if (i >= total8) return;
   const int k8 = Kpad / 8;
   const int64_t row = i / k8;
   const int kk = (int)(i % k8) * 8;
-  const int Ho = H * up, Wo = W * up;
   const int ox = (int)(row % Wo), oy = (int)((row / Wo) % Ho);
   const int64_t n = row / ((int64_t)Wo * Ho);
   uint4 v = make_uint4(0, 0, 0, 0);
   if (kk < 9 * C) {
     const int tap = kk / C, c = kk % C, ky = tap / 3, kx = tap % 3;
-    const int yy = oy + ky - 1, xx = ox + kx - 1;
-    if (yy >= 0 && yy < Ho && xx >= 0 && xx < Wo)
-      v = *reinterpret_cast<const uint4*>(x + (((int64_t)n * H + yy / up) * W + xx / up) * C + c);
+    const int yy = oy * STRIDE + ky - PAD, xx = ox * STRIDE + kx - PAD;
+    if (yy >= 0 && yy < H * UP && xx >= 0 && xx < W * UP)
+      v = *reinterpret_cast<const uint4*>(x + (((int64_t)n * H + yy / UP) * W + xx / UP) * C + c);
   }
   *reinterpret_cast<uint4*>(col + row * Kpad + kk) = v;
 }
-extern "C" int ln3d_im2col3x3(const void* x, void* col, int N, int H, int W, int C, int upsample, int Kpad, void* stream) {
-  if (!x || !col || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || Kpad % 8 || Kpad < 9 * C || (upsample != 1 && upsample != 2))
-    return LN3D_ERR_BAD_ARG;
-  const int64_t rows = (int64_t)N * H * upsample * W * upsample;
-  const int64_t total8 = rows * (Kpad / 8);
-  hipLaunchKernelGGL(im2col3x3_kernel, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                     (bf16_t*)col, H, W, C, upsample, Kpad, total8);
+// every front names its instantiation, so the combinations that exist are the four below and no other
+template <int UP, int STRIDE, int PAD>
+static int im2col3x3_launch(const void* x, void* col, int N, int H, int W, int C, int Kpad, void* stream) {
+  if (!x || !col || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || Kpad % 8 || Kpad < 9 * C) return LN3D_ERR_BAD_ARG;
+  const int64_t Ho = ((int64_t)H * UP + PAD + 1 - 3) / STRIDE + 1, Wo = ((int64_t)W * UP + PAD + 1 - 3) / STRIDE + 1;
+  if (Ho > 0x7fffffff || Wo > 0x7fffffff) return LN3D_ERR_BAD_ARG;      // the kernel's H * UP, Ho and Wo are ints
+  const int64_t total8 = (int64_t)N * Ho * Wo * (Kpad / 8);
+  hipLaunchKernelGGL((im2col3x3_kernel<UP, STRIDE, PAD>), dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)x, (bf16_t*)col, H, W, C, (int)Ho, (int)Wo, Kpad, total8);
   return ln3d_check_launch();
+}
+// pad 1, optional nearest-2x upsample in front (the VAE decoder's Upsample): Ho = H * up
+extern "C" int ln3d_im2col3x3(const void* x, void* col, int N, int H, int W, int C, int upsample, int Kpad, void* stream) {
+  if (upsample == 1) return im2col3x3_launch<1, 1, 1>(x, col, N, H, W, C, Kpad, stream);
+  if (upsample == 2) return im2col3x3_launch<2, 1, 1>(x, col, N, H, W, C, Kpad, stream);
+  return LN3D_ERR_BAD_ARG;
+}
+// pad 1 with a stride (the U-Net's Downsample.op, unet.py:150-153): Ho = (H - 1) / stride + 1
+extern "C" int ln3d_im2col3x3_strided(const void* x, void* col, int N, int H, int W, int C, int stride, int Kpad, void* stream) {
+  if (stride == 1) return im2col3x3_launch<1, 1, 1>(x, col, N, H, W, C, Kpad, stream);
+  if (stride == 2) return im2col3x3_launch<1, 2, 1>(x, col, N, H, W, C, Kpad, stream);
+  return LN3D_ERR_BAD_ARG;
+}
+// the encoder's Downsample: F.pad(x, (0,1,0,1)) + 3x3 conv, stride 2, padding 0: Ho = (H - 2) / 2 + 1
+extern "C" int ln3d_im2col3x3_pad01(const void* x, void* col, int N, int H, int W, int C, int Kpad, void* stream) {
+  if (H < 2 || W < 2) return LN3D_ERR_BAD_ARG;
+  return im2col3x3_launch<1, 2, 0>(x, col, N, H, W, C, Kpad, stream);
 }
 
 // ------------------------------------------------------------------ [NP, 3, H, W, C] f32 channel-last -> [NP, 3*C, H, W] (reference layout)
@@ -149,33 +172,6 @@ extern "C" int ln3d_planes_to_nchw(const float* src, float* dst, int NP, int C, 
   if (!src || !dst || NP <= 0 || H <= 0 || W <= 0 || C != 32) return LN3D_ERR_BAD_ARG;
   const int HW = H * W;
   hipLaunchKernelGGL(cl_to_nchw_kernel, dim3((HW + 31) / 32, NP * 3), dim3(256), 0, (hipStream_t)stream, src, dst, C, HW);
-  return ln3d_check_launch();
-}
-
-// ------------------------------------------------------------------ encoder Downsample: F.pad(x, (0,1,0,1)) + 3x3 conv, stride 2, padding 0
-// col[(n*Ho*Wo + oy*Wo + ox), (ky*3+kx)*C + c] = x[n, 2*oy+ky, 2*ox+kx, c] (0 at or past H / W), zero pad to Kpad
-__global__ void im2col3x3_pad01_kernel(const bf16_t* x, bf16_t* col, int H, int W, int C, int Ho, int Wo, int Kpad, int64_t total8) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // one 16-B (8 x bf16) piece
-  if (i >= total8) return;
-  const int k8 = Kpad / 8;
-  const int64_t row = i / k8;
-  const int kk = (int)(i % k8) * 8;
-  const int ox = (int)(row % Wo), oy = (int)((row / Wo) % Ho);
-  const int64_t n = row / ((int64_t)Wo * Ho);
-  uint4 v = make_uint4(0, 0, 0, 0);
-  if (kk < 9 * C) {
-    const int tap = kk / C, c = kk % C, ky = tap / 3, kx = tap % 3;
-    const int yy = 2 * oy + ky, xx = 2 * ox + kx;
-    if (yy < H && xx < W) v = *reinterpret_cast<const uint4*>(x + (((int64_t)n * H + yy) * W + xx) * C + c);
-  }
-  *reinterpret_cast<uint4*>(col + row * Kpad + kk) = v;
-}
-extern "C" int ln3d_im2col3x3_pad01(const void* x, void* col, int N, int H, int W, int C, int Kpad, void* stream) {
-  if (!x || !col || N <= 0 || H < 2 || W < 2 || C <= 0 || C % 8 || Kpad % 8 || Kpad < 9 * C) return LN3D_ERR_BAD_ARG;
-  const int Ho = (H - 2) / 2 + 1, Wo = (W - 2) / 2 + 1;           // floor((H + 1 - 3) / 2) + 1
-  const int64_t total8 = (int64_t)N * Ho * Wo * (Kpad / 8);
-  hipLaunchKernelGGL(im2col3x3_pad01_kernel, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                     (bf16_t*)col, H, W, C, Ho, Wo, Kpad, total8);
   return ln3d_check_launch();
 }
 

@@ -1,4 +1,5 @@
 // Kernel of the FFHQ VAE decoder class (include/ln3d_ffhq.h): the 3 x 3 roll-out group convolution of conv_sr as an implicit GEMM.
+// (The class's other entry point, the roll-out means of bf16 planes, is an instantiation of shapenet_ops.hip's kernel and lives there.)
 //
 // The im2col + GEMM composition the ShapeNet class uses writes and re-reads a [H*W, 27*C] bf16 matrix per plane: 453 MB at C = 128,
 // H = W = 256.  Here a workgroup owns TH x TW = 8 x 32 output pixels of one plane and stages what they read once in LDS, as bf16:
@@ -141,24 +142,6 @@ __global__ __launch_bounds__(256) void conv3x3_rollout_kernel(const ConvArgs p) 
   }
 }
 
-// rollout_means_kernel of shapenet_ops.hip for bf16 planes (conv3D_0 pools the up-sampled planes, which only exist as the bf16 GEMM
-// operand): grid (H + W, N), blocks y < H reduce row y over x, the others a column over the rows; thread = channel
-__global__ __launch_bounds__(128) void rollout_means_bf16_kernel(const bf16_t* x, float* rowmean, float* colmean, int H, int W, int C) {
-  const int n = blockIdx.y, r = blockIdx.x;
-  const bf16_t* xn = x + (int64_t)n * H * W * C;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    float s = 0.f;
-    if (r < H) {
-      for (int xx = 0; xx < W; ++xx) s += bf2f(xn[((int64_t)r * W + xx) * C + c]);
-      rowmean[((int64_t)n * H + r) * C + c] = s / (float)W;
-    } else {
-      const int xc = r - H;
-      for (int yy = 0; yy < H; ++yy) s += bf2f(xn[((int64_t)yy * W + xc) * C + c]);
-      colmean[((int64_t)n * W + xc) * C + c] = s / (float)H;
-    }
-  }
-}
-
 template <int CT>
 int launch(const ConvArgs& p, hipStream_t s) {
   const int LDS = (HY * HX + HY + HX) * (2 * p.C + 16);
@@ -182,11 +165,4 @@ extern "C" int ln3d_conv3x3_rollout_bf16(const void* x, int x_is_bf16, const flo
   if (C == 128) return launch<128>(p, s);
   if (C == 32) return launch<32>(p, s);
   return launch<0>(p, s);
-}
-
-extern "C" int ln3d_rollout_means_bf16(const void* x, float* rowmean, float* colmean, int N, int H, int W, int C, void* stream) {
-  if (!x || !rowmean || !colmean || N <= 0 || N > 65535 || H <= 0 || W <= 0 || C <= 0) return LN3D_ERR_BAD_ARG;
-  hipLaunchKernelGGL(rollout_means_bf16_kernel, dim3(H + W, N), dim3(128), 0, (hipStream_t)stream, static_cast<const bf16_t*>(x), rowmean,
-                     colmean, H, W, C);
-  return ln3d_check_launch();
 }

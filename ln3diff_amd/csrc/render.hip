@@ -23,6 +23,7 @@
 //    cdf by a wave prefix sum, searchsorted by a 6-step binary search on the per-wave LDS copy of the
 //    cdf, the coarse+fine merge by rank counting (no sort), final sums by wave reductions.
 #include <stdlib.h>
+#include <type_traits>
 #include "common.h"
 #include "../../include/ln3d.h"
 #include "../../include/ln3d_planes16.h"
@@ -1168,30 +1169,6 @@ extern "C" int ln3d_query_points_f16(const void* planes, int H, int W, const flo
   return query_points_t<_Float16>(planes, H, W, points, P, dec_w0, dec_b0, dec_w1, dec_b1, box_warp, sigma, rgb, scalars, stream);
 }
 
-// ------------------------------------------------------------------ [NP, 3*C, H, W] -> [NP, 3, H, W, C]
-__global__ void planes_to_cl_kernel(const float* src, float* dst, int C, int HW, int64_t total) {
-  // one thread per (np*3 + n, hw, c): read src[(pn*C + c)*HW + hw] -> dst[(pn*HW + hw)*C + c]
-  __shared__ float tile[32][33];
-  const int pn = blockIdx.y;
-  const int hw0 = blockIdx.x * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-  for (int c = ty; c < C; c += 8) {
-    const int hw = hw0 + tx;
-    tile[c][tx] = hw < HW ? src[((int64_t)pn * C + c) * HW + hw] : 0.f;
-  }
-  __syncthreads();
-  for (int r = ty; r < 32; r += 8) {
-    const int hw = hw0 + r;
-    if (hw < HW && tx < C) dst[((int64_t)pn * HW + hw) * C + tx] = tile[tx][r];
-  }
-}
-extern "C" int ln3d_planes_to_channel_last(const float* src, float* dst, int NP, int C, int H, int W, void* stream) {
-  if (!src || !dst || NP <= 0 || H <= 0 || W <= 0 || C != 32) return LN3D_ERR_BAD_ARG;
-  const int HW = H * W;
-  hipLaunchKernelGGL(planes_to_cl_kernel, dim3((HW + 31) / 32, NP * 3), dim3(256), 0, (hipStream_t)stream, src, dst, C, HW, (int64_t)NP * 3 * C * HW);
-  return ln3d_check_launch();
-}
-
 // ------------------------------------------------------------------ f32 -> binary16 texels (include/ln3d_planes16.h)
 // round to nearest even; everything beyond +-65504 (the infinities included) saturates to +-65504; a NaN stays a NaN
 __device__ __forceinline__ uint16_t f32_to_f16_sat(float x) {
@@ -1199,8 +1176,11 @@ __device__ __forceinline__ uint16_t f32_to_f16_sat(float x) {
   const _Float16 h = (_Float16)c;
   return __builtin_bit_cast(uint16_t, h);
 }
-// the tile transpose of planes_to_cl_kernel; a thread writes two channels (4 bytes) of one texel
-__global__ void planes_to_cl_f16_kernel(const float* src, uint32_t* dst, int C, int HW) {
+
+// ------------------------------------------------------------------ [NP, 3*C, H, W] f32 -> [NP, 3, H, W, C] texels of type TX
+// a 32-pixel x C tile through LDS: read src[(pn*C + c)*HW + hw] along hw, write dst[(pn*HW + hw)*C + c] along c
+template <typename TX>
+__global__ void planes_to_cl_kernel(const float* src, TX* dst, int C, int HW) {
   __shared__ float tile[32][33];
   const int pn = blockIdx.y;
   const int hw0 = blockIdx.x * 32;
@@ -1210,19 +1190,34 @@ __global__ void planes_to_cl_f16_kernel(const float* src, uint32_t* dst, int C, 
     tile[c][tx] = hw < HW ? src[((int64_t)pn * C + c) * HW + hw] : 0.f;
   }
   __syncthreads();
-  const int cx = threadIdx.x & 15, ry = threadIdx.x >> 4;   // 16 channel pairs x 16 texels
-  for (int r = ry; r < 32; r += 16) {
-    const int hw = hw0 + r;
-    if (hw < HW && 2 * cx < C)
-      dst[((int64_t)pn * HW + hw) * (C / 2) + cx] = (uint32_t)f32_to_f16_sat(tile[2 * cx][r]) | ((uint32_t)f32_to_f16_sat(tile[2 * cx + 1][r]) << 16);
+  if constexpr (std::is_same<TX, float>::value) {             // float: a thread writes one channel of one texel
+    for (int r = ty; r < 32; r += 8) {
+      const int hw = hw0 + r;
+      if (hw < HW && tx < C) dst[((int64_t)pn * HW + hw) * C + tx] = tile[tx][r];
+    }
+  } else {                                                    // binary16: a thread writes two channels (4 bytes) of one texel
+    const int cx = threadIdx.x & 15, ry = threadIdx.x >> 4;   // 16 channel pairs x 16 texels
+    uint32_t* d2 = reinterpret_cast<uint32_t*>(dst);          // dst is 4-byte aligned (a device allocation; C is even, so every texel is)
+    for (int r = ry; r < 32; r += 16) {
+      const int hw = hw0 + r;
+      if (hw < HW && 2 * cx < C)
+        d2[((int64_t)pn * HW + hw) * (C / 2) + cx] = (uint32_t)f32_to_f16_sat(tile[2 * cx][r]) | ((uint32_t)f32_to_f16_sat(tile[2 * cx + 1][r]) << 16);
+    }
   }
 }
-extern "C" int ln3d_planes_to_channel_last_f16(const float* src, void* dst, int NP, int C, int H, int W, void* stream) {
+template <typename TX>
+static int planes_to_cl(const float* src, void* dst, int NP, int C, int H, int W, void* stream) {
   if (!src || !dst || NP <= 0 || H <= 0 || W <= 0 || C != 32) return LN3D_ERR_BAD_ARG;
   if ((int64_t)H * W > 0x7fffffff - 31 || (int64_t)NP * 3 > 65535) return LN3D_ERR_BAD_ARG;     // HW + 31 is an int, NP * 3 the grid's y extent
   const int HW = H * W;
-  hipLaunchKernelGGL(planes_to_cl_f16_kernel, dim3((HW + 31) / 32, NP * 3), dim3(256), 0, (hipStream_t)stream, src, reinterpret_cast<uint32_t*>(dst), C, HW);
+  hipLaunchKernelGGL(planes_to_cl_kernel<TX>, dim3((HW + 31) / 32, NP * 3), dim3(256), 0, (hipStream_t)stream, src, static_cast<TX*>(dst), C, HW);
   return ln3d_check_launch();
+}
+extern "C" int ln3d_planes_to_channel_last(const float* src, float* dst, int NP, int C, int H, int W, void* stream) {
+  return planes_to_cl<float>(src, dst, NP, C, H, W, stream);
+}
+extern "C" int ln3d_planes_to_channel_last_f16(const float* src, void* dst, int NP, int C, int H, int W, void* stream) {
+  return planes_to_cl<uint16_t>(src, dst, NP, C, H, W, stream);
 }
 
 __global__ __launch_bounds__(256) void planes_f32_to_f16_kernel(const float* src, uint16_t* dst, int64_t n) {

@@ -1,10 +1,12 @@
 // Kernels of the ShapeNet VAE decoder class (include/ln3d_shapenet.h): the cross-plane attention of its paired ViT blocks and the
-// layout / resize / roll-out pieces of its super-resolution convs.  The convolutions themselves run on the MFMA GEMM (gemm_bf16.hip);
-// these kernels are memory-bound gathers and small reductions.
+// layout / resize / roll-out pieces of its super-resolution convs, with the roll-out row / column means of both plane types (f32
+// here, bf16 for the FFHQ class).  The convolutions themselves run on the MFMA GEMM (gemm_bf16.hip); these kernels are memory-bound
+// gathers and small reductions.
 #include "common.h"
 #include "resize.h"
 #include "../../include/ln3d.h"
 #include "../../include/ln3d_shapenet.h"
+#include "../../include/ln3d_ffhq.h"
 
 // ------------------------------------------------------------------ cross-plane attention (2p keys per query, Dh 64)
 // One wavefront per (query token, head): lane j < 2p scores key j, the softmax is two wave reductions, lane d sums the value column d.
@@ -143,30 +145,44 @@ extern "C" int ln3d_resize_add_lrelu(const float* base, const float* t, float* o
   return ln3d_check_launch();
 }
 
-// ------------------------------------------------------------------ roll-out: row / column means and the gathered im2col
-// grid (H + W, N): blocks y < H reduce row y over x, blocks y >= H column y - H over the rows; thread = channel (strided by 256)
-__global__ __launch_bounds__(256) void rollout_means_kernel(const float* x, float* rowmean, float* colmean, int H, int W, int C) {
+// ------------------------------------------------------------------ roll-out: row / column means
+// grid (H + W, N): blocks y < H reduce row y over x, blocks y >= H column y - H over the rows; thread = channel (strided by the block size)
+// T = float (the ShapeNet class's f32 planes) or bf16_t (include/ln3d_ffhq.h: conv3D_0 pools the up-sampled planes, which only exist
+// as the bf16 GEMM operand); BLOCK = threads per block, each entry point's own
+__device__ __forceinline__ float rollout_elem(const float* p) { return *p; }
+__device__ __forceinline__ float rollout_elem(const bf16_t* p) { return bf2f(*p); }
+template <typename T, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void rollout_means_kernel(const T* x, float* rowmean, float* colmean, int H, int W, int C) {
   const int n = blockIdx.y;
   const int r = blockIdx.x;
-  const float* xn = x + (int64_t)n * H * W * C;
+  const T* xn = x + (int64_t)n * H * W * C;
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     float s = 0.f;
     if (r < H) {
-      for (int xx = 0; xx < W; ++xx) s += xn[((int64_t)r * W + xx) * C + c];
+      for (int xx = 0; xx < W; ++xx) s += rollout_elem(xn + ((int64_t)r * W + xx) * C + c);
       rowmean[((int64_t)n * H + r) * C + c] = s / (float)W;
     } else {
       const int xc = r - H;
-      for (int yy = 0; yy < H; ++yy) s += xn[((int64_t)yy * W + xc) * C + c];
+      for (int yy = 0; yy < H; ++yy) s += rollout_elem(xn + ((int64_t)yy * W + xc) * C + c);
       colmean[((int64_t)n * W + xc) * C + c] = s / (float)H;
     }
   }
 }
-extern "C" int ln3d_rollout_means(const float* x, float* rowmean, float* colmean, int N, int H, int W, int C, void* stream) {
-  if (!x || !rowmean || !colmean || N <= 0 || H <= 0 || W <= 0 || C <= 0) return LN3D_ERR_BAD_ARG;
-  hipLaunchKernelGGL(rollout_means_kernel, dim3(H + W, N), dim3(256), 0, (hipStream_t)stream, x, rowmean, colmean, H, W, C);
+template <typename T, int BLOCK>
+static int rollout_means(const void* x, float* rowmean, float* colmean, int N, int H, int W, int C, void* stream) {
+  if (!x || !rowmean || !colmean || N <= 0 || N > 65535 || H <= 0 || W <= 0 || C <= 0) return LN3D_ERR_BAD_ARG;     // N: the grid's y extent
+  hipLaunchKernelGGL((rollout_means_kernel<T, BLOCK>), dim3(H + W, N), dim3(BLOCK), 0, (hipStream_t)stream, static_cast<const T*>(x), rowmean,
+                     colmean, H, W, C);
   return ln3d_check_launch();
 }
+extern "C" int ln3d_rollout_means(const float* x, float* rowmean, float* colmean, int N, int H, int W, int C, void* stream) {
+  return rollout_means<float, 256>(x, rowmean, colmean, N, H, W, C, stream);
+}
+extern "C" int ln3d_rollout_means_bf16(const void* x, float* rowmean, float* colmean, int N, int H, int W, int C, void* stream) {
+  return rollout_means<bf16_t, 128>(x, rowmean, colmean, N, H, W, C, stream);
+}
 
+// ------------------------------------------------------------------ roll-out: the gathered im2col
 // one thread per 4 columns of one output row
 __global__ void im2col3x3_rollout_kernel(const float* x, const float* rowmean, const float* colmean, bf16_t* col, int plane, int H, int W,
                                          int C, int Kpad, int64_t total4) {

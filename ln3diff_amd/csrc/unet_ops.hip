@@ -1,8 +1,8 @@
 // Kernels of the U-Net denoiser (guided_diffusion/unet.py + ldm/modules/attention_compat.py) that the DiT / conv-decoder kernels do
-// not already cover: GroupNorm at any channel count with the ResBlock's per-sample embedding folded in, strided im2col for the 3x3
-// stride-2 Downsample, GEGLU, attention at arbitrary head sizes over short sequences, NCHW <-> channel-last conversion and the
-// mixed-prediction combination.  The convolutions and linears themselves run on the MFMA GEMM (gemm_bf16.hip); all of this is
-// HBM / latency bound glue on [N, H*W, C] channel-last activations (32x32 latents: a few MB per tensor).
+// not already cover: GroupNorm at any channel count with the ResBlock's per-sample embedding folded in, GEGLU, attention at
+// arbitrary head sizes over short sequences, NCHW <-> channel-last conversion and the mixed-prediction combination.  The
+// convolutions and linears themselves run on the MFMA GEMM (gemm_bf16.hip), the stride-2 Downsample through conv_ops.hip's im2col;
+// all of this is HBM / latency bound glue on [N, H*W, C] channel-last activations (32x32 latents: a few MB per tensor).
 #include "common.h"
 #include "../../include/ln3d.h"
 
@@ -65,34 +65,6 @@ extern "C" int ln3d_groupnorm_any(const float* x, const float* add_row, const fl
   if ((mod_scale == nullptr) != (mod_shift == nullptr)) return LN3D_ERR_BAD_ARG;
   hipLaunchKernelGGL(gn_any_kernel, dim3(N * groups), dim3(256), 0, (hipStream_t)stream, x, add_row, w, b, mod_scale, mod_shift, (bf16_t*)y_bf16, HW,
                      C, groups, eps, swish);
-  return ln3d_check_launch();
-}
-
-// ------------------------------------------------------------------ im2col 3x3 pad 1 with a stride (Downsample.op, unet.py:150-153)
-// col[(n*Ho*Wo + oy*Wo + ox), (ky*3+kx)*C + c] = x[n, oy*stride+ky-1, ox*stride+kx-1, c] (0 outside), zero pad to Kpad
-__global__ void im2col3x3_strided_kernel(const bf16_t* x, bf16_t* col, int H, int W, int C, int stride, int Ho, int Wo, int Kpad, int64_t total8) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total8) return;
-  const int k8 = Kpad / 8;
-  const int64_t row = i / k8;
-  const int kk = (int)(i % k8) * 8;
-  const int ox = (int)(row % Wo), oy = (int)((row / Wo) % Ho);
-  const int64_t n = row / ((int64_t)Wo * Ho);
-  uint4 v = make_uint4(0, 0, 0, 0);
-  if (kk < 9 * C) {
-    const int tap = kk / C, c = kk % C, ky = tap / 3, kx = tap % 3;
-    const int yy = oy * stride + ky - 1, xx = ox * stride + kx - 1;
-    if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = *reinterpret_cast<const uint4*>(x + (((int64_t)n * H + yy) * W + xx) * C + c);
-  }
-  *reinterpret_cast<uint4*>(col + row * Kpad + kk) = v;
-}
-extern "C" int ln3d_im2col3x3_strided(const void* x, void* col, int N, int H, int W, int C, int stride, int Kpad, void* stream) {
-  if (!x || !col || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || Kpad % 8 || Kpad < 9 * C || stride < 1 || stride > 2)
-    return LN3D_ERR_BAD_ARG;
-  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;          // floor((H + 2 - 3) / stride) + 1
-  const int64_t total8 = (int64_t)N * Ho * Wo * (Kpad / 8);
-  hipLaunchKernelGGL(im2col3x3_strided_kernel, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                     (bf16_t*)col, H, W, C, stride, Ho, Wo, Kpad, total8);
   return ln3d_check_launch();
 }
 

@@ -254,6 +254,19 @@ def test_zero_sizes_are_bad_arguments(hip_lib):
         assert getattr(hip_lib, name)(*args) == -1, (name, args)              # LN3D_ERR_BAD_ARG, before any launch
 
 
+def test_merged_glue_kernels_keep_every_front_refusal(hip_lib):
+    """One kernel serves the three im2col fronts, both plane layouts and both roll-out means: each front still refuses what only it
+    refuses, and the f32 entry points refuse the grid limits their f16 / bf16 twins always did.  Fake addresses: nothing launches."""
+    assert hip_lib.ln3d_im2col3x3(P, P, 1, 8, 8, 64, 3, 576, N) == -1                     # upsample in {1, 2}
+    assert hip_lib.ln3d_im2col3x3_strided(P, P, 1, 8, 8, 64, 3, 576, N) == -1             # stride in {1, 2}
+    assert hip_lib.ln3d_im2col3x3_pad01(P, P, 1, 1, 8, 64, 576, N) == -1                  # H >= 2
+    for entry in (hip_lib.ln3d_planes_to_channel_last, hip_lib.ln3d_planes_to_channel_last_f16):
+        assert entry(P, P, 21846, 32, 8, 8, N) == -1                                      # NP * 3 > 65535, the grid's y extent
+        assert entry(P, P, 1, 32, 46341, 46341, N) == -1                                  # H * W + 31 is no int
+    for entry in (hip_lib.ln3d_rollout_means, hip_lib.ln3d_rollout_means_bf16):
+        assert entry(P, P, P, 65536, 8, 8, 32, N) == -1                                   # N > 65535, the grid's y extent
+
+
 # ---- the mesh simplification (include/ln3d_meshsimplify.h): name -> (a valid argument list on fake addresses, indices of its buffers,
 # indices of its counts)
 A = 0x10000                                  # a fake device address

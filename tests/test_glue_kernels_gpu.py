@@ -329,8 +329,9 @@ def test_planes_layout_round_trip(o, H, W):
 
 @pytest.mark.parametrize("upsample", [1, 2])
 @pytest.mark.parametrize("C,Kpad", [(8, 80), (16, 160), (64, 576)])
-def test_im2col3x3(o, C, Kpad, upsample):
-    N, H, W = 2, 5, 7
+@pytest.mark.parametrize("H,W", [(1, 1), (5, 7), (8, 3)])          # 1 x 1 under upsample 2: every tap at or across an edge
+def test_im2col3x3(o, C, Kpad, upsample, H, W):
+    N = 2
     x = torch.randn(N, H, W, C).to(torch.bfloat16)
     Ho, Wo = H * upsample, W * upsample
     col = torch.full((N * Ho * Wo * Kpad + 8,), 7.0, dtype=torch.bfloat16, device=DEV)
