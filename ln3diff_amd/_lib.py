@@ -74,7 +74,8 @@ class RenderArgs(C.Structure):
 class NormalsArgs(C.Structure):         # ln3d_normals_args (include/ln3d_normals.h)
     _fields_ = [("planes", vp), ("H", i32), ("W", i32), ("plane_index", vp), ("cams", vp), ("V", i32), ("res", i32),
                 ("ray_o", vp), ("ray_d", vp), ("rays_per_view", i32), ("dec_w0", vp), ("dec_b0", vp), ("dec_w1", vp), ("dec_b1", vp),
-                ("box_warp", f32), ("depth", vp), ("wsum", vp), ("mask_threshold", f32), ("space", i32), ("normal", vp), ("points", vp)]
+                ("box_warp", f32), ("depth", vp), ("wsum", vp), ("mask_threshold", f32), ("space", i32), ("normal", vp), ("points", vp),
+                ("mode", i32), ("samples", i32), ("weights", vp), ("coords", vp), ("weight_floor", f32), ("accum", vp)]
 
 
 def _int(*argtypes):

@@ -1549,8 +1549,95 @@ __global__ __launch_bounds__(256) void surface_normals_kernel(ln3d_normals_args 
   }
 }
 
+// mode 1 (include/ln3d_normals.h): N = sum_j omega_j n_j over the T sorted samples of a finished render, one wavefront per ray, four
+// waves in a block, grid-stride over the rays.  Lane l owns the samples j = l (mod 64) in ascending j; a pass of 64 samples in which
+// no lane has omega_j > weight_floor is skipped as a whole, and in the others only the active lanes enter the ONE call site of
+// sigma_grad_point (no barrier inside it; its LDS reads are broadcasts under any mask).  The 64 partial sums meet in a fixed xor
+// butterfly, so every lane ends with the same N and two runs give the same bits.  Rounded once per operation, as the snap kernel is.
+template <typename TX>
+__global__ __launch_bounds__(256) void composite_normals_kernel(ln3d_normals_args a, int M, float coord_scale) {
+#pragma clang fp contract(off)
+  __shared__ __attribute__((aligned(16))) float dl[NG_FLOATS];
+  stage_grad_decoder(dl, a.dec_w0, a.dec_b0, a.dec_w1, a.dec_b1);
+  const int lane = threadIdx.x & 63, T = a.samples;
+  const int64_t nr = (int64_t)a.V * M, nw = (int64_t)gridDim.x * 4;
+  for (int64_t ray = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); ray < nr; ray += nw) {
+    const int v = (int)(ray / M), pix = (int)(ray % M);
+    const float* w = a.weights + ray * (T - 1);
+    const float* co = a.coords + ray * T * 3;
+    const TX* planes = reinterpret_cast<const TX*>(a.planes) + (int64_t)a.plane_index[v] * 3 * a.H * a.W * 32;
+    float s[3] = {0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int base = 0; base < T; base += 64) {
+      const int j = base + lane;
+      float om = 0.f;
+      if (j < T) {
+        const float wl = j > 0 ? w[j - 1] : 0.f, wr = j < T - 1 ? w[j] : 0.f;
+        om = j == 0 ? 0.5f * wr : j == T - 1 ? 0.5f * wl : 0.5f * (wl + wr);
+      }
+      const bool act = om > a.weight_floor;                 // false for a NaN, a zero and a negative omega (the floor is >= 0)
+      if (__builtin_amdgcn_ballot_w64(act) == 0) continue;
+      if (act) {
+        float sg, g[3];
+        sigma_grad_point<TX>(planes, a.H, a.W, coord_scale, dl, co[3 * j], co[3 * j + 1], co[3 * j + 2], sg, g);
+        const float m = fmaxf(fmaxf(fabsf(g[0]), fabsf(g[1])), fabsf(g[2]));
+        if (m > 0.f && m <= 3.0e38f && g[0] == g[0] && g[1] == g[1] && g[2] == g[2]) {
+          const float u[3] = {g[0] / m, g[1] / m, g[2] / m};
+          const float inv = -1.0f / sqrtf((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
+#pragma unroll
+          for (int ax = 0; ax < 3; ++ax) s[ax] = s[ax] + om * (u[ax] * inv);
+        }
+      }
+    }
+#pragma unroll
+    for (int x = 32; x >= 1; x >>= 1) {
+#pragma unroll
+      for (int ax = 0; ax < 3; ++ax) s[ax] = s[ax] + __shfl_xor(s[ax], x, 64);
+    }
+    if (lane != 0) continue;
+    float n[3] = {0.f, 0.f, 0.f};
+    const float m = fmaxf(fmaxf(fabsf(s[0]), fabsf(s[1])), fabsf(s[2]));
+    if (a.wsum[ray] >= a.mask_threshold && m > 0.f && m <= 3.0e38f && s[0] == s[0] && s[1] == s[1] && s[2] == s[2]) {
+      const float u[3] = {s[0] / m, s[1] / m, s[2] / m};
+      const float inv = 1.0f / sqrtf((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
+      n[0] = u[0] * inv; n[1] = u[1] * inv; n[2] = u[2] * inv;
+      if (a.space == 1) {                                   // R^T n, as in mode 0
+        const float* c = a.cams + 25 * v;
+        const float w0 = n[0], w1 = n[1], w2 = n[2];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) n[k] = (c[k] * w0 + c[4 + k] * w1) + c[8 + k] * w2;
+      }
+    }
+    const int64_t o = (int64_t)v * 3 * M + pix;
+    a.normal[o] = n[0]; a.normal[o + M] = n[1]; a.normal[o + 2 * (int64_t)M] = n[2];
+    if (a.accum) { a.accum[o] = s[0]; a.accum[o + M] = s[1]; a.accum[o + 2 * (int64_t)M] = s[2]; }
+  }
+}
+
+template <typename TX>
+static int composite_normals_t(const ln3d_normals_args* a, void* stream) {
+  if (!a->planes || !a->plane_index || !a->wsum || !a->normal || !a->weights || !a->coords || !a->dec_w0 || !a->dec_b0 || !a->dec_w1 ||
+      !a->dec_b1) return LN3D_ERR_BAD_ARG;
+  if (a->samples < 2 || a->samples > 256) return LN3D_ERR_BAD_ARG;
+  if (!(a->weight_floor >= 0.f) || !(a->weight_floor - a->weight_floor == 0.f)) return LN3D_ERR_BAD_ARG;
+  if (a->V <= 0 || a->rays_per_view < 0) return LN3D_ERR_BAD_ARG;
+  if (a->rays_per_view == 0 && (a->res <= 0 || a->res > 32768)) return LN3D_ERR_BAD_ARG;               // M = res * res (an int)
+  if (a->space != 0 && a->space != 1) return LN3D_ERR_BAD_ARG;
+  if (a->space == 1 && !a->cams) return LN3D_ERR_BAD_ARG;
+  if (!(a->mask_threshold > 0.f && a->mask_threshold <= 1.f)) return LN3D_ERR_BAD_ARG;
+  if (!planes_ok(a->H, a->W, a->box_warp, (int)sizeof(TX))) return LN3D_ERR_BAD_ARG;
+  const int M = a->rays_per_view > 0 ? a->rays_per_view : a->res * a->res;
+  const int64_t nr = (int64_t)a->V * M;
+  int64_t blocks = (nr + 3) / 4;
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  hipLaunchKernelGGL(composite_normals_kernel<TX>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *a, M, (float)(2.0 / (double)a->box_warp));
+  return ln3d_check_launch();
+}
+
 template <typename TX>
 static int surface_normals_t(const ln3d_normals_args* a, void* stream) {
+  if (a && a->mode == 1) return composite_normals_t<TX>(a, stream);
+  if (a && a->mode != 0) return LN3D_ERR_BAD_ARG;
   if (!a || !a->planes || !a->plane_index || !a->depth || !a->wsum || !a->normal || !a->dec_w0 || !a->dec_b0 || !a->dec_w1 || !a->dec_b1)
     return LN3D_ERR_BAD_ARG;
   if (a->V <= 0 || a->rays_per_view < 0 || (a->res <= 0 && a->rays_per_view <= 0)) return LN3D_ERR_BAD_ARG;

@@ -121,6 +121,7 @@ def create_argparser(objaverse=True):
         dit_precision='bf16',                # matmul precision of the T23D DiT (no reference counterpart): bf16 or the opt-in mxfp8
         plane_precision='fp32',              # texel storage of the renderer's tri-planes (no reference counterpart): fp32 or the opt-in fp16
         save_normal_maps=False,              # normal_sample{i}.npy [V,3,R,R]: world-space surface normal maps next to the frames
+        normal_map_mode='surface',           # what those maps hold: the normal at the expected-depth point, or the opt-in 'composited' one
         **_MESH_FLAGS)
     d.update(_IGNORED_DEFAULTS)
     d.update({k: v[0] for k, v in _CHECKED.items()})
@@ -128,6 +129,15 @@ def create_argparser(objaverse=True):
     add_dict_to_argparser(ap, d)
     ap.set_defaults(entry_objaverse=objaverse)             # which script's defaults these are (the default --prompt differs)
     return ap
+
+
+def recorded_args(args):
+    """vars(args) as args.json records them: an opt-in flag is recorded when set, so a run without them writes the args.json it always wrote"""
+    meta = dict(vars(args))
+    for k, default in dict(_MESH_FLAGS, save_normal_maps=False, normal_map_mode='surface').items():
+        if meta.get(k, default) == default:
+            meta.pop(k, None)
+    return meta
 
 
 def _mesh_post(args):
@@ -189,6 +199,12 @@ def validate(args):
             raise SystemExit(f"--{_mesh_flag(field)}: there is no mesh to {purpose} without --export_mesh true")
     if post.simplify_placement != 'mean' and not post.simplify_cell:
         raise SystemExit(f"--mesh_simplify_placement {post.simplify_placement}: there is nothing to place without --mesh_simplify_cell > 0")
+    nmode = getattr(args, 'normal_map_mode', 'surface')
+    from .ops import NORMAL_MODES
+    if nmode not in NORMAL_MODES:
+        raise SystemExit(f"--normal_map_mode {nmode}: expected one of {list(NORMAL_MODES)}")
+    if nmode != 'surface' and not getattr(args, 'save_normal_maps', False):
+        raise SystemExit(f"--normal_map_mode {nmode}: there is no normal map to composite without --save_normal_maps true")
     if getattr(args, 'save_normal_maps', False):
         world = int(os.environ.get('WORLD_SIZE', '1'))
         if world > 1 and args.num_samples % world != 0:
@@ -489,10 +505,7 @@ def run(args, objaverse=None):
         raise SystemExit("conditioning failed on rank 0: " + res[2])
     cond_all, cond_src = res[0], res[1]
     if rank == 0:
-        meta = dict(vars(args), conditioning=cond_src, weights={k: (v or 'synthetic') for k, v in weights_from.items()})
-        for k, default in dict(_MESH_FLAGS, save_normal_maps=False).items():      # recorded when set: a run without them writes the args.json it always wrote
-            if meta[k] == default:
-                del meta[k]
+        meta = dict(recorded_args(args), conditioning=cond_src, weights={k: (v or 'synthetic') for k, v in weights_from.items()})
         with open(os.path.join(args.logdir, 'args.json'), 'w') as f:
             json.dump(meta, f, indent=2)
     P = next(iter(cond_all.values())).shape[0]                                             # the noClip multi-view denoisers take 'concat' only
@@ -544,7 +557,7 @@ def run(args, objaverse=None):
 
     def render_fn(latent_all, pairs):                             # this rank's (sample, view) pairs: views are shared out when Bt < world
         return render_pairs(latent_all, ae, cams, pairs, args.triplane_scaling_divider, resolution=args.image_size, noise_seed=args.seed,
-                            return_normals=args.save_normal_maps)
+                            return_normals=args.save_normal_maps, normal_mode=getattr(args, 'normal_map_mode', 'surface'))
 
     lat_all, frames, pairs = parallel.sharded_step(sample_fn, render_fn, Bt, V, rank, world)
     lo, hi = parallel.shard_range(Bt, rank, world)

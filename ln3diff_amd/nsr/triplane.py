@@ -16,7 +16,8 @@ import torch.nn as nn
 
 from .. import ops, _cache
 from .._lib import RENDER_SCRATCH_FLOATS, RENDER_MAX_CALLS
-from .volumetric_rendering.renderer import ImportanceRenderer, check_rendering_options, draw_render_noise, render_call_kwargs  # noqa: F401
+from .volumetric_rendering.renderer import (ImportanceRenderer, check_rendering_options, draw_render_noise, render_call_kwargs,  # noqa: F401
+                                             composited_normals, NORMAL_MODES)
 
 
 class FullyConnectedLayer(nn.Module):      # nsr/networks_stylegan2.py:122-157 (container; gain applied in-kernel)
@@ -122,7 +123,8 @@ class Triplane(_cache.PackedWeights, nn.Module):
     @torch.no_grad()
     def forward(self, planes=None, c=None, neural_rendering_resolution=None, jitter=None, u_fine=None,
                 planes_channel_last=None, plane_index=None, return_debug=False, views_per_call=0, return_normals=False,
-                normal_space='world', normal_mask_threshold=0.5, **_):
+                normal_space='world', normal_mask_threshold=0.5, normal_mode='surface', normal_weight_floor=0.0, normal_scratch_bytes=None,
+                **_):
         """planes [V,96,H,W] (one tri-plane per camera row, as the reference) or
         planes_channel_last [NP,3,H,W,32] f32 or f16 + plane_index [V] (many views of few tri-planes).
         views_per_call: the reference reduces the ray-limit fix-up and the depth clamp range over everything ONE forward() call
@@ -132,7 +134,16 @@ class Triplane(_cache.PackedWeights, nn.Module):
         |grad sigma| at each ray's expected-depth surface point o + (depth / wsum) d (depth = 'image_depth', the renderer's clamped
         output), in normal_space 'world' or 'camera'; 0 where
         wsum < normal_mask_threshold or the gradient vanishes.  A second launch behind the render on the planes the render read;
-        every other key keeps its bits."""
+        every other key keeps its bits.
+        normal_mode 'composited' (with return_normals): 'image_normal' is instead the unit volume-composited normal N / |N|, N = the
+        per-sample normals composited by the marcher's own weights the way the colour is (include/ln3d_normals.h, mode 1; samples with
+        a weight <= normal_weight_floor are skipped), and 'image_normal_raw' [V,3,res,res] is N itself in world space: |N| / wsum tells
+        how well the normals along the ray agree.  Costs a second, generic-kernel render of the views into at most
+        normal_scratch_bytes (default 1 GiB) of per-sample scratch (renderer.composited_normals); every other key keeps its bits."""
+        if normal_mode not in NORMAL_MODES:
+            raise ValueError(f"normal_mode {normal_mode!r}: expected one of {NORMAL_MODES}")
+        if normal_mode != 'surface' and not return_normals:                  # as the pipeline functions: a mistake, not a default
+            raise ValueError(f"normal_mode={normal_mode!r} needs return_normals=True")
         res = neural_rendering_resolution or self.neural_rendering_resolution
         self.neural_rendering_resolution = res
         if not c.is_cuda:
@@ -178,7 +189,12 @@ class Triplane(_cache.PackedWeights, nn.Module):
         ret = {'feature_image': rgb, 'image_raw': rgb, 'image_depth': depth, 'weights_samples': wsum,
                'image_mask': wsum * (1 + 2 * 0.001) - 0.001,
                'shape_synthesized': {'image_depth': depth, 'depth': depth.reshape(V, M, 1)}}
-        if return_normals:
+        if return_normals and normal_mode == 'composited':
+            nrm, acc = composited_normals(planes_channel_last, H, W, pidx, self._decoder_dev(dev), rk, wsum, jitter, u_fine, cams=cam, res=res,
+                                          views_per_call=views_per_call, mask_threshold=normal_mask_threshold, space=normal_space,
+                                          weight_floor=normal_weight_floor, normal_scratch_bytes=normal_scratch_bytes)
+            ret['image_normal'], ret['image_normal_raw'] = nrm.reshape(V, 3, res, res), acc.reshape(V, 3, res, res)
+        elif return_normals:
             nrm = torch.empty(V, 3, res, res, device=dev)
             ops.surface_normals(planes_channel_last, H, W, pidx, self._decoder_dev(dev), rk['box_warp'], depth, wsum, nrm, cams=cam, res=res,
                                 mask_threshold=normal_mask_threshold, space=normal_space)

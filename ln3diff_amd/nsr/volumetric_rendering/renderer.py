@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ..._lib import RENDER_SCRATCH_FLOATS
+from ..._lib import RENDER_SCRATCH_FLOATS, RENDER_MAX_CALLS
 
 
 def draw_render_noise(V, M, S=64, generator=None, device='cpu', n_importance=None):
@@ -70,6 +70,53 @@ def decoder_weights(decoder, device):
     return tuple(t.detach().to(device, torch.float32).contiguous() for t in (n[0].weight, n[0].bias, n[2].weight[:4], n[2].bias[:4]))
 
 
+NORMAL_MODES = ops.NORMAL_MODES
+NORMAL_SCRATCH_BYTES = 1 << 30      # per-sample weights and coordinates of the second pass: 133 MB per 256^2 view at 64 + 64 samples
+
+
+def composited_normals(planes_channel_last, H, W, plane_index, dec, rk, wsum, jitter, u_fine, cams=None, res=0, ray_o=None, ray_d=None,
+                       views_per_call=0, mask_threshold=0.5, space='world', weight_floor=0.0, normal_scratch_bytes=None,
+                       weights=None, all_coords=None):
+    """The second pass behind a finished render that volume-composited normals need (include/ln3d_normals.h, mode 1) ->
+    (normal [V, 3, M], accum [V, 3, M]).  Asking ln3d_render_triplane for `weights` / `all_coords` sends it down the generic kernel, and
+    the primary render keeps its bits, so the rays are rendered AGAIN - same planes, noise (jitter [V, M, S], u_fine [V * M, NI]),
+    render_call_kwargs and call grouping - into scratch rgb / depth / wsum that are thrown away, with the per-sample weights and sorted
+    coordinates kept; then ln3d_surface_normals composites, masked by `wsum`, the PRIMARY render's.  The views go in chunks of whole
+    reference calls (views_per_call views each; 0 = all V are one call), which is exact because calls are independent: as many calls
+    as fit normal_scratch_bytes (default NORMAL_SCRATCH_BYTES) of per-sample scratch and one launch's RENDER_MAX_CALLS, at least one.
+    weights [V, M, T - 1(, 1)] / all_coords [V, M, T, 3] of a render that already returned them (return_meta): no second render."""
+    dev = wsum.device
+    V = plane_index.shape[0]
+    M = res * res if ray_o is None else ray_o.shape[1]
+    S, NI = rk.get('depth_resolution', 64), rk.get('depth_resolution_importance', 64)
+    T = S + NI
+    normal, accum = torch.empty(V, 3, M, device=dev), torch.empty(V, 3, M, device=dev)
+    common = dict(res=res, rays_per_view=0 if ray_o is None else M, mask_threshold=mask_threshold, space=space, mode='composited',
+                  weight_floor=weight_floor)
+    if weights is not None:
+        ops.surface_normals(planes_channel_last, H, W, plane_index, dec, rk['box_warp'], None, wsum, normal, cams=cams, n_views=V,
+                            weights=weights, coords=all_coords, accum=accum, **common)
+        return normal, accum
+    vpc = V if (views_per_call <= 0 or views_per_call > V) else views_per_call
+    per_view = M * ((T - 1) + 3 * T) * 4
+    budget = NORMAL_SCRATCH_BYTES if normal_scratch_bytes is None else int(normal_scratch_bytes)
+    calls = max(1, min(RENDER_MAX_CALLS, budget // (per_view * vpc)))
+    chunk = min(V, calls * vpc)
+    wbuf, cbuf = torch.empty(chunk, M, T - 1, device=dev), torch.empty(chunk, M, T, 3, device=dev)
+    rgb, dep, ws = torch.empty(chunk, 3, M, device=dev), torch.empty(chunk, M, device=dev), torch.empty(chunk, M, device=dev)
+    lim, scal = torch.empty(chunk * M * 2, device=dev), torch.empty(RENDER_SCRATCH_FLOATS, device=dev)
+    sl = lambda t, a, b: None if t is None else t[a:b]
+    for a in range(0, V, chunk):
+        b = min(V, a + chunk)
+        n = b - a
+        ops.render_triplane(planes_channel_last, H, W, plane_index[a:b], sl(cams, a, b), res, dec, jitter[a:b], u_fine[a * M:b * M],
+                            rgb[:n], dep[:n], ws[:n], lim, scal, ray_o=sl(ray_o, a, b), ray_d=sl(ray_d, a, b), n_views=n, views_per_call=vpc,
+                            rays_per_view=0 if ray_o is None else M, weights=wbuf[:n], all_coords=cbuf[:n], **render_call_kwargs(rk))
+        ops.surface_normals(planes_channel_last, H, W, plane_index[a:b], dec, rk['box_warp'], None, wsum[a:b], normal[a:b], cams=sl(cams, a, b),
+                            n_views=n, weights=wbuf[:n], coords=cbuf[:n], accum=accum[a:b], **common)
+    return normal, accum
+
+
 class ImportanceRenderer(nn.Module):
     def __init__(self):
         super().__init__()
@@ -77,7 +124,7 @@ class ImportanceRenderer(nn.Module):
     @torch.no_grad()
     def forward(self, planes, decoder, ray_origins, ray_directions, rendering_options, return_meta=False,
                 jitter=None, u_fine=None, planes_channel_last=None, plane_index=None, decoder_weights_dev=None, return_normals=False,
-                normal_mask_threshold=0.5):
+                normal_mask_threshold=0.5, normal_mode='surface', normal_weight_floor=0.0, normal_scratch_bytes=None):
         """planes [N, 3, C, H, W] (or [N, 3*C, H, W]); ray_origins / ray_directions [N, M, 3], any M.
         Alternatively planes_channel_last [NP, 3, H, W, 32] + plane_index [N] (many ray bundles over few tri-planes).
         Returns the reference's dict (renderer.py:276-300): feature_samples [N, M, 3], depth_samples [N, M, 1], weights_samples [N, M, 1],
@@ -85,9 +132,19 @@ class ImportanceRenderer(nn.Module):
         feature_volume [N, M, S + NI, 3] (return_meta needs rendering_options['return_sampling_details_flag'] in the reference - it
         reads shape_synthesized['coarse_coords'] - and does not here).
         return_normals (opt-in; no reference counterpart): adds normal_samples [N, M, 3], the unit outward world-space normal at each
-        ray's expected-depth surface point (ln3d_surface_normals), 0 where weights_samples < normal_mask_threshold."""
+        ray's expected-depth surface point (ln3d_surface_normals), 0 where weights_samples < normal_mask_threshold.
+        normal_mode 'composited': normal_samples is the unit volume-composited normal instead (composited_normals above; samples with a
+        weight <= normal_weight_floor skipped) and normal_samples_raw [N, M, 3] the un-normalised sum; with return_meta the per-sample
+        tensors of this call are reused, otherwise the rays are rendered a second time.  This call is ONE reference call, the unit the
+        second pass works in, so its per-sample scratch is whatever N * M rays need ((4 T - 1) * 4 bytes each): normal_scratch_bytes
+        limits nothing here (it does in Triplane.forward, which renders several calls).  A normal_mode other than 'surface' without
+        return_normals is a ValueError."""
         rk = rendering_options
         check_rendering_options(rk)
+        if normal_mode not in NORMAL_MODES:
+            raise ValueError(f"normal_mode {normal_mode!r}: expected one of {NORMAL_MODES}")
+        if normal_mode != 'surface' and not return_normals:
+            raise ValueError(f"normal_mode={normal_mode!r} needs return_normals=True")
         if not ray_origins.is_cuda:
             raise RuntimeError("ln3diff_amd.ImportanceRenderer runs on the HIP device only (no CPU fallback)")
         dev = ray_origins.device
@@ -127,7 +184,13 @@ class ImportanceRenderer(nn.Module):
                             weights=wall, all_coords=call, feature_volume=fvol, **render_call_kwargs(rk))
         ret = {'feature_samples': rgb.permute(0, 2, 1), 'depth_samples': depth, 'weights_samples': wsum,
                'shape_synthesized': {'depth': depth}, 'visibility': vis}
-        if return_normals:
+        if return_normals and normal_mode == 'composited':
+            nrm, acc = composited_normals(planes_channel_last, H, W, plane_index.to(dev, torch.int32).contiguous(), dec, rk, wsum, jitter, u_fine,
+                                          ray_o=ray_origins.to(torch.float32).contiguous(), ray_d=ray_directions.to(torch.float32).contiguous(),
+                                          mask_threshold=normal_mask_threshold, weight_floor=normal_weight_floor,
+                                          normal_scratch_bytes=normal_scratch_bytes, weights=wall, all_coords=call)
+            ret['normal_samples'], ret['normal_samples_raw'] = nrm.permute(0, 2, 1), acc.permute(0, 2, 1)
+        elif return_normals:
             nrm = torch.empty(N, 3, M, device=dev)
             ops.surface_normals(planes_channel_last, H, W, plane_index.to(dev, torch.int32).contiguous(), dec, rk['box_warp'], depth, wsum, nrm,
                                 ray_o=ray_origins.to(torch.float32).contiguous(), ray_d=ray_directions.to(torch.float32).contiguous(),

@@ -265,17 +265,49 @@ def query_points_grad(planes_cl, H, W, points, dec, box_warp, sigma, grad):
 
 
 NORMAL_SPACES = {'world': 0, 'camera': 1}
+NORMAL_MODES = ('surface', 'composited')
 
 
 def surface_normals(planes_cl, H, W, plane_index, dec, box_warp, depth, wsum, normal, cams=None, res=0, ray_o=None, ray_d=None, n_views=None,
-                    rays_per_view=0, mask_threshold=0.5, space='world', points=None):
+                    rays_per_view=0, mask_threshold=0.5, space='world', points=None, mode='surface', weights=None, coords=None,
+                    weight_floor=0.0, accum=None):
     """normal [V, 3, M] at the expected-depth surface point of every ray of a finished render (its depth / wsum [V, M]); the rays are
     cams [V, 25] + res (generated as the marcher generates them) or explicit ray_o / ray_d [V, M, 3].  space: 'world' or 'camera'
-    (needs cams).  points: optional [V, M, 3] output, the surface points (include/ln3d_normals.h)."""
+    (needs cams).  points: optional [V, M, 3] output, the surface points (include/ln3d_normals.h).
+    mode 'composited': the per-sample normals at coords [V, M, T, 3] composited by weights [V, M, T - 1] (both outputs of a finished
+    ops.render_triplane call over the same rays), samples with a weight <= weight_floor skipped; depth and the rays are not read
+    (depth may be None; M = rays_per_view or res * res), points is not written, accum: optional [V, 3, M] output, the un-normalised
+    sum."""
     if space not in NORMAL_SPACES:
         raise ValueError(f"normal space {space!r}: expected one of {sorted(NORMAL_SPACES)}")
+    if mode not in NORMAL_MODES:
+        raise ValueError(f"normal mode {mode!r}: expected one of {sorted(NORMAL_MODES)}")
     entry = _plane_entry(planes_cl, "surface_normals")
     a = L.NormalsArgs()
+    if n_views is None and cams is None:
+        raise ValueError("surface_normals: the number of views comes from cams [V, 25] or n_views; got neither")
+    if mode == 'composited':
+        V = n_views if n_views is not None else cams.shape[0]
+        M = int(rays_per_view) if rays_per_view else int(res) * int(res)
+        if weights is None or coords is None:
+            raise ValueError("surface_normals(mode='composited') needs weights [V, M, T - 1] and coords [V, M, T, 3] of a finished render")
+        if points is not None:
+            raise ValueError("surface_normals(mode='composited') writes no points")
+        T = coords.numel() // max(1, 3 * V * M)
+        for name, t, n in (('weights', weights, V * M * (T - 1)), ('coords', coords, V * M * T * 3), ('wsum', wsum, V * M),
+                           ('normal', normal, V * 3 * M), ('accum', accum, V * 3 * M)):
+            if t is None:
+                continue
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise TypeError(f"surface_normals(mode='composited'): {name} must be a contiguous torch.float32 tensor, got {t.dtype}"
+                                f"{'' if t.is_contiguous() else ', not contiguous'}")
+            if t.numel() < n or (name in ('weights', 'coords') and t.numel() != n):
+                raise ValueError(f"surface_normals(mode='composited'): {name} has {t.numel()} elements, V = {V}, M = {M}, T = {T} need {n}")
+        if not 2 <= T <= 256:
+            raise ValueError(f"surface_normals(mode='composited'): 2 ... 256 samples per ray, got {T}")
+        a.mode, a.samples, a.weights, a.coords, a.weight_floor, a.accum = 1, T, _p(weights), _p(coords), float(weight_floor), _p(accum)
+    elif weights is not None or coords is not None or accum is not None or weight_floor != 0.0:
+        raise ValueError("surface_normals: weights / coords / weight_floor / accum belong to mode='composited'")
     a.planes, a.H, a.W, a.plane_index, a.cams = _p(planes_cl), H, W, _p(plane_index), _p(cams)
     a.V, a.res = (n_views if n_views is not None else cams.shape[0]), int(res)
     a.ray_o, a.ray_d, a.rays_per_view = _p(ray_o), _p(ray_d), int(rays_per_view)

@@ -24,13 +24,14 @@ TRIPLANE_SCALING_DIVIDER = 0.96806      # the released Objaverse runs (shell_scr
 @torch.no_grad()
 def render_video_given_triplane(planes, rec_model, cams, triplane_scaling_divider=TRIPLANE_SCALING_DIVIDER, latent_name='latent_normalized_2Ddiffusion',
                                 export_mesh=False, mesh_size=192, mesh_thres=10, mesh_path=None, resolution=None, jitter=None, u_fine=None,
-                                plane_precision=None, return_normals=False, **mesh_post):
+                                plane_precision=None, return_normals=False, normal_mode='surface', **mesh_post):
     """planes: sampled latent [B, 12, 32, 32] (scaled IN PLACE like the reference, :188); rec_model: `AE`; cams [V, 25] rendered
     for every sample.  plane_precision: 'fp32' | 'fp16' = the renderer's Triplane.set_plane_precision FOR THIS CALL (the renderer's own
     setting is restored on the way out; None: render with the setting it has); under 'fp16' the decoded planes are converted once and
     the mesh and every view read the f16 texels.  Returns {'latent_after_vit' (if produced), 'image_raw' [B,V,3,R,R], 'image_depth', 'weights_samples',
     'image_mask', 'mesh': [(verts, faces, colors)] when export_mesh}.  return_normals (opt-in) adds 'image_normal' [B,V,3,R,R], the
-    world-space surface normal maps of Triplane.forward(return_normals=True).
+    world-space surface normal maps of Triplane.forward(return_normals=True); normal_mode 'composited' makes them the volume-composited
+    ones (Triplane.forward's normal_mode) and adds 'image_normal_raw' [B,V,3,R,R], at the price of a second render of every view.
     **mesh_post: the nine fields of mesh.MeshPost by their keywords (MeshPost.keyword), all opt-in, all ignored without export_mesh - a bad
     value is the ValueError of the mesh function, so only when a mesh is made; any other keyword is a TypeError either way.  The record goes
     to mesh.mesh_from_record for every sample; mesh_from_grid and textured_mesh_from_grid document what each option does:
@@ -57,13 +58,23 @@ def render_video_given_triplane(planes, rec_model, cams, triplane_scaling_divide
         tp.set_plane_precision(plane_precision)
     try:
         return _render_video_decoded(ddpm_latent, planes, rec_model, cams, export_mesh, mesh_size, mesh_thres, mesh_path, resolution, jitter, u_fine,
-                                     return_normals, post)
+                                     return_normals, post, normal_mode)
     finally:
         tp.set_plane_precision(before)
 
 
+def _normal_keys(return_normals, normal_mode):
+    """the keys the normal maps add to a render dict; a normal_mode without return_normals is a mistake, not a default"""
+    from .ops import NORMAL_MODES
+    if normal_mode not in NORMAL_MODES:
+        raise ValueError(f"normal_mode {normal_mode!r}: expected one of {NORMAL_MODES}")
+    if normal_mode != 'surface' and not return_normals:
+        raise ValueError(f"normal_mode={normal_mode!r} needs return_normals=True")
+    return () if not return_normals else ('image_normal',) if normal_mode == 'surface' else ('image_normal', 'image_normal_raw')
+
+
 def _render_video_decoded(ddpm_latent, planes, rec_model, cams, export_mesh, mesh_size, mesh_thres, mesh_path, resolution, jitter, u_fine,
-                          return_normals, post):
+                          return_normals, post, normal_mode='surface'):
     tp = rec_model.decoder.triplane_decoder
     if ddpm_latent.get('planes_channel_last') is not None:
         ddpm_latent['planes_channel_last'] = tp.cast_planes(ddpm_latent['planes_channel_last'])
@@ -79,11 +90,14 @@ def _render_video_decoded(ddpm_latent, planes, rec_model, cams, export_mesh, mes
     pcl = ddpm_latent.get('planes_channel_last')
     if pcl is not None:
         kw['plane_index'] = torch.arange(B, device=planes.device, dtype=torch.int32).repeat_interleave(V)
+    normal_keys = _normal_keys(return_normals, normal_mode)
     if return_normals:
         kw['return_normals'] = True
+        if normal_mode != 'surface':
+            kw['normal_mode'] = normal_mode
     # one camera per reference call (:262-283): call-wide reductions of the renderer are per view
     pred = rec_model(img=None, c=cams.repeat(B, 1), latent=ddpm_latent, behaviour='triplane_dec', jitter=jitter, u_fine=u_fine, views_per_call=1, **kw)
-    for k in ('image_raw', 'image_depth', 'weights_samples', 'image_mask') + (('image_normal',) if return_normals else ()):
+    for k in ('image_raw', 'image_depth', 'weights_samples', 'image_mask') + normal_keys:
         out[k] = pred[k].view(B, V, *pred[k].shape[1:])
     if 'latent_after_vit' in ddpm_latent:
         out['latent_after_vit'] = ddpm_latent['latent_after_vit']
@@ -93,21 +107,23 @@ def _render_video_decoded(ddpm_latent, planes, rec_model, cams, export_mesh, mes
 
 @torch.no_grad()
 def render_pairs(latent_all, rec_model, cams, pairs, triplane_scaling_divider=TRIPLANE_SCALING_DIVIDER, resolution=None, noise_seed=None,
-                 latent_name='latent_normalized_2Ddiffusion', return_normals=False):
+                 latent_name='latent_normalized_2Ddiffusion', return_normals=False, normal_mode='surface'):
     """The (sample, view) units of one rank (parallel.shard_pairs): decode the samples that occur in `pairs` ONCE, render all
     listed views in one launch (views_per_call=1: the reference's one-camera-per-call reductions, so a view's pixels do not depend
     on which other views share the launch).  latent_all [B, 12, 32, 32] is NOT modified.  noise_seed: None draws the stratified /
     importance noise from the device's default generator in bulk; an int seeds a generator per (sample, view) pair, which makes a
     frame independent of the world size bit for bit.  Returns {'image_raw' [P,3,R,R], 'image_depth', 'weights_samples',
-    'image_mask', 'pair_index' [P, 2] = (sample, view)}; with return_normals also 'image_normal' [P,3,R,R]."""
+    'image_mask', 'pair_index' [P, 2] = (sample, view)}; with return_normals also 'image_normal' [P,3,R,R] (normal_mode 'composited': the
+    volume-composited ones, and 'image_normal_raw' beside them, as in render_video_given_triplane)."""
     from .nsr.triplane import draw_render_noise
+    normal_keys = _normal_keys(return_normals, normal_mode)
     dev = latent_all.device
     res = resolution or rec_model.decoder.triplane_decoder.neural_rendering_resolution
     V_all = cams.shape[0]
     if not pairs:
         z = lambda c: torch.empty(0, c, res, res, device=dev)
         return {'image_raw': z(3), 'image_depth': z(1), 'weights_samples': z(1), 'image_mask': z(1),
-                'pair_index': torch.empty(0, 2, dtype=torch.int64, device=dev), **({'image_normal': z(3)} if return_normals else {})}
+                'pair_index': torch.empty(0, 2, dtype=torch.int64, device=dev), **{k: z(3) for k in normal_keys}}
     samples = sorted({s for s, _, _ in pairs})
     local = {s: i for i, s in enumerate(samples)}
     planes = latent_all[samples].clone()
@@ -129,8 +145,9 @@ def render_pairs(latent_all, rec_model, cams, pairs, triplane_scaling_divider=TR
             us.append(u)
         jitter, u_fine = torch.cat(js), torch.cat(us)
     pred = rec_model(img=None, c=c, latent=ddpm_latent, behaviour='triplane_dec', jitter=jitter, u_fine=u_fine, views_per_call=1,
-                     plane_index=pidx, neural_rendering_resolution=res, **({'return_normals': True} if return_normals else {}))
-    out = {k: pred[k] for k in ('image_raw', 'image_depth', 'weights_samples', 'image_mask') + (('image_normal',) if return_normals else ())}
+                     plane_index=pidx, neural_rendering_resolution=res, **({'return_normals': True} if return_normals else {}),
+                     **({'normal_mode': normal_mode} if normal_mode != 'surface' else {}))
+    out = {k: pred[k] for k in ('image_raw', 'image_depth', 'weights_samples', 'image_mask') + normal_keys}
     out['pair_index'] = pair_index
     return out
 
@@ -350,7 +367,8 @@ class GuidedDiffusionEngine:
 
 @torch.no_grad()
 def reconstruct(rec_model, img, cams, latent_dir=None, ins_names=None, sample_posterior=True, eps=None, export_mesh=False, mesh_size=192,
-                mesh_thres=10, mesh_path=None, resolution=None, jitter=None, u_fine=None, plane_precision=None, return_normals=False, **mesh_post):
+                mesh_thres=10, mesh_path=None, resolution=None, jitter=None, u_fine=None, plane_precision=None, return_normals=False,
+                normal_mode='surface', **mesh_post):
     """Posed views -> tri-plane latent -> renders (and meshes): TrainLoop.eval_novelview_loop(save_latent=True) of the VAE
     reconstruction launcher (vae_xl_reconstruction.sh; nsr/train_nv_util.py:1176-1213).  rec_model: `AE` with the released encoder;
     img [B*F, 10, 256, 256] (F = rec_model.encoder.num_frames views per object); cams [V, 25] rendered for every object.
@@ -380,6 +398,6 @@ def reconstruct(rec_model, img, cams, latent_dir=None, ins_names=None, sample_po
             np.save(os.path.join(latent_dir, name, 'latent.npy'), zc[b])
     out = render_video_given_triplane(z.clone(), rec_model, cams, triplane_scaling_divider=1.0, export_mesh=export_mesh, mesh_size=mesh_size,
                                       mesh_thres=mesh_thres, mesh_path=mesh_path, resolution=resolution, jitter=jitter, u_fine=u_fine,
-                                      plane_precision=plane_precision, return_normals=return_normals, **mesh_post)
+                                      plane_precision=plane_precision, return_normals=return_normals, normal_mode=normal_mode, **mesh_post)
     out['latent'] = lat
     return out
